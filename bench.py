@@ -2,20 +2,31 @@
 """Headline benchmark: 512x512x5 tiles/sec, training step (fwd + bwd + AdamW) of the 19-class U-Net
 (ResNet-34 encoder) on synthetic tiles, data-parallel over N MI355X (BASELINE.json).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 A "step" = one pass of the hot path over one batch of 32 tiles per GPU (weak scaling): NCHW f32 batch ->
 NHWC bf16, encoder / decoder conv stack (HIP implicit-GEMM on MFMA), BN / pool / upsample kernels, fused
 softmax-CE (+argmax), full backward, gradient mean over ranks (RCCL, overlapped), AdamW + OneCycleLR.
-Inputs are generated on the device before the timed region (random, never zeros: DVFS).
+Inputs are generated on the device before the timed region (random, never zeros: DVFS) from fixed seeds, and a fixed
+number of steps precedes the timed ones: the same arguments give the same inputs and the same trained state in every run.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
-  roofline     -- the dominant kernel symbol of the step, timed live with HIP events on the stream the
-                  kernels run on: achieved = algorithmic FLOPs of its launches / their summed duration
-  cpu_baseline -- the oracle (torch-CPU fp32 restatement of the same step, kind "port") timed on this
-                  box's host cores on a bounded sample (rank 0, N=1 only).
+Rank 0 prints ONE JSON line: the headline rate (metric, value, unit, higher_is_better, dtype, ms_per_step) and the
+step configuration.  A plain run does nothing else.  --full adds what takes runs of its own:
+  ms_per_step_eager   -- the same K steps launched eagerly
+  roofline            -- the dominant kernel symbol of the step, timed live with HIP events on the stream the
+                         kernels run on: achieved = algorithmic FLOPs of its launches / their summed duration
+  roofline_hbm        -- the same for the HBM-bound kernels of the step
+  swin_t, fusion_sentinel -- short measurements of BASELINE.json configs[3] / configs[4] (N=1 only, --no-extras skips)
+  cpu_baseline        -- the oracle (torch-CPU fp32 restatement of the same step, kind "port") timed on the
+                         host cores on a bounded sample (N=1 only, --no-cpu-baseline skips).
+
+--dump-outputs DIR writes what the last timed step left for its caller (rank 0) as DIR/<name>.npy:
+  loss.npy         -- float64, the step's loss
+  predictions.npy  -- float32, a fixed seeded sample of the step's per-pixel class predictions
+  parameters.npy   -- float32, a fixed seeded sample of every model parameter after the optimizer step
+  buffers.npy      -- float32, every floating-point model buffer (BatchNorm running statistics) after the step
 """
 from __future__ import annotations
 
@@ -38,7 +49,12 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense, /opt/skills/guides/MI355X_MICROARCH.md
 MFMA_F32_PEAK_TFLOPS = 157.3
 TASK = "AERIAL_LABEL-COSIA"
 MOD = "AERIAL_RGBI"
-SETTLE_MAX_STEPS = 200  # untimed steps the settle phase may take before the counted warm-up
+SETTLE_STEPS = 30  # untimed steps of the settle phase before the counted warm-up
+# OneCycleLR length beyond 2 x (warm-up + timed steps).  The steps it covers (graph warm-up, settle, --full passes) need
+# fewer than this; the value is the schedule length the benchmark has always used (16 + the 200 steps the settle phase
+# once allowed), and changing it changes the learning rate of every step -- final_loss and --dump-outputs with it.
+SCHEDULE_SPARE_STEPS = 216
+DUMP_SAMPLE = {"predictions": 1 << 21, "parameters": 1 << 22}  # elements kept of the larger outputs (~24 MB in all)
 
 
 def _hk_tag(w, dtype) -> str:
@@ -362,6 +378,34 @@ def cpu_baseline(budget_s: float = 14.0, B: int = 2):
                       f"oracle/unet_resnet34.py on '{cpu_model}'"}
 
 
+def _sample(flat: torch.Tensor, n: int, seed: int) -> torch.Tensor:
+    """n elements of a 1-D tensor at indices drawn from a fixed seed (all of it when it is no longer than n)"""
+    if flat.numel() <= n:
+        return flat
+    idx = torch.randint(0, flat.numel(), (n,), generator=torch.Generator().manual_seed(seed))
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir: str, task, loss: torch.Tensor) -> None:
+    """What the last timed step handed its caller: the loss, the predictions behind the metric update, and the model
+    state the optimizer left (module docstring)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    preds = task.criterion[TASK].last_prediction()
+    if preds is None:
+        raise RuntimeError("the loss kept no predictions of the last step")
+    model = task.model
+    arrays = {
+        "loss": loss.detach().double().reshape(1),
+        "predictions": _sample(preds.reshape(-1), DUMP_SAMPLE["predictions"], 1).float(),
+        "parameters": _sample(torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]),
+                              DUMP_SAMPLE["parameters"], 2),
+        "buffers": torch.cat([b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -370,16 +414,24 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="tiles per GPU per step")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--tile", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement: eager step time, roofline objects, the BASELINE configs[3] / "
+                         "configs[4] measurements and the CPU baseline (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (implies --full)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the short BASELINE configs[3] / configs[4] measurements appended to the line (N = 1 only)")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel-symbol table to stderr")
+                    help="--full without the short BASELINE configs[3] / configs[4] measurements (N = 1 only; implies "
+                         "--full)")
+    ap.add_argument("--breakdown", action="store_true",
+                    help="print the per-kernel-symbol table of the roofline pass to stderr (implies --full)")
     ap.add_argument("--no-graph", action="store_true", help="run the step eagerly instead of as one hipGraph replay")
     ap.add_argument("--ddp-graph", action="store_true", help="(default since round 3, kept for old command lines)")
     ap.add_argument("--ddp-eager", action="store_true",
                     help="N > 1: eager step with the all-reduces issued from autograd hooks (overlapped with backward) "
                          "instead of the default graph(fwd+bwd) -> bucketed all-reduce -> graph(AdamW)")
     args = ap.parse_args()
+    # the options that only shape the --full measurements ask for it: a caller that passes them gets what it asked for
+    full = args.full or args.breakdown or args.no_cpu_baseline or args.no_extras
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -411,7 +463,7 @@ def main():
 
     total_steps = args.steps + args.warmup
     cfg = unet_resnet34_config(in_channels=5, precision=args.precision, batch_size=args.batch,
-                               total_steps=2 * total_steps + 16 + SETTLE_MAX_STEPS)  # + graph warm-up, settle, roofline pass
+                               total_steps=2 * total_steps + SCHEDULE_SPARE_STEPS)
     torch.manual_seed(cfg["hyperparams"]["seed"])
     task = build_segmentation_module(cfg, {MOD: args.tile}, "train").to(dev)
     task.train()
@@ -426,7 +478,8 @@ def main():
     batch = {MOD: x, TASK: t}
 
     timer = KernelTimer()
-    timer.install()
+    if full:
+        timer.install()
 
     def eager_step(i):
         loss = task.training_step(batch, i)
@@ -477,27 +530,17 @@ def main():
 
     # Settle phase, before the counted warm-up: a fresh box starts with the GPU in a low power state and (eager mode)
     # an allocator that still grows -- the first 10-25 steps were measured at 23-25 ms against 15.5 afterwards on
-    # some boxes.  Run windows of ten steps until two consecutive windows agree within 1.5 % (at most
-    # SETTLE_MAX_STEPS steps / 3 s); every rank runs the same number of windows.
-    prev, calm, t_settle = None, 0, time.perf_counter()
-    for w in range(SETTLE_MAX_STEPS // 10):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(10):
-            step(i)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        calm = calm + 1 if (prev is not None and abs(dt - prev) <= 0.015 * prev) else 0
-        prev = dt
-        stop = calm >= 2 or time.perf_counter() - t_settle > 3.0
-        if world > 1:  # a common decision (the collectives inside the step need every rank)
-            flag = torch.tensor([1.0 if stop else 0.0], device=dev)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            stop = bool(flag.item() > 0.5)
-        if stop:
-            break
+    # some boxes.  The phase is a fixed SETTLE_STEPS steps on every rank, past that ramp, and not a count that follows
+    # the clock: each step trains the model, and the timed steps must start from the same state in every run for the
+    # --dump-outputs of two builds to be comparable.
+    torch.cuda.synchronize()
+    t_settle = time.perf_counter()
+    for i in range(SETTLE_STEPS):
+        step(i)
+    torch.cuda.synchronize()
     if rank == 0:
-        print(f"[bench] settle: {10 * (w + 1)} steps, last window {prev / 10 * 1e3:.2f} ms/step", file=sys.stderr)
+        print(f"[bench] settle: {SETTLE_STEPS} steps, {(time.perf_counter() - t_settle) / SETTLE_STEPS * 1e3:.2f} ms/step",
+              file=sys.stderr)
     for i in range(args.warmup):
         step(i)
     if world > 1:
@@ -511,64 +554,83 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # roofline pass: the same step run eagerly a few times with HIP events around every MFMA kernel launch (all ranks
-    # take part: the eager step of a multi-process run contains the gradient all-reduce)
-    final_loss_t = loss.detach().clone()
-    # nothing may keep the replayed step's autograd graph alive into the eager pass: its AccumulateGrad nodes belong
-    # to the capture stream (the stream-mismatch warning of round 1, and the capture hazard trainers.py documents)
-    del loss
-    if graphed is not None:
-        graphed.loss = graphed.loss.detach()
-    roof_steps = 3
-    timer.enabled = True
-    for i in range(roof_steps):
-        eager_step(args.warmup + args.steps + i)
-    torch.cuda.synchronize()
-    timer.enabled = False
-    # second roofline pass, the precise one: the 3x3 MFMA launches carry their OWN start / stop events
-    # (ffa_ktime_begin / _end: hipExtLaunchKernelGGL), i.e. the kernel's duration as rocprofv3 reports it; the event pairs
-    # of the pass above bracket the launch call and with it ~4-5 us of dispatch gap per launch
-    ktime = {}
-    try:
-        import ctypes as C
-        from flairhip import lib as _fl
-        _lib = _fl.load()
-        cap = 4096
-        _fl.check(_lib.ffa_ktime_begin(cap), "ktime_begin")
-        for i in range(roof_steps):
-            eager_step(args.warmup + args.steps + roof_steps + i)
-        ms_buf, tag_buf = (C.c_float * cap)(), (C.c_int * cap)()
-        n_timed = _lib.ffa_ktime_end(ms_buf, tag_buf, cap)
-        for j in range(max(0, min(n_timed, cap))):
-            a = ktime.setdefault(int(tag_buf[j]), [0.0, 0])
-            a[0] += float(ms_buf[j]) * 1e-3
-            a[1] += 1
-    except Exception as e:  # measurement aid only
-        print(f"[bench] kernel timing session unavailable ({type(e).__name__}: {e})", file=sys.stderr)
-    if rank == 0 and args.breakdown:
-        print("[bench] timed launches by tag (seconds, launches):", ktime, file=sys.stderr)
-    loss = final_loss_t
-    # the same K steps run eagerly (launch by launch, uninstrumented): a multi-GPU value must be compared with the
-    # one-GPU value of the SAME step mode, so both are in every line
     if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        eager_step(args.warmup + args.steps + 2 * roof_steps + i)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed_eager = time.perf_counter() - t0
-    if world > 1:
-        tt = torch.tensor([elapsed, elapsed_eager], device=dev, dtype=torch.float64)
+        tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed, elapsed_eager = float(tt[0].item()), float(tt[1].item())
-
-    final_loss = float(loss.item())
+        elapsed = float(tt.item())
+    final_loss_t = loss.detach().clone()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, task, final_loss_t)
+    final_loss = float(final_loss_t.item())
+    ms = elapsed / args.steps * 1e3
     if rank == 0:
-        ms = elapsed / args.steps * 1e3
         tiles_per_s = world * B * args.steps / elapsed
+        out = {
+            "metric": "512x512x5 tiles/sec (train fwd+bwd+AdamW), U-Net ResNet-34, 19 classes",
+            "value": round(tiles_per_s, 2), "unit": "tiles/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+            "config": {"workload": f"synthetic {S}x{S}x5 tiles, 19-class U-Net (ResNet-34 encoder), batch {B} per GPU, "
+                                   f"train step (BASELINE.json configs[{1 if world == 1 else 2}])",
+                       "global_batch": B * world, "tile": S, "parallelism": f"dp{world}"},
+            "final_loss": round(final_loss, 5), "hip_graph": bool(use_graph),
+            "step_mode": ("hipgraph(whole step)" if not ddp else "hipgraph(fwd+bwd) -> bucketed all-reduce -> hipgraph(adamw)")
+                         if use_graph else ("eager" if not ddp else "eager, all-reduce from autograd hooks"),
+        }
+    if full:
+        # roofline pass: the same step run eagerly a few times with HIP events around every MFMA kernel launch (all
+        # ranks take part: the eager step of a multi-process run contains the gradient all-reduce)
+        # nothing may keep the replayed step's autograd graph alive into the eager pass: its AccumulateGrad nodes belong
+        # to the capture stream (the stream-mismatch warning of round 1, and the capture hazard trainers.py documents)
+        del loss
+        if graphed is not None:
+            graphed.loss = graphed.loss.detach()
+        roof_steps = 3
+        timer.enabled = True
+        for i in range(roof_steps):
+            eager_step(args.warmup + args.steps + i)
+        torch.cuda.synchronize()
+        timer.enabled = False
+        # second roofline pass, the precise one: the 3x3 MFMA launches carry their OWN start / stop events
+        # (ffa_ktime_begin / _end: hipExtLaunchKernelGGL), i.e. the kernel's duration as rocprofv3 reports it; the event
+        # pairs of the pass above bracket the launch call and with it ~4-5 us of dispatch gap per launch
+        ktime = {}
+        try:
+            import ctypes as C
+            from flairhip import lib as _fl
+            _lib = _fl.load()
+            cap = 4096
+            _fl.check(_lib.ffa_ktime_begin(cap), "ktime_begin")
+            for i in range(roof_steps):
+                eager_step(args.warmup + args.steps + roof_steps + i)
+            ms_buf, tag_buf = (C.c_float * cap)(), (C.c_int * cap)()
+            n_timed = _lib.ffa_ktime_end(ms_buf, tag_buf, cap)
+            for j in range(max(0, min(n_timed, cap))):
+                a = ktime.setdefault(int(tag_buf[j]), [0.0, 0])
+                a[0] += float(ms_buf[j]) * 1e-3
+                a[1] += 1
+        except Exception as e:  # measurement aid only
+            print(f"[bench] kernel timing session unavailable ({type(e).__name__}: {e})", file=sys.stderr)
+        if rank == 0 and args.breakdown:
+            print("[bench] timed launches by tag (seconds, launches):", ktime, file=sys.stderr)
+        # the same K steps run eagerly (launch by launch, uninstrumented): a multi-GPU value must be compared with the
+        # one-GPU value of the SAME step mode, so both are in every --full line
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            eager_step(args.warmup + args.steps + 2 * roof_steps + i)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        elapsed_eager = time.perf_counter() - t0
+        if world > 1:
+            tt = torch.tensor([elapsed_eager], device=dev, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            elapsed_eager = float(tt.item())
+
+    if full and rank == 0:
         summ = timer.summary()
         dom = max(summ.items(), key=lambda kv: kv[1]["seconds"])
         peak = MFMA_BF16_PEAK_TFLOPS if args.precision == "bf16" else MFMA_F32_PEAK_TFLOPS
@@ -598,20 +660,8 @@ def main():
                       f"{v['flops'] / v['seconds'] / 1e12:8.1f} TFLOP/s", file=sys.stderr)
             print(f"  MFMA kernels total {mfma_total / args.steps * 1e3:.3f} ms of {ms:.3f} ms/step; loss {final_loss:.4f}",
                   file=sys.stderr)
-        out = {
-            "metric": "512x512x5 tiles/sec (train fwd+bwd+AdamW), U-Net ResNet-34, 19 classes",
-            "value": round(tiles_per_s, 2), "unit": "tiles/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": f"synthetic {S}x{S}x5 tiles, 19-class U-Net (ResNet-34 encoder), batch {B} per GPU, "
-                                   f"train step (BASELINE.json configs[{1 if world == 1 else 2}])",
-                       "global_batch": B * world, "tile": S, "parallelism": f"dp{world}"},
-            "final_loss": round(final_loss, 5), "hip_graph": bool(use_graph),
-            "step_mode": ("hipgraph(whole step)" if not ddp else "hipgraph(fwd+bwd) -> bucketed all-reduce -> hipgraph(adamw)")
-                         if use_graph else ("eager" if not ddp else "eager, all-reduce from autograd hooks"),
-            "ms_per_step_eager": round(elapsed_eager / args.steps * 1e3, 3),
-            "roofline": roofline,
-        }
+        out["ms_per_step_eager"] = round(elapsed_eager / args.steps * 1e3, 3)
+        out["roofline"] = roofline
         hsum = timer.hbm_summary()
         if hsum:
             # the HBM-bound group of the step, TIME-WEIGHTED: every bracketed streaming kernel (BatchNorm apply /
@@ -658,6 +708,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(B=2)
             out["cpu_baseline_b8"] = cpu_baseline(B=8)  # B = 2 (config 1) and B = 8
+    if rank == 0:
         print(json.dumps(out))
     if ddp:
         dist.destroy_process_group()

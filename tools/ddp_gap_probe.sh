@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/ddp_gap
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 export FFA_BENCH_FORCE_DDP=1
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT" -o r -- python3 "$R/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --no-extras > "$OUT/bench.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT" -o r -- python3 "$R/bench.py" --steps 20 --warmup 3 > "$OUT/bench.log" 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
