@@ -1,0 +1,874 @@
+"""In-situ checks of the kernels of a training step ("teacher forcing at the op level").
+
+``Recorder`` patches the kernel-launching functions of ``flairhip.ops`` while a real training step runs.  Every
+outermost call is checked as it happens: the call's own inputs (cloned before the call, so in-place updates can be
+checked too) go through a float64 reference of the same operation, and the product's outputs are compared element by
+element -- or, in projection mode, through seeded random projections over the channels (a Freivalds check) -- against
+a bound made of the rounding of the stored output plus an f32 summation term:
+
+    bf16-stored outputs:  |o - r| <= ulp_bf16(r) + REL * a
+    f32 outputs:          |o - r| <= REL * a
+
+with ``a`` the same linear operation on absolute values.  The inputs are exactly what the kernel saw, so an error in
+one layer does not avalanche into the next one's check.  Only summaries are kept.
+
+The references work on any device (CPU for tests/test_insitu_checker.py, the GPU in float64 for the step).
+"""
+from __future__ import annotations
+
+import inspect
+from collections import defaultdict
+from typing import Dict, List, Optional
+
+import torch
+import torch.nn.functional as F
+
+REL = 2.0 ** -16          # f32 summation term, relative to the magnitude bound a
+AMBIG_REL = 2.0 ** -20    # |pre-activation| below this * (|x*s| + |t|): the ReLU mask may go either way
+AMBIG_MAX_FRACTION = 1e-4
+F64 = torch.float64
+
+BCO_RING, BCO_THIN, BCO_STEM = 0x1000, 0x2000, 0x8000
+
+# functions of flairhip.ops that launch no kernel of their own (or only packers, covered through the conv results)
+HELPERS = {
+    "pad_channels", "conv_out_size", "conv_stat_rows", "workspace", "upcat_supported", "pro_supported",
+    "conv_is_persistent", "pack_conv_weight", "coop_barrier_failed", "slice_grid", "write_window",
+}
+
+
+def layout_of(pw) -> str:
+    if pw.bco & BCO_STEM:
+        return "stem"
+    if pw.bco & BCO_THIN:
+        return "thin"
+    if pw.bco & BCO_RING:
+        return "ring16"
+    return "igemm"
+
+
+# --------------------------------------------------------------------------------------------------
+# rounding units
+
+def ulp_bf16(r: torch.Tensor) -> torch.Tensor:
+    """unit in the last place of a bf16 number of the magnitude of r (8 significant bits)"""
+    _, e = torch.frexp(r.abs())
+    u = torch.ldexp(torch.ones_like(r), (e - 8).to(torch.int32))
+    return torch.clamp(torch.where(r == 0, torch.zeros_like(r), u), min=2.0 ** -133)
+
+
+def ulp_f32(r: torch.Tensor) -> torch.Tensor:
+    _, e = torch.frexp(r.abs())
+    u = torch.ldexp(torch.ones_like(r), (e - 24).to(torch.int32))
+    return torch.clamp(torch.where(r == 0, torch.zeros_like(r), u), min=2.0 ** -149)
+
+
+def bf16_round(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.bfloat16).to(F64)
+
+
+# --------------------------------------------------------------------------------------------------
+# float64 references of the linear operations (NHWC activations, OIHW weights)
+
+def conv_gather(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, ho: int, wo: int) -> torch.Tensor:
+    """forward convolution: out[b,y,x,o] = sum x[b, y*s - p + ky, x*s - p + kx, i] w[o,i,ky,kx]"""
+    B, H, W, I = x.shape
+    O, _, kh, kw = w.shape
+    hp = max(H + 2 * pad, kh - 1 + stride * (ho - 1) + 1)
+    wp = max(W + 2 * pad, kw - 1 + stride * (wo - 1) + 1)
+    xp = x.new_zeros((B, hp, wp, I))
+    xp[:, pad:pad + H, pad:pad + W] = x
+    out = x.new_zeros((B, ho, wo, O))
+    for ky in range(kh):
+        for kx in range(kw):
+            sl = xp[:, ky:ky + stride * (ho - 1) + 1:stride, kx:kx + stride * (wo - 1) + 1:stride]
+            out += sl @ w[:, :, ky, kx].t()
+    return out
+
+
+def conv_scatter(dy: torch.Tensor, w: torch.Tensor, stride: int, pad: int, hi: int, wi: int) -> torch.Tensor:
+    """input gradient of conv_gather (out channels = w's input channels)"""
+    B, ho, wo, O = dy.shape
+    _, I, kh, kw = w.shape
+    hp = max(hi + 2 * pad, kh - 1 + stride * (ho - 1) + 1)
+    wp = max(wi + 2 * pad, kw - 1 + stride * (wo - 1) + 1)
+    dxp = dy.new_zeros((B, hp, wp, I))
+    for ky in range(kh):
+        for kx in range(kw):
+            dxp[:, ky:ky + stride * (ho - 1) + 1:stride, kx:kx + stride * (wo - 1) + 1:stride] += dy @ w[:, :, ky, kx]
+    return dxp[:, pad:pad + hi, pad:pad + wi]
+
+
+def conv_wgrad_ref(x: torch.Tensor, dy: torch.Tensor, kh: int, kw: int, stride: int, pad: int) -> torch.Tensor:
+    """dW[o,i,ky,kx] = sum dy[b,y,x,o] x[b, y*s - p + ky, x*s - p + kx, i]"""
+    B, H, W, I = x.shape
+    _, ho, wo, O = dy.shape
+    hp = max(H + 2 * pad, kh - 1 + stride * (ho - 1) + 1)
+    wp = max(W + 2 * pad, kw - 1 + stride * (wo - 1) + 1)
+    xp = x.new_zeros((B, hp, wp, I))
+    xp[:, pad:pad + H, pad:pad + W] = x
+    d = dy.reshape(-1, O).t()
+    out = x.new_zeros((O, I, kh, kw))
+    for ky in range(kh):
+        for kx in range(kw):
+            sl = xp[:, ky:ky + stride * (ho - 1) + 1:stride, kx:kx + stride * (wo - 1) + 1:stride]
+            out[:, :, ky, kx] = d @ sl.reshape(-1, I)
+    return out
+
+
+def up2(t: torch.Tensor) -> torch.Tensor:
+    return t.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+
+
+def pool2_sum(t: torch.Tensor) -> torch.Tensor:
+    B, H, W, C = t.shape
+    return t.reshape(B, H // 2, 2, W // 2, 2, C).sum(dim=(2, 4))
+
+
+def upcat(lo, skip):
+    u = up2(lo)
+    return u if skip is None else torch.cat([u, skip], dim=-1)
+
+
+# --------------------------------------------------------------------------------------------------
+# comparison
+
+class Result(dict):
+    """one checked quantity: op, module, what, shape, worst (error / bound), fail (count), n, where, block, ..."""
+
+    @property
+    def ok(self) -> bool:
+        return self["fail"] == 0 and not self.get("error")
+
+    def line(self) -> str:
+        s = f"{self['op']}[{self.get('module', '')}] {self['what']} {self.get('shape')}: worst err/bound {self['worst']:.3g}"
+        if self["fail"]:
+            s += f", {self['fail']} of {self['n']} outside the bound, worst at {self.get('where')}, " \
+                 f"worst 16x16x16 block at {self.get('block')} ({self.get('block_fail')} failing)"
+        if self.get("error"):
+            s += f" -- {self['error']}"
+        return s
+
+
+def _compare(o: torch.Tensor, r: torch.Tensor, tol: torch.Tensor, what: str, exclude: Optional[torch.Tensor] = None):
+    """-> Result fields for |o - r| <= tol (elementwise, exclude: mask of elements left out)"""
+    err = (o.to(F64) - r).abs()
+    bad = err > tol
+    if exclude is not None:
+        bad = bad & ~exclude
+        err = torch.where(exclude, torch.zeros_like(err), err)
+    ratio = torch.where(tol > 0, err / torch.where(tol > 0, tol, torch.ones_like(tol)),
+                        torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+    nfail = int(bad.sum().item())
+    res = {"what": what, "shape": tuple(o.shape), "n": o.numel(), "fail": nfail,
+           "worst": float(ratio.max().item()) if ratio.numel() else 0.0}
+    if nfail:
+        flat = int(torch.argmax(torch.where(bad, ratio, torch.zeros_like(ratio))).item())
+        res["where"] = tuple(int(v) for v in torch.unravel_index(torch.tensor(flat), o.shape))
+        res["got"], res["want"], res["bound"] = float(o.reshape(-1)[flat]), float(r.reshape(-1)[flat]), float(tol.reshape(-1)[flat])
+        if o.dim() == 4:  # (image, row, col, channel): count failures per 16 x 16 pixel x 16 channel block
+            B, H, W, C = o.shape
+            pb = bad.to(torch.int32)
+            pb = F.pad(pb, (0, (-C) % 16, 0, (-W) % 16, 0, (-H) % 16))
+            Hb, Wb, Cb = pb.shape[1] // 16, pb.shape[2] // 16, pb.shape[3] // 16
+            cnt = pb.reshape(B, Hb, 16, Wb, 16, Cb, 16).sum(dim=(2, 4, 6))
+            k = int(torch.argmax(cnt).item())
+            b, by, bx, bc = (int(v) for v in torch.unravel_index(torch.tensor(k), cnt.shape))
+            res["block"] = (b, by * 16, bx * 16, bc * 16)
+            res["block_fail"] = int(cnt.reshape(-1)[k])
+    return res
+
+
+def _exact_zero(t: torch.Tensor, what: str):
+    nz = t != 0
+    res = {"what": what, "shape": tuple(t.shape), "n": t.numel(), "fail": int(nz.sum().item()), "worst": 0.0}
+    if res["fail"]:
+        res["worst"] = float("inf")
+        flat = int(torch.argmax(nz.reshape(-1).to(torch.int8)).item())
+        res["where"] = tuple(int(v) for v in torch.unravel_index(torch.tensor(flat), t.shape))
+        res["got"] = float(t.reshape(-1)[flat])
+    return res
+
+
+def _merge(parts: List[dict], what: str):
+    """combine the Result fields of chunks (batch slices) of one comparison; `where` / `block` carry the image offset"""
+    out = {"what": what, "n": sum(p["n"] for p in parts), "fail": sum(p["fail"] for p in parts),
+           "worst": max((p["worst"] for p in parts), default=0.0)}
+    out["shape"] = parts[0]["shape"] if len(parts) == 1 else (parts[0].get("full_shape") or parts[0]["shape"])
+    failing = [p for p in parts if p["fail"]]
+    if failing:
+        w = max(failing, key=lambda p: p["worst"])
+        for k in ("where", "block", "block_fail", "got", "want", "bound"):
+            if k in w:
+                out[k] = w[k]
+    return out
+
+
+def _shift(res: dict, b0: int, full_shape) -> dict:
+    res["full_shape"] = tuple(full_shape)
+    for k in ("where", "block"):
+        if k in res:
+            res[k] = (res[k][0] + b0,) + tuple(res[k][1:])
+    return res
+
+
+# --------------------------------------------------------------------------------------------------
+# the checker: references per op
+
+class Checker:
+    """mode "full": elementwise; "proj": conv-family outputs through random projections over the channels.
+    weights: id(PackedWeight) -> dict(name, transpose, weight (f32 OIHW master at pack time))."""
+
+    def __init__(self, mode: str = "full", chunk: int = 2, seed: int = 1234, nproj: int = 2):
+        assert mode in ("full", "proj")
+        self.mode, self.chunk, self.nproj = mode, chunk, nproj
+        self.gen_seed = seed
+        self.weights: Dict[int, dict] = {}
+        self.results: List[Result] = []
+        self.calls: List[dict] = []  # one summary per checked call: op, module, layout, family flags
+        self.grad_sources: List[tuple] = []  # (tag, f32 tensor) outputs that autograd hands to parameters
+        self.ambiguous = [0, 0]  # ReLU mask: ambiguous elements, elements
+
+    # ---- helpers -------------------------------------------------------------------------------
+
+    def _u(self, n: int, device) -> torch.Tensor:
+        g = torch.Generator().manual_seed(self.gen_seed + n)
+        self.gen_seed += 1
+        return torch.randn(n, self.nproj, generator=g, dtype=F64).to(device)
+
+    def _add(self, call: dict, res: dict):
+        r = Result(call)
+        r.update(res)
+        self.results.append(r)
+        return r
+
+    def _weight(self, pw):
+        info = self.weights.get(id(pw))
+        if info is None:
+            raise KeyError("operand not produced by HipConv2d.packed during the recording")
+        return info
+
+    def _chunks(self, B: int):
+        c = max(1, self.chunk)
+        return [(b, min(B, b + c)) for b in range(0, B, c)]
+
+    # ---- conv family ---------------------------------------------------------------------------
+
+    def _check_linear(self, call, o, real_c, ref_fn, what, B, extra=None, force_full=False):
+        """o [B,H,W,pitch] bf16 product output whose first real_c channels are ref_fn(b0, b1, wsel) where wsel maps the
+        op's output channels (None: all, else a [real_c, k] matrix to contract them with) -> (r, a) chunk tensors.
+        extra(b0, b1) -> (add, add_abs) over all real channels (bias / residual), or None"""
+        parts = []
+        pitch = o.shape[-1]
+        if pitch > real_c:
+            self._add(call, _exact_zero(o[..., real_c:], what + " pad channels"))
+        full = self.mode == "full" or force_full
+        if full:
+            for b0, b1 in self._chunks(B):
+                r, a = ref_fn(b0, b1, None)
+                if extra is not None:
+                    e, ea = extra(b0, b1)
+                    r, a = r + e, a + ea
+                oc = o[b0:b1, ..., :real_c]
+                parts.append(_shift(_compare(oc, r, ulp_bf16(r) + REL * a, what), b0, o.shape))
+        else:
+            u = self._u(real_c, o.device)
+            for b0, b1 in self._chunks(B):
+                r, a = ref_fn(b0, b1, u)
+                if extra is not None:
+                    e, ea = extra(b0, b1)
+                    r, a = r + e @ u, a + ea @ u.abs()
+                oc = o[b0:b1, ..., :real_c].to(F64)
+                tol = ulp_bf16(oc) @ u.abs() + REL * a
+                parts.append(_shift(_compare(oc @ u, r, tol, what), b0, o.shape))
+        return self._add(call, _merge(parts, what + ("" if full else " (projected)")))
+
+    def conv_forward(self, call, x, w64, stride, pad, o, bias=None, residual=None, relu=False):
+        """o = relu?(conv(x, w) + bias + residual): x [B,H,W,Ipitch] (bf16 values), w64 [O,I,k,k] float64 (bf16 values)"""
+        O, I = w64.shape[:2]
+        B, Ho, Wo = o.shape[:3]
+        wa = w64.abs()
+
+        def ref(b0, b1, u):
+            xc = x[b0:b1, ..., :I].to(F64)
+            if u is None:
+                return conv_gather(xc, w64, stride, pad, Ho, Wo), conv_gather(xc.abs(), wa, stride, pad, Ho, Wo)
+            wu = torch.einsum("oikl,oj->jikl", w64, u)
+            wua = torch.einsum("oikl,oj->jikl", wa, u.abs())
+            return conv_gather(xc, wu, stride, pad, Ho, Wo), conv_gather(xc.abs(), wua, stride, pad, Ho, Wo)
+
+        extra = None
+        if bias is not None or residual is not None:
+            def extra(b0, b1):
+                e = o.new_zeros((b1 - b0, Ho, Wo, O), dtype=F64)
+                if bias is not None:
+                    e = e + bias[:O].to(F64)
+                ea = e.abs()
+                if residual is not None:
+                    rr = residual[b0:b1, ..., :O].to(F64)
+                    e, ea = e + rr, ea + rr.abs()
+                return e, ea
+        if not relu:
+            return self._check_linear(call, o, O, ref, "out", B, extra=extra)
+
+        def ref_relu(b0, b1, u):  # not linear: always elementwise
+            r, a = ref(b0, b1, None)
+            if extra is not None:
+                e, ea = extra(b0, b1)
+                r, a = r + e, a + ea
+            return r.clamp_min(0), a
+        return self._check_linear(call, o, O, ref_relu, "out", B, force_full=True)
+
+    def conv_dgrad(self, call, dy, w64, stride, pad, o, residual=None):
+        """o = conv_scatter(dy, w) (+ residual): the input gradient of a conv with weight w64 [O,I,k,k]"""
+        O, I = w64.shape[:2]
+        B, Hi, Wi = o.shape[:3]
+        wa = w64.abs()
+
+        def ref(b0, b1, u):
+            d = dy[b0:b1, ..., :O].to(F64)
+            if u is None:
+                return conv_scatter(d, w64, stride, pad, Hi, Wi), conv_scatter(d.abs(), wa, stride, pad, Hi, Wi)
+            wu = torch.einsum("oikl,ij->ojkl", w64, u)
+            wua = torch.einsum("oikl,ij->ojkl", wa, u.abs())
+            return conv_scatter(d, wu, stride, pad, Hi, Wi), conv_scatter(d.abs(), wua, stride, pad, Hi, Wi)
+
+        extra = None
+        if residual is not None:
+            def extra(b0, b1):
+                rr = residual[b0:b1, ..., :I].to(F64)
+                return rr, rr.abs()
+        return self._check_linear(call, o, I, ref, "dx", B, extra=extra)
+
+    def conv_wgrad(self, call, x, dy, kh, kw, stride, pad, o, before=None):
+        """o [co, ci, kh, kw] f32 = wgrad(x[..., :ci], dy[..., :co]) (+ before when accumulating)"""
+        co, ci = o.shape[:2]
+        B = x.shape[0]
+        if self.mode == "full":
+            r = o.new_zeros(o.shape, dtype=F64)
+            a = o.new_zeros(o.shape, dtype=F64)
+            for b0, b1 in self._chunks(B):
+                xc, dc = x[b0:b1, ..., :ci].to(F64), dy[b0:b1, ..., :co].to(F64)
+                r += conv_wgrad_ref(xc, dc, kh, kw, stride, pad)
+                a += conv_wgrad_ref(xc.abs(), dc.abs(), kh, kw, stride, pad)
+            if before is not None:
+                r, a = r + before.to(F64), a + before.to(F64).abs()
+            return self._add(call, _compare(o, r, REL * a, "dW"))
+        u, v = self._u(co, o.device), self._u(ci, o.device)
+        rl = o.new_zeros((self.nproj, ci, kh, kw), dtype=F64)
+        al = torch.zeros_like(rl)
+        rr = o.new_zeros((co, self.nproj, kh, kw), dtype=F64)
+        ar = torch.zeros_like(rr)
+        for b0, b1 in self._chunks(B):
+            xc, dc = x[b0:b1, ..., :ci].to(F64), dy[b0:b1, ..., :co].to(F64)
+            rl += conv_wgrad_ref(xc, dc @ u, kh, kw, stride, pad)
+            al += conv_wgrad_ref(xc.abs(), dc.abs() @ u.abs(), kh, kw, stride, pad)
+            rr += conv_wgrad_ref(xc @ v, dc, kh, kw, stride, pad)
+            ar += conv_wgrad_ref(xc.abs() @ v.abs(), dc.abs(), kh, kw, stride, pad)
+        o64 = o.to(F64)
+        if before is not None:
+            b64 = before.to(F64)
+            rl += torch.einsum("oikl,oj->jikl", b64, u)
+            al += torch.einsum("oikl,oj->jikl", b64.abs(), u.abs())
+            rr += torch.einsum("oikl,ij->ojkl", b64, v)
+            ar += torch.einsum("oikl,ij->ojkl", b64.abs(), v.abs())
+        self._add(call, _compare(torch.einsum("oikl,oj->jikl", o64, u), rl, REL * al, "u^T dW (projected)"))
+        return self._add(call, _compare(torch.einsum("oikl,ij->ojkl", o64, v), rr, REL * ar, "dW v (projected)"))
+
+    # ---- BatchNorm -----------------------------------------------------------------------------
+
+    def bn_stats(self, call, y0, gamma, beta, rm0, rv0, rm1, rv1, momentum, eps, scale, shift, mean, rstd):
+        """statistics of the stored conv output y0 as the finalize kernel takes them; rm0/rv0 before, rm1/rv1 after"""
+        C = y0.shape[-1]
+        s1 = y0.new_zeros(C, dtype=F64)
+        s2 = y0.new_zeros(C, dtype=F64)
+        sa = y0.new_zeros(C, dtype=F64)
+        for b0, b1 in self._chunks(y0.shape[0]):
+            v = y0[b0:b1].to(F64).reshape(-1, C)
+            s1 += v.sum(0)
+            s2 += (v * v).sum(0)
+            sa += v.abs().sum(0)
+        n = y0.numel() // C
+        m = s1 / n
+        var = (s2 / n - m * m).clamp_min(0)
+        t_m = REL * sa / n + ulp_f32(m)
+        t_v = REL * s2 / n
+        rs = 1.0 / torch.sqrt(var + eps)
+        t_rs = 0.5 * rs ** 3 * t_v + ulp_f32(rs)
+        g = gamma.to(F64) if gamma is not None else torch.ones_like(m)
+        bt = beta.to(F64) if beta is not None else torch.zeros_like(m)
+        sc = g * rs
+        t_sc = g.abs() * t_rs + ulp_f32(sc)
+        sh = bt - m * sc
+        t_sh = sc.abs() * t_m + m.abs() * t_sc + 2 * ulp_f32(bt.abs() + (m * sc).abs())
+        self._add(call, _compare(mean, m, t_m, "mean"))
+        self._add(call, _compare(rstd, rs, t_rs, "rstd"))
+        self._add(call, _compare(scale, sc, t_sc, "scale"))
+        self._add(call, _compare(shift, sh, t_sh, "shift"))
+        if rm1 is not None:
+            mo = float(momentum)
+            unb = var * n / (n - 1) if n > 1 else var
+            rm = (1 - mo) * rm0.to(F64) + mo * m
+            rv = (1 - mo) * rv0.to(F64) + mo * unb
+            self._add(call, _compare(rm1, rm, mo * t_m + 2 * ulp_f32(rm.abs() + rm0.to(F64).abs()), "running_mean"))
+            self._add(call, _compare(rv1, rv, mo * t_v * n / max(n - 1, 1) + 2 * ulp_f32(rv.abs() + rv0.to(F64).abs()),
+                                     "running_var"))
+
+    def bn_apply(self, call, x, scale, shift, residual, relu, o):
+        C = x.shape[-1]
+        s, t = scale[:C].to(F64), shift[:C].to(F64)
+        parts = []
+        for b0, b1 in self._chunks(x.shape[0]):
+            xc = x[b0:b1].to(F64)
+            r = xc * s + t
+            a = (xc * s).abs() + t.abs()
+            if residual is not None:
+                rr = residual[b0:b1].to(F64)
+                r, a = r + rr, a + rr.abs()
+            if relu:
+                r = r.clamp_min(0)
+            parts.append(_shift(_compare(o[b0:b1], r, ulp_bf16(r) + REL * a, "y"), b0, o.shape))
+        return self._add(call, _merge(parts, "y"))
+
+    def bn_bwd(self, call, x, dy, y, gamma, beta, mean, rstd, relu, dx, dres, dgamma, dbeta):
+        C = x.shape[-1]
+        mode = 0 if not relu else (1 if y is not None else 2)
+        n = x.numel() // C
+        g64 = gamma.to(F64) if gamma is not None else x.new_ones(C, dtype=F64)
+        mu, rs = mean.to(F64), rstd.to(F64)
+        # the kernel's forward affine for the mask of mode 2: f32 gamma * rstd, beta - mean * scale
+        sc32 = (gamma if gamma is not None else torch.ones_like(rstd)) * rstd
+        sh32 = (beta if beta is not None else torch.zeros_like(mean)) - mean * sc32
+        sc, sh = sc32.to(F64), sh32.to(F64)
+
+        def masks(b0, b1):
+            xc, dc = x[b0:b1].to(F64), dy[b0:b1].to(F64)
+            amb = None
+            if mode == 0:
+                gm = dc
+            elif mode == 1:
+                gm = torch.where(y[b0:b1] > 0, dc, torch.zeros_like(dc))
+            else:
+                pre = xc * sc + sh
+                gm = torch.where(pre > 0, dc, torch.zeros_like(dc))
+                amb = pre.abs() <= AMBIG_REL * ((xc * sc).abs() + sh.abs())
+            return xc, dc, gm, amb
+
+        sb, sg, ab, ag, xb, xg = (x.new_zeros(C, dtype=F64) for _ in range(6))
+        namb = 0
+        for b0, b1 in self._chunks(x.shape[0]):
+            xc, dc, gm, amb = masks(b0, b1)
+            xh = (xc - mu) * rs
+            sb += gm.reshape(-1, C).sum(0)
+            sg += (gm * xh).reshape(-1, C).sum(0)
+            ab += gm.abs().reshape(-1, C).sum(0)
+            ag += (gm * xh).abs().reshape(-1, C).sum(0)
+            if amb is not None:
+                namb += int(amb.sum().item())
+                xb += torch.where(amb, dc.abs(), torch.zeros_like(dc)).reshape(-1, C).sum(0)
+                xg += torch.where(amb, (dc * xh).abs(), torch.zeros_like(dc)).reshape(-1, C).sum(0)
+        if mode == 2:
+            self.ambiguous[0] += namb
+            self.ambiguous[1] += x.numel()
+            if namb > AMBIG_MAX_FRACTION * x.numel():
+                self._add(call, {"what": "ambiguous ReLU masks", "shape": tuple(x.shape), "n": x.numel(), "fail": namb,
+                                 "worst": float("inf"), "error": f"{namb} ambiguous of {x.numel()}"})
+        t_b = REL * ab + xb + ulp_f32(sb)
+        t_g = REL * ag + xg + ulp_f32(sg)
+        self._add(call, dict(_compare(dbeta, sb, t_b, "dbeta"), ambiguous=namb))
+        self._add(call, _compare(dgamma, sg, t_g, "dgamma"))
+        self.grad_sources += [("dgamma", dgamma.detach().clone()), ("dbeta", dbeta.detach().clone())]
+        kg = g64.abs() * rs
+        pdx, pres = [], []
+        for b0, b1 in self._chunks(x.shape[0]):
+            xc, dc, gm, amb = masks(b0, b1)
+            xh = (xc - mu) * rs
+            r = g64 * rs * (gm - sb / n - xh * sg / n)
+            a = kg * (gm.abs() + sb.abs() / n + rs * (xc.abs() + mu.abs()) * sg.abs() / n)
+            tol = ulp_bf16(r) + REL * a + kg * (t_b / n + xh.abs() * t_g / n)
+            pdx.append(_shift(_compare(dx[b0:b1], r, tol, "dx", exclude=amb), b0, dx.shape))
+            if dres is not None:
+                pres.append(_shift(_compare(dres[b0:b1], gm, ulp_bf16(gm) * 0, "dres", exclude=amb), b0, dx.shape))
+        self._add(call, _merge(pdx, "dx"))
+        if dres is not None:
+            self._add(call, _merge(pres, "dres"))
+
+    def channel_sums(self, call, x, s, q):
+        C = x.shape[-1]
+        v = x.to(F64).reshape(-1, C)
+        self._add(call, _compare(s, v.sum(0), REL * v.abs().sum(0), "sum"))
+        self._add(call, _compare(q, (v * v).sum(0), REL * (v * v).sum(0), "sum of squares"))
+
+    # ---- pooling, loss, layout -------------------------------------------------------------------
+
+    def maxpool_fwd(self, call, x, y, idx):
+        B, H, W, C = x.shape
+        Ho, Wo = y.shape[1:3]
+        hp, wp = max(H + 2, 2 * Ho + 1), max(W + 2, 2 * Wo + 1)
+        xp = F.pad(x.to(F64), (0, 0, 1, wp - W - 1, 1, hp - H - 1), value=float("-inf"))
+        taps = torch.stack([xp[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] for r in range(3) for s in range(3)])
+        r = taps.max(0).values
+        self._add(call, _compare(y, r, torch.zeros_like(r), "pooled max"))
+        il = idx.long()
+        picked = torch.gather(taps, 0, il.clamp(0, 8).unsqueeze(0)).squeeze(0)
+        bad = (il > 8) | (picked != y.to(F64))
+        res = _exact_zero(bad.to(torch.int8), "x[idx] == pooled")
+        self._add(call, res)
+
+    def maxpool_bwd(self, call, dy, idx, in_hw, add, dx):
+        B, Ho, Wo, C = dy.shape
+        H, W = in_hw
+        hp, wp = max(H + 2, 2 * Ho + 1), max(W + 2, 2 * Wo + 1)
+        parts = []
+        for b0, b1 in self._chunks(B):
+            d = dy[b0:b1].to(F64)
+            il = idx[b0:b1]
+            acc = d.new_zeros((b1 - b0, hp, wp, C))
+            acca = torch.zeros_like(acc)
+            for t in range(9):
+                r, s = divmod(t, 3)
+                v = torch.where(il == t, d, torch.zeros_like(d))
+                acc[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] += v
+                acca[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] += v.abs()
+            ref, a = acc[:, 1:1 + H, 1:1 + W], acca[:, 1:1 + H, 1:1 + W]
+            if add is not None:
+                ad = add[b0:b1].to(F64)
+                ref, a = ref + ad, a + ad.abs()
+            parts.append(_shift(_compare(dx[b0:b1], ref, ulp_bf16(ref) + REL * a, "dx"), b0, dx.shape))
+        return self._add(call, _merge(parts, "dx"))
+
+    def softmax_ce(self, call, logits, targets, weights, K, grad_scale, out):
+        loss, wsum, dlogits, pred = out[:4]
+        sums = out[4] if len(out) > 4 else None
+        Cp = logits.shape[-1]
+        gs = 1.0 if grad_scale is None else float(grad_scale.reshape(-1)[0])
+        w = weights.to(F64)
+        tot_w = tot_l = tot_la = 0.0
+        parts_d, parts_p = [], []
+        s_ref = logits.new_zeros(Cp, dtype=F64)
+        s_abs = logits.new_zeros(Cp, dtype=F64)
+        B = logits.shape[0]
+        chunks = self._chunks(B)
+        wp_list = []
+        for b0, b1 in chunks:
+            z = logits[b0:b1, ..., :K].to(F64)
+            t = targets[b0:b1].long()
+            wp = w[t.clamp(max=K - 1)] * (t < K)
+            lse = torch.logsumexp(z, dim=-1)
+            zt = torch.gather(z, -1, t.clamp(max=K - 1).unsqueeze(-1)).squeeze(-1)
+            tot_w += float(wp.sum())
+            tot_l += float((wp * (lse - zt)).sum())
+            tot_la += float((wp * (lse.abs() + zt.abs())).sum())
+            wp_list.append(wp)
+            if pred is not None:
+                zb = logits[b0:b1, ..., :K].to(F64)
+                pk = pred[b0:b1].long()
+                ok = (pk < K) & (torch.gather(zb, -1, pk.clamp(max=K - 1).unsqueeze(-1)).squeeze(-1) == zb.max(-1).values)
+                parts_p.append(_shift(_exact_zero((~ok).to(torch.int8), "pred is a maximiser"), b0, pred.shape))
+        self._add(call, _compare(wsum, torch.tensor([tot_w], dtype=F64, device=wsum.device),
+                                 torch.tensor([REL * tot_w], dtype=F64, device=wsum.device), "wsum"))
+        self._add(call, _compare(loss, torch.tensor([tot_l / tot_w], dtype=F64, device=loss.device),
+                                 torch.tensor([REL * tot_la / tot_w], dtype=F64, device=loss.device), "loss"))
+        if parts_p:
+            self._add(call, _merge(parts_p, "pred"))
+        if dlogits is not None:
+            for (b0, b1), wp in zip(chunks, wp_list):
+                z = logits[b0:b1, ..., :K].to(F64)
+                t = targets[b0:b1].long()
+                p = torch.softmax(z, dim=-1)
+                oh = F.one_hot(t.clamp(max=K - 1), K).to(F64)
+                f = (gs / tot_w) * wp.unsqueeze(-1)
+                r = f * (p - oh)
+                a = f.abs() * (p + oh)
+                o = dlogits[b0:b1]
+                parts_d.append(_shift(_compare(o[..., :K], r, ulp_bf16(r) + REL * a, "dlogits"), b0, dlogits.shape))
+                if Cp > K:
+                    parts_d.append(_shift(_exact_zero(o[..., K:], "dlogits pad channels"), b0, dlogits.shape))
+                parts_d.append(_shift(_exact_zero(torch.where((wp == 0).unsqueeze(-1), o, torch.zeros_like(o)),
+                                                  "dlogits on zero-weight pixels"), b0, dlogits.shape))
+                ov = o.to(F64).reshape(-1, Cp)
+                s_ref += ov.sum(0)
+                s_abs += ov.abs().sum(0)
+            self._add(call, _merge([p for p in parts_d if p["what"] == "dlogits"], "dlogits"))
+            self._add(call, _merge([p for p in parts_d if p["what"] != "dlogits"], "dlogits exact zeros"))
+        if sums is not None:
+            self._add(call, _compare(sums, s_ref, REL * s_abs, "per-class sums of the stored dlogits"))
+            self.grad_sources.append(("dlogit sums", sums[:K].detach().clone()))
+
+    def scale_inplace(self, call, before, scale, after):
+        s = float(scale.reshape(-1)[0])
+        r = before.to(F64) * s
+        tol = torch.zeros_like(r) if s == 1.0 else ulp_bf16(r) if before.dtype == torch.bfloat16 else ulp_f32(r)
+        return self._add(call, _compare(after, r, tol, "x * s"))
+
+    def nchw_to_nhwc(self, call, x, out):
+        C = x.shape[1]
+        r = x.float().permute(0, 2, 3, 1).to(out.dtype).to(F64)
+        self._add(call, _compare(out[..., :C], r, torch.zeros_like(r), "values"))
+        if out.shape[-1] > C:
+            self._add(call, _exact_zero(out[..., C:], "pad channels"))
+
+    def confusion(self, call, before, after, pred, target):
+        K = before.shape[0]
+        idx = target.reshape(-1).long() * K + pred.reshape(-1).long()
+        r = before + torch.bincount(idx, minlength=K * K).view(K, K).to(before.device)
+        self._add(call, _exact_zero((after != r).to(torch.int8), "counts"))
+
+
+# --------------------------------------------------------------------------------------------------
+# the recorder: patches flairhip.ops and dispatches every outermost call to the Checker
+
+def _clone(v):
+    return v.detach().clone() if torch.is_tensor(v) else v
+
+
+class Recorder(Checker):
+    """with Recorder(model, mode) as rec: <training step>  -- then rec.results / rec.calls / rec.unchecked"""
+
+    def __init__(self, model, mode="full", chunk=2, seed=1234):
+        super().__init__(mode, chunk, seed)
+        self.model = model
+        self.names = {id(m): n for n, m in model.named_modules()}
+        self.depth = 0
+        self.unchecked = defaultdict(int)
+        self.counts = defaultdict(int)
+        self._saved = []
+        self._wcache = {}
+
+    # ---- patching ------------------------------------------------------------------------------
+
+    def __enter__(self):
+        from flairhip import nn as hnn
+        from flairhip import ops
+        self._ops = ops
+        for name, fn in list(vars(ops).items()):
+            if name.startswith("_") or not inspect.isfunction(fn) or fn.__module__ != ops.__name__:
+                continue
+            if name in HELPERS:
+                continue
+            self._saved.append((ops, name, fn))
+            setattr(ops, name, self._wrap(name, fn))
+        orig_packed = hnn.HipConv2d.packed
+        rec = self
+
+        def packed(mod, dtype, transpose=False, *a, **kw):
+            pw = orig_packed(mod, dtype, transpose, *a, **kw)
+            key = (id(mod), mod.weight._version, mod.weight.data_ptr(), hnn.state_epoch())
+            w = rec._wcache.get(key)
+            if w is None:
+                w = rec._wcache[key] = mod.weight.detach().clone()
+            rec.weights[id(pw)] = {"name": rec.names.get(id(mod), "?"), "transpose": bool(transpose), "weight": w,
+                                   "stride": mod.stride, "padding": mod.padding}
+            return pw
+
+        self._saved.append((hnn.HipConv2d, "packed", orig_packed))
+        hnn.HipConv2d.packed = packed
+        return self
+
+    def __exit__(self, *exc):
+        for obj, name, fn in reversed(self._saved):
+            setattr(obj, name, fn)
+        self._saved = []
+        return False
+
+    def _wrap(self, name, fn):
+        sig = inspect.signature(fn)
+        rec = self
+
+        def wrapper(*args, **kw):
+            if rec.depth > 0:
+                return fn(*args, **kw)
+            check = getattr(rec, "_op_" + name, None)
+            if check is None:
+                rec.unchecked[name] += 1
+                return fn(*args, **kw)
+            ba = sig.bind(*args, **kw)
+            ba.apply_defaults()
+            pre = {k: _clone(v) for k, v in ba.arguments.items()}
+            rec.depth += 1
+            try:
+                out = fn(*args, **kw)
+            finally:
+                rec.depth -= 1
+            rec.counts[name] += 1
+            call = {"op": name, "call": len(rec.calls)}
+            try:
+                with torch.no_grad():
+                    check(call, pre, ba.arguments, out)
+            except Exception as e:  # a reference that cannot run is a failed check, not a crash of the step
+                rec._add(call, {"what": "reference", "shape": None, "n": 0, "fail": 1, "worst": float("inf"),
+                                "error": f"{type(e).__name__}: {e}"})
+            rec.calls.append(call)
+            return out
+
+        return wrapper
+
+    # ---- per-op adapters: (call summary, cloned inputs, live arguments, outputs) ----------------
+
+    def _conv_call(self, call, a, out, w, dil, residual, bias=None, relu=False, stats=False):
+        info = self._weight(a["w"])
+        pw = a["w"]
+        W = info["weight"]
+        w64 = bf16_round(W) if pw.data.dtype == torch.bfloat16 else W.to(F64)
+        call.update(module=info["name"], layout=layout_of(pw), transpose=info["transpose"], kernel=f"{pw.kh}x{pw.kw}",
+                    dil=dil, residual=residual is not None, stats=stats)
+        x = a["x"]
+        if not info["transpose"]:
+            call["family"] = "fwd"
+            return self.conv_forward(call, x, w64, pw.stride, a["pad"], out, bias=bias, residual=residual, relu=relu)
+        call["family"] = "dgrad" + ("_dil2" if dil == 2 else "") + ("_residual" if residual is not None else "")
+        if bias is not None or relu:
+            raise ValueError("dgrad call with bias / relu")
+        return self.conv_dgrad(call, x, w64, dil, pw.kh - 1 - a["pad"], out, residual=residual)
+
+    def _op_conv2d(self, call, a, live, out):
+        if a["stats"] is not None:
+            raise ValueError("conv2d with a statistics buffer outside conv2d_bn_stats")
+        self._conv_call(call, a, out, a["w"], a["dil"], a["residual"], bias=a["bias"], relu=a["relu"])
+
+    def _op_conv2d_bn_stats(self, call, a, live, out):
+        y0, scale, shift, mean, rstd = out
+        self._conv_call(call, a, y0, a["w"], 1, None, stats=True)
+        self.bn_stats(dict(call, family="bn_stats", layout=None), y0, a["gamma"], a["beta"], a["running_mean"], a["running_var"], live["running_mean"],
+                      live["running_var"], a["momentum"], a["eps"], scale, shift, mean, rstd)
+
+    def _upcat_weight(self, call, pw):
+        info = self._weight(pw)
+        W = info["weight"]
+        call.update(module=info["name"], layout=layout_of(pw), transpose=info["transpose"], kernel="3x3")
+        return bf16_round(W) if pw.data.dtype == torch.bfloat16 else W.to(F64)
+
+    def _op_conv2d_upcat(self, call, a, live, out, stats=False):
+        if out is None:
+            return
+        w64 = self._upcat_weight(call, a["w"])
+        call.update(family="upcat_fwd", stats=stats)
+        lo, skip = a["lo"], a["skip"]
+        c1, c2 = lo.shape[-1], (0 if skip is None else skip.shape[-1])
+        if w64.shape[1] != c1 + c2:
+            raise ValueError("two-source conv: pitch != real input channels")
+
+        class _Cat:  # lazily concatenated input, sliced per batch chunk
+            shape = (lo.shape[0], 2 * lo.shape[1], 2 * lo.shape[2], c1 + c2)
+
+            def __getitem__(self, idx):
+                bs = idx[0]
+                return upcat(lo[bs].to(F64), None if skip is None else skip[bs].to(F64))[..., :c1 + c2]
+
+        return self.conv_forward(call, _Cat(), w64, 1, 1, out, bias=a.get("bias"), relu=a.get("relu", False))
+
+    def _op_conv2d_upcat_bn_stats(self, call, a, live, out):
+        y0, scale, shift, mean, rstd = out
+        self._op_conv2d_upcat(call, dict(a, bias=None, relu=False), live, y0, stats=True)
+        self.bn_stats(dict(call, family="bn_stats", layout=None), y0, a["gamma"], a["beta"], a["running_mean"], a["running_var"], live["running_mean"],
+                      live["running_var"], a["momentum"], a["eps"], scale, shift, mean, rstd)
+
+    def _op_conv2d_dgrad_upcat(self, call, a, live, out):
+        if out is None:
+            return
+        dlo, dskip = out
+        w64 = self._upcat_weight(call, a["wt"])
+        call["family"] = "upcat_dgrad"
+        c1, c2 = a["c1"], a["c2"]
+        dy = a["dy"]
+        B, H, W, _ = dy.shape
+        O = w64.shape[0]
+        wa = w64.abs()
+        for part, sel, o in (("dlo", slice(0, c1), dlo), ("dskip", slice(c1, c1 + c2), dskip)):
+            if o is None:
+                continue
+            wp, wpa = w64[:, sel], wa[:, sel]
+            pool = part == "dlo"
+
+            def ref(b0, b1, u, wp=wp, wpa=wpa, pool=pool):
+                d = dy[b0:b1, ..., :O].to(F64)
+                if u is not None:
+                    wp_, wpa_ = torch.einsum("oikl,ij->ojkl", wp, u), torch.einsum("oikl,ij->ojkl", wpa, u.abs())
+                else:
+                    wp_, wpa_ = wp, wpa
+                r, aa = conv_scatter(d, wp_, 1, 1, H, W), conv_scatter(d.abs(), wpa_, 1, 1, H, W)
+                return (pool2_sum(r), pool2_sum(aa)) if pool else (r, aa)
+
+            self._check_linear(call, o, wp.shape[1], ref, part, B)
+
+    def _op_conv_wgrad(self, call, a, live, out):
+        call.update(family="wgrad", kernel=f"{a['kh']}x{a['kw']}", stride=a["stride"],
+                    layout="thin" if (a["x"].shape[-1] <= 32 and a["dy"].shape[-1] <= 32 and a["kh"] == 3
+                                      and a["stride"] == 1) else "general")
+        before = a["out"] if a["accumulate"] else None
+        self.conv_wgrad(call, a["x"], a["dy"], a["kh"], a["kw"], a["stride"], a["pad"], out, before=before)
+        self.grad_sources.append(("dW", out.detach().clone()))
+
+    def _op_conv_wgrad_upcat(self, call, a, live, out):
+        if out is None:
+            return
+        call.update(family="upcat_wgrad", kernel="3x3")
+        lo, skip = a["lo"], a["skip"]
+        x = upcat(lo, skip)
+        self.conv_wgrad(call, x, a["dy"], 3, 3, 1, 1, out)
+        self.grad_sources.append(("dW", out.detach().clone()))
+
+    def _op_bn_apply(self, call, a, live, out):
+        call["family"] = "bn_apply"
+        self.bn_apply(call, a["x"], a["scale"], a["shift"], a["residual"], a["relu"], out)
+
+    def _op_bn_bwd(self, call, a, live, out):
+        dx, dres, dg, db = out
+        mode = 0 if not a["relu"] else (1 if a["y"] is not None else 2)
+        call.update(family=f"bn_bwd_mode{mode}", dres=dres is not None)
+        self.bn_bwd(call, a["x"], a["dy"], a["y"], a["gamma"], a["beta"], a["mean"], a["rstd"], a["relu"], dx, dres, dg, db)
+
+    def _op_bn_stats(self, call, a, live, out):
+        scale, shift, mean, rstd = out
+        call["family"] = "bn_stats"
+        self.bn_stats(call, a["x"], a["gamma"], a["beta"], a["running_mean"], a["running_var"], live["running_mean"],
+                      live["running_var"], a["momentum"], a["eps"], scale, shift, mean, rstd)
+
+    def _op_channel_sums(self, call, a, live, out):
+        call["family"] = "channel_sums"
+        self.channel_sums(call, a["x"], *out)
+
+    def _op_maxpool3x3s2_fwd(self, call, a, live, out):
+        call["family"] = "maxpool_fwd"
+        self.maxpool_fwd(call, a["x"], *out)
+
+    def _op_maxpool3x3s2_bwd(self, call, a, live, out):
+        call.update(family="maxpool_bwd" + ("_add" if a["add"] is not None else ""))
+        self.maxpool_bwd(call, a["dy"], a["idx"], a["in_hw"], a["add"], out)
+
+    def _op_softmax_ce(self, call, a, live, out):
+        call["family"] = "softmax_ce"
+        self.softmax_ce(call, a["logits"], a["targets"], a["class_weights"], a["num_classes"], a["grad_scale"], out)
+
+    def _op_scale_inplace(self, call, a, live, out):
+        call["family"] = "scale_inplace"
+        self.scale_inplace(call, a["x"], a["scale"], out)
+
+    def _op_nchw_to_nhwc(self, call, a, live, out):
+        call["family"] = "nchw_to_nhwc"
+        self.nchw_to_nhwc(call, a["x"], out)
+
+    def _op_confusion_matrix_update(self, call, a, live, out):
+        call["family"] = "confusion_matrix"
+        self.confusion(call, a["counts"], live["counts"], a["pred"], a["target"])
+
+    # ---- report --------------------------------------------------------------------------------
+
+    def failures(self) -> List[Result]:
+        return [r for r in self.results if not r.ok]
+
+    def table(self) -> str:
+        fam = defaultdict(lambda: {"calls": set(), "layouts": set(), "worst": 0.0, "checks": 0})
+        for r in self.results:
+            f = fam[r.get("family", r["op"])]
+            f["calls"].add(r["call"])
+            if r.get("layout"):
+                f["layouts"].add(r["layout"])
+            f["checks"] += 1
+            f["worst"] = max(f["worst"], r["worst"])
+        lines = [f"{'family':<24}{'calls':>6}{'checks':>8}  {'worst err/bound':>16}  layouts"]
+        for k in sorted(fam):
+            f = fam[k]
+            lines.append(f"{k:<24}{len(f['calls']):>6}{f['checks']:>8}  {f['worst']:>16.4g}  {','.join(sorted(f['layouts']))}")
+        lines.append(f"ambiguous ReLU masks (bn_bwd mode 2): {self.ambiguous[0]} of {self.ambiguous[1]} elements")
+        return "\n".join(lines)

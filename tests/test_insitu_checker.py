@@ -1,0 +1,273 @@
+"""Power of the in-situ comparator (tests/insitu.py), without a GPU.
+
+"Product" outputs are made with torch at small shapes: f32 arithmetic in another summation order than the float64
+references, rounded to bf16 where the kernels store bf16.  In both modes (elementwise and projected) the comparator
+must pass these honest results and flag each planted fault that applies to the mode -- the subtle ways a kernel of the
+training step goes wrong in situ: a halo shift of one tile, a channel block with its neighbour's weights, a dropped
+split-K partial, a lost tile of a BatchNorm reduction, swapped parity planes of a stride-2 dgrad, a nonzero pad
+channel, a max-pool gradient routed to the wrong tap, a biased running variance.
+"""
+import pytest
+import torch
+import torch.nn.functional as F
+from torch.nn.grad import conv2d_input, conv2d_weight
+
+import insitu
+from insitu import Checker
+
+B, H, W = 2, 32, 48
+CI, CO, CO_PITCH, C2 = 48, 72, 80, 64  # stride-1 layer 48 -> 72 (stored pitch 80), stride-2 layer 48 -> 64
+MOM, EPS = 0.1, 1e-5
+
+
+def _bf(t):
+    return t.to(torch.bfloat16).float()
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2).contiguous()
+
+
+def _store(t_nchw, pitch=None):
+    """f32 NCHW result -> bf16 NHWC stored tensor (pad channels zero)"""
+    o = _nhwc(t_nchw).to(torch.bfloat16)
+    if pitch is not None and pitch > o.shape[-1]:
+        o = F.pad(o, (0, pitch - o.shape[-1]))
+    return o
+
+
+@pytest.fixture(scope="module")
+def case():
+    g = torch.Generator().manual_seed(5)
+    c = {}
+    x = _bf(torch.randn(B, CI, H, W, generator=g))
+    w1 = _bf(torch.randn(CO, CI, 3, 3, generator=g) / 20)
+    w2 = _bf(torch.randn(C2, CI, 3, 3, generator=g) / 20)
+    c.update(x=x, w1=w1, w2=w2)
+    # stride-1 forward (pitch 80 for 72 real channels)
+    c["y1"] = _store(F.conv2d(x, w1, padding=1), CO_PITCH)
+    # stride-2 forward + BatchNorm statistics of its stored output
+    y0 = _store(F.conv2d(x, w2, stride=2, padding=1))
+    v = y0.float().reshape(-1, C2)
+    n = v.shape[0]
+    mean, var = v.mean(0), v.var(0, unbiased=False)
+    rstd = 1.0 / torch.sqrt(var + EPS)
+    gamma = torch.rand(C2, generator=g) * 0.5 + 0.75
+    beta = torch.randn(C2, generator=g) * 0.1
+    rm0, rv0 = torch.randn(C2, generator=g) * 0.1, torch.rand(C2, generator=g) + 0.5
+    scale = gamma * rstd
+    shift = beta - mean * scale
+    c.update(y0=y0, gamma=gamma, beta=beta, rm0=rm0, rv0=rv0, mean=mean, rstd=rstd, scale=scale, shift=shift,
+             rm1=(1 - MOM) * rm0 + MOM * mean, rv1=(1 - MOM) * rv0 + MOM * var * n / (n - 1), var=var, n=n)
+    # BatchNorm + ReLU backward, mask recomputed from the pre-activation (mode 2)
+    dy = _bf(torch.randn(B, H // 2, W // 2, C2, generator=g) * 0.1).to(torch.bfloat16)
+    xf = y0.float()
+    gm = torch.where(xf * scale + shift > 0, dy.float(), torch.zeros(()))
+    xh = (xf - mean) * rstd
+    dbeta = gm.reshape(-1, C2).sum(0)
+    dgamma = (gm * xh).reshape(-1, C2).sum(0)
+    dx = (gamma * rstd * (gm - dbeta / n - xh * dgamma / n)).to(torch.bfloat16)
+    c.update(bdy=dy, bdx=dx, dgamma=dgamma, dbeta=dbeta, gm=gm, xh=xh)
+    # stride-2 dgrad (the zero-insertion call) and stride-1 weight gradient
+    d2 = _bf(torch.randn(B, C2, H // 2, W // 2, generator=g) * 0.1)
+    c.update(d2=_nhwc(d2).to(torch.bfloat16), dx2=_store(conv2d_input((B, CI, H, W), w2, d2, stride=2, padding=1)))
+    d1 = _bf(torch.randn(B, CO, H, W, generator=g) * 0.1)
+    c.update(d1=F.pad(_nhwc(d1), (0, CO_PITCH - CO)).to(torch.bfloat16),
+             dw1=conv2d_weight(x, w1.shape, d1, padding=1), d1_nchw=d1)
+    # max-pool 3x3 s2 p1 forward (first maximal tap in row-major order) and backward with an `add` input
+    xp = torch.randn(B, H, W, 32, generator=g).to(torch.bfloat16)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    pad = F.pad(xp.float(), (0, 0, 1, 1, 1, 1), value=float("-inf"))
+    taps = torch.stack([pad[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] for r in range(3) for s in range(3)])
+    best = taps.max(0).values
+    idx = torch.argmax((taps == best).to(torch.int8), dim=0).to(torch.uint8)
+    pdy = torch.randn(B, Ho, Wo, 32, generator=g).to(torch.bfloat16)
+    add = torch.randn(B, H, W, 32, generator=g).to(torch.bfloat16)
+    c.update(px=xp, pidx=idx, pdy=pdy, padd=add, pdx=_route(pdy, idx, add, H, W))
+    return c
+
+
+def _route(dy, idx, add, H, W):
+    Bn, Ho, Wo, C = dy.shape
+    acc = torch.zeros(Bn, 2 * Ho + 1, 2 * Wo + 1, C)
+    for t in range(9):
+        r, s = divmod(t, 3)
+        acc[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] += torch.where(idx == t, dy.float(), torch.zeros(()))
+    return (acc[:, 1:1 + H, 1:1 + W] + add.float()).to(torch.bfloat16)
+
+
+def _f64(t):
+    return t.to(torch.float64)
+
+
+# --------------------------------------------------------------------------------------------------
+# one entry per checked kernel call: run(checker, case, fault) -> results of that call
+
+def run_fwd(ck, c, fault):
+    y = c["y1"].clone()
+    if fault == "halo":  # one 16x16 tile of the last image read one pixel off
+        ys = _store(F.conv2d(torch.roll(c["x"], 1, dims=3), c["w1"], padding=1), CO_PITCH)
+        y[-1, 16:32, 16:32] = ys[-1, 16:32, 16:32]
+    elif fault == "channel_block":  # output channels 16..31 computed with the weights of 32..47
+        w = c["w1"].clone()
+        w[16:32] = w[32:48]
+        y[..., 16:32] = _store(F.conv2d(c["x"], w, padding=1), CO_PITCH)[..., 16:32]
+    elif fault == "pad_channel":
+        y[0, 3, 5, CO + 3] = 1e-3
+    ck.conv_forward({"op": "conv2d"}, _nhwc(c["x"]).to(torch.bfloat16), _f64(c["w1"]), 1, 1, y)
+
+
+def run_dgrad_s2(ck, c, fault):
+    dx = c["dx2"].clone()
+    if fault == "parity":  # even and odd rows of the zero-insertion dgrad exchanged
+        dx = torch.stack([dx[:, 1::2], dx[:, 0::2]], dim=2).reshape(dx.shape)
+    ck.conv_dgrad({"op": "conv2d"}, c["d2"], _f64(c["w2"]), 2, 1, dx)
+
+
+def run_wgrad(ck, c, fault):
+    dw = c["dw1"].clone()
+    if fault == "split_k":  # image 1 missing from one 16 x 16 (out x in) channel block
+        part = conv2d_weight(c["x"][1:], c["w1"].shape, c["d1_nchw"][1:], padding=1)
+        dw[0:16, 16:32] -= part[0:16, 16:32]
+    ck.conv_wgrad({"op": "conv_wgrad"}, _nhwc(c["x"]).to(torch.bfloat16), c["d1"], 3, 3, 1, 1, dw)
+
+
+def run_bn_stats(ck, c, fault):
+    rv1 = c["rv1"].clone()
+    if fault == "biased_var":
+        rv1 = (1 - MOM) * c["rv0"] + MOM * c["var"]
+    ck.bn_stats({"op": "conv2d_bn_stats"}, c["y0"], c["gamma"], c["beta"], c["rm0"], c["rv0"], c["rm1"], rv1, MOM, EPS,
+                c["scale"], c["shift"], c["mean"], c["rstd"])
+
+
+def run_bn_bwd(ck, c, fault):
+    dgamma = c["dgamma"].clone()
+    if fault == "dgamma_tile":  # channel 5 misses the partial sum of one 16 x 16 tile
+        dgamma[5] -= (c["gm"][0, 0:16, 0:16, 5] * c["xh"][0, 0:16, 0:16, 5]).sum()
+    ck.bn_bwd({"op": "bn_bwd"}, c["y0"], c["bdy"], None, c["gamma"], c["beta"], c["mean"], c["rstd"], True, c["bdx"],
+              None, dgamma, c["dbeta"])
+
+
+def run_maxpool_bwd(ck, c, fault):
+    dx = c["pdx"]
+    if fault == "route":  # one pixel's gradient sent to another tap of its window
+        idx = c["pidx"].clone()
+        idx[1, 5, 7, 3] = (int(idx[1, 5, 7, 3]) + 4) % 9
+        dx = _route(c["pdy"], idx, c["padd"], H, W)
+    ck.maxpool_bwd({"op": "maxpool3x3s2_bwd"}, c["pdy"], c["pidx"], (H, W), c["padd"], dx)
+
+
+CALLS = {"fwd": run_fwd, "dgrad_s2": run_dgrad_s2, "wgrad": run_wgrad, "bn_stats": run_bn_stats, "bn_bwd": run_bn_bwd,
+         "maxpool_bwd": run_maxpool_bwd}
+# fault -> (call it lives in, modes it applies to)
+FAULTS = {
+    "halo": ("fwd", ("full", "proj")),
+    "channel_block": ("fwd", ("full", "proj")),
+    "split_k": ("wgrad", ("full", "proj")),
+    "dgamma_tile": ("bn_bwd", ("full", "proj")),
+    "parity": ("dgrad_s2", ("full", "proj")),
+    "pad_channel": ("fwd", ("full", "proj")),
+    "route": ("maxpool_bwd", ("full",)),
+    "biased_var": ("bn_stats", ("full", "proj")),
+}
+
+
+@pytest.mark.parametrize("mode", ["full", "proj"])
+@pytest.mark.parametrize("call", sorted(CALLS))
+def test_honest_bf16_results_pass(case, mode, call):
+    ck = Checker(mode, chunk=1)
+    CALLS[call](ck, case, None)
+    assert ck.results
+    bad = [r.line() for r in ck.results if not r.ok]
+    assert not bad, bad
+    if call == "bn_bwd":  # mode 2 recomputes the mask: near-ties are counted, never more than the allowed fraction
+        assert ck.ambiguous[0] <= insitu.AMBIG_MAX_FRACTION * ck.ambiguous[1]
+
+
+@pytest.mark.parametrize("fault,mode", [(f, m) for f in sorted(FAULTS) for m in FAULTS[f][1]])
+def test_planted_fault_is_flagged(case, mode, fault):
+    call = FAULTS[fault][0]
+    ck = Checker(mode, chunk=1)
+    CALLS[call](ck, case, fault)
+    bad = [r for r in ck.results if not r.ok]
+    assert bad, f"{fault} passed the {mode} comparator: " + "; ".join(r.line() for r in ck.results)
+
+
+def test_failure_report_locates_the_fault(case):
+    """the worst element and the worst 16x16x16 block name the planted tile"""
+    ck = Checker("full", chunk=1)
+    run_fwd(ck, case, "halo")
+    bad = [r for r in ck.results if not r.ok]
+    assert len(bad) == 1
+    r = bad[0]
+    b, y, x, _ = r["where"]
+    assert b == B - 1 and 16 <= y < 32 and 16 <= x < 32, r.line()
+    assert r["block"][:3] == (B - 1, 16, 16), r.line()
+
+
+def test_ulp_units():
+    t = torch.tensor([1.0, 1.5, 2.0, -3.0, 0.0], dtype=torch.float64)
+    assert insitu.ulp_bf16(t).tolist()[:4] == [2.0 ** -7, 2.0 ** -7, 2.0 ** -6, 2.0 ** -6]
+    assert insitu.ulp_f32(t).tolist()[:3] == [2.0 ** -23, 2.0 ** -23, 2.0 ** -22]
+
+
+def test_honest_elementwise_and_loss_results_pass():
+    """the remaining references of the step: max-pool forward, bn_apply, softmax-CE (loss, dlogits, pred, sums),
+    the dlogits rescale, the input layout change and the confusion-matrix update"""
+    g = torch.Generator().manual_seed(9)
+    ck = Checker("full", chunk=1)
+    x = torch.randn(B, H, W, 32, generator=g).to(torch.bfloat16)
+    x[0, 0, 0, 0] = x[0, 0, 1, 0]  # a tie inside a window
+    pad = F.pad(x.float(), (0, 0, 1, 1, 1, 1), value=float("-inf"))
+    Ho, Wo = H // 2, W // 2
+    taps = torch.stack([pad[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] for r in range(3) for s in range(3)])
+    y = taps.max(0).values.to(torch.bfloat16)
+    idx = torch.argmax((taps == taps.max(0).values).to(torch.int8), dim=0).to(torch.uint8)
+    ck.maxpool_fwd({"op": "maxpool3x3s2_fwd"}, x, y, idx)
+    sc, sh = torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g)
+    res = torch.randn(B, H, W, 32, generator=g).to(torch.bfloat16)
+    ck.bn_apply({"op": "bn_apply"}, x, sc, sh, res, True, torch.relu(x.float() * sc + sh + res.float()).to(torch.bfloat16))
+    K, Cp = 19, 32
+    logits = F.pad(torch.randn(B, H, W, K, generator=g) * 3, (0, Cp - K)).to(torch.bfloat16)
+    t = torch.randint(0, K, (B, H, W), generator=g).to(torch.uint8)
+    cw = torch.tensor([1.0] * 15 + [0.0] * 4)
+    z = logits.float()[..., :K]
+    wp = cw[t.long()]
+    wsum = wp.sum()
+    loss = (wp * (torch.logsumexp(z, -1) - torch.gather(z, -1, t.long().unsqueeze(-1)).squeeze(-1))).sum() / wsum
+    d = F.pad((wp / wsum).unsqueeze(-1) * (torch.softmax(z, -1) - F.one_hot(t.long(), K)), (0, Cp - K)).to(torch.bfloat16)
+    pred = z.argmax(-1).to(torch.uint8)
+    sums = d.float().reshape(-1, Cp).sum(0)
+    ck.softmax_ce({"op": "softmax_ce"}, logits, t, cw, K, None, (loss.reshape(1), wsum.reshape(1), d, pred, sums))
+    ck.scale_inplace({"op": "scale_inplace"}, d, torch.ones(1), d.clone())
+    xin = torch.randn(B, 5, H, W, generator=g)
+    ck.nchw_to_nhwc({"op": "nchw_to_nhwc"}, xin, F.pad(_nhwc(xin), (0, 11)).to(torch.bfloat16))
+    cm = torch.randint(0, 5, (K, K), generator=g)
+    after = cm + torch.bincount(t.reshape(-1).long() * K + pred.reshape(-1).long(), minlength=K * K).view(K, K)
+    ck.confusion({"op": "confusion"}, cm, after, pred, t)
+    bad = [r.line() for r in ck.results if not r.ok]
+    assert len(ck.results) >= 13 and not bad, bad
+    # and each of them notices a wrong value
+    for corrupt in ("y", "loss", "pred", "dlogits_zero_weight", "sums"):
+        ck = Checker("full", chunk=1)
+        y2, loss2, pred2, d2, sums2 = y.clone(), loss.clone(), pred.clone(), d.clone(), sums.clone()
+        if corrupt == "y":
+            y2[1, 3, 4, 5] = y2[1, 3, 4, 6]
+            ck.maxpool_fwd({"op": "maxpool3x3s2_fwd"}, x, y2, idx)
+        else:
+            if corrupt == "loss":
+                loss2 = loss2 * (1 + 1e-4)
+            elif corrupt == "pred":
+                k = int(torch.nonzero(z[0, 0, 0] < z[0, 0, 0].max())[0])
+                pred2[0, 0, 0] = k
+            elif corrupt == "dlogits_zero_weight":
+                p = torch.nonzero(wp == 0)[0]
+                d2[p[0], p[1], p[2], 0] = 2.0 ** -20
+            else:
+                sums2[3] += 1e-3 * sums2.abs().max()
+            ck.softmax_ce({"op": "softmax_ce"}, logits, t, cw, K, None, (loss2.reshape(1), wsum.reshape(1), d2, pred2, sums2))
+        assert any(not r.ok for r in ck.results), corrupt
