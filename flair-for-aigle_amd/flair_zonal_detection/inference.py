@@ -12,8 +12,10 @@ last writer wins -- and moves the per-pixel work onto the GPU:
     scipy nearest zoom (optional)                    0.19 MB per tile; window maths by ffa_write_window
     rasterio window write                            (bit-exact with inference.py:318-335), then the same write
 
-Polygonisation (:359-466, :566-630), geozone loading (:229-252) and COG conversion are product glue outside
-the hot path and are not provided.
+Polygonisation of the written raster (raster_to_polygons, reference :359-413) runs on the GPU as well
+(csrc/polygonize.hip: labelling, boundary edges, ring assembly) with a host topology-preserving simplifier
+(csrc/polygon_simplify.cpp) and a GDAL-free GeoPackage writer (gpkg.py).  Geozone loading (:229-252), clipping /
+reprojection of the polygons (postprocess_results) and COG conversion are product glue and are not provided.
 """
 from __future__ import annotations
 
@@ -373,3 +375,95 @@ def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tu
     inference_and_write(model, loader, tiles, config, outputs, ref_img)
     logger.info("zonal inference of %d tiles took %.1f s", len(tiles), time.time() - t0)
     return outputs
+
+
+def _polygon_source(tiff_path):
+    """The raster raster_to_polygons reads: the reference passes the output_files dict of init_outputs / run_inference
+    and opens its 'AERIAL_LABEL-COSIA' entry (inference.py:389); a lone entry, a path or a raster object also do."""
+    src = tiff_path
+    if isinstance(src, dict):
+        if "AERIAL_LABEL-COSIA" in src:
+            src = src["AERIAL_LABEL-COSIA"]
+        elif len(src) == 1:
+            src = next(iter(src.values()))
+        else:
+            raise KeyError(f"raster_to_polygons: no 'AERIAL_LABEL-COSIA' entry among {sorted(src)}")
+    if isinstance(src, (str, bytes, os.PathLike)):
+        return open_raster(src)
+    from flair_zonal_detection.geotiff import GeoTiffWriter
+    if isinstance(src, GeoTiffWriter) or getattr(src, "mode", "r") != "r":  # an output raster: read the written file
+        path = getattr(src, "path", None) or getattr(src, "name", None)
+        if not getattr(src, "closed", False):
+            raise ValueError(f"raster_to_polygons: {path} is still open for writing; close it first")
+        return open_raster(path)
+    return src
+
+
+def min_pixels_for_area(min_area: float, pixel_area: float) -> int:
+    """Smallest pixel count k with k * pixel_area >= min_area in float64: the components the reference keeps
+    (it drops a polygon when poly.area < min_area)."""
+    if not min_area > 0:
+        return 1
+    k = max(1, int(np.ceil(min_area / pixel_area)))
+    while k > 1 and (k - 1) * pixel_area >= min_area:
+        k -= 1
+    while k * pixel_area < min_area:
+        k += 1
+    return k
+
+
+def raster_to_polygons(tiff_path, ignore_background: bool = True, background_value: int = 18, min_area: float = 1.0,
+                       simplification: float = 0.1, n_jobs: Optional[int] = None):
+    """Vector polygons of a class raster -- the reference's raster_to_polygons (inference.py:377-413) with its
+    signature and call form ``raster_to_polygons(output_files, n_jobs=4)``.
+
+    One polygon per 4-connected component of equal value (what rasterio.features.shapes(mask, mask=mask,
+    connectivity=4) yields per class); every value except ``background_value`` (when ``ignore_background``) is a
+    class -- 0 in never-written areas included, a reference quirk kept on purpose.  A polygon is dropped when its
+    unsimplified area, pixel count * |xres * yres| in float64, is below ``min_area``; the reference computes that area
+    with GEOS's shoelace on absolute coordinates, which can differ only for areas equal to min_area to within about
+    1e-9 relative.  Map coordinates are left + col * xres, top - row * yres in float64 (north-up rasters only).  With
+    ``simplification`` > 0 each polygon is simplified like shapely's simplify(tol, preserve_topology=True)
+    (csrc/polygon_simplify.cpp; not vertex-for-vertex identical to GEOS).  ``n_jobs`` bounds the simplifier's host
+    threads (at most 16).  Labelling and ring assembly run on the GPU (ops.polygonize).
+
+    Returns a GeoDataFrame(class_id, geometry, crs) when geopandas and shapely are importable, else a
+    polygons.PolygonFrame with the same columns, ``crs`` and ``to_file(path, driver="GPKG")``.  Polygons come in
+    (class, first pixel) order, which the reference's process pool does not fix.  Multi-band rasters (class_prob
+    outputs) raise ValueError -- the reference would silently polygonise band 1.
+    """
+    from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
+    src = _polygon_source(tiff_path)
+    if src.count != 1:
+        raise ValueError(f"raster_to_polygons needs a one-band class raster (argmax output), got {src.count} bands")
+    data = np.asarray(src.read(1))
+    if data.dtype != np.uint8:
+        raise ValueError(f"raster_to_polygons: uint8 class raster expected, got {data.dtype}")
+    xres, yres = (float(v) for v in src.res)
+    b = src.bounds
+    left, top = float(b.left if hasattr(b, "left") else b[0]), float(b.top if hasattr(b, "top") else b[3])
+    crs = src.crs
+    min_pixels = min_pixels_for_area(float(min_area), abs(xres * yres))
+    bg = int(background_value) if ignore_background else None
+    if bg is not None and not 0 <= bg <= 255:
+        bg = None  # no uint8 pixel can hold it: every value is a class
+    dev = torch.device("cuda")
+    pc, _, pro, rvo, verts = (t.cpu().numpy() for t in
+                              ops.polygonize(torch.from_numpy(data).to(dev), bg, min_pixels))
+    xy = np.empty(verts.shape, dtype=np.float64)
+    xy[:, 0] = left + verts[:, 0] * xres
+    xy[:, 1] = top - verts[:, 1] * yres
+    if simplification and simplification > 0 and len(pc):
+        threads = max(1, min(16, int(n_jobs) if n_jobs else (os.cpu_count() or 1)))
+        keep = ops.polygon_simplify(xy, rvo, pro, float(simplification), threads)
+        kept_before = np.concatenate([[0], np.cumsum(keep)])
+        rvo = kept_before[rvo].astype(np.int32)
+        xy = xy[keep]
+    flat = FlatPolygons(pc.astype(np.int32), pro.astype(np.int32), rvo.astype(np.int32), xy)
+    try:
+        import geopandas as gpd  # type: ignore
+        from shapely.geometry import Polygon as ShapelyPolygon  # type: ignore
+    except ImportError:
+        return PolygonFrame.from_flat(flat, crs)
+    geoms = [ShapelyPolygon(r[0], r[1:]) for r in (flat.rings(q) for q in range(len(flat)))]
+    return gpd.GeoDataFrame({"class_id": flat.class_id.astype(np.int64), "geometry": geoms}, crs=crs)

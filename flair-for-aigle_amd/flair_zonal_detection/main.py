@@ -89,14 +89,22 @@ def main(argv=None) -> None:
     parser = argparse.ArgumentParser(description="Run zonal detection inference.")
     parser.add_argument("--config", type=str, required=True, help="Path to the detection config file")
     parser.add_argument("--keep-parts", action="store_true", help="sharded runs: keep the per-rank part files")
+    parser.add_argument("--polygons", type=str, default=None, metavar="PATH.gpkg",
+                        help="also polygonise the written class raster (raster_to_polygons with the reference's "
+                             "defaults) and write the polygons as a GeoPackage; sharded runs: rank 0, after the merge")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
-        run_sharded(args.config, int(os.environ.get("RANK", "0")), world, keep_parts=args.keep_parts)
+        outputs = run_sharded(args.config, int(os.environ.get("RANK", "0")), world, keep_parts=args.keep_parts)
     else:
         from flair_zonal_detection.inference import run_inference
-        run_inference(args.config)
+        outputs = run_inference(args.config)
+    if args.polygons and outputs is not None:
+        from flair_zonal_detection.inference import raster_to_polygons
+        gdf = raster_to_polygons(outputs)
+        gdf.to_file(args.polygons, driver="GPKG")
+        logger.info("wrote %d polygons to %s", len(gdf), args.polygons)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,113 @@
+"""Polygon results of raster_to_polygons without geopandas / shapely.
+
+``FlatPolygons`` holds the polygons as flat arrays (class ids, ring offsets per polygon, vertex offsets per ring,
+float64 map coordinates, rings not closed).  ``PolygonFrame`` is the small pandas.DataFrame subclass returned when
+geopandas is not importable: columns ``class_id`` and ``geometry`` like the reference's GeoDataFrame, a ``crs``
+attribute and ``to_file(path, driver="GPKG")``.  Its geometry values are ``Polygon`` views that read the flat arrays
+only when asked (exterior / interiors as closed float64 [n, 2] arrays, ``area``, ``wkb``).
+"""
+from __future__ import annotations
+
+import struct
+from dataclasses import dataclass
+
+import numpy as np
+import pandas as pd
+
+
+@dataclass
+class FlatPolygons:
+    class_id: np.ndarray          # int32 [P]
+    poly_ring_offsets: np.ndarray  # int32 [P + 1]
+    ring_vertex_offsets: np.ndarray  # int32 [R + 1]
+    xy: np.ndarray                # float64 [V, 2]
+
+    def __len__(self) -> int:
+        return len(self.class_id)
+
+    def rings(self, q: int):
+        r0, r1 = int(self.poly_ring_offsets[q]), int(self.poly_ring_offsets[q + 1])
+        return [self.xy[self.ring_vertex_offsets[j]:self.ring_vertex_offsets[j + 1]] for j in range(r0, r1)]
+
+
+def _closed(r: np.ndarray) -> np.ndarray:
+    return np.concatenate([r, r[:1]]) if len(r) else r
+
+
+def _shoelace(r: np.ndarray) -> float:
+    x, y = r[:, 0] - r[0, 0], r[:, 1] - r[0, 1]  # about the first vertex: map coordinates are large
+    return 0.5 * float(np.dot(x, np.roll(y, -1)) - np.dot(np.roll(x, -1), y))
+
+
+class Polygon:
+    """Minimal polygon value: exterior first, holes after (closed float64 arrays, map coordinates)."""
+    __slots__ = ("_store", "_q")
+    geom_type = "Polygon"
+
+    def __init__(self, store: FlatPolygons, q: int):
+        self._store, self._q = store, q
+
+    @property
+    def exterior(self) -> np.ndarray:
+        return _closed(self._store.rings(self._q)[0])
+
+    @property
+    def interiors(self):
+        return [_closed(r) for r in self._store.rings(self._q)[1:]]
+
+    @property
+    def is_empty(self) -> bool:
+        return False
+
+    @property
+    def area(self) -> float:
+        rings = self._store.rings(self._q)
+        return abs(_shoelace(rings[0])) - sum(abs(_shoelace(r)) for r in rings[1:])
+
+    @property
+    def bounds(self):
+        e = self._store.rings(self._q)[0]
+        return (float(e[:, 0].min()), float(e[:, 1].min()), float(e[:, 0].max()), float(e[:, 1].max()))
+
+    @property
+    def wkb(self) -> bytes:
+        rings = [_closed(r) for r in self._store.rings(self._q)]
+        out = [struct.pack("<BII", 1, 3, len(rings))]
+        for r in rings:
+            out.append(struct.pack("<I", len(r)))
+            out.append(np.ascontiguousarray(r, dtype="<f8").tobytes())
+        return b"".join(out)
+
+    def __repr__(self) -> str:
+        rings = self._store.rings(self._q)
+        return f"<Polygon: {len(rings[0])} exterior vertices, {len(rings) - 1} holes>"
+
+
+class PolygonFrame(pd.DataFrame):
+    """DataFrame(class_id, geometry) with ``crs`` and ``to_file`` (GeoPackage only)."""
+    _metadata = ["crs"]
+
+    @property
+    def _constructor(self):
+        return PolygonFrame
+
+    @classmethod
+    def from_flat(cls, flat: FlatPolygons, crs=None) -> "PolygonFrame":
+        geoms = np.empty(len(flat), dtype=object)
+        for q in range(len(flat)):
+            geoms[q] = Polygon(flat, q)
+        df = cls({"class_id": flat.class_id.astype(np.int64), "geometry": geoms})
+        df.crs = crs
+        return df
+
+    def to_file(self, path: str, driver: str = "GPKG", layer=None, **_ignored) -> str:
+        if str(driver).upper() != "GPKG":
+            raise ValueError(f"PolygonFrame.to_file writes GeoPackage only (driver='GPKG'), not {driver!r}")
+        from flair_zonal_detection.gpkg import write_polygons
+
+        def rings_of(g):
+            if isinstance(g, Polygon):
+                return g._store.rings(g._q)
+            return [np.asarray(g.exterior)] + [np.asarray(r) for r in g.interiors]
+        return write_polygons(path, ((int(c), rings_of(g)) for c, g in zip(self["class_id"], self["geometry"])),
+                              crs=self.crs, layer=layer)

@@ -936,6 +936,64 @@ def write_window(left, top, img_bounds, out_res, pred_h: int, pred_w: int):
 
 
 # --------------------------------------------------------------------------------------------------
+# polygonisation of a class raster (csrc/polygonize.hip, csrc/polygon_simplify.cpp)
+
+def polygonize(classes: torch.Tensor, background: Optional[int] = None, min_pixels: int = 1):
+    """Polygons of a device uint8 class map [H, W]: one per 4-connected component of equal class (``background``:
+    that value is no class; None: every value is one), components of fewer than ``min_pixels`` pixels dropped.
+
+    Returns device tensors (poly_class int32 [P], poly_pixels int64 [P], poly_ring_offsets int32 [P + 1],
+    ring_vertex_offsets int32 [R + 1], vertices int32 [V, 2] as (col, row) pixel corners); layout and order as in
+    include/flairhip.h.  The one host synchronisation is the read of the three counts between the two phases."""
+    lib = _l.load()
+    if not (classes.is_cuda and classes.dtype == torch.uint8 and classes.dim() == 2):
+        raise ValueError("polygonize: a CUDA uint8 [H, W] class map expected")
+    if background is not None and not 0 <= int(background) <= 255:
+        raise ValueError(f"polygonize: background {background} is not a uint8 value")
+    H, W = classes.shape
+    if 4 * H * W >= 1 << 31:
+        raise ValueError(f"polygonize: a {H} x {W} raster exceeds the limit 4 * H * W < 2^31 (about 536 Mpx per call)")
+    classes = classes.contiguous()
+    nbytes = lib.ffa_polygonize_workspace_bytes(H, W)
+    if nbytes < 0:
+        _l.check(int(nbytes), "polygonize")
+    dev = classes.device
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    st = _stream()
+    _l.check(lib.ffa_polygonize_label(classes.data_ptr(), H, W, -1 if background is None else int(background),
+                                      int(max(min_pixels, 0)), ws.data_ptr(), int(nbytes), counts.data_ptr(), st),
+             "polygonize_label")
+    P, R, V, _ = (int(v) for v in counts.cpu().tolist())
+    poly_class = torch.empty(P, dtype=torch.int32, device=dev)
+    poly_pixels = torch.empty(P, dtype=torch.int64, device=dev)
+    poly_ring_offsets = torch.empty(P + 1, dtype=torch.int32, device=dev)
+    ring_vertex_offsets = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    vertices = torch.empty((V, 2), dtype=torch.int32, device=dev)
+    _l.check(lib.ffa_polygonize_emit(ws.data_ptr(), int(nbytes), H, W, P, R, V, _ptr(poly_class) if P else None,
+                                     _ptr(poly_pixels) if P else None, poly_ring_offsets.data_ptr(),
+                                     ring_vertex_offsets.data_ptr(), _ptr(vertices) if V else None, st),
+             "polygonize_emit")
+    return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices
+
+
+def polygon_simplify(xy, ring_vertex_offsets, poly_ring_offsets, tolerance: float, n_threads: int = 1):
+    """Host: keep mask (numpy bool [V]) of topology-preserving Douglas-Peucker over float64 coordinates xy [V, 2] in
+    the flat polygon layout of ``polygonize`` (csrc/polygon_simplify.cpp)."""
+    import numpy as np
+    lib = _l.load()
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    rvo = np.ascontiguousarray(ring_vertex_offsets, dtype=np.int32)
+    pro = np.ascontiguousarray(poly_ring_offsets, dtype=np.int32)
+    keep = np.zeros(len(xy), dtype=np.uint8)
+    P = len(pro) - 1
+    if P > 0:
+        _l.check(lib.ffa_polygon_simplify(xy.ctypes.data, rvo.ctypes.data, pro.ctypes.data, P, float(tolerance),
+                                          int(n_threads), keep.ctypes.data), "polygon_simplify")
+    return keep.astype(bool)
+
+
+# --------------------------------------------------------------------------------------------------
 # U-TAE Sentinel branch (flair_hub/models/multitemp_model.py): small kernels around conv2d
 
 def reflect_pad1(x: torch.Tensor) -> torch.Tensor:

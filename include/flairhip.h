@@ -489,6 +489,36 @@ long long ffa_tiff_lzw_encode(const uint8_t* src, long long n, uint8_t* dst, lon
  * horizontal neighbours of one band; undo != 0 accumulates (read), 0 differences (write) */
 int ffa_tiff_hpredict(void* buf, long long rows, long long row_samples, int sample_bytes, int stride, int undo);
 
+/* ---- polygonisation of a class raster (flair_zonal_detection/inference.py raster_to_polygons) ------------------ */
+/* The reference turns the uint8 prediction raster into polygons with rasterio.features.shapes (GDAL's polygonizer) once
+ * per class, 4-connected, then shapely's simplify(preserve_topology=True) (inference.py:359-413).  Here: one polygon per
+ * 4-connected component of equal class (all classes in one pass), pixel-corner vertices as exact integers.
+ * Two phases keep the ABI rules (no synchronisation, caller workspace) although the output size depends on the data:
+ *   1. ffa_polygonize_label runs everything up to the sizes and writes counts_dev[4] (int64, device memory):
+ *      polygons P, rings R, vertices V, boundary edges;
+ *   2. the caller reads the counts, allocates the outputs and calls ffa_polygonize_emit with them (same workspace,
+ *      untouched in between, same stream):
+ *        poly_class[P] (int32), poly_pixels[P] (int64), poly_ring_offsets[P + 1] (int32, rings of polygon q are
+ *        poly_ring_offsets[q] .. [q + 1] - 1), ring_vertex_offsets[R + 1] (int32), vertices[V][2] (int32 col, row).
+ * Polygons are sorted by (class, label = row-major index of the component's first pixel); the first ring of a polygon
+ * is its exterior, then its holes in ring-id order (ring id = the smallest boundary edge id 4 * pixel + side on the
+ * ring); a ring starts at the first direction change at or after its ring-id edge's start corner and is not closed
+ * (no repeated first vertex), has no collinear or repeated vertices and is simple; exteriors are counter-clockwise and
+ * holes clockwise in map coordinates (x = col, y = -row).  A component touching itself diagonally gives an exterior
+ * and a hole that meet at one vertex.  Components with fewer than min_pixels pixels are dropped; background = -1 makes
+ * every value a class.  Deterministic: equal inputs give equal bytes.  Limit: 4 * H * W < 2^31. */
+long long ffa_polygonize_workspace_bytes(int H, int W); /* < 0 (FFA_ERR_ARG) beyond the limit */
+int ffa_polygonize_label(const uint8_t* classes, int H, int W, int background, long long min_pixels, void* ws,
+                         long long ws_bytes, long long* counts_dev, ffa_stream_t stream);
+int ffa_polygonize_emit(const void* ws, long long ws_bytes, int H, int W, long long n_polys, long long n_rings,
+                        long long n_vertices, int32_t* poly_class, int64_t* poly_pixels, int32_t* poly_ring_offsets,
+                        int32_t* ring_vertex_offsets, int32_t* vertices, ffa_stream_t stream);
+/* Host only: topology-preserving Douglas-Peucker (shapely / JTS TopologyPreservingSimplifier semantics within each
+ * polygon; csrc/polygon_simplify.cpp) over float64 map coordinates xy[V][2] laid out as above; keep[V] receives 1 for
+ * the vertices that stay.  tolerance 0 keeps all; n_threads (1 .. 16) splits the polygons between host threads. */
+int ffa_polygon_simplify(const double* xy, const int32_t* ring_offsets, const int32_t* poly_ring_offsets,
+                         long long n_polys, double tolerance, int n_threads, uint8_t* keep);
+
 /* ---- hardware layout probes (tests only) ---------------------------------------------------------- */
 int ffa_probe_tr16(const uint16_t* src, uint16_t* dst, ffa_stream_t stream);
 int ffa_probe_mfma(const float* A, const float* B, float* D, int use_f32, ffa_stream_t stream);

@@ -1,0 +1,148 @@
+"""Polygonisation timings on synthetic class maps (GPU required).
+
+    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3]
+
+Maps: 'voronoi' (blocky nearest-seed map of 19 classes with 2 % label noise), 'checker' (checkerboard: every pixel a
+component, four boundary edges per pixel -- the worst case for edges).  Per map it prints one JSON line with
+  * device time of the label phase and of the emit phase (hip events around each, after a warm-up call),
+  * D2H time of the five output arrays,
+  * host times: float64 map coordinates, simplifier (0.1 m at 0.2 m pixels, 16 threads), object build
+    (PolygonFrame), GeoPackage write,
+  * the counts and a lower bound of the bytes the label phase must move (class map read, labels written and read
+    back, edge arrays), with the time that bound would take at the HBM rate (8 TB/s).
+Per-kernel times: run under `rocprofv3 --kernel-trace --stats -- python tools/bench_polygonize.py`.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "flair-for-aigle_amd")]
+
+HBM_BYTES_PER_S = 8.0e12
+
+
+def voronoi(n: int, seed: int = 0) -> np.ndarray:
+    g = np.random.default_rng(seed)
+    cell = 64
+    k = n // cell + 2
+    jitter = g.integers(0, cell, (k, k, 2))
+    lab = g.integers(0, 19, (k, k)).astype(np.uint8)
+    out = np.zeros((n, n), np.uint8)
+    xx = np.arange(n)[None, :]
+    cx = xx // cell
+    for y0 in range(0, n, 512):  # row blocks keep the temporaries small at 16384^2
+        yy = np.arange(y0, min(n, y0 + 512))[:, None]
+        cy = yy // cell
+        best = np.full((len(yy), n), np.iinfo(np.int64).max)
+        for dy in (0, 1):
+            for dx in (0, 1):
+                sy, sx = np.minimum(cy + dy, k - 1), np.minimum(cx + dx, k - 1)
+                d = (sy * cell + jitter[sy, sx, 0] - yy) ** 2 + (sx * cell + jitter[sy, sx, 1] - xx) ** 2
+                m = d < best
+                best[m] = d[m]
+                out[y0:y0 + len(yy)][m] = lab[sy, sx][m]
+    noise = g.random((n, n), dtype=np.float32) < 0.02
+    out[noise] = g.integers(0, 19, int(noise.sum()), dtype=np.uint8)
+    return out
+
+
+def checker(n: int) -> np.ndarray:
+    return (np.add.outer(np.arange(n), np.arange(n)) % 2).astype(np.uint8)
+
+
+def run(name: str, cls: np.ndarray, reps: int) -> dict:
+    import torch
+    from flairhip import lib as L
+    from flairhip import ops
+    from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
+    lib = L.load()
+    H, W = cls.shape
+    dev = torch.device("cuda")
+    x = torch.from_numpy(cls).to(dev)
+    nbytes = lib.ffa_polygonize_workspace_bytes(H, W)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    res = {"map": name, "H": H, "W": W, "workspace_GB": round(nbytes / 1e9, 3)}
+    t_label, t_emit, t_d2h = [], [], []
+    out = None
+    for rep in range(reps + 1):
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        e0.record()
+        L.check(lib.ffa_polygonize_label(x.data_ptr(), H, W, 18, 1, ws.data_ptr(), int(nbytes), counts.data_ptr(), st))
+        e1.record()
+        P, R, V, E = (int(v) for v in counts.cpu().tolist())
+        bufs = [torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int64, device=dev),
+                torch.empty(P + 1, dtype=torch.int32, device=dev), torch.empty(R + 1, dtype=torch.int32, device=dev),
+                torch.empty((V, 2), dtype=torch.int32, device=dev)]
+        e1b = torch.cuda.Event(enable_timing=True)
+        e1b.record()
+        L.check(lib.ffa_polygonize_emit(ws.data_ptr(), int(nbytes), H, W, P, R, V, bufs[0].data_ptr(),
+                                        bufs[1].data_ptr(), bufs[2].data_ptr(), bufs[3].data_ptr(), bufs[4].data_ptr(),
+                                        st))
+        e2.record()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = [b.cpu().numpy() for b in bufs]
+        t1 = time.perf_counter()
+        if rep:
+            t_label.append(e0.elapsed_time(e1))
+            t_emit.append(e1b.elapsed_time(e2))
+            t_d2h.append((t1 - t0) * 1e3)
+    pc, pp, pro, rvo, verts = out
+    res.update({"polygons": P, "rings": R, "vertices": V, "edges": E,
+                "label_ms": round(min(t_label), 3), "emit_ms": round(min(t_emit), 3), "d2h_ms": round(min(t_d2h), 3)})
+    # bytes the label phase cannot avoid: class map (1 B) + labels written, read by counts / edges (3 x 4 B) per pixel,
+    # then the compacted edge arrays (eid, succ written; ~log2(E) pointer-jumping rounds read 2 x 4 B and write 2 x 4 B)
+    rounds = max(1, int(np.ceil(np.log2(max(4 * H * W, 2)))))
+    lb = H * W * 13 + E * 8 + 2 * rounds * E * 16
+    res["label_bytes_lower_bound_GB"] = round(lb / 1e9, 3)
+    res["label_ms_at_hbm_rate"] = round(lb / HBM_BYTES_PER_S * 1e3, 3)
+    t0 = time.perf_counter()
+    xy = np.empty(verts.shape, np.float64)
+    xy[:, 0] = 651992.36 + verts[:, 0] * 0.2
+    xy[:, 1] = 6860417.84 - verts[:, 1] * 0.2
+    t1 = time.perf_counter()
+    keep = ops.polygon_simplify(xy, rvo, pro, 0.1, 16)
+    t2 = time.perf_counter()
+    before = np.concatenate([[0], np.cumsum(keep)])
+    flat = FlatPolygons(pc, pro, before[rvo].astype(np.int32), xy[keep])
+    frame = PolygonFrame.from_flat(flat, "EPSG:2154")
+    t3 = time.perf_counter()
+    with tempfile.TemporaryDirectory() as d:
+        frame.to_file(os.path.join(d, "p.gpkg"), driver="GPKG")
+        t4 = time.perf_counter()
+        res["gpkg_MB"] = round(os.path.getsize(os.path.join(d, "p.gpkg")) / 1e6, 1)
+    res.update({"coords_ms": round((t1 - t0) * 1e3, 1), "simplify_ms": round((t2 - t1) * 1e3, 1),
+                "objects_ms": round((t3 - t2) * 1e3, 1), "gpkg_ms": round((t4 - t3) * 1e3, 1),
+                "vertices_after_simplify": int(keep.sum())})
+    return res
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[5000, 16384])
+    ap.add_argument("--maps", nargs="+", default=["voronoi", "checker"])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--checker-size", type=int, default=5000)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_polygonize needs an MI355X")
+    if "voronoi" in args.maps:
+        for n in args.sizes:
+            print(json.dumps(run("voronoi", voronoi(n), args.reps)), flush=True)
+    if "checker" in args.maps:
+        print(json.dumps(run("checker", checker(args.checker_size), args.reps)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
