@@ -594,6 +594,70 @@ __global__ __launch_bounds__(kT) void emit_vertices_kernel(const int* n_dev, int
   }
 }
 
+// ---- 7. zonal sums (optional third ABI call) --------------------------------------------------------------------------
+
+constexpr int kZSlots = 1024;  // LDS accumulator slots per block (power of two)
+constexpr int kZProbes = 4;
+
+// sums[polygon of label lab] += v, nothing for labels of dropped components.  polyidx is only written for kept
+// components, so what it holds for lab counts only when poly_label maps that polygon back to lab.
+__device__ __forceinline__ void zonal_flush(int lab, unsigned int v, int P, const int* __restrict__ polyidx,
+                                            const int* __restrict__ poly_label,
+                                            unsigned long long* __restrict__ sums) {
+  const int q = polyidx[lab];
+  if ((unsigned int)q < (unsigned int)P && poly_label[q] == lab) atomicAdd(&sums[q], (unsigned long long)v);
+}
+
+// One block per kChunk consecutive pixels, three levels of partial sums so that a component of millions of pixels
+// costs one 64-bit global atomic per block: (1) segmented wave sum over runs of equal labels (the count_kernel
+// pattern), (2) the run totals meet in an LDS table keyed by label (open addressing, a few probes; a block sums at
+// most kChunk * 255 < 2^32), (3) one global atomic per occupied slot.  A run that finds no slot goes to global memory
+// directly (blocks with thousands of tiny components).  Integer adds only: the result does not depend on the order.
+__global__ __launch_bounds__(kT) void zonal_sum_kernel(int N, int P, const int* __restrict__ L,
+                                                       const uint8_t* __restrict__ values,
+                                                       const int* __restrict__ polyidx,
+                                                       const int* __restrict__ poly_label,
+                                                       unsigned long long* __restrict__ sums) {
+  __shared__ int key[kZSlots];
+  __shared__ unsigned int acc[kZSlots];
+  for (int s = threadIdx.x; s < kZSlots; s += kT) {
+    key[s] = -1;
+    acc[s] = 0u;
+  }
+  __syncthreads();
+  const int lane = lane_id();
+  const long long base = (long long)blockIdx.x * kChunk + threadIdx.x;
+  for (int k = 0; k < kItems; ++k) {  // every lane runs every iteration: the shuffles and the ballot need whole waves
+    const long long p = base + (long long)k * kT;
+    const int lab = p < N ? L[p] : -2;
+    int v = (p < N && lab >= 0) ? (int)values[p] : 0;
+    const int prev = __shfl_up(lab, 1);
+    const bool head = lane == 0 || prev != lab;
+    const unsigned long long heads = __ballot(head);
+    const int end = run_end(heads, lane);
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_down(v, d);
+      if (lane + d < end) v += u;
+    }
+    if (head && lab >= 0) {
+      unsigned int h = ((unsigned int)lab * 2654435761u) >> 22;  // 10 bits = kZSlots
+      bool placed = false;
+      for (int t = 0; t < kZProbes && !placed; ++t) {
+        const int old = atomicCAS(&key[h], -1, lab);
+        if (old == -1 || old == lab) {
+          atomicAdd(&acc[h], (unsigned int)v);
+          placed = true;
+        }
+        h = (h + 1) & (kZSlots - 1);
+      }
+      if (!placed) zonal_flush(lab, (unsigned int)v, P, polyidx, poly_label, sums);
+    }
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < kZSlots; s += kT)
+    if (key[s] >= 0) zonal_flush(key[s], acc[s], P, polyidx, poly_label, sums);
+}
+
 // ---- workspace ----------------------------------------------------------------------------------------------------
 
 struct Layout {
@@ -835,4 +899,24 @@ extern "C" int ffa_polygonize_emit(const void* ws_c, long long ws_bytes, int H, 
                        at<int>(ws, lo.ring_s), at<int>(ws, lo.ring_pos), at<int>(ws, lo.voff), vertices);
   }
   return ffa_check_launch("polygonize_emit");
+}
+
+// Reads the workspace ffa_polygonize_label left (labels, polygon index) and nothing ffa_polygonize_emit writes, so it
+// may run before or after that call; it writes caller memory only.
+extern "C" int ffa_polygonize_zonal_sum_u8(const void* ws_c, long long ws_bytes, int H, int W, const uint8_t* values,
+                                           long long n_polys, int64_t* sums, hipStream_t st) {
+  Layout lo;
+  FFA_REQUIRE(make_layout(H, W, &lo), "polygonize: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
+  FFA_REQUIRE(ws_c && ws_bytes >= lo.total, "polygonize_zonal_sum_u8: workspace missing or too small");
+  FFA_REQUIRE(n_polys >= 0 && n_polys <= lo.N, "polygonize_zonal_sum_u8: %lld polygons are not those of "
+              "ffa_polygonize_label", n_polys);
+  FFA_REQUIRE(values && (n_polys == 0 || sums), "polygonize_zonal_sum_u8: null pointer");
+  if (n_polys == 0) return FFA_OK;
+  void* ws = const_cast<void*>(ws_c);
+  (void)hipMemsetAsync(sums, 0, 8 * n_polys, st);
+  const int N = (int)lo.N;
+  hipLaunchKernelGGL(zonal_sum_kernel, dim3((unsigned int)((lo.N + kChunk - 1) / kChunk)), dim3(kT), 0, st, N,
+                     (int)n_polys, at<int>(ws, lo.L), values, at<int>(ws, lo.polyidx), at<int>(ws, lo.poly_label),
+                     reinterpret_cast<unsigned long long*>(sums));
+  return ffa_check_launch("polygonize_zonal_sum_u8");
 }

@@ -820,21 +820,76 @@ __global__ void class_prob_crop_kernel(const T* __restrict__ logits, uint8_t* __
   }
 }
 
-// mode 0: argmax -> out [B][h][w]; mode 1: class_prob -> out [B][K][h][w]
+// label + confidence in one pass: plane 0 of out [B][2][h][w] is the argmax of argmax_crop_kernel, plane 1 the
+// largest band class_prob_crop_kernel writes for the pixel.  The arithmetic is that kernel's, operation for
+// operation (max, expf(z - m), sum in class order, e / se * 255, rintf), evaluated for the winning class only:
+// expf is monotone, so the band of the maximum logit is the largest band and the two outputs agree bit for bit.
+template <typename T>
+__global__ void label_conf_crop_kernel(const T* __restrict__ logits, uint8_t* __restrict__ out, int B, int H, int W,
+                                       int K, int Cp, int y0, int x0, int h, int w) {
+  const long long total = (long long)B * h * w;
+  const long long plane = (long long)h * w;
+  const int nv = Cp / 8;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % w);
+    long long p = i / w;
+    const int y = (int)(p % h);
+    const long long b = p / h;
+    const T* src = logits + ((b * H + y0 + y) * W + x0 + x) * Cp;
+    float z[FFA_CE_MAXK];
+#pragma unroll
+    for (int v = 0; v < FFA_CE_MAXK / 8; ++v) {
+      if (v < nv) {
+        float tmp[8];
+        ffa_load8<T>(src + v * 8, tmp);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) z[v * 8 + e] = tmp[e];
+      }
+    }
+    float m = -INFINITY, mm = -INFINITY;
+    int am = 0;
+#pragma unroll
+    for (int k = 0; k < FFA_CE_MAXK; ++k)
+      if (k < K) {
+        m = fmaxf(m, z[k]);
+        if (z[k] > mm) {  // strict '>' keeps the lowest index on ties (torch.argmax)
+          mm = z[k];
+          am = k;
+        }
+      }
+    float se = 0.f, top = 0.f;
+#pragma unroll
+    for (int k = 0; k < FFA_CE_MAXK; ++k)
+      if (k < K) {
+        const float e = expf(z[k] - m);
+        se += e;
+        top = fmaxf(top, e);
+      }
+    const long long o = b * 2 * plane + (long long)y * w + x;
+    out[o] = (uint8_t)am;
+    out[o + plane] = (uint8_t)rintf(top / se * 255.f);
+  }
+}
+
+// mode 0: argmax -> out [B][h][w]; mode 1: class_prob -> out [B][K][h][w]; mode 2: argmax + maximum class_prob ->
+// out [B][2][h][w] (label plane, confidence plane)
 extern "C" int ffa_predict_u8(int dtype, int mode, const void* logits, uint8_t* out, int B, int H, int W, int K,
                               int Cp, int y0, int x0, int h, int w, hipStream_t stream) {
   FFA_REQUIRE(logits && out, "predict_u8: null pointer");
   FFA_REQUIRE(K >= 1 && K <= FFA_CE_MAXK && Cp % 8 == 0 && Cp >= K && Cp <= FFA_CE_MAXK,
               "predict_u8: unsupported class count %d (pitch %d)", K, Cp);
   FFA_REQUIRE(y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && y0 + h <= H && x0 + w <= W, "predict_u8: crop outside the tile");
-  FFA_REQUIRE(mode == 0 || mode == 1, "predict_u8: unknown mode %d", mode);
+  FFA_REQUIRE(mode == 0 || mode == 1 || mode == 2, "predict_u8: unknown mode %d", mode);
   const long long items = (long long)B * h * w;
 #define FFA_PRED(KER, TT) \
   hipLaunchKernelGGL(KER<TT>, dim3(ew_grid(items)), dim3(FFA_EW_THREADS), 0, stream, (const TT*)logits, out, B, H, W, K, Cp, y0, x0, h, w)
   if (mode == 0) {
     if (dtype == FFA_BF16) FFA_PRED(argmax_crop_kernel, ffa_bf16); else FFA_PRED(argmax_crop_kernel, float);
-  } else {
+  } else if (mode == 1) {
     if (dtype == FFA_BF16) FFA_PRED(class_prob_crop_kernel, ffa_bf16); else FFA_PRED(class_prob_crop_kernel, float);
+  } else {
+    if (dtype == FFA_BF16) FFA_PRED(label_conf_crop_kernel, ffa_bf16); else FFA_PRED(label_conf_crop_kernel, float);
   }
 #undef FFA_PRED
   return ffa_check_launch("predict_u8");

@@ -18,10 +18,23 @@ def load_config(path: str) -> dict:
         return yaml.safe_load(f)
 
 
+def validate_write_confidence(config: dict) -> bool:
+    """The optional key write_confidence (default false): a second one-band uint8 raster per task that holds
+    rint(255 * max softmax) of every written pixel.  Only legal with output_type argmax."""
+    write_confidence = config.get("write_confidence", False)
+    if not isinstance(write_confidence, bool):
+        raise ValueError(f"write_confidence must be true or false, got {write_confidence!r}")
+    if write_confidence and config.get("output_type", "argmax") != "argmax":
+        raise ValueError("write_confidence needs output_type: argmax (a class_prob raster already holds every "
+                         f"probability), got {config.get('output_type')!r}")
+    return write_confidence
+
+
 def validate_config(config: dict) -> None:
     for key in REQUIRED_KEYS:
         if key not in config:
             raise ValueError(f"Missing required config key: {key}")
+    validate_write_confidence(config)
     if not os.path.isfile(config["model_weights"]):
         raise FileNotFoundError(f"Model weights not found at: {config['model_weights']}")
     os.makedirs(config["output_path"], exist_ok=True)

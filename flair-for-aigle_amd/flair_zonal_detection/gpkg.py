@@ -6,7 +6,8 @@ same kind of file from the flat polygon arrays of ``raster_to_polygons``:
   * ``PRAGMA application_id`` = 0x47504B47 ("GPKG"), ``PRAGMA user_version`` = 10200 (version 1.2.0)
   * ``gpkg_spatial_ref_sys`` with the three mandatory rows (-1 undefined Cartesian, 0 undefined geographic, 4326
     WGS 84) plus one row for the raster's EPSG code, ``gpkg_contents``, ``gpkg_geometry_columns``
-  * one feature table: ``fid`` INTEGER PRIMARY KEY, ``geom`` POLYGON, ``class_id`` INTEGER
+  * one feature table: ``fid`` INTEGER PRIMARY KEY, ``geom`` POLYGON, ``class_id`` INTEGER, then the optional extra
+    attribute columns (``REAL`` for float values, ``INTEGER`` for int values; e.g. ``confidence``, ``pixels``)
   * geometry blobs: the GeoPackage header ("GP", version 0, flags = little endian + [minx, maxx, miny, maxy] envelope,
     srs_id) followed by little-endian WKB (Polygon, rings closed)
 
@@ -108,9 +109,26 @@ def parse_blob(blob: bytes) -> Tuple[int, Tuple[float, ...], list]:
     return srs_id, env, rings
 
 
+def _column_type(name: str, values) -> str:
+    kind = np.asarray(values).dtype.kind
+    if kind == "f":
+        return "REAL"
+    if kind in "iub":
+        return "INTEGER"
+    raise ValueError(f"write_polygons: column {name!r} must hold float or int values, not dtype kind {kind!r}")
+
+
 def write_polygons(path: str, polygons: Iterable[Tuple[int, Sequence[np.ndarray]]], crs=None,
-                   layer: Optional[str] = None) -> str:
-    """Write (class_id, rings) pairs as one POLYGON layer (default name: the file's base name, as OGR does)."""
+                   layer: Optional[str] = None, columns: Optional[dict] = None) -> str:
+    """Write (class_id, rings) pairs as one POLYGON layer (default name: the file's base name, as OGR does).
+    ``columns``: optional {name: values} of extra attribute columns after class_id, one value per polygon, float ->
+    REAL, int -> INTEGER; without it the table is (fid, geom, class_id)."""
+    columns = dict(columns or {})
+    for name in columns:
+        if not (isinstance(name, str) and name.isidentifier()) or name.lower() in ("fid", "geom", "class_id"):
+            raise ValueError(f"write_polygons: {name!r} is not a usable attribute column name")
+    types = {name: _column_type(name, v) for name, v in columns.items()}
+    columns = {name: np.asarray(v).tolist() for name, v in columns.items()}  # Python float / int for sqlite3
     layer = layer or os.path.splitext(os.path.basename(path))[0]
     code = epsg_code(crs)
     srs_id = code if code is not None else -1
@@ -128,7 +146,7 @@ def write_polygons(path: str, polygons: Iterable[Tuple[int, Sequence[np.ndarray]
             srs_rows.append((f"EPSG:{code}", code, "EPSG", code, "undefined", None))
         con.executemany("INSERT INTO gpkg_spatial_ref_sys VALUES (?, ?, ?, ?, ?, ?)", srs_rows)
         con.execute(f'CREATE TABLE "{layer}" (fid INTEGER PRIMARY KEY AUTOINCREMENT NOT NULL, geom POLYGON, '
-                    f'class_id INTEGER)')
+                    f'class_id INTEGER' + "".join(f', "{n}" {t}' for n, t in types.items()) + ')')
         bbox = [np.inf, np.inf, -np.inf, -np.inf]
         rows = []
         for fid, (cid, rings) in enumerate(polygons, start=1):
@@ -136,7 +154,14 @@ def write_polygons(path: str, polygons: Iterable[Tuple[int, Sequence[np.ndarray]
             env = struct.unpack("<4d", blob[8:40])
             bbox = [min(bbox[0], env[0]), min(bbox[1], env[2]), max(bbox[2], env[1]), max(bbox[3], env[3])]
             rows.append((fid, blob, int(cid)))
-        con.executemany(f'INSERT INTO "{layer}" (fid, geom, class_id) VALUES (?, ?, ?)', rows)
+        for name, v in columns.items():
+            if len(v) != len(rows):
+                raise ValueError(f"write_polygons: column {name!r} has {len(v)} values for {len(rows)} polygons")
+        if columns:
+            rows = [r + extra for r, extra in zip(rows, zip(*columns.values()))]
+        names = "".join(f', "{n}"' for n in columns)
+        con.executemany(f'INSERT INTO "{layer}" (fid, geom, class_id{names}) VALUES (?, ?, ?{", ?" * len(columns)})',
+                        rows)
         ext = bbox if rows else [None] * 4
         con.execute("INSERT INTO gpkg_contents VALUES (?, 'features', ?, '', ?, ?, ?, ?, ?, ?)",
                     (layer, layer, LAST_CHANGE, ext[0], ext[1], ext[2], ext[3], srs_id))

@@ -16,6 +16,13 @@ Polygonisation of the written raster (raster_to_polygons, reference :359-413) ru
 (csrc/polygonize.hip: labelling, boundary edges, ring assembly) with a host topology-preserving simplifier
 (csrc/polygon_simplify.cpp) and a GDAL-free GeoPackage writer (gpkg.py).  Geozone loading (:229-252), clipping /
 reprojection of the polygons (postprocess_results) and COG conversion are product glue and are not provided.
+
+Per-polygon confidence (the column the fork's driver fills with random numbers, scripts/
+run_fast_aigle_segmentation.py:162-163, and its unused second path :566-630 means to compute): with the config key
+``write_confidence`` the tile loop writes a second uint8 raster, rint(255 * max softmax) of every pixel, from the same
+kernel pass as the label, and ``raster_to_polygons(..., confidence=...)`` adds the columns ``confidence`` (mean over
+the polygon's pixels, from exact integer sums taken on the GPU) and ``pixels``.  ``logits_to_labels_and_confidence``
+and ``vectorize_segmentation_parallel`` carry the fork's names for that path.
 """
 from __future__ import annotations
 
@@ -30,7 +37,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from flairhip import ops
-from flair_zonal_detection.config import config_recap_1, config_recap_2, load_config, validate_config
+from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_config,
+                                          validate_write_confidence)
 from flair_zonal_detection.dataset import MultiModalSlicedDataset, TileBatcher, pad_series_collate
 from flair_zonal_detection.model_utils import build_inference_model, compute_patch_sizes
 from flair_zonal_detection.postprocess import convert  # noqa: F401  (re-exported like the reference)
@@ -132,9 +140,13 @@ def prep_dataset(config: Dict, tiles_gdf, patch_sizes: Dict[str, int]) -> MultiM
                                    device_normalize=bool(config.get("device_normalize", True)))
 
 
+CONFIDENCE_SUFFIX = "_confidence"  # outputs / paths key of a task's confidence raster: f"{task}_confidence"
+
+
 def init_outputs(config: Dict, ref_img, i=None) -> Tuple[Dict[str, object], Dict[str, str]]:
     """One uint8 output raster per active task (1 band for argmax, K for class_prob), on the reference raster's
-    grid or on an output_px_meters grid when that differs from the reference resolution."""
+    grid or on an output_px_meters grid when that differs from the reference resolution.  With write_confidence a
+    second one-band raster per task, ``<output_name>_<task>_confidence_i.tif``, under the key f"{task}_confidence"."""
     output_type = config["output_type"]
     ref_res = config["reference_resolution"]
     out_res = config.get("output_px_meters", ref_res)
@@ -145,41 +157,44 @@ def init_outputs(config: Dict, ref_img, i=None) -> Tuple[Dict[str, object], Dict
         if not task["active"]:
             continue
         k = len(task["class_names"])
-        count = k if output_type == "class_prob" else 1
         suffix = "argmax" if output_type == "argmax" else "class-prob"
-        path = os.path.join(config["output_path"], f"{config['output_name']}_{task['name']}_{suffix}_i.tif")
-        if config.get("shard") is not None:  # one part file per rank; geotiff.merge_shard_files joins them
-            path = path[:-4] + ".r{}of{}.tif".format(*config["shard"])
+        rasters = [(task["name"], k if output_type == "class_prob" else 1, suffix)]
+        if validate_write_confidence(config):
+            rasters.append((task["name"] + CONFIDENCE_SUFFIX, 1, "confidence"))
         if needs_rescale:
             h = int(round((ib["top"] - ib["bottom"]) / out_res))
             w = int(round((ib["right"] - ib["left"]) / out_res))
         else:
             h, w = ref_img.height, ref_img.width
-        if isinstance(ref_img, ArrayRaster):
-            outputs[task["name"]] = ArrayRaster(np.zeros((count, h, w), np.uint8), ib["left"], ib["top"], out_res,
-                                                ref_img.crs)
-        else:
-            try:
-                import rasterio  # type: ignore
-            except ImportError:
-                rasterio = None
-            # a sharded run joins per-rank part files + "written" masks (geotiff.merge_shard_files): that protocol
-            # belongs to the built-in writer, so it is used for the parts even where rasterio is installed
-            if rasterio is None or config.get("shard") is not None:  # tiled, LZW, written on close()
-                from flair_zonal_detection.geotiff import GeoTiffWriter
-                os.makedirs(config["output_path"], exist_ok=True)
-                outputs[task["name"]] = GeoTiffWriter.like(path, ref_img, count, np.uint8, width=w, height=h,
-                                                           left=ib["left"], top=ib["top"],
-                                                           res=out_res if needs_rescale else ref_img.res)
+        for key, count, suffix in rasters:
+            path = os.path.join(config["output_path"], f"{config['output_name']}_{task['name']}_{suffix}_i.tif")
+            if config.get("shard") is not None:  # one part file per rank; geotiff.merge_shard_files joins them
+                path = path[:-4] + ".r{}of{}.tif".format(*config["shard"])
+            if isinstance(ref_img, ArrayRaster):
+                outputs[key] = ArrayRaster(np.zeros((count, h, w), np.uint8), ib["left"], ib["top"], out_res,
+                                           ref_img.crs)
             else:
-                from rasterio.transform import from_origin  # type: ignore
-                profile = ref_img.profile.copy()
-                profile.update({"count": count, "dtype": "uint8", "compress": "lzw"})
-                if needs_rescale:
-                    profile.update({"driver": "GTiff", "height": h, "width": w,
-                                    "transform": from_origin(ib["left"], ib["top"], out_res, out_res)})
-                outputs[task["name"]] = rasterio.open(path, "w", **profile)
-        paths[task["name"]] = path
+                try:
+                    import rasterio  # type: ignore
+                except ImportError:
+                    rasterio = None
+                # a sharded run joins per-rank part files + "written" masks (geotiff.merge_shard_files): that protocol
+                # belongs to the built-in writer, so it is used for the parts even where rasterio is installed
+                if rasterio is None or config.get("shard") is not None:  # tiled, LZW, written on close()
+                    from flair_zonal_detection.geotiff import GeoTiffWriter
+                    os.makedirs(config["output_path"], exist_ok=True)
+                    outputs[key] = GeoTiffWriter.like(path, ref_img, count, np.uint8, width=w, height=h,
+                                                      left=ib["left"], top=ib["top"],
+                                                      res=out_res if needs_rescale else ref_img.res)
+                else:
+                    from rasterio.transform import from_origin  # type: ignore
+                    profile = ref_img.profile.copy()
+                    profile.update({"count": count, "dtype": "uint8", "compress": "lzw"})
+                    if needs_rescale:
+                        profile.update({"driver": "GTiff", "height": h, "width": w,
+                                        "transform": from_origin(ib["left"], ib["top"], out_res, out_res)})
+                    outputs[key] = rasterio.open(path, "w", **profile)
+            paths[key] = path
     return outputs, paths
 
 
@@ -223,6 +238,10 @@ def inference_and_write(model: torch.nn.Module, dataloader: DataLoader, tiles_gd
     output_type = config["output_type"]
     if output_type not in ("argmax", "class_prob"):
         raise ValueError(f"Unknown output type: {output_type}")
+    # label + confidence: one kernel pass, one [B, 2, h, w] tensor per task through zoom, D2H and window placement, so
+    # the two planes of a pixel always come from the same tile
+    with_conf = validate_write_confidence(config)
+    predict_mode = "argmax_conf" if with_conf else output_type
     ref_res = config["reference_resolution"]
     out_res = config.get("output_px_meters", ref_res)
     needs_rescale = abs(ref_res - out_res) > 1e-6
@@ -247,7 +266,7 @@ def inference_and_write(model: torch.nn.Module, dataloader: DataLoader, tiles_gd
         logits_tasks, _ = model(inputs)
         preds = {}
         for task_name, logits in logits_tasks.items():
-            preds[task_name] = ops.predict_u8(logits._ffa_nhwc, logits._ffa_classes, output_type,
+            preds[task_name] = ops.predict_u8(logits._ffa_nhwc, logits._ffa_classes, predict_mode,
                                               crop=(margin, margin, keep, keep))
         return preds
 
@@ -255,7 +274,7 @@ def inference_and_write(model: torch.nn.Module, dataloader: DataLoader, tiles_gd
         """host side of one batch: window placement + raster writes (reference inference.py:297-352)"""
         for task_name, (buf, done) in host_preds.items():
             done.synchronize()
-            pred = buf[:len(indices)].numpy()  # uint8: [B,h,w] or [B,K,h,w]
+            pred = buf[:len(indices)].numpy()  # uint8: [B,h,w], [B,K,h,w] or [B,2,h,w] (label, confidence)
             for i in range(len(indices)):
                 ti = int(indices[i])
                 p = pred[i]
@@ -265,7 +284,10 @@ def inference_and_write(model: torch.nn.Module, dataloader: DataLoader, tiles_gd
                     continue
                 p = p[..., :win.height, :win.width]
                 window = make_window(win.col_off, win.row_off, win.width, win.height)
-                if output_type == "argmax":
+                if with_conf:
+                    output_files[task_name].write(p[0], 1, window=window)
+                    output_files[task_name + CONFIDENCE_SUFFIX].write(p[1], 1, window=window)
+                elif output_type == "argmax":
                     output_files[task_name].write(p, 1, window=window)
                 else:
                     for c in range(p.shape[0]):
@@ -380,14 +402,23 @@ def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tu
 def _polygon_source(tiff_path):
     """The raster raster_to_polygons reads: the reference passes the output_files dict of init_outputs / run_inference
     and opens its 'AERIAL_LABEL-COSIA' entry (inference.py:389); a lone entry, a path or a raster object also do."""
-    src = tiff_path
-    if isinstance(src, dict):
-        if "AERIAL_LABEL-COSIA" in src:
-            src = src["AERIAL_LABEL-COSIA"]
-        elif len(src) == 1:
-            src = next(iter(src.values()))
-        else:
-            raise KeyError(f"raster_to_polygons: no 'AERIAL_LABEL-COSIA' entry among {sorted(src)}")
+    return _open_polygon_raster(_class_entry(tiff_path)[1])
+
+
+def _class_entry(src):
+    """(key, value) of the class raster in an outputs dict (confidence rasters are not candidates); (None, src) for
+    anything that is not a dict"""
+    if not isinstance(src, dict):
+        return None, src
+    if "AERIAL_LABEL-COSIA" in src:
+        return "AERIAL_LABEL-COSIA", src["AERIAL_LABEL-COSIA"]
+    classes = {k: v for k, v in src.items() if not str(k).endswith(CONFIDENCE_SUFFIX)}
+    if len(classes) == 1:
+        return next(iter(classes.items()))
+    raise KeyError(f"raster_to_polygons: no 'AERIAL_LABEL-COSIA' entry among {sorted(src)}")
+
+
+def _open_polygon_raster(src):
     if isinstance(src, (str, bytes, os.PathLike)):
         return open_raster(src)
     from flair_zonal_detection.geotiff import GeoTiffWriter
@@ -412,8 +443,62 @@ def min_pixels_for_area(min_area: float, pixel_area: float) -> int:
     return k
 
 
+def _bounds4(raster):
+    b = raster.bounds
+    return tuple(float(v) for v in ((b.left, b.bottom, b.right, b.top) if hasattr(b, "left") else tuple(b)[:4]))
+
+
+def _confidence_source(tiff_path, confidence):
+    """The raster behind raster_to_polygons' ``confidence`` argument: True = the f"{task}_confidence" entry of the
+    outputs dict passed as ``tiff_path``; else a raster / path / writer like ``tiff_path`` itself."""
+    if confidence is True:
+        if not isinstance(tiff_path, dict):
+            raise ValueError("raster_to_polygons: confidence=True needs the outputs dict of a write_confidence run")
+        key = _class_entry(tiff_path)[0] + CONFIDENCE_SUFFIX
+        if key not in tiff_path:
+            raise KeyError(f"raster_to_polygons: no {key!r} entry among {sorted(tiff_path)} (write_confidence off?)")
+        confidence = tiff_path[key]
+    elif isinstance(confidence, dict):
+        raise ValueError("raster_to_polygons: confidence must be True, a raster or a path, not a dict")
+    return _open_polygon_raster(confidence)
+
+
+def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, top: float, xres: float, yres: float,
+                   crs, bg: Optional[int], min_pixels: int, simplification: float, n_jobs: Optional[int]):
+    """Shared tail of raster_to_polygons / vectorize_segmentation_parallel: GPU polygonisation (+ zonal sums of the
+    uint8 confidence plane), map coordinates, host simplification, frame."""
+    from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
+    dev = torch.device("cuda")
+    values = None if conf is None else torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
+    res = [t.cpu().numpy() for t in ops.polygonize(torch.from_numpy(np.ascontiguousarray(data)).to(dev), bg,
+                                                   min_pixels, **({} if values is None else {"values": values}))]
+    pc, pix, pro, rvo, verts = res[:5]
+    xy = np.empty(verts.shape, dtype=np.float64)
+    xy[:, 0] = left + verts[:, 0] * xres
+    xy[:, 1] = top - verts[:, 1] * yres
+    if simplification and simplification > 0 and len(pc):
+        threads = max(1, min(16, int(n_jobs) if n_jobs else (os.cpu_count() or 1)))
+        keep = ops.polygon_simplify(xy, rvo, pro, float(simplification), threads)
+        kept_before = np.concatenate([[0], np.cumsum(keep)])
+        rvo = kept_before[rvo].astype(np.int32)
+        xy = xy[keep]
+    flat = FlatPolygons(pc.astype(np.int32), pro.astype(np.int32), rvo.astype(np.int32), xy)
+    columns = {}
+    if conf is not None:
+        pixels = pix.astype(np.int64)
+        # exact integer sum / (255 * pixel count), one float64 division per polygon: a number in [0, 1]
+        columns = {"confidence": res[5].astype(np.int64) / (255.0 * pixels), "pixels": pixels}
+    try:
+        import geopandas as gpd  # type: ignore
+        from shapely.geometry import Polygon as ShapelyPolygon  # type: ignore
+    except ImportError:
+        return PolygonFrame.from_flat(flat, crs, **({"columns": columns} if columns else {}))
+    geoms = [ShapelyPolygon(r[0], r[1:]) for r in (flat.rings(q) for q in range(len(flat)))]
+    return gpd.GeoDataFrame({"class_id": flat.class_id.astype(np.int64), **columns, "geometry": geoms}, crs=crs)
+
+
 def raster_to_polygons(tiff_path, ignore_background: bool = True, background_value: int = 18, min_area: float = 1.0,
-                       simplification: float = 0.1, n_jobs: Optional[int] = None):
+                       simplification: float = 0.1, n_jobs: Optional[int] = None, confidence=None):
     """Vector polygons of a class raster -- the reference's raster_to_polygons (inference.py:377-413) with its
     signature and call form ``raster_to_polygons(output_files, n_jobs=4)``.
 
@@ -431,8 +516,16 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     polygons.PolygonFrame with the same columns, ``crs`` and ``to_file(path, driver="GPKG")``.  Polygons come in
     (class, first pixel) order, which the reference's process pool does not fix.  Multi-band rasters (class_prob
     outputs) raise ValueError -- the reference would silently polygonise band 1.
+
+    ``confidence``: None (the columns above), a confidence raster (path, raster object or closed writer; one band,
+    uint8, the class raster's shape, bounds and resolution, else ValueError) or True = the f"{task}_confidence" entry
+    of the outputs dict a ``write_confidence`` run returned.  Two columns then follow ``class_id``: ``confidence``
+    (float64) = sum of the raster's values over the polygon's pixels / (255.0 * pixels), the mean over the polygon of
+    the winning class's softmax probability as the uint8 raster holds it, and ``pixels`` (int64), the unsimplified
+    pixel count that mean was taken over.  The sums are exact integers taken on the GPU
+    (ffa_polygonize_zonal_sum_u8), so equal rasters give equal columns; geometry, order and class_id do not depend on
+    ``confidence``.
     """
-    from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
     src = _polygon_source(tiff_path)
     if src.count != 1:
         raise ValueError(f"raster_to_polygons needs a one-band class raster (argmax output), got {src.count} bands")
@@ -440,30 +533,96 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     if data.dtype != np.uint8:
         raise ValueError(f"raster_to_polygons: uint8 class raster expected, got {data.dtype}")
     xres, yres = (float(v) for v in src.res)
-    b = src.bounds
-    left, top = float(b.left if hasattr(b, "left") else b[0]), float(b.top if hasattr(b, "top") else b[3])
-    crs = src.crs
+    left, _, _, top = _bounds4(src)
+    conf = None
+    if confidence is not None and confidence is not False:
+        csrc = _confidence_source(tiff_path, confidence)
+        if csrc.count != 1:
+            raise ValueError(f"raster_to_polygons: the confidence raster must have one band, got {csrc.count}")
+        conf = np.asarray(csrc.read(1))
+        if conf.dtype != np.uint8:
+            raise ValueError(f"raster_to_polygons: uint8 confidence raster expected, got {conf.dtype}")
+        if conf.shape != data.shape:
+            raise ValueError(f"raster_to_polygons: confidence raster is {conf.shape}, the class raster {data.shape}")
+        if tuple(float(v) for v in csrc.res) != (xres, yres) or _bounds4(csrc) != _bounds4(src):
+            raise ValueError("raster_to_polygons: the confidence raster's bounds / resolution differ from the class "
+                             f"raster's ({_bounds4(csrc)}, {tuple(csrc.res)} vs {_bounds4(src)}, {(xres, yres)})")
     min_pixels = min_pixels_for_area(float(min_area), abs(xres * yres))
     bg = int(background_value) if ignore_background else None
     if bg is not None and not 0 <= bg <= 255:
         bg = None  # no uint8 pixel can hold it: every value is a class
-    dev = torch.device("cuda")
-    pc, _, pro, rvo, verts = (t.cpu().numpy() for t in
-                              ops.polygonize(torch.from_numpy(data).to(dev), bg, min_pixels))
-    xy = np.empty(verts.shape, dtype=np.float64)
-    xy[:, 0] = left + verts[:, 0] * xres
-    xy[:, 1] = top - verts[:, 1] * yres
-    if simplification and simplification > 0 and len(pc):
-        threads = max(1, min(16, int(n_jobs) if n_jobs else (os.cpu_count() or 1)))
-        keep = ops.polygon_simplify(xy, rvo, pro, float(simplification), threads)
-        kept_before = np.concatenate([[0], np.cumsum(keep)])
-        rvo = kept_before[rvo].astype(np.int32)
-        xy = xy[keep]
-    flat = FlatPolygons(pc.astype(np.int32), pro.astype(np.int32), rvo.astype(np.int32), xy)
-    try:
-        import geopandas as gpd  # type: ignore
-        from shapely.geometry import Polygon as ShapelyPolygon  # type: ignore
-    except ImportError:
-        return PolygonFrame.from_flat(flat, crs)
-    geoms = [ShapelyPolygon(r[0], r[1:]) for r in (flat.rings(q) for q in range(len(flat)))]
-    return gpd.GeoDataFrame({"class_id": flat.class_id.astype(np.int64), "geometry": geoms}, crs=crs)
+    return _polygon_table(data, conf, left, top, xres, yres, src.crs, bg, min_pixels, simplification, n_jobs)
+
+
+def logits_to_labels_and_confidence(probs):
+    """The reference's helper of the same name (inference.py:566-572): per-class scores [K, H, W] (numpy or torch,
+    any real dtype) -> (uint8 labels = argmax over K, first maximum; confidence = max over K in the input's dtype).
+    Thin and off the hot path: the tile loop gets both planes from ffa_predict_u8 mode 2 instead."""
+    if torch.is_tensor(probs):
+        probs = probs.detach().cpu().numpy()
+    probs = np.asarray(probs)
+    if probs.ndim != 3 or probs.shape[0] < 1:
+        raise ValueError(f"logits_to_labels_and_confidence: a [K, H, W] array expected, got shape {probs.shape}")
+    if probs.shape[0] > 256:
+        raise ValueError(f"logits_to_labels_and_confidence: {probs.shape[0]} classes do not fit uint8 labels")
+    return probs.argmax(axis=0).astype(np.uint8), probs.max(axis=0)
+
+
+def _affine6(transform):
+    """(a, b, c, d, e, f) of an affine object with .a .. .f or of a 6-tuple: x = a col + b row + c, y = d col + e row + f"""
+    if all(hasattr(transform, n) for n in "abcdef"):
+        t = tuple(float(getattr(transform, n)) for n in "abcdef")
+    else:
+        try:
+            t = tuple(float(v) for v in transform)
+        except TypeError:
+            raise ValueError("vectorize_segmentation_parallel: transform must be an affine object or a 6-tuple") from None
+        if len(t) != 6:
+            raise ValueError(f"vectorize_segmentation_parallel: a 6-tuple (a, b, c, d, e, f) expected, got {len(t)} values")
+    a, b, c, d, e, f = t
+    if b != 0.0 or d != 0.0 or not a > 0.0 or not e < 0.0:
+        raise ValueError(f"vectorize_segmentation_parallel: north-up transforms only (b = d = 0, a > 0, e < 0), got {t}")
+    return t
+
+
+def quantize_confidence(confidence) -> np.ndarray:
+    """uint8 confidence plane: uint8 input as it is (value / 255 is the probability), float input in [0, 1] as
+    rint(255 c) -- the quantisation the tile loop's confidence raster has."""
+    if torch.is_tensor(confidence):
+        confidence = confidence.detach().cpu().numpy()
+    confidence = np.asarray(confidence)
+    if confidence.dtype == np.uint8:
+        return confidence
+    if confidence.dtype.kind != "f":
+        raise ValueError(f"confidence must be uint8 or float in [0, 1], got {confidence.dtype}")
+    if not np.all((confidence >= 0.0) & (confidence <= 1.0)):  # NaN fails both comparisons
+        raise ValueError("float confidence must lie in [0, 1]")
+    return np.rint(255.0 * confidence.astype(np.float64)).astype(np.uint8)
+
+
+def vectorize_segmentation_parallel(labels, confidence, transform, n_jobs: int = 4, simplification_tolerance: float = 1.0,
+                                    min_area: float = 4.0, crs="EPSG:5490"):
+    """The reference's vectorize_segmentation_parallel (inference.py:606-630) with its argument names and defaults:
+    polygons of a label map [H, W] (uint8; class 0 is the background, :617-618) with the columns ``class_id``,
+    ``confidence``, ``pixels`` and ``geometry`` (frame type as raster_to_polygons).
+
+    ``confidence`` is uint8 (value / 255) or float in [0, 1]; float input is quantised with rint(255 c) first, so the
+    result equals that of the uint8 raster the tile loop writes.  ``transform`` is an affine object with .a .. .f or
+    the 6-tuple (a, b, c, d, e, f), north-up only.  ``n_jobs`` bounds the simplifier's host threads; the polygons of
+    all classes come from one GPU pass, not from a process per class.
+
+    One deliberate departure: the reference takes ``confidence[mask].mean()`` over ALL pixels of a class and gives
+    every polygon of that class the same number (:590-598); here each polygon gets the mean over its own pixels."""
+    if torch.is_tensor(labels):
+        labels = labels.detach().cpu().numpy()
+    labels = np.asarray(labels)
+    if labels.ndim != 2 or labels.dtype != np.uint8:
+        raise ValueError(f"vectorize_segmentation_parallel: uint8 [H, W] labels expected, got {labels.dtype} "
+                         f"{labels.shape}")
+    conf = quantize_confidence(confidence)
+    if conf.shape != labels.shape:
+        raise ValueError(f"vectorize_segmentation_parallel: confidence is {conf.shape}, labels {labels.shape}")
+    a, _, c, _, e, f = _affine6(transform)
+    xres, yres = a, -e
+    min_pixels = min_pixels_for_area(float(min_area), abs(xres * yres))
+    return _polygon_table(labels, conf, c, f, xres, yres, crs, 0, min_pixels, simplification_tolerance, n_jobs)

@@ -91,7 +91,8 @@ def main(argv=None) -> None:
     parser.add_argument("--keep-parts", action="store_true", help="sharded runs: keep the per-rank part files")
     parser.add_argument("--polygons", type=str, default=None, metavar="PATH.gpkg",
                         help="also polygonise the written class raster (raster_to_polygons with the reference's "
-                             "defaults) and write the polygons as a GeoPackage; sharded runs: rank 0, after the merge")
+                             "defaults) and write the polygons as a GeoPackage, with the columns confidence and pixels "
+                             "when the config sets write_confidence; sharded runs: rank 0, after the merge")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -102,7 +103,9 @@ def main(argv=None) -> None:
         outputs = run_inference(args.config)
     if args.polygons and outputs is not None:
         from flair_zonal_detection.inference import raster_to_polygons
-        gdf = raster_to_polygons(outputs)
+        # a write_confidence run also returns f"{task}_confidence" rasters: the polygons then carry their mean
+        with_conf = any(str(k).endswith("_confidence") for k in outputs)
+        gdf = raster_to_polygons(outputs, **({"confidence": True} if with_conf else {}))
         gdf.to_file(args.polygons, driver="GPKG")
         logger.info("wrote %d polygons to %s", len(gdf), args.polygons)
 

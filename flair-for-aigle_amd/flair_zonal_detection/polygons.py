@@ -2,8 +2,9 @@
 
 ``FlatPolygons`` holds the polygons as flat arrays (class ids, ring offsets per polygon, vertex offsets per ring,
 float64 map coordinates, rings not closed).  ``PolygonFrame`` is the small pandas.DataFrame subclass returned when
-geopandas is not importable: columns ``class_id`` and ``geometry`` like the reference's GeoDataFrame, a ``crs``
-attribute and ``to_file(path, driver="GPKG")``.  Its geometry values are ``Polygon`` views that read the flat arrays
+geopandas is not importable: columns ``class_id`` and ``geometry`` like the reference's GeoDataFrame (plus optional
+numeric attribute columns between them, e.g. ``confidence`` and ``pixels``), a ``crs`` attribute and
+``to_file(path, driver="GPKG")``.  Its geometry values are ``Polygon`` views that read the flat arrays
 only when asked (exterior / interiors as closed float64 [n, 2] arrays, ``area``, ``wkb``).
 """
 from __future__ import annotations
@@ -84,7 +85,7 @@ class Polygon:
 
 
 class PolygonFrame(pd.DataFrame):
-    """DataFrame(class_id, geometry) with ``crs`` and ``to_file`` (GeoPackage only)."""
+    """DataFrame(class_id, [numeric attribute columns,] geometry) with ``crs`` and ``to_file`` (GeoPackage only)."""
     _metadata = ["crs"]
 
     @property
@@ -92,11 +93,19 @@ class PolygonFrame(pd.DataFrame):
         return PolygonFrame
 
     @classmethod
-    def from_flat(cls, flat: FlatPolygons, crs=None) -> "PolygonFrame":
+    def from_flat(cls, flat: FlatPolygons, crs=None, columns=None) -> "PolygonFrame":
+        """``columns``: optional {name: array of len(flat)} of float / int attributes, placed after class_id."""
         geoms = np.empty(len(flat), dtype=object)
         for q in range(len(flat)):
             geoms[q] = Polygon(flat, q)
-        df = cls({"class_id": flat.class_id.astype(np.int64), "geometry": geoms})
+        data = {"class_id": flat.class_id.astype(np.int64)}
+        for name, v in (columns or {}).items():
+            v = np.asarray(v)
+            if v.shape != (len(flat),) or v.dtype.kind not in "fiub":
+                raise ValueError(f"PolygonFrame: column {name!r} needs {len(flat)} float or int values")
+            data[name] = v
+        data["geometry"] = geoms
+        df = cls(data)
         df.crs = crs
         return df
 
@@ -109,5 +118,7 @@ class PolygonFrame(pd.DataFrame):
             if isinstance(g, Polygon):
                 return g._store.rings(g._q)
             return [np.asarray(g.exterior)] + [np.asarray(r) for r in g.interiors]
+        extra = {c: self[c].to_numpy() for c in self.columns
+                 if c not in ("class_id", "geometry") and self[c].dtype.kind in "fiub"}
         return write_polygons(path, ((int(c), rings_of(g)) for c, g in zip(self["class_id"], self["geometry"])),
-                              crs=self.crs, layer=layer)
+                              crs=self.crs, layer=layer, **({"columns": extra} if extra else {}))

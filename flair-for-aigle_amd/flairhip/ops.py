@@ -869,22 +869,27 @@ def scale_inplace(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return x
 
 
+_PREDICT_MODES = {"argmax": 0, "class_prob": 1, "argmax_conf": 2}
+
+
 def predict_u8(logits: torch.Tensor, num_classes: int, mode: str = "argmax", crop: Optional[Tuple[int, int, int, int]] = None
                ) -> torch.Tensor:
     """NHWC logits -> uint8 prediction of the cropped window (y0, x0, h, w).
 
     'argmax' -> [B, h, w];  'class_prob' -> [B, K, h, w] = rint(softmax * 255)
-    (flair_zonal_detection/postprocess.py:9-30 semantics; unknown modes raise ValueError like the reference).
+    (flair_zonal_detection/postprocess.py:9-30 semantics; unknown modes raise ValueError like the reference);
+    'argmax_conf' -> [B, 2, h, w]: plane 0 the 'argmax' output, plane 1 the confidence rint(255 * max softmax) = the
+    maximum over the bands of the 'class_prob' output, both bit for bit, from one pass over the logits.
     """
     lib = _l.load()
     _chk_nhwc(logits, "logits")
-    if mode not in ("argmax", "class_prob"):
+    if mode not in _PREDICT_MODES:
         raise ValueError(f"Unknown output type: {mode}")
     B, H, W, cp = logits.shape
     y0, x0, h, w = crop if crop is not None else (0, 0, H, W)
-    shape = (B, h, w) if mode == "argmax" else (B, num_classes, h, w)
+    shape = {"argmax": (B, h, w), "class_prob": (B, num_classes, h, w), "argmax_conf": (B, 2, h, w)}[mode]
     out = torch.empty(shape, dtype=torch.uint8, device=logits.device)
-    _l.check(lib.ffa_predict_u8(_dt(logits), 0 if mode == "argmax" else 1, logits.data_ptr(), out.data_ptr(), B, H, W,
+    _l.check(lib.ffa_predict_u8(_dt(logits), _PREDICT_MODES[mode], logits.data_ptr(), out.data_ptr(), B, H, W,
                                 num_classes, cp, y0, x0, h, w, _stream()), "predict_u8")
     return out
 
@@ -938,19 +943,27 @@ def write_window(left, top, img_bounds, out_res, pred_h: int, pred_w: int):
 # --------------------------------------------------------------------------------------------------
 # polygonisation of a class raster (csrc/polygonize.hip, csrc/polygon_simplify.cpp)
 
-def polygonize(classes: torch.Tensor, background: Optional[int] = None, min_pixels: int = 1):
+def polygonize(classes: torch.Tensor, background: Optional[int] = None, min_pixels: int = 1,
+               values: Optional[torch.Tensor] = None):
     """Polygons of a device uint8 class map [H, W]: one per 4-connected component of equal class (``background``:
     that value is no class; None: every value is one), components of fewer than ``min_pixels`` pixels dropped.
 
     Returns device tensors (poly_class int32 [P], poly_pixels int64 [P], poly_ring_offsets int32 [P + 1],
     ring_vertex_offsets int32 [R + 1], vertices int32 [V, 2] as (col, row) pixel corners); layout and order as in
-    include/flairhip.h.  The one host synchronisation is the read of the three counts between the two phases."""
+    include/flairhip.h.  The one host synchronisation is the read of the three counts between the two phases.
+    With ``values`` (device uint8 [H, W]) a sixth tensor follows: int64 [P], the exact sum of ``values`` over the
+    pixels of each polygon (ffa_polygonize_zonal_sum_u8); the first five are the same bytes either way."""
     lib = _l.load()
     if not (classes.is_cuda and classes.dtype == torch.uint8 and classes.dim() == 2):
         raise ValueError("polygonize: a CUDA uint8 [H, W] class map expected")
     if background is not None and not 0 <= int(background) <= 255:
         raise ValueError(f"polygonize: background {background} is not a uint8 value")
     H, W = classes.shape
+    if values is not None:
+        if not (values.is_cuda and values.dtype == torch.uint8 and tuple(values.shape) == (H, W)
+                and values.device == classes.device):
+            raise ValueError(f"polygonize: values must be a CUDA uint8 [{H}, {W}] tensor on the device of classes")
+        values = values.contiguous()
     if 4 * H * W >= 1 << 31:
         raise ValueError(f"polygonize: a {H} x {W} raster exceeds the limit 4 * H * W < 2^31 (about 536 Mpx per call)")
     classes = classes.contiguous()
@@ -974,7 +987,12 @@ def polygonize(classes: torch.Tensor, background: Optional[int] = None, min_pixe
                                      _ptr(poly_pixels) if P else None, poly_ring_offsets.data_ptr(),
                                      ring_vertex_offsets.data_ptr(), _ptr(vertices) if V else None, st),
              "polygonize_emit")
-    return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices
+    if values is None:
+        return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices
+    sums = torch.empty(P, dtype=torch.int64, device=dev)
+    _l.check(lib.ffa_polygonize_zonal_sum_u8(ws.data_ptr(), int(nbytes), H, W, values.data_ptr(), P,
+                                             _ptr(sums) if P else None, st), "polygonize_zonal_sum_u8")
+    return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices, sums
 
 
 def polygon_simplify(xy, ring_vertex_offsets, poly_ring_offsets, tolerance: float, n_threads: int = 1):

@@ -449,6 +449,10 @@ int ffa_softmax_ce_sums(int dtype, const void* logits, const uint8_t* targets, c
  * dlogits ffa_softmax_ce wrote in the forward pass (for an upstream gradient of 1) when autograd hands the loss a
  * different grad_output -- replaces the second softmax pass torch.autograd would make (tasks_module.py:155). */
 int ffa_scale_inplace(int dtype, void* x, long long n, const float* scale, ffa_stream_t stream);
+/* Margin crop (y0, x0, h, w) + uint8 conversion of NHWC logits [B][H][W][Cp] (K classes, pitch Cp a multiple of 8):
+ * mode 0: out [B][h][w] = argmax (first maximum); mode 1: out [B][K][h][w] = rint(softmax * 255), half to even;
+ * mode 2: out [B][2][h][w] = the argmax plane of mode 0 and a confidence plane = rint(255 * largest softmax
+ * probability), bit for bit the maximum over the K bands mode 1 writes for the pixel, in one pass over the logits. */
 int ffa_predict_u8(int dtype, int mode, const void* logits, uint8_t* out, int B, int H, int W, int K, int Cp, int y0,
                    int x0, int h, int w, ffa_stream_t stream);
 int ffa_onehot_to_index(const float* onehot, uint8_t* idx, int B, int K, int H, int W, ffa_stream_t stream);
@@ -513,6 +517,14 @@ int ffa_polygonize_label(const uint8_t* classes, int H, int W, int background, l
 int ffa_polygonize_emit(const void* ws, long long ws_bytes, int H, int W, long long n_polys, long long n_rings,
                         long long n_vertices, int32_t* poly_class, int64_t* poly_pixels, int32_t* poly_ring_offsets,
                         int32_t* ring_vertex_offsets, int32_t* vertices, ffa_stream_t stream);
+/* Optional, after ffa_polygonize_label on the same untouched workspace and stream, before or after
+ * ffa_polygonize_emit (it reads the labels and the polygon index, which emit leaves alone; the workspace size is
+ * unchanged): sums[q] = the exact sum of values[H][W] (uint8, device) over the pixels of polygon q, in the polygon
+ * order of ffa_polygonize_emit; sums[n_polys] (int64, device) is written, not accumulated.  Background pixels and
+ * components dropped by min_pixels contribute nowhere.  Integer atomics only: equal inputs give equal bytes.
+ * n_polys = counts_dev[0]; with n_polys == 0 nothing is written. */
+int ffa_polygonize_zonal_sum_u8(const void* ws, long long ws_bytes, int H, int W, const uint8_t* values,
+                                long long n_polys, int64_t* sums, ffa_stream_t stream);
 /* Host only: topology-preserving Douglas-Peucker (shapely / JTS TopologyPreservingSimplifier semantics within each
  * polygon; csrc/polygon_simplify.cpp) over float64 map coordinates xy[V][2] laid out as above; keep[V] receives 1 for
  * the vertices that stay.  tolerance 0 keeps all; n_threads (1 .. 16) splits the polygons between host threads. */

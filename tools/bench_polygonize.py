@@ -1,16 +1,20 @@
 """Polygonisation timings on synthetic class maps (GPU required).
 
-    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3]
+    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3] [--confidence]
 
 Maps: 'voronoi' (blocky nearest-seed map of 19 classes with 2 % label noise), 'checker' (checkerboard: every pixel a
-component, four boundary edges per pixel -- the worst case for edges).  Per map it prints one JSON line with
+component, four boundary edges per pixel -- the worst case for edges), 'uniform' (one class: a single component over
+the whole raster, the worst case for contention on one accumulator; on request).  Per map it prints one JSON line with
   * device time of the label phase and of the emit phase (hip events around each, after a warm-up call),
   * D2H time of the five output arrays,
   * host times: float64 map coordinates, simplifier (0.1 m at 0.2 m pixels, 16 threads), object build
     (PolygonFrame), GeoPackage write,
   * the counts and a lower bound of the bytes the label phase must move (class map read, labels written and read
     back, edge arrays), with the time that bound would take at the HBM rate (8 TB/s).
-Per-kernel times: run under `rocprofv3 --kernel-trace --stats -- python tools/bench_polygonize.py`.
+With --confidence the zonal-sum stage (ffa_polygonize_zonal_sum_u8 over a random uint8 plane, after emit) is timed
+as well: "zonal_sum_ms", and the 5 bytes per pixel it must read (label + value) at the HBM rate.
+Per-kernel times (count_kernel, the labelling kernels and zonal_sum_kernel of the same run side by side): run under
+`rocprofv3 --kernel-trace --stats -- python tools/bench_polygonize.py --confidence --device-only`.
 """
 from __future__ import annotations
 
@@ -58,7 +62,7 @@ def checker(n: int) -> np.ndarray:
     return (np.add.outer(np.arange(n), np.arange(n)) % 2).astype(np.uint8)
 
 
-def run(name: str, cls: np.ndarray, reps: int) -> dict:
+def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_only: bool = False) -> dict:
     import torch
     from flairhip import lib as L
     from flairhip import ops
@@ -72,8 +76,9 @@ def run(name: str, cls: np.ndarray, reps: int) -> dict:
     counts = torch.empty(4, dtype=torch.int64, device=dev)
     st = torch.cuda.current_stream().cuda_stream
     res = {"map": name, "H": H, "W": W, "workspace_GB": round(nbytes / 1e9, 3)}
-    t_label, t_emit, t_d2h = [], [], []
+    t_label, t_emit, t_d2h, t_zonal = [], [], [], []
     out = None
+    values = torch.randint(0, 256, (H, W), dtype=torch.uint8, device=dev) if confidence else None
     for rep in range(reps + 1):
         e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         e0.record()
@@ -89,7 +94,15 @@ def run(name: str, cls: np.ndarray, reps: int) -> dict:
                                         bufs[1].data_ptr(), bufs[2].data_ptr(), bufs[3].data_ptr(), bufs[4].data_ptr(),
                                         st))
         e2.record()
+        if confidence:
+            sums = torch.empty(P, dtype=torch.int64, device=dev)
+            e3 = torch.cuda.Event(enable_timing=True)
+            L.check(lib.ffa_polygonize_zonal_sum_u8(ws.data_ptr(), int(nbytes), H, W, values.data_ptr(), P,
+                                                    sums.data_ptr() if P else None, st))
+            e3.record()
         torch.cuda.synchronize()
+        if confidence and rep:
+            t_zonal.append(e2.elapsed_time(e3))
         t0 = time.perf_counter()
         out = [b.cpu().numpy() for b in bufs]
         t1 = time.perf_counter()
@@ -106,6 +119,12 @@ def run(name: str, cls: np.ndarray, reps: int) -> dict:
     lb = H * W * 13 + E * 8 + 2 * rounds * E * 16
     res["label_bytes_lower_bound_GB"] = round(lb / 1e9, 3)
     res["label_ms_at_hbm_rate"] = round(lb / HBM_BYTES_PER_S * 1e3, 3)
+    if confidence:
+        assert int(sums.sum()) == int(values[x != 18].sum(dtype=torch.int64))  # every non-background pixel, once
+        res["zonal_sum_ms"] = round(min(t_zonal), 3)
+        res["zonal_sum_ms_at_hbm_rate"] = round(H * W * 5 / HBM_BYTES_PER_S * 1e3, 3)
+    if device_only:
+        return res
     t0 = time.perf_counter()
     xy = np.empty(verts.shape, np.float64)
     xy[:, 0] = 651992.36 + verts[:, 0] * 0.2
@@ -133,15 +152,21 @@ def main() -> None:
     ap.add_argument("--maps", nargs="+", default=["voronoi", "checker"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--checker-size", type=int, default=5000)
+    ap.add_argument("--confidence", action="store_true", help="also time the zonal-sum stage (per-polygon sums)")
+    ap.add_argument("--device-only", action="store_true",
+                    help="skip the host stages (simplifier, objects, GeoPackage: minutes on the checkerboard)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_polygonize needs an MI355X")
     if "voronoi" in args.maps:
         for n in args.sizes:
-            print(json.dumps(run("voronoi", voronoi(n), args.reps)), flush=True)
+            print(json.dumps(run("voronoi", voronoi(n), args.reps, args.confidence, args.device_only)), flush=True)
+    if "uniform" in args.maps:
+        for n in args.sizes:
+            print(json.dumps(run("uniform", np.full((n, n), 3, np.uint8), args.reps, args.confidence, args.device_only)), flush=True)
     if "checker" in args.maps:
-        print(json.dumps(run("checker", checker(args.checker_size), args.reps)), flush=True)
+        print(json.dumps(run("checker", checker(args.checker_size), args.reps, args.confidence, args.device_only)), flush=True)
 
 
 if __name__ == "__main__":

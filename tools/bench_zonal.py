@@ -1,12 +1,13 @@
 #!/usr/bin/env python
 """Zonal inference throughput on a synthetic in-memory raster.
 
-  python tools/bench_zonal.py [--size 6048] [--batch 8]
+  python tools/bench_zonal.py [--size 6048] [--batch 8] [--write-confidence]
 
 Reports (a) the model forward alone (eval mode: BatchNorm folded into the conv operands, bias / ReLU / decoder
 upsample+concat in conv epilogues / prologues) at the loop's batch size and at 32, and (b) the whole
 run_inference loop: slicing, windowed reads + normalisation (numpy, host), H2D, forward, fused margin-crop + argmax,
-D2H of 1 byte per kept pixel, window placement, writes into the in-memory output raster.
+D2H of 1 byte per kept pixel, window placement, writes into the in-memory output raster.  --write-confidence turns the
+config key write_confidence on: label + confidence from one kernel pass, 2 bytes per kept pixel, two rasters.
 """
 from __future__ import annotations
 
@@ -36,6 +37,8 @@ def main():
     ap.add_argument("--channels", type=int, default=5)
     ap.add_argument("--forward-only", action="store_true", help="skip the tile loop (kernel profiles of the network)")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--write-confidence", action="store_true",
+                    help="run the tile loop with write_confidence: true (argmax output only)")
     args = ap.parse_args()
     from flairhip.configs import unet_resnet34_config
     from flair_hub.models.flair_model import FLAIR_HUB_Model
@@ -75,6 +78,8 @@ def main():
                "output_px_meters": 0.2, "output_type": args.output_type, "batch_size": args.batch, "num_worker": 0,
                "hardware": {"precision": args.precision}, "model_weights": "/tmp/bench_zonal_weights.ckpt",
                "monotemp_arch": args.arch})
+    if args.write_confidence:
+        zc["write_confidence"] = True
     torch.save({"state_dict": {"model." + k: v.cpu() for k, v in model.state_dict().items()}}, zc["model_weights"])
     zc["modalities"][MOD].update({"input_img_path": ras, "channels": list(range(1, C + 1)),
                                   "normalization": {"type": "custom", "means": [110.0] * C, "stds": [50.0] * C}})
