@@ -225,10 +225,12 @@ class FLAIR_HUB_Model(nn.Module):
         hw = (size, size) if isinstance(size, int) else tuple(size)
         return hnn.bilinear(x, hw)
 
-    def _input_nhwc(self, x: torch.Tensor, mod: str, norm=None) -> torch.Tensor:
+    def _input_nhwc(self, x: torch.Tensor, mod: str, norm=None, aug=None) -> torch.Tensor:
         """batch tensor -> NHWC compute tensor.  Besides the reference's normalised f32 [B,C,H,W] tensors, raw raster
         samples (uint8 / uint16 / int16 / float32) are accepted when the batch carries '<MOD>_NORM' = f32 [2,C]
-        (mean, std): the zonal dataset's (x - mean) / std then happens in the layout kernel on the device."""
+        (mean, std): the zonal dataset's (x - mean) / std then happens in the layout kernel on the device.
+        ``aug`` (batch['AUG'], uint8 [B] on the device): the training augmentation's per-sample flip / rotation codes
+        (flairhip.augment), applied by the same pass."""
         enc = self.encoders[mod].seg_model
         if x.ndim != 4 or x.shape[1] != enc.in_channels:
             raise ValueError(f"batch['{mod}'] must be [B,{enc.in_channels},H,W], got {tuple(x.shape)}")
@@ -241,11 +243,17 @@ class FLAIR_HUB_Model(nn.Module):
             if norm is None:
                 raise ValueError(f"batch['{mod}'] is {x.dtype}: batch['{mod}_NORM'] (f32 [2,C]: mean, std) is required")
             norm = norm.to(x.device, torch.float32)
+            if aug is not None:
+                return ops.d4_layout(x.contiguous(), self.compute_dtype, aug, norm[0].contiguous(), norm[1].contiguous(),
+                                     getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
             if x.dtype == torch.uint8:
                 return ops.u8_nchw_to_nhwc(x.contiguous(), self.compute_dtype, norm[0].contiguous(),
                                            norm[1].contiguous(), getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
             return ops.raw_nchw_to_nhwc(x.contiguous(), self.compute_dtype, norm[0].contiguous(), norm[1].contiguous(),
                                         getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
+        if aug is not None:
+            return ops.d4_layout(x.contiguous(), self.compute_dtype, aug,
+                                 cp=getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
         return hnn.to_nhwc(x, self.compute_dtype, getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
 
     def modality_dropout(self, feature_maps: Dict[str, list], modalities_dropout_dict: Dict[str, float]):
@@ -289,6 +297,12 @@ class FLAIR_HUB_Model(nn.Module):
         else:
             img_size = tuple(batch[first_mod].shape[-2:])
 
+        # training augmentation: one flip / rotation code per sample, applied to every modality by its layout pass (the
+        # task applies the same codes to the labels); without the key nothing changes
+        aug = batch.get("AUG")
+        if aug is not None:
+            aug = aug.to(batch[first_mod].device, torch.uint8)
+
         logits_tasks: Dict[str, torch.Tensor] = {}
         logits_aux: Dict[str, torch.Tensor] = {}
 
@@ -309,7 +323,7 @@ class FLAIR_HUB_Model(nn.Module):
         scores: Dict[str, torch.Tensor] = {}  # class scores of the time-series branches (NHWC)
         for mod, encoder in self.encoders.items():
             if mod in self.mono_keys:
-                fmaps[mod] = encoder.seg_model(self._input_nhwc(batch[mod], mod, batch.get(mod + "_NORM")))
+                fmaps[mod] = encoder.seg_model(self._input_nhwc(batch[mod], mod, batch.get(mod + "_NORM"), aug))
                 if self.aux_losses.get(mod):
                     for task in labels:
                         logits_aux[f"aux_{mod}_{task}"] = decode(self.aux_decoders[f"{mod}__{task}"], fmaps[mod], task)
@@ -318,7 +332,7 @@ class FLAIR_HUB_Model(nn.Module):
                 dates = batch.get(mod.replace("TS", "DATES"))
                 if dates is None:
                     raise KeyError(f"batch['{mod.replace('TS', 'DATES')}'] (acquisition dates, [B, T]) is required")
-                s_nhwc, maps, _ = encoder.forward_nhwc(batch[mod], dates)
+                s_nhwc, maps, _ = encoder.forward_nhwc(batch[mod], dates, aug=aug)
                 scores[mod] = self.interpolate_map(s_nhwc, img_size)
                 fmaps[mod] = maps
                 if self.aux_losses.get(mod):

@@ -81,10 +81,16 @@ class SegmentationTask(nn.Module):
         apply_mod_dropout = self.mod_dropout if training else False
         dict_logits_task, dict_logits_aux = self.forward(batch, apply_mod_dropout)
 
+        # training augmentation: the model flipped / rotated every input by batch['AUG'] (flairhip.augment); the labels
+        # take the same codes here, so loss, predictions and metrics all see the transformed pair
+        aug = batch.get("AUG")
+        if aug is not None:
+            aug = aug.to(self.device, torch.uint8)
+
         loss_sum = 0
         all_preds, all_targets = {}, {}
         for task, logits in dict_logits_task.items():
-            targets = HipCrossEntropyLoss.prepare_targets(batch[task].to(self.device))
+            targets = HipCrossEntropyLoss.prepare_targets(batch[task].to(self.device), aug)
             crit = self.criterion[task]
             main_loss = crit(logits, targets)
             self._check_for_invalid_loss(main_loss, task)
@@ -97,6 +103,10 @@ class SegmentationTask(nn.Module):
             all_preds[task] = main_preds
             all_targets[task] = targets
         return loss_sum, all_preds, all_targets
+
+    @staticmethod
+    def _without_aug(batch):
+        return {k: v for k, v in batch.items() if k != "AUG"} if "AUG" in batch else batch
 
     def _compute_aux_loss(self, dict_logits_aux, task, targets):
         # The reference tests `task in dict_logits_aux` against keys 'aux_<mod>_<task>' (tasks_module.py:180),
@@ -149,6 +159,7 @@ class SegmentationTask(nn.Module):
         self.train_loss.reset()
 
     def validation_step(self, batch, batch_idx):
+        batch = self._without_aug(batch)  # validation never augments
         loss, all_preds, all_targets = self.step(batch, training=False)
         self.val_loss.update(loss)
         for task in all_preds:
@@ -176,7 +187,7 @@ class SegmentationTask(nn.Module):
 
     def predict_step(self, batch, batch_idx=0, dataloader_idx=0):
         """{'preds_<task>': argmax(softmax(logits))} -- uint8 class maps straight from the logits kernel."""
-        dict_logits_task, _ = self.forward(batch, apply_mod_dropout=False)
+        dict_logits_task, _ = self.forward(self._without_aug(batch), apply_mod_dropout=False)  # nor does prediction
         out = {}
         for task, logits in dict_logits_task.items():
             nhwc = getattr(logits, "_ffa_nhwc", None)

@@ -69,6 +69,45 @@ class DevicePrefetcher:
             cur = self._stage(next(it, None))  # fetch + copy of batch k+1 overlap step k on the device
 
 
+class AugmentedLoader:
+    """Training loader + ``batch["AUG"]``: one flip / rotation code per sample (flairhip.augment.draw_codes, the
+    reference's use_augmentation draws), a pinned uint8 [B] host tensor that the prefetcher stages like every other
+    entry; the layout and label kernels apply it on the device.  The generator is seeded from (seed, rank, epoch), so
+    ranks draw different transforms and a rerun draws the same.  A batch that already carries "AUG" (a dataset drawing
+    its own, as the reference's does) is left alone."""
+
+    def __init__(self, loader: Iterable, config: Dict[str, Any], seed: int = 0, rank: int = 0):
+        self.loader, self.seed, self.rank, self.epoch = loader, seed, rank, 0
+        mods = config["modalities"]
+        # the entries whose leading dimension is the batch size: labels first, then the active inputs
+        self.keys = list(config.get("labels", [])) + [m for m, on in mods.get("inputs", {}).items() if on]
+
+    def __len__(self) -> int:
+        return len(self.loader)
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = epoch
+        if isinstance(self.loader, ShardedLoader):
+            self.loader.set_epoch(epoch)  # a new shared permutation per epoch, as Lightning does
+
+    def rng(self):
+        from flairhip.augment import rank_epoch_rng
+        return rank_epoch_rng(self.seed, self.rank, self.epoch)
+
+    def __iter__(self):
+        from flairhip.augment import draw_codes
+        rng = self.rng()
+        for batch in self.loader:
+            if "AUG" not in batch:
+                key = next((k for k in self.keys if k in batch and torch.is_tensor(batch[k])), None)
+                if key is None:
+                    raise KeyError("use_augmentation: the batch holds none of the configured labels / inputs")
+                codes = torch.from_numpy(draw_codes(int(batch[key].shape[0]), rng=rng))
+                batch = dict(batch)
+                batch["AUG"] = codes.pin_memory() if torch.cuda.is_available() else codes
+            yield batch
+
+
 class HipTrainer:
     """The subset of pytorch_lightning.Trainer the reference relies on."""
 
@@ -123,6 +162,9 @@ class HipTrainer:
             val_dataloaders = datamodule.val_dataloader() if hasattr(datamodule, "val_dataloader") else None
         train_dataloaders = self._shard(train_dataloaders, drop_last=True)
         val_dataloaders = self._shard(val_dataloaders, shuffle=False, drop_last=False)
+        if model.config.get("modalities", {}).get("pre_processings", {}).get("use_augmentation", False):
+            # flips and rotations by k * 90 degrees, drawn per sample here and applied inside the layout / label kernels
+            train_dataloaders = AugmentedLoader(train_dataloaders, model.config, self.seed, self.rank)
         steps_per_epoch = len(train_dataloaders)
         self.estimated_stepping_batches = self.max_steps or steps_per_epoch * self.max_epochs
 
@@ -151,7 +193,7 @@ class HipTrainer:
         graphed, graph_sig, loss = None, None, None
         for epoch in range(self.max_epochs):
             model.train()
-            if isinstance(train_dataloaders, ShardedLoader):
+            if isinstance(train_dataloaders, (ShardedLoader, AugmentedLoader)):
                 train_dataloaders.set_epoch(epoch)  # a new shared permutation per epoch, as Lightning does
             for i, batch in enumerate(DevicePrefetcher(train_dataloaders, self.device)):
                 if use_graph and graphed is None and model.global_step >= 2:

@@ -143,6 +143,9 @@ SIGNATURES = {
     "ffa_u8_nchw_to_nhwc": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "ffa_raw_nchw_to_nhwc": (_i, [_i, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "ffa_nhwc_to_nchw": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ffa_d4_nchw_to_nhwc": (_i, [_i, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p]),
+    "ffa_d4_labels_u8": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "ffa_d4_onehot_to_index": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "ffa_upsample_nearest2x_concat_fwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ffa_upsample_nearest2x_concat_bwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ffa_bilinear_fwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

@@ -817,7 +817,14 @@ class HipCrossEntropyLoss(nn.Module):
         self.last = {}
 
     @staticmethod
-    def prepare_targets(t: torch.Tensor) -> torch.Tensor:
+    def prepare_targets(t: torch.Tensor, aug: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> contiguous uint8 class indices [B,H,W]; with ``aug`` (uint8 [B] on the device, flairhip.augment) the
+        flipped / rotated ones, from the same single pass"""
+        if aug is not None:
+            if t.ndim == 4:
+                return ops.d4_onehot_to_index(t, aug)
+            return ops.d4_labels(t if (t.dtype == torch.uint8 and t.is_contiguous()) else t.to(torch.uint8).contiguous(),
+                                 aug)
         if t.ndim == 4:  # one-hot NCHW (flair_hub/tasks/tasks_module.py:153)
             return ops.onehot_to_index(t)
         return t if (t.dtype == torch.uint8 and t.is_contiguous()) else t.to(torch.uint8).contiguous()

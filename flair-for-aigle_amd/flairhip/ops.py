@@ -751,6 +751,73 @@ def raw_nchw_to_nhwc(x: torch.Tensor, dtype: torch.dtype, mean: torch.Tensor, st
     return out
 
 
+def _d4_codes(codes: torch.Tensor, n: int, dev, what: str) -> torch.Tensor:
+    """per-sample augmentation codes (flairhip.augment): uint8 [n] on the device.  Only shape and dtype are looked at:
+    the values stay on the device (a captured step replays with new ones)."""
+    if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.ndim != 1 or codes.numel() != n:
+        raise ValueError(f"{what}: codes must be a uint8 vector with one entry per sample ({n})")
+    if codes.device != dev:
+        raise ValueError(f"{what}: codes live on {codes.device}, the data on {dev}")
+    return codes.contiguous()
+
+
+def d4_layout(x: torch.Tensor, dtype: torch.dtype, codes: torch.Tensor, mean: Optional[torch.Tensor] = None,
+              std: Optional[torch.Tensor] = None, cp: Optional[int] = None, group: int = 1) -> torch.Tensor:
+    """nchw_to_nhwc / u8_nchw_to_nhwc / raw_nchw_to_nhwc of the flipped / rotated images in one pass: image b of the
+    contiguous [B,C,n,n] tensor (uint8 / uint16 / int16 with mean and std, float32 with or without) is read through the
+    gather of ``codes[b // group]`` (flairhip.augment.d4_source_index).  Same values, bit for bit, as the plain kernel
+    on a pre-permuted input."""
+    lib = _l.load()
+    if x.dtype not in RAW_SAMPLE_KINDS or x.ndim != 4 or not x.is_contiguous():
+        raise ValueError(f"d4_layout: contiguous [B,C,H,W] of uint8 / uint16 / int16 / float32 expected, "
+                         f"got {x.dtype} {tuple(x.shape)}")
+    B, C_, H, W = x.shape
+    if H != W:
+        raise ValueError(f"d4_layout: rotations need square planes, got {H} x {W}")
+    if group < 1 or B % group:
+        raise ValueError(f"d4_layout: {B} images do not split into groups of {group}")
+    if (mean is None) != (std is None) or (mean is None and x.dtype != torch.float32):
+        raise ValueError("d4_layout: mean and std come together, and integer samples need them")
+    if mean is not None and (mean.numel() < C_ or std.numel() < C_ or mean.dtype != torch.float32 or
+                             std.dtype != torch.float32):
+        raise ValueError("d4_layout: mean / std must be f32 vectors with one entry per channel")
+    codes = _d4_codes(codes, B // group, x.device, "d4_layout")
+    cp = pad_channels(C_) if cp is None else cp
+    out = torch.empty((B, H, W, cp), dtype=dtype, device=x.device)
+    _l.check(lib.ffa_d4_nchw_to_nhwc(_dtype_id(dtype), RAW_SAMPLE_KINDS[x.dtype], x.data_ptr(), out.data_ptr(), B, C_, H,
+                                     W, cp, _ptr(mean), _ptr(std), codes.data_ptr(), group, _stream()), "d4_layout")
+    return out
+
+
+def d4_labels(t: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """uint8 class-index maps [B,n,n] -> the flipped / rotated maps (same gather as d4_layout)"""
+    lib = _l.load()
+    if t.dtype != torch.uint8 or t.ndim != 3 or not t.is_contiguous():
+        raise ValueError("d4_labels: contiguous uint8 [B,H,W] expected")
+    B, H, W = t.shape
+    if H != W:
+        raise ValueError(f"d4_labels: rotations need square planes, got {H} x {W}")
+    codes = _d4_codes(codes, B, t.device, "d4_labels")
+    out = torch.empty_like(t)
+    _l.check(lib.ffa_d4_labels_u8(t.data_ptr(), out.data_ptr(), B, H, W, codes.data_ptr(), _stream()), "d4_labels")
+    return out
+
+
+def d4_onehot_to_index(onehot: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """onehot_to_index (first maximum) of the flipped / rotated one-hot map [B,K,n,n], in one pass"""
+    lib = _l.load()
+    if onehot.dtype != torch.float32 or not onehot.is_contiguous():
+        onehot = onehot.float().contiguous()
+    B, K, H, W = onehot.shape
+    if H != W:
+        raise ValueError(f"d4_onehot_to_index: rotations need square planes, got {H} x {W}")
+    codes = _d4_codes(codes, B, onehot.device, "d4_onehot_to_index")
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=onehot.device)
+    _l.check(lib.ffa_d4_onehot_to_index(onehot.data_ptr(), out.data_ptr(), B, K, H, W, codes.data_ptr(), _stream()),
+             "d4_onehot_to_index")
+    return out
+
+
 def nhwc_to_nchw(x: torch.Tensor, channels: int) -> torch.Tensor:
     lib = _l.load()
     _chk_nhwc(x, "nhwc_to_nchw input")

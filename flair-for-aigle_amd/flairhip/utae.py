@@ -427,11 +427,12 @@ class HipUTAE(nn.Module):
 
     # ---- forward -------------------------------------------------------------------------------------
 
-    def forward_nhwc(self, x: torch.Tensor, batch_positions: torch.Tensor):
+    def forward_nhwc(self, x: torch.Tensor, batch_positions: torch.Tensor, aug: Optional[torch.Tensor] = None):
         """x f32 [B,T,C,H,W], batch_positions [B,T] -> (logits NHWC [B,H,W,pitch], maps NHWC (coarse to fine),
-        attn f32 [n_head,B,T,H,W])"""
+        attn f32 [n_head,B,T,H,W]).  ``aug`` (uint8 [B] on the device): per-sample flip / rotation codes of the training
+        augmentation (flairhip.augment), applied to all T dates of a sample by the layout pass."""
         if self.training and torch.is_grad_enabled():
-            return self._forward_train(x, batch_positions)
+            return self._forward_train(x, batch_positions, aug)
         if self.training:
             raise NotImplementedError("HipUTAE in training mode runs under autograd only (BatchNorm batch statistics "
                                       "and dropout belong to the training step); call .eval() for inference")
@@ -446,7 +447,7 @@ class HipUTAE(nn.Module):
         # Temporal_Aggregator branches on pad_mask.any() (:609) only to skip a multiplication by (~pad_mask): applying the
         # mask always is the same arithmetic and needs no device -> host synchronisation (the step stays graph-capturable)
         any_pad = True
-        cur = ops.nchw_to_nhwc(flat, self.dtype, ops.pad_channels(C))
+        cur = self._layout(flat, C, T, aug)
 
         def shared(t):  # TemporallySharedBlock.smart_forward: padded dates come out as pad_value
             return ops.mask_images_(t, pad, self.pad_value)
@@ -504,7 +505,14 @@ class HipUTAE(nn.Module):
             logits = self._conv_bn(logits, seq, 3 * j, f"o{j}")
         return logits, maps, attn.view(self.n_head, B, T, H, W)
 
-    def _forward_train(self, x: torch.Tensor, batch_positions: torch.Tensor):
+    def _layout(self, flat: torch.Tensor, C: int, T: int, aug: Optional[torch.Tensor]) -> torch.Tensor:
+        """[B*T,C,H,W] f32 -> NHWC compute tensor; with codes, every date of sample b is read through codes[b]'s gather
+        (a padded date is constant, so the pad detection on the unpermuted images holds)"""
+        if aug is None:
+            return ops.nchw_to_nhwc(flat, self.dtype, ops.pad_channels(C))
+        return ops.d4_layout(flat, self.dtype, aug, cp=ops.pad_channels(C), group=T)
+
+    def _forward_train(self, x: torch.Tensor, batch_positions: torch.Tensor, aug: Optional[torch.Tensor] = None):
         """training-mode forward_nhwc through autograd nodes (same return convention)"""
         if not x.is_cuda:
             raise RuntimeError("HipUTAE runs on the MI355X only (no CPU path in the product)")
@@ -515,7 +523,7 @@ class HipUTAE(nn.Module):
         flat = x.reshape(N, C, H, W).float().contiguous()
         pad = ops.detect_pad_images(flat, self.pad_value)
         any_pad = True  # see forward_nhwc: the mask is applied unconditionally (no host synchronisation)
-        cur = ops.nchw_to_nhwc(flat, self.dtype, ops.pad_channels(C))
+        cur = self._layout(flat, C, T, aug)
 
         def gn(t, seq, idx, tag, residual=None):
             conv, nrm = seq[idx], seq[idx + 1]

@@ -415,6 +415,21 @@ int ffa_raw_nchw_to_nhwc(int dtype, int src_kind, const void* src, void* dst, in
                          const float* mean, const float* stdv, ffa_stream_t stream);
 int ffa_nhwc_to_nchw(int dtype, const void* src, float* dst, int B, int C, int H, int W, int Cp, ffa_stream_t stream);
 
+/* ---- training augmentation inside the layout / label passes (flair_hub/data/utils_data/augmentations.py:6-48):
+ *      per-sample flips and rotations by k * 90 degrees as a gather on the read side.  codes: uint8 on the device, one
+ *      per sample, bit 0 horizontal flip, bit 1 vertical flip, bits 2-3 k (masked with 15); the reference's order (flip
+ *      axis -1, flip axis -2, rot90(k)): out[i][j] = in[si][sj], (si, sj) = (i, j), k times (si, sj) <- (sj, n-1-si),
+ *      vflip: si <- n-1-si, hflip: sj <- n-1-sj.  Planes must be square (H == W). */
+/* The work of ffa_nchw_to_nhwc / ffa_u8_nchw_to_nhwc / ffa_raw_nchw_to_nhwc with that gather: src_kind FFA_SRC_*; mean and
+ * stdv both null (FFA_SRC_F32 only) = plain layout without normalisation; image b reads codes[b / group] (group = T for a
+ * [B,T,C,h,w] series viewed as B*T images).  Bit-identical to the plain kernel run on a pre-permuted input. */
+int ffa_d4_nchw_to_nhwc(int dtype, int src_kind, const void* src, void* dst, int B, int C, int H, int W, int Cp,
+                        const float* mean, const float* stdv, const uint8_t* codes, int group, ffa_stream_t stream);
+int ffa_d4_labels_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const uint8_t* codes, ffa_stream_t stream);
+/* ffa_onehot_to_index (first maximum) of the permuted one-hot map */
+int ffa_d4_onehot_to_index(const float* onehot, uint8_t* idx, int B, int K, int H, int W, const uint8_t* codes,
+                           ffa_stream_t stream);
+
 /* ---- decoder resampling (smp DecoderBlock nearest x2 + cat; flair_model.py:318-327 interpolate_map) */
 int ffa_upsample_nearest2x_concat_fwd(int dtype, const void* lo, const void* skip, void* out, int B, int Hl, int Wl,
                                       int C1, int C2, ffa_stream_t stream);

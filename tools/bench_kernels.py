@@ -108,6 +108,10 @@ def bench_bn(args):
     dyp = torch.randn_like(yp)
     add = torch.randn_like(x)
     xin = torch.randn(B, 5, 512, 512, device=dev)
+    xu8 = torch.randint(0, 255, (B, 5, 512, 512), device=dev, dtype=torch.uint8)
+    mu, sd = torch.full((5,), 110.0, device=dev), torch.full((5,), 50.0, device=dev)
+    flip, rot = torch.full((B,), 3, dtype=torch.uint8, device=dev), torch.full((B,), 4, dtype=torch.uint8, device=dev)
+    u8_bytes = xu8.numel() + B * 512 * 512 * 16 * 2
     logits = torch.randn(B, 512, 512, 32, device=dev).to(dt)
     tgt = torch.randint(0, 19, (B, 512, 512), device=dev, dtype=torch.uint8)
     cw = torch.tensor([1.0] * 15 + [0.0] * 4, device=dev)
@@ -116,12 +120,49 @@ def bench_bn(args):
         ("maxpool", "fwd", lambda: ops.maxpool3x3s2_fwd(x), nb + nb // 4 + nb // 8),
         ("maxpool", "bwd+add", lambda: ops.maxpool3x3s2_bwd(dyp, idx, (256, 256), add), 2 * nb + nb // 4 + nb // 8),
         ("layout", "nchw->nhwc", lambda: ops.nchw_to_nhwc(xin, dt), xin.numel() * 4 + B * 512 * 512 * 16 * 2),
+        ("layout", "u8->nhwc", lambda: ops.u8_nchw_to_nhwc(xu8, dt, mu, sd, 16), u8_bytes),
+        # the training augmentation in the same pass (csrc/augment.hip): both flips (even k), a rotation by 90 degrees
+        ("layout", "d4 flips", lambda: ops.d4_layout(xu8, dt, flip, mu, sd, 16), u8_bytes),
+        ("layout", "d4 rot90", lambda: ops.d4_layout(xu8, dt, rot, mu, sd, 16), u8_bytes),
         ("loss", "softmax_ce", lambda: ops.softmax_ce(logits, tgt, cw, 19, want_grad=True, want_pred=True),
          2 * logits.numel() * 2 + 2 * tgt.numel()),
     ]
     for name, kname, fn, nbytes in runs:
         us = timeit(fn, iters=args.iters)
         print(f"{name:10s} {kname:10s} {us:9.1f} {nbytes / us / 1e3:9.0f}")
+
+
+def bench_layout(args):
+    """ops.d4_layout (the layout pass with the training augmentation's gather) per code against the existing
+    u8_nchw_to_nhwc on the flagship input, 32 x 5 x 512 x 512 uint8 -> bf16 pitch 16, same process: us, the ratio to the
+    existing kernel and TB/s of algorithmic bytes (source read once, destination written once); then the label passes"""
+    dev = torch.device("cuda:0")
+    dt = torch.bfloat16
+    x = torch.randint(0, 255, (B, 5, 512, 512), device=dev, dtype=torch.uint8)
+    mu, sd = torch.full((5,), 110.0, device=dev), torch.full((5,), 50.0, device=dev)
+    nbytes = x.numel() + B * 512 * 512 * 16 * 2
+    base = timeit(lambda: ops.u8_nchw_to_nhwc(x, dt, mu, sd, 16), iters=args.iters)
+    print(f"{'kernel':24s} {'us':>9s} {'ratio':>7s} {'TB/s':>7s}")
+    print(f"{'u8_nchw_to_nhwc':24s} {base:9.1f} {1.0:7.2f} {nbytes / base / 1e6:7.2f}")
+    for code in range(16):
+        codes = torch.full((B,), code, dtype=torch.uint8, device=dev)
+        us = timeit(lambda: ops.d4_layout(x, dt, codes, mu, sd, 16), iters=args.iters)
+        name = f"d4_layout code {code:2d} (k={code >> 2}{' v' if code & 2 else ''}{' h' if code & 1 else ''})"
+        print(f"{name:24s} {us:9.1f} {us / base:7.2f} {nbytes / us / 1e6:7.2f}")
+    mixed = torch.arange(B, device=dev).to(torch.uint8) % 16
+    us = timeit(lambda: ops.d4_layout(x, dt, mixed, mu, sd, 16), iters=args.iters)
+    print(f"{'d4_layout mixed codes':24s} {us:9.1f} {us / base:7.2f} {nbytes / us / 1e6:7.2f}")
+    tgt = torch.randint(0, 19, (B, 512, 512), device=dev, dtype=torch.uint8)
+    onehot = torch.nn.functional.one_hot(tgt.long(), 19).permute(0, 3, 1, 2).float().contiguous()
+    base = timeit(lambda: ops.onehot_to_index(onehot), iters=args.iters)
+    print(f"{'onehot_to_index':24s} {base:9.1f} {1.0:7.2f} {(onehot.numel() * 4 + tgt.numel()) / base / 1e6:7.2f}")
+    for label, codes in (("even k", torch.full((B,), 3, dtype=torch.uint8, device=dev)),
+                         ("odd k", torch.full((B,), 4, dtype=torch.uint8, device=dev))):
+        us = timeit(lambda: ops.d4_onehot_to_index(onehot, codes), iters=args.iters)
+        print(f"{'d4_onehot_to_index ' + label:24s} {us:9.1f} {us / base:7.2f} "
+              f"{(onehot.numel() * 4 + tgt.numel()) / us / 1e6:7.2f}")
+        us = timeit(lambda: ops.d4_labels(tgt, codes), iters=args.iters)
+        print(f"{'d4_labels ' + label:24s} {us:9.1f} {'':>7s} {2 * tgt.numel() / us / 1e6:7.2f}")
 
 
 def bench_blas(args):
@@ -154,12 +195,15 @@ def main():
     ap.add_argument("--kinds", default="fwd,dgrad,wgrad")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--bn", action="store_true", help="BatchNorm kernels instead of the convolutions")
+    ap.add_argument("--layout", action="store_true", help="the input layout pass with and without the augmentation gather")
     ap.add_argument("--data", default="randn", choices=["randn", "relu", "zeros"],
                     help="activation values: randn (worst case for power), relu (post-ReLU: half zeros, no "
                          "negative values -- what the network's 3x3 convs actually read), zeros")
     args = ap.parse_args()
     if args.bn:
         return bench_bn(args)
+    if args.layout:
+        return bench_layout(args)
     if args.blas:
         return bench_blas(args)
     dev = torch.device("cuda:0")

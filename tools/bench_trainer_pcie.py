@@ -4,7 +4,12 @@ over, for the reference's batch schema (f32 imagery + f32 one-hot labels, 25 MB 
 the product also accepts (uint8 imagery + '<MOD>_NORM' + uint8 class indices, 1.6 MB per tile).  bench.py's `value`
 has its inputs resident in HBM; this is the number next to it.
 
-  python tools/bench_trainer_pcie.py [--batch 32] [--steps 30]
+  python tools/bench_trainer_pcie.py [--batch 32] [--steps 30] [--schemas compact,reference] [--repeat 1] [--augment]
+
+--augment: the same run with modalities.pre_processings.use_augmentation on (per-sample flips / rotations drawn by the
+trainer, applied inside the layout and label kernels).  --schemas picks the schemas to run and --repeat N runs each N
+times in this process (a fresh model per run): the spread of the number, which a comparison against another commit or
+against --augment has to be read next to.  One JSON line per run, then the box's pinned H2D rate.
 """
 from __future__ import annotations
 
@@ -36,11 +41,12 @@ class Cycle:
             yield self.batches[i % len(self.batches)]
 
 
-def run(schema: str, B: int, steps: int, warm: int = 10):
+def run(schema: str, B: int, steps: int, warm: int = 10, augment: bool = False):
     from flairhip.configs import unet_resnet34_config
     from flair_hub.tasks.module_setup import build_segmentation_module
     from flair_hub.tasks.trainers import HipTrainer
     cfg = unet_resnet34_config(in_channels=5, precision="bf16", batch_size=B, total_steps=steps + warm + 8)
+    cfg["modalities"]["pre_processings"]["use_augmentation"] = bool(augment)
     torch.manual_seed(2025)
     task = build_segmentation_module(cfg, {MOD: 512}, "train")
     g = torch.Generator().manual_seed(1)
@@ -68,7 +74,7 @@ def run(schema: str, B: int, steps: int, warm: int = 10):
     tr = HipTrainer(max_epochs=1, max_steps=warm + steps, hip_graph=True)
     tr.fit(task, train_dataloaders=Cycle(batches, warm + steps + 1))
     dt = marks[warm + steps] - marks[warm]
-    return {"schema": schema, "host_MB_per_batch": round(mb, 1), "ms_per_step": round(dt / steps * 1e3, 3),
+    return {"schema": schema, "augment": bool(augment), "host_MB_per_batch": round(mb, 1), "ms_per_step": round(dt / steps * 1e3, 3),
             "tiles_per_s": round(B * steps / dt, 1), "h2d_GBps_needed": round(mb / 1024 / (dt / steps), 1)}
 
 
@@ -76,9 +82,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--schemas", default="compact,reference")
+    ap.add_argument("--augment", action="store_true", help="use_augmentation on")
+    ap.add_argument("--repeat", type=int, default=1, help="runs per schema (the spread of the number)")
     args = ap.parse_args()
-    for schema in ("compact", "reference"):
-        print(json.dumps(run(schema, args.batch, args.steps)), flush=True)
+    for schema in args.schemas.split(","):
+        for _ in range(args.repeat):
+            print(json.dumps(run(schema, args.batch, args.steps, augment=args.augment)), flush=True)
     # raw H2D rate of this box for scale
     x = torch.empty(1 << 30, dtype=torch.uint8).pin_memory()
     d = torch.empty_like(x, device="cuda")
