@@ -30,11 +30,21 @@ def validate_write_confidence(config: dict) -> bool:
     return write_confidence
 
 
+def validate_skip_tiles_outside_zone(config: dict) -> bool:
+    """The optional key skip_tiles_outside_zone (default false): with a geozone, run_inference drops the tiles whose
+    kept area (grown by a pixel) holds no pixel centre inside the zone contour before the tile loop."""
+    skip = config.get("skip_tiles_outside_zone", False)
+    if not isinstance(skip, bool):
+        raise ValueError(f"skip_tiles_outside_zone must be true or false, got {skip!r}")
+    return skip
+
+
 def validate_config(config: dict) -> None:
     for key in REQUIRED_KEYS:
         if key not in config:
             raise ValueError(f"Missing required config key: {key}")
     validate_write_confidence(config)
+    validate_skip_tiles_outside_zone(config)
     if not os.path.isfile(config["model_weights"]):
         raise FileNotFoundError(f"Model weights not found at: {config['model_weights']}")
     os.makedirs(config["output_path"], exist_ok=True)

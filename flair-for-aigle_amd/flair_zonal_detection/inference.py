@@ -14,8 +14,11 @@ last writer wins -- and moves the per-pixel work onto the GPU:
 
 Polygonisation of the written raster (raster_to_polygons, reference :359-413) runs on the GPU as well
 (csrc/polygonize.hip: labelling, boundary edges, ring assembly) with a host topology-preserving simplifier
-(csrc/polygon_simplify.cpp) and a GDAL-free GeoPackage writer (gpkg.py).  Geozone loading (:229-252), clipping /
-reprojection of the polygons (postprocess_results) and COG conversion are product glue and are not provided.
+(csrc/polygon_simplify.cpp) and a GDAL-free GeoPackage writer (gpkg.py).  Clipping to the geozone and the class filter
+of the fork's postprocess_results happen on the pixel grid before polygonisation (``raster_to_polygons(zone=, classes=)``,
+csrc/zone_mask.hip, zone.py), and with the config key ``skip_tiles_outside_zone`` the tile loop leaves out the tiles
+that hold no zone pixel.  Reprojection of the zone or the polygons and COG conversion are product glue and are not
+provided.
 
 Per-polygon confidence (the column the fork's driver fills with random numbers, scripts/
 run_fast_aigle_segmentation.py:162-163, and its unused second path :566-630 means to compute): with the config key
@@ -38,7 +41,7 @@ from torch.utils.data import DataLoader
 
 from flairhip import ops
 from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_config,
-                                          validate_write_confidence)
+                                          validate_skip_tiles_outside_zone, validate_write_confidence)
 from flair_zonal_detection.dataset import MultiModalSlicedDataset, TileBatcher, pad_series_collate
 from flair_zonal_detection.model_utils import build_inference_model, compute_patch_sizes
 from flair_zonal_detection.postprocess import convert  # noqa: F401  (re-exported like the reference)
@@ -360,11 +363,42 @@ def merge_shard_outputs(outputs_by_rank):
     return merged
 
 
+def tile_zone_windows(tiles, left: float, top: float, xres: float, yres: float) -> np.ndarray:
+    """int64 [n, 4] pixel rectangles (r0, c0, r1, c1) of the tiles' kept bounds on the grid anchored at (left, top):
+    snapped outward and grown by one pixel on every side (not clamped: ops.zone_window_counts clamps)."""
+    tl, tb, tr, tt = (np.asarray(tiles[k], dtype=np.float64) for k in ("left", "bottom", "right", "top"))
+    win = np.empty((len(tl), 4), dtype=np.int64)
+    win[:, 0] = np.floor((top - tt) / yres) - 1
+    win[:, 1] = np.floor((tl - left) / xres) - 1
+    win[:, 2] = np.ceil((top - tb) / yres) + 1
+    win[:, 3] = np.ceil((tr - left) / xres) + 1
+    return win
+
+
+def drop_tiles_outside_zone(tiles, ref_img, geozone):
+    """The tiles whose kept area can hold a zone pixel (config key skip_tiles_outside_zone).  The zone is rasterised on
+    the reference raster's grid (pixel centre inside the contour) and counted per tile over the kept bounds snapped
+    outward and grown by a pixel, so a dropped tile cannot have written a zone pixel whatever output rescaling or
+    the clamping of the last row / column does: inside the zone the rasters equal those of the full run."""
+    from flair_zonal_detection.zone import zone_mask
+    b = ref_img.bounds
+    left, top = float(b.left), float(b.top)
+    xres, yres = (float(v) for v in ref_img.res)
+    H, W = int(ref_img.shape[0]), int(ref_img.shape[1])
+    mask = zone_mask(geozone, left, top, xres, yres, H, W)
+    counts = ops.zone_window_counts(mask, tile_zone_windows(tiles, left, top, xres, yres)).cpu().numpy()
+    keep = counts > 0
+    logger.info("%d of %d tiles outside the zone skipped", int((~keep).sum()), len(keep))
+    return tiles[keep].reset_index(drop=True)
+
+
 def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tuple[int, int]] = None,
                   before_loop=None) -> Dict[str, object]:
     """End-to-end zonal run with upstream FLAIR-HUB's one-argument semantics (the fork's own run_inference is
     stale: inference.py:650-665 calls its helpers with the wrong arity).  Returns the output rasters.
-    ``shard=(rank, world)`` (or config['shard']) restricts the run to that rank's slice of the tile grid: one process
+    ``geozone`` (any form zone.zone_rings reads, in the raster's CRS) restricts the tile grid to its bounding box;
+    with the config key ``skip_tiles_outside_zone: true`` the tiles holding no pixel of the zone are dropped as well
+    (drop_tiles_outside_zone).  ``shard=(rank, world)`` (or config['shard']) restricts the run to that rank's slice of the tile grid: one process
     per GPU, no communication; in-memory outputs then track their writes for merge_shard_outputs.  ``before_loop``
     (optional) is called with the freshly initialised outputs before the first tile is processed."""
     t0 = time.time()
@@ -372,6 +406,8 @@ def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tu
     ref_path = config["modalities"][config["reference_modality"]]["input_img_path"]
     ref_img = ref_raster if ref_raster is not None else open_raster(ref_path)
     tiles = generate_patches_from_reference(config, ref_img, geozone)
+    if validate_skip_tiles_outside_zone(config) and geozone is not None and len(tiles):
+        tiles = drop_tiles_outside_zone(tiles, ref_img, geozone)
     shard = shard if shard is not None else config.get("shard")
     if shard is not None:
         config["shard"] = (int(shard[0]), int(shard[1]))
@@ -464,14 +500,32 @@ def _confidence_source(tiff_path, confidence):
 
 
 def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, top: float, xres: float, yres: float,
-                   crs, bg: Optional[int], min_pixels: int, simplification: float, n_jobs: Optional[int]):
-    """Shared tail of raster_to_polygons / vectorize_segmentation_parallel: GPU polygonisation (+ zonal sums of the
+                   crs, bg: Optional[int], min_pixels: int, simplification: float, n_jobs: Optional[int],
+                   zone=None, classes=None):
+    """Shared tail of raster_to_polygons / vectorize_segmentation_parallel: zone clip and class filter on the device
+    copy of the raster (one ffa_zone_clip_u8 pass, only when asked for), GPU polygonisation (+ zonal sums of the
     uint8 confidence plane), map coordinates, host simplification, frame."""
     from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
     dev = torch.device("cuda")
     values = None if conf is None else torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
-    res = [t.cpu().numpy() for t in ops.polygonize(torch.from_numpy(np.ascontiguousarray(data)).to(dev), bg,
-                                                   min_pixels, **({} if values is None else {"values": values}))]
+    cls_dev = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+    if zone is not None or classes is not None:
+        keep = None if classes is None else sorted({int(c) for c in classes})
+        if keep is not None and not all(0 <= c <= 255 for c in keep):
+            raise ValueError(f"raster_to_polygons: class ids must be uint8 values, got {keep}")
+        if bg is None:
+            # every value is a class, so there is no background to reuse: 255 stands in, unless the raster needs it
+            bg = 255
+            if (keep is None or 255 in keep) and bool((data == 255).any()):
+                raise ValueError("raster_to_polygons: with ignore_background=False the zone / class filter uses 255 as "
+                                 "the fill value, but the raster holds 255 in a kept class")
+        mask = None
+        if zone is not None:
+            from flair_zonal_detection.zone import zone_mask
+            mask = zone_mask(zone, left, top, xres, yres, data.shape[0], data.shape[1])
+        ops.zone_clip_(cls_dev, mask, keep_classes=keep, fill=bg)
+    res = [t.cpu().numpy() for t in ops.polygonize(cls_dev, bg, min_pixels,
+                                                   **({} if values is None else {"values": values}))]
     pc, pix, pro, rvo, verts = res[:5]
     xy = np.empty(verts.shape, dtype=np.float64)
     xy[:, 0] = left + verts[:, 0] * xres
@@ -498,7 +552,8 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
 
 
 def raster_to_polygons(tiff_path, ignore_background: bool = True, background_value: int = 18, min_area: float = 1.0,
-                       simplification: float = 0.1, n_jobs: Optional[int] = None, confidence=None):
+                       simplification: float = 0.1, n_jobs: Optional[int] = None, confidence=None, zone=None,
+                       classes=None):
     """Vector polygons of a class raster -- the reference's raster_to_polygons (inference.py:377-413) with its
     signature and call form ``raster_to_polygons(output_files, n_jobs=4)``.
 
@@ -525,6 +580,16 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     pixel count that mean was taken over.  The sums are exact integers taken on the GPU
     (ffa_polygonize_zonal_sum_u8), so equal rasters give equal columns; geometry, order and class_id do not depend on
     ``confidence``.
+
+    ``zone``: a geozone in the raster's CRS (any form zone.zone_rings reads: GeoJSON dict or file, objects with
+    ``__geo_interface__``, bounds, sequences of those).  It is rasterised on the class raster's own grid -- a pixel
+    belongs to the zone when its centre is inside the contour, as rasterio.mask.mask means it -- and pixels outside
+    take the background value before polygonisation: the fork's ``intersection(contour_union)`` to within half a
+    pixel, with integer vertices and valid rings kept.  ``classes``: an iterable of class ids; only those are
+    polygonised (the fork's ``class_id == 6`` filter).  Both are one pass on the GPU copy of the raster
+    (ffa_zone_clip_u8); the confidence sums need no change since background pixels contribute nowhere.  With
+    ``ignore_background=False`` there is no background value to reuse: 255 is the fill, and a raster that holds 255
+    in a kept class raises ValueError.  With ``zone=None, classes=None`` nothing changes.
     """
     src = _polygon_source(tiff_path)
     if src.count != 1:
@@ -551,7 +616,8 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     bg = int(background_value) if ignore_background else None
     if bg is not None and not 0 <= bg <= 255:
         bg = None  # no uint8 pixel can hold it: every value is a class
-    return _polygon_table(data, conf, left, top, xres, yres, src.crs, bg, min_pixels, simplification, n_jobs)
+    return _polygon_table(data, conf, left, top, xres, yres, src.crs, bg, min_pixels, simplification, n_jobs,
+                          zone=zone, classes=classes)
 
 
 def logits_to_labels_and_confidence(probs):
@@ -612,7 +678,10 @@ def vectorize_segmentation_parallel(labels, confidence, transform, n_jobs: int =
     all classes come from one GPU pass, not from a process per class.
 
     One deliberate departure: the reference takes ``confidence[mask].mean()`` over ALL pixels of a class and gives
-    every polygon of that class the same number (:590-598); here each polygon gets the mean over its own pixels."""
+    every polygon of that class the same number (:590-598); here each polygon gets the mean over its own pixels.
+
+    The signature is the reference's and stays so: clipping to a geozone and the class filter are arguments of
+    raster_to_polygons (``zone=``, ``classes=``)."""
     if torch.is_tensor(labels):
         labels = labels.detach().cpu().numpy()
     labels = np.asarray(labels)

@@ -49,10 +49,11 @@ def _wait_for(paths, timeout_s: float, newer_than: float = 0.0) -> None:
         time.sleep(0.2)
 
 
-def run_sharded(config, rank: int, world: int, timeout_s: float = 3600.0, keep_parts: bool = False
+def run_sharded(config, rank: int, world: int, timeout_s: float = 3600.0, keep_parts: bool = False, geozone=None
                 ) -> Optional[Dict[str, str]]:
     """This rank's share of a zonal run over ``world`` processes (one per GPU).  Rank 0 returns {task: merged path}
-    once every rank's part file exists; the other ranks return None as soon as their own part is written."""
+    once every rank's part file exists; the other ranks return None as soon as their own part is written.
+    ``geozone`` is passed on to run_inference (every rank slices and filters the same tile grid)."""
     import torch
     from flair_zonal_detection.geotiff import WRITTEN_SUFFIX, GeoTiffWriter, merge_shard_files
     from flair_zonal_detection.inference import run_inference
@@ -62,7 +63,7 @@ def run_sharded(config, rank: int, world: int, timeout_s: float = 3600.0, keep_p
     # --keep-parts) run left under the same names must not be mistaken for this run's: every rank removes its own
     # part + mask before it starts, and rank 0 only accepts parts at least as new as its own start.
     t_start = time.time()
-    outputs = run_inference(config, shard=(rank, world), before_loop=_remove_stale_parts)
+    outputs = run_inference(config, geozone=geozone, shard=(rank, world), before_loop=_remove_stale_parts)
     for task, o in outputs.items():
         if not isinstance(o, GeoTiffWriter):
             raise TypeError("a sharded multi-process run needs file outputs (GeoTIFF paths), not in-memory rasters")
@@ -93,19 +94,31 @@ def main(argv=None) -> None:
                         help="also polygonise the written class raster (raster_to_polygons with the reference's "
                              "defaults) and write the polygons as a GeoPackage, with the columns confidence and pixels "
                              "when the config sets write_confidence; sharded runs: rank 0, after the merge")
+    parser.add_argument("--zone", type=str, default=None, metavar="PATH.geojson",
+                        help="geozone contour (GeoJSON, in the raster's CRS): only its bounding box is sliced (and, with "
+                             "skip_tiles_outside_zone in the config, only the tiles that hold a zone pixel are inferred); "
+                             "with --polygons the polygons are clipped to the contour")
+    parser.add_argument("--classes", type=str, default=None, metavar="ID[,ID...]",
+                        help="with --polygons: polygonise these class ids only, e.g. 6,7")
     args = parser.parse_args(argv)
+    try:
+        classes = None if args.classes is None else [int(c) for c in args.classes.split(",") if c.strip()]
+    except ValueError:
+        parser.error(f"--classes expects comma-separated integers, got {args.classes!r}")
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
-        outputs = run_sharded(args.config, int(os.environ.get("RANK", "0")), world, keep_parts=args.keep_parts)
+        outputs = run_sharded(args.config, int(os.environ.get("RANK", "0")), world, keep_parts=args.keep_parts,
+                              geozone=args.zone)
     else:
         from flair_zonal_detection.inference import run_inference
-        outputs = run_inference(args.config)
+        outputs = run_inference(args.config, geozone=args.zone)
     if args.polygons and outputs is not None:
         from flair_zonal_detection.inference import raster_to_polygons
         # a write_confidence run also returns f"{task}_confidence" rasters: the polygons then carry their mean
         with_conf = any(str(k).endswith("_confidence") for k in outputs)
-        gdf = raster_to_polygons(outputs, **({"confidence": True} if with_conf else {}))
+        extra = {k: v for k, v in (("zone", args.zone), ("classes", classes)) if v is not None}
+        gdf = raster_to_polygons(outputs, **({"confidence": True} if with_conf else {}), **extra)
         gdf.to_file(args.polygons, driver="GPKG")
         logger.info("wrote %d polygons to %s", len(gdf), args.polygons)
 

@@ -45,9 +45,16 @@ def _zone_bounds(src, geozone) -> Optional[Tuple[float, float, float, float]]:
         gb = geozone.bounds
     elif isinstance(geozone, Sequence) and len(geozone) == 4 and all(isinstance(v, (int, float)) for v in geozone):
         gb = tuple(geozone)
-    else:  # iterable of geometries
-        bs = [g.bounds for g in geozone]
-        gb = (min(b[0] for b in bs), min(b[1] for b in bs), max(b[2] for b in bs), max(b[3] for b in bs))
+    else:
+        geoms = None
+        if not isinstance(geozone, (str, bytes, os.PathLike, dict)) and not hasattr(geozone, "__geo_interface__"):
+            geoms = list(geozone)
+        if geoms is not None and all(hasattr(g, "bounds") for g in geoms):  # iterable of geometries
+            bs = [g.bounds for g in geoms]
+            gb = (min(b[0] for b in bs), min(b[1] for b in bs), max(b[2] for b in bs), max(b[3] for b in bs))
+        else:  # GeoJSON dicts, files, __geo_interface__ objects, nested sequences (zone.zone_rings)
+            from flair_zonal_detection.zone import zone_bounds
+            gb = zone_bounds(geozone if geoms is None else geoms)
     h, w = src.shape[0], src.shape[1]
     c0 = max(0, math.floor((gb[0] - rb.left) / res))
     c1 = min(w, math.ceil((gb[2] - rb.left) / res))

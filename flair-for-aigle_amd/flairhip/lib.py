@@ -169,6 +169,10 @@ SIGNATURES = {
     "ffa_polygonize_emit": (_i, [_p, _ll, _i, _i, _ll, _ll, _ll, _p, _p, _p, _p, _p, _p]),
     "ffa_polygonize_zonal_sum_u8": (_i, [_p, _ll, _i, _i, _p, _ll, _p, _p]),
     "ffa_polygon_simplify": (_i, [_p, _p, _p, _ll, _d, _i, _p]),
+    "ffa_zone_mask_workspace_bytes": (_ll, [_i, _i, _ll]),
+    "ffa_zone_mask_u8": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _ll, _p]),
+    "ffa_zone_clip_u8": (_i, [_p, _p, _p, _ll, _i, _p]),
+    "ffa_zone_window_counts": (_i, [_p, _i, _i, _p, _i, _p, _p]),
     "ffa_probe_tr16": (_i, [_p, _p, _p]),
     "ffa_probe_mfma": (_i, [_p, _p, _p, _i, _p]),
 }

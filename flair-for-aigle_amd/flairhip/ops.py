@@ -1079,6 +1079,99 @@ def polygon_simplify(xy, ring_vertex_offsets, poly_ring_offsets, tolerance: floa
 
 
 # --------------------------------------------------------------------------------------------------
+# geozone clipping on the pixel grid (csrc/zone_mask.hip)
+
+ZONE_WORKSPACE_SLOT = "zone_mask"
+
+
+def rasterize_zone(rings_pix, ring_offsets, H: int, W: int, out: Optional[torch.Tensor] = None,
+                   accumulate: bool = False) -> torch.Tensor:
+    """Inside mask (device uint8 [H, W], 0 / 1) of polygon rings given in pixel coordinates: float64 [V, 2] pairs
+    (px, py), ring k = vertices ring_offsets[k] .. ring_offsets[k + 1] - 1.  A pixel is inside when its centre is,
+    even-odd over all rings of the call (holes are further rings); the exact rule is in include/flairhip.h.  With
+    ``accumulate`` the result is ORed into ``out`` (union of several polygons, one call each); otherwise ``out`` is
+    overwritten, or allocated on the current device when None."""
+    import numpy as np
+    lib = _l.load()
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"rasterize_zone: raster {H} x {W} outside 1 <= H, W")
+    xy = rings_pix.detach().cpu().numpy() if torch.is_tensor(rings_pix) else np.asarray(rings_pix)
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    ro = ring_offsets.detach().cpu().numpy() if torch.is_tensor(ring_offsets) else np.asarray(ring_offsets)
+    ro = np.ascontiguousarray(ro, dtype=np.int64).reshape(-1)
+    if len(ro) < 1 or ro[0] != 0 or ro[-1] != len(xy) or np.any(np.diff(ro) < 0):
+        raise ValueError(f"rasterize_zone: ring_offsets must rise from 0 to the vertex count {len(xy)}, got {ro.tolist()}")
+    if not np.all(np.isfinite(xy)):
+        raise ValueError("rasterize_zone: non-finite ring coordinate")
+    if accumulate and out is None:
+        raise ValueError("rasterize_zone: accumulate needs the mask to accumulate into (out=)")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+    elif not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (H, W) and out.is_contiguous()):
+        raise ValueError(f"rasterize_zone: out must be a contiguous CUDA uint8 [{H}, {W}] tensor")
+    dev = out.device
+    n_rings = len(ro) - 1
+    nbytes = lib.ffa_zone_mask_workspace_bytes(H, W, len(xy))
+    if nbytes < 0:
+        _l.check(int(nbytes), "rasterize_zone")
+    ws = workspace(int(nbytes), dev, ZONE_WORKSPACE_SLOT)
+    xy_d = torch.from_numpy(xy).to(dev) if len(xy) else None
+    ro_d = torch.from_numpy(ro.astype(np.int32)).to(dev)
+    _l.check(lib.ffa_zone_mask_u8(_ptr(xy_d), ro_d.data_ptr(), n_rings if len(xy) else 0, H, W, out.data_ptr(),
+                                  1 if accumulate else 0, ws.data_ptr(), int(ws.numel()), _stream()), "zone_mask_u8")
+    return out
+
+
+def zone_clip_(classes: torch.Tensor, mask: Optional[torch.Tensor], keep_classes=None, fill: int = 0) -> torch.Tensor:
+    """In place over a device uint8 class map: pixels where ``mask`` (device uint8, same shape; None = everywhere
+    inside) is 0, and pixels whose class is not in ``keep_classes`` (iterable of ints; None = all), become ``fill``."""
+    lib = _l.load()
+    if not (classes.is_cuda and classes.dtype == torch.uint8 and classes.is_contiguous()):
+        raise ValueError("zone_clip_: a contiguous CUDA uint8 class map expected")
+    if not 0 <= int(fill) <= 255:
+        raise ValueError(f"zone_clip_: fill {fill} is not a uint8 value")
+    if mask is not None:
+        if not (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == classes.shape
+                and mask.device == classes.device):
+            raise ValueError(f"zone_clip_: mask must be a CUDA uint8 {tuple(classes.shape)} tensor on the device of classes")
+        mask = mask.contiguous()
+    lut = None
+    if keep_classes is not None:
+        keep = sorted({int(c) for c in keep_classes})
+        if keep and not (0 <= keep[0] and keep[-1] <= 255):
+            raise ValueError(f"zone_clip_: class ids must be uint8 values, got {keep}")
+        table = torch.full((256,), int(fill), dtype=torch.uint8)
+        if keep:
+            idx = torch.tensor(keep, dtype=torch.long)
+            table[idx] = idx.to(torch.uint8)
+        lut = table.to(classes.device)
+    _l.check(lib.ffa_zone_clip_u8(classes.data_ptr(), _ptr(mask), _ptr(lut), classes.numel(), int(fill), _stream()),
+             "zone_clip_u8")
+    return classes
+
+
+def zone_window_counts(mask: torch.Tensor, windows) -> torch.Tensor:
+    """Device int64 [N]: the number of non-zero pixels of ``mask`` (device uint8 [H, W]) in each pixel rectangle
+    ``windows[n] = (r0, c0, r1, c1)`` (rows r0 .. r1 - 1, columns c0 .. c1 - 1, clamped to the raster)."""
+    import numpy as np
+    lib = _l.load()
+    if not (mask.is_cuda and mask.dtype == torch.uint8 and mask.dim() == 2):
+        raise ValueError("zone_window_counts: a CUDA uint8 [H, W] mask expected")
+    mask = mask.contiguous()
+    if torch.is_tensor(windows):
+        win = windows.to(device=mask.device, dtype=torch.int32).reshape(-1, 4).contiguous()
+    else:
+        w = np.asarray(windows, dtype=np.int64).reshape(-1, 4)
+        win = torch.from_numpy(np.clip(w, -(1 << 30), 1 << 30).astype(np.int32)).to(mask.device)
+    counts = torch.zeros(win.shape[0], dtype=torch.int64, device=mask.device)
+    H, W = mask.shape
+    _l.check(lib.ffa_zone_window_counts(mask.data_ptr(), H, W, _ptr(win) if len(win) else None, int(win.shape[0]),
+                                        _ptr(counts) if len(win) else None, _stream()), "zone_window_counts")
+    return counts
+
+
+# --------------------------------------------------------------------------------------------------
 # U-TAE Sentinel branch (flair_hub/models/multitemp_model.py): small kernels around conv2d
 
 def reflect_pad1(x: torch.Tensor) -> torch.Tensor:

@@ -546,6 +546,42 @@ int ffa_polygonize_zonal_sum_u8(const void* ws, long long ws_bytes, int H, int W
 int ffa_polygon_simplify(const double* xy, const int32_t* ring_offsets, const int32_t* poly_ring_offsets,
                          long long n_polys, double tolerance, int n_threads, uint8_t* keep);
 
+/* ---- geozone clipping on the pixel grid (flair_zonal_detection/zone.py, raster_to_polygons(zone=, classes=)) ------ */
+/* The reference clips its polygons to the zone contour in vector space (shapely intersection).  Here the zone is
+ * rasterised on the class raster's own grid and applied before polygonisation: a pixel belongs to the zone when its
+ * centre is inside the contour (rasterio.mask.mask / GDAL rasterize with all_touched = False), which keeps the
+ * polygoniser's integer vertices, valid rings and byte-equal outputs.
+ *
+ * Definition (normative).  Rings arrive in pixel coordinates as float64 pairs xy_pix[V][2] = (px, py) with
+ * px = (x - left) / xres, py = (top - y) / yres; ring k owns the vertices ring_offsets[k] .. ring_offsets[k + 1] - 1
+ * (int32, ring_offsets[n_rings] = V), need not be closed and may have either orientation; holes are further rings:
+ * the rule is even-odd over all rings of one call.  For an edge (x0, y0) -> (x1, y1) with y0 != y1 (the last vertex
+ * of a ring connects to its first) and a row r with yc = r + 0.5:
+ *   - the edge crosses the row iff (y0 <= yc) != (y1 <= yc);
+ *   - xc = x0 + ((yc - y0) * (x1 - x0)) / (y1 - y0), every operation rounded separately in IEEE float64 (no fma);
+ *   - the crossing toggles column c0 = floor(xc - 0.5) + 1, clamped to [0, W]; a toggle at W has no effect;
+ *   - inside(r, c) = XOR of the toggles of row r at columns <= c.
+ * A box with corners on the pixel centres (10.5, 20.5) and (30.5, 40.5) covers rows 20..39 and columns 11..30.
+ * Edges with a non-finite coordinate are ignored.
+ *
+ * ffa_zone_mask_u8 writes mask[H][W] (uint8, 0 / 1); with accumulate != 0 it ORs into the existing mask instead (one
+ * call per polygon gives the union of a MultiPolygon).  All pointers are device memory; the workspace
+ * (ffa_zone_mask_workspace_bytes(H, W, V) bytes, contents irrelevant on entry) also bounds the vertices the kernels
+ * read: vertices beyond the count it was sized for are ignored.  XOR atomics on single bits: equal inputs give equal
+ * bytes.
+ * ffa_zone_clip_u8: classes[i] = mask[i] ? lut256[classes[i]] : fill, in place over n pixels.  mask == NULL: every
+ * pixel is inside (a class filter alone); lut256 == NULL: the identity.  lut256 is 256 bytes of device memory.
+ * ffa_zone_window_counts: counts[k] (int64, device, written) = the number of non-zero mask pixels in rows
+ * windows[k][0] .. windows[k][2] - 1 and columns windows[k][1] .. windows[k][3] - 1 (int32 (r0, c0, r1, c1), device),
+ * clamped to the raster; empty or inverted rectangles give 0. */
+long long ffa_zone_mask_workspace_bytes(int H, int W, long long n_vertices); /* < 0 (FFA_ERR_ARG) on bad arguments */
+int ffa_zone_mask_u8(const double* xy_pix, const int32_t* ring_offsets, int n_rings, int H, int W, uint8_t* mask,
+                     int accumulate, void* ws, long long ws_bytes, ffa_stream_t stream);
+int ffa_zone_clip_u8(uint8_t* classes, const uint8_t* mask, const uint8_t* lut256, long long n, int fill,
+                     ffa_stream_t stream);
+int ffa_zone_window_counts(const uint8_t* mask, int H, int W, const int32_t* windows, int n_windows, int64_t* counts,
+                           ffa_stream_t stream);
+
 /* ---- hardware layout probes (tests only) ---------------------------------------------------------- */
 int ffa_probe_tr16(const uint16_t* src, uint16_t* dst, ffa_stream_t stream);
 int ffa_probe_mfma(const float* A, const float* B, float* D, int use_f32, ffa_stream_t stream);

@@ -1,6 +1,6 @@
 """Polygonisation timings on synthetic class maps (GPU required).
 
-    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3] [--confidence]
+    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3] [--confidence] [--zone]
 
 Maps: 'voronoi' (blocky nearest-seed map of 19 classes with 2 % label noise), 'checker' (checkerboard: every pixel a
 component, four boundary edges per pixel -- the worst case for edges), 'uniform' (one class: a single component over
@@ -13,6 +13,11 @@ the whole raster, the worst case for contention on one accumulator; on request).
     back, edge arrays), with the time that bound would take at the HBM rate (8 TB/s).
 With --confidence the zonal-sum stage (ffa_polygonize_zonal_sum_u8 over a random uint8 plane, after emit) is timed
 as well: "zonal_sum_ms", and the 5 bytes per pixel it must read (label + value) at the HBM rate.
+With --zone one more JSON line per voronoi size: a jagged star contour of 50 000 vertices covering about 40 % of the
+map is rasterised (ffa_zone_mask_u8) and applied (ffa_zone_clip_u8), hip-event times, best of --reps after a warm-up,
+next to the time the unavoidable traffic would take at the HBM rate (H W bytes of mask written, H W / 8 bytes of toggles
+written and read; 3 H W bytes for the clip), and the polygon count and host time (objects + GeoPackage) of the
+clipped map and of the whole one.
 Per-kernel times (count_kernel, the labelling kernels and zonal_sum_kernel of the same run side by side): run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_polygonize.py --confidence --device-only`.
 """
@@ -146,6 +151,76 @@ def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_
     return res
 
 
+def star_contour(n: int, points: int = 25000) -> np.ndarray:
+    """pixel coordinates of a 2 * points-vertex star about the map centre whose area pi R r is 40 % of n^2"""
+    k = np.arange(2 * points)
+    ang = np.pi * k / points
+    rad = np.where(k % 2 == 0, 0.37, 0.344) * n  # pi * 0.37 * 0.344 = 0.400
+    return np.stack([n / 2 + 0.3 + rad * np.cos(ang), n / 2 - 0.2 + rad * np.sin(ang)], axis=1)
+
+
+def host_stage(out) -> dict:
+    """simplifier, objects and GeoPackage of polygonize's five arrays (host): the part a zone clip shortens"""
+    from flairhip import ops
+    from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
+    pc, pp, pro, rvo, verts = out
+    xy = np.empty(verts.shape, np.float64)
+    xy[:, 0] = 651992.36 + verts[:, 0] * 0.2
+    xy[:, 1] = 6860417.84 - verts[:, 1] * 0.2
+    t1 = time.perf_counter()
+    keep = ops.polygon_simplify(xy, rvo, pro, 0.1, 16)
+    t2 = time.perf_counter()
+    before = np.concatenate([[0], np.cumsum(keep)])
+    frame = PolygonFrame.from_flat(FlatPolygons(pc, pro, before[rvo].astype(np.int32), xy[keep]), "EPSG:2154")
+    t3 = time.perf_counter()
+    with tempfile.TemporaryDirectory() as d:
+        frame.to_file(os.path.join(d, "p.gpkg"), driver="GPKG")
+        t4 = time.perf_counter()
+    return {"polygons": len(pc), "simplify_ms": round((t2 - t1) * 1e3, 1), "objects_ms": round((t3 - t2) * 1e3, 1),
+            "gpkg_ms": round((t4 - t3) * 1e3, 1)}
+
+
+def run_zone(cls: np.ndarray, reps: int, device_only: bool = False) -> dict:
+    import torch
+    from flairhip import lib as L
+    from flairhip import ops
+    lib = L.load()
+    H, W = cls.shape
+    dev = torch.device("cuda")
+    ring = star_contour(H)
+    xy = torch.from_numpy(ring).to(dev)
+    ro = torch.tensor([0, len(ring)], dtype=torch.int32, device=dev)
+    nbytes = int(lib.ffa_zone_mask_workspace_bytes(H, W, len(ring)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    x0 = torch.from_numpy(cls).to(dev)
+    t_mask, t_clip = [], []
+    for rep in range(reps + 1):
+        x = x0.clone()
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        e0.record()
+        L.check(lib.ffa_zone_mask_u8(xy.data_ptr(), ro.data_ptr(), 1, H, W, mask.data_ptr(), 0, ws.data_ptr(), nbytes, st))
+        e1.record()
+        L.check(lib.ffa_zone_clip_u8(x.data_ptr(), mask.data_ptr(), None, H * W, 18, st))
+        e2.record()
+        torch.cuda.synchronize()
+        if rep:
+            t_mask.append(e0.elapsed_time(e1))
+            t_clip.append(e1.elapsed_time(e2))
+    mask_lb, clip_lb = H * W + 2 * (H * W // 8), 3 * H * W
+    res = {"map": "voronoi+zone", "H": H, "W": W, "zone_vertices": len(ring),
+           "zone_fraction": round(float(mask.sum(dtype=torch.int64)) / (H * W), 4),
+           "zone_mask_ms": round(min(t_mask), 4), "zone_mask_ms_at_hbm_rate": round(mask_lb / HBM_BYTES_PER_S * 1e3, 4),
+           "zone_clip_ms": round(min(t_clip), 4), "zone_clip_ms_at_hbm_rate": round(clip_lb / HBM_BYTES_PER_S * 1e3, 4)}
+    res["zone_mask_fraction_of_bound"] = round(res["zone_mask_ms_at_hbm_rate"] / res["zone_mask_ms"], 4)
+    if device_only:
+        return res
+    for name, t in (("with_zone", x), ("without_zone", x0)):
+        res[name] = host_stage([a.cpu().numpy() for a in ops.polygonize(t, 18, 1)])
+    return res
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[5000, 16384])
@@ -155,10 +230,16 @@ def main() -> None:
     ap.add_argument("--confidence", action="store_true", help="also time the zonal-sum stage (per-polygon sums)")
     ap.add_argument("--device-only", action="store_true",
                     help="skip the host stages (simplifier, objects, GeoPackage: minutes on the checkerboard)")
+    ap.add_argument("--zone", action="store_true",
+                    help="voronoi maps only: time the zone mask + clip and the host stages with and without the zone")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_polygonize needs an MI355X")
+    if args.zone:
+        for n in args.sizes:
+            print(json.dumps(run_zone(voronoi(n), args.reps, args.device_only)), flush=True)
+        return
     if "voronoi" in args.maps:
         for n in args.sizes:
             print(json.dumps(run("voronoi", voronoi(n), args.reps, args.confidence, args.device_only)), flush=True)

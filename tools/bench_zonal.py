@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """Zonal inference throughput on a synthetic in-memory raster.
 
-  python tools/bench_zonal.py [--size 6048] [--batch 8] [--write-confidence]
+  python tools/bench_zonal.py [--size 6048] [--batch 8] [--write-confidence] [--zone]
 
 Reports (a) the model forward alone (eval mode: BatchNorm folded into the conv operands, bias / ReLU / decoder
 upsample+concat in conv epilogues / prologues) at the loop's batch size and at 32, and (b) the whole
 run_inference loop: slicing, windowed reads + normalisation (numpy, host), H2D, forward, fused margin-crop + argmax,
 D2H of 1 byte per kept pixel, window placement, writes into the in-memory output raster.  --write-confidence turns the
 config key write_confidence on: label + confidence from one kernel pass, 2 bytes per kept pixel, two rasters.
+--zone: instead of (b), the loop under a disc-shaped geozone covering about 40 % of the raster, with
+skip_tiles_outside_zone off (every tile of the zone's bounding box is inferred) and on, in one process: tiles skipped
+and the wall time of the tile loop (inference_and_write) of both.
 """
 from __future__ import annotations
 
@@ -39,6 +42,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--write-confidence", action="store_true",
                     help="run the tile loop with write_confidence: true (argmax output only)")
+    ap.add_argument("--zone", action="store_true",
+                    help="time the tile loop under a geozone with skip_tiles_outside_zone off and on")
     args = ap.parse_args()
     from flairhip.configs import unet_resnet34_config
     from flair_hub.models.flair_model import FLAIR_HUB_Model
@@ -84,6 +89,34 @@ def main():
     zc["modalities"][MOD].update({"input_img_path": ras, "channels": list(range(1, C + 1)),
                                   "normalization": {"type": "custom", "means": [110.0] * C, "stds": [50.0] * C}})
     zc["tasks"] = [{"name": TASK, "active": True, "class_names": {i: f"c{i}" for i in range(19)}}]
+    if args.zone:
+        import copy
+        from flair_zonal_detection import inference as zi
+        ang = np.linspace(0.0, 2.0 * np.pi, 720, endpoint=False)
+        rad = np.sqrt(0.4 / np.pi) * H * 0.2  # disc of 40 % of the raster, in metres
+        cx, cy = 651000.0 + W * 0.1, 6865000.0 - H * 0.1
+        zone = {"type": "Polygon", "coordinates": [np.stack([cx + rad * np.cos(ang), cy + rad * np.sin(ang)], 1).tolist()]}
+        loops = []
+        inner = zi.inference_and_write
+
+        def timed(model_, loader_, tiles_, *a, **k):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            inner(model_, loader_, tiles_, *a, **k)
+            torch.cuda.synchronize()
+            loops.append((len(tiles_), time.time() - t0))
+        zi.inference_and_write = timed
+        run_inference(copy.deepcopy(zc), geozone=zone)  # warm-up: kernels, workspaces, graph capture
+        for skip in (False, True, False, True):
+            c = copy.deepcopy(zc)
+            c["skip_tiles_outside_zone"] = skip
+            run_inference(c, geozone=zone)
+        zi.inference_and_write = inner
+        (n_off, _), (n_on, _) = loops[1], loops[2]
+        off, on = min(loops[1][1], loops[3][1]), min(loops[2][1], loops[4][1])
+        print(f"zone of 40 % on {H}x{W} px: skip off {n_off} tiles, tile loop {off:.2f} s; skip on {n_on} tiles "
+              f"({n_off - n_on} of {n_off} skipped), tile loop {on:.2f} s (best of 2 each)")
+        return
     t0 = time.time()
     out = run_inference(zc)
     torch.cuda.synchronize()
