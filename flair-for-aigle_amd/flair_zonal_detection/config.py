@@ -39,12 +39,29 @@ def validate_skip_tiles_outside_zone(config: dict) -> bool:
     return skip
 
 
+def validate_geozone_crs(config: dict):
+    """The optional key geozone_crs (default none: the geozone is in the raster's CRS): the CRS the geozone is given
+    in -- 'EPSG:4326', an EPSG code, or 'auto' (GeoJSON: the legacy crs member, else EPSG:4326).  run_inference
+    reprojects the zone to the raster's CRS before slicing.  An unsupported CRS raises ValueError here."""
+    geozone_crs = config.get("geozone_crs")
+    if geozone_crs is None:
+        return None
+    if isinstance(geozone_crs, str) and geozone_crs.strip().lower() == "auto":
+        return "auto"
+    from flair_zonal_detection import crs
+    if isinstance(geozone_crs, bool) or not isinstance(geozone_crs, (str, int)):
+        raise ValueError(f"geozone_crs must be 'auto', 'EPSG:NNNN' or an EPSG code, got {geozone_crs!r}")
+    crs.parse(geozone_crs)
+    return geozone_crs
+
+
 def validate_config(config: dict) -> None:
     for key in REQUIRED_KEYS:
         if key not in config:
             raise ValueError(f"Missing required config key: {key}")
     validate_write_confidence(config)
     validate_skip_tiles_outside_zone(config)
+    validate_geozone_crs(config)
     if not os.path.isfile(config["model_weights"]):
         raise FileNotFoundError(f"Model weights not found at: {config['model_weights']}")
     os.makedirs(config["output_path"], exist_ok=True)

@@ -5,7 +5,8 @@ same kind of file from the flat polygon arrays of ``raster_to_polygons``:
 
   * ``PRAGMA application_id`` = 0x47504B47 ("GPKG"), ``PRAGMA user_version`` = 10200 (version 1.2.0)
   * ``gpkg_spatial_ref_sys`` with the three mandatory rows (-1 undefined Cartesian, 0 undefined geographic, 4326
-    WGS 84) plus one row for the raster's EPSG code, ``gpkg_contents``, ``gpkg_geometry_columns``
+    WGS 84) plus one row for the layer's EPSG code (none for 4326: polygons reprojected to EPSG:4326 use the mandatory
+    row), ``gpkg_contents``, ``gpkg_geometry_columns``
   * one feature table: ``fid`` INTEGER PRIMARY KEY, ``geom`` POLYGON, ``class_id`` INTEGER, then the optional extra
     attribute columns (``REAL`` for float values, ``INTEGER`` for int values; e.g. ``confidence``, ``pixels``)
   * geometry blobs: the GeoPackage header ("GP", version 0, flags = little endian + [minx, maxx, miny, maxy] envelope,

@@ -17,8 +17,9 @@ Polygonisation of the written raster (raster_to_polygons, reference :359-413) ru
 (csrc/polygon_simplify.cpp) and a GDAL-free GeoPackage writer (gpkg.py).  Clipping to the geozone and the class filter
 of the fork's postprocess_results happen on the pixel grid before polygonisation (``raster_to_polygons(zone=, classes=)``,
 csrc/zone_mask.hip, zone.py), and with the config key ``skip_tiles_outside_zone`` the tile loop leaves out the tiles
-that hold no zone pixel.  Reprojection of the zone or the polygons and COG conversion are product glue and are not
-provided.
+that hold no zone pixel.  A zone in another CRS than the raster's (``geozone_crs`` / ``zone_crs``) and polygons wanted in
+another one (``target_crs``) are reprojected on the GPU (csrc/crs_transform.hip, crs.py).  COG conversion is product
+glue and is not provided.
 
 Per-polygon confidence (the column the fork's driver fills with random numbers, scripts/
 run_fast_aigle_segmentation.py:162-163, and its unused second path :566-630 means to compute): with the config key
@@ -41,7 +42,8 @@ from torch.utils.data import DataLoader
 
 from flairhip import ops
 from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_config,
-                                          validate_skip_tiles_outside_zone, validate_write_confidence)
+                                          validate_geozone_crs, validate_skip_tiles_outside_zone,
+                                          validate_write_confidence)
 from flair_zonal_detection.dataset import MultiModalSlicedDataset, TileBatcher, pad_series_collate
 from flair_zonal_detection.model_utils import build_inference_model, compute_patch_sizes
 from flair_zonal_detection.postprocess import convert  # noqa: F401  (re-exported like the reference)
@@ -393,18 +395,25 @@ def drop_tiles_outside_zone(tiles, ref_img, geozone):
 
 
 def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tuple[int, int]] = None,
-                  before_loop=None) -> Dict[str, object]:
+                  before_loop=None, geozone_crs=None) -> Dict[str, object]:
     """End-to-end zonal run with upstream FLAIR-HUB's one-argument semantics (the fork's own run_inference is
     stale: inference.py:650-665 calls its helpers with the wrong arity).  Returns the output rasters.
     ``geozone`` (any form zone.zone_rings reads, in the raster's CRS) restricts the tile grid to its bounding box;
     with the config key ``skip_tiles_outside_zone: true`` the tiles holding no pixel of the zone are dropped as well
-    (drop_tiles_outside_zone).  ``shard=(rank, world)`` (or config['shard']) restricts the run to that rank's slice of the tile grid: one process
+    (drop_tiles_outside_zone).  ``geozone_crs`` (or the config key of that name; None = the raster's CRS, as before)
+    names the CRS the zone is given in -- anything crs.parse accepts, or "auto" for GeoJSON -- and the zone is then
+    reprojected to the raster's CRS once, before slicing (zone.zone_in_raster_crs, the reference's
+    ``gdf_geozone.to_crs(config.input_crs)``).  ``shard=(rank, world)`` (or config['shard']) restricts the run to that rank's slice of the tile grid: one process
     per GPU, no communication; in-memory outputs then track their writes for merge_shard_outputs.  ``before_loop``
     (optional) is called with the freshly initialised outputs before the first tile is processed."""
     t0 = time.time()
     config = prep_config(config_path)
     ref_path = config["modalities"][config["reference_modality"]]["input_img_path"]
     ref_img = ref_raster if ref_raster is not None else open_raster(ref_path)
+    if geozone is not None:
+        from flair_zonal_detection.zone import zone_in_raster_crs
+        geozone_crs = geozone_crs if geozone_crs is not None else validate_geozone_crs(config)
+        geozone = zone_in_raster_crs(geozone, geozone_crs, getattr(ref_img, "crs", None))
     tiles = generate_patches_from_reference(config, ref_img, geozone)
     if validate_skip_tiles_outside_zone(config) and geozone is not None and len(tiles):
         tiles = drop_tiles_outside_zone(tiles, ref_img, geozone)
@@ -501,10 +510,11 @@ def _confidence_source(tiff_path, confidence):
 
 def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, top: float, xres: float, yres: float,
                    crs, bg: Optional[int], min_pixels: int, simplification: float, n_jobs: Optional[int],
-                   zone=None, classes=None):
+                   zone=None, classes=None, zone_crs=None, target_crs=None):
     """Shared tail of raster_to_polygons / vectorize_segmentation_parallel: zone clip and class filter on the device
     copy of the raster (one ffa_zone_clip_u8 pass, only when asked for), GPU polygonisation (+ zonal sums of the
-    uint8 confidence plane), map coordinates, host simplification, frame."""
+    uint8 confidence plane), map coordinates, host simplification, reprojection of the kept vertices to
+    ``target_crs`` (one ffa_crs_transform_f64 pass, only when asked for), frame."""
     from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
     dev = torch.device("cuda")
     values = None if conf is None else torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
@@ -522,7 +532,8 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
         mask = None
         if zone is not None:
             from flair_zonal_detection.zone import zone_mask
-            mask = zone_mask(zone, left, top, xres, yres, data.shape[0], data.shape[1])
+            mask = zone_mask(zone, left, top, xres, yres, data.shape[0], data.shape[1], zone_crs=zone_crs,
+                             raster_crs=crs)
         ops.zone_clip_(cls_dev, mask, keep_classes=keep, fill=bg)
     res = [t.cpu().numpy() for t in ops.polygonize(cls_dev, bg, min_pixels,
                                                    **({} if values is None else {"values": values}))]
@@ -536,6 +547,14 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
         kept_before = np.concatenate([[0], np.cumsum(keep)])
         rvo = kept_before[rvo].astype(np.int32)
         xy = xy[keep]
+    if target_crs is not None:
+        from flair_zonal_detection import crs as crs_table
+        if not isinstance(crs, crs_table.CrsParams) and crs_table.epsg_code(crs) is None:
+            raise ValueError(f"raster_to_polygons: target_crs needs a raster with a recognisable CRS, got {crs!r}")
+        dst = crs_table.parse(target_crs)
+        if not crs_table.same(crs, dst):
+            xy = ops.reproject_points(np.ascontiguousarray(xy), crs, dst)
+            crs = str(dst)
     flat = FlatPolygons(pc.astype(np.int32), pro.astype(np.int32), rvo.astype(np.int32), xy)
     columns = {}
     if conf is not None:
@@ -553,7 +572,7 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
 
 def raster_to_polygons(tiff_path, ignore_background: bool = True, background_value: int = 18, min_area: float = 1.0,
                        simplification: float = 0.1, n_jobs: Optional[int] = None, confidence=None, zone=None,
-                       classes=None):
+                       classes=None, zone_crs=None, target_crs=None):
     """Vector polygons of a class raster -- the reference's raster_to_polygons (inference.py:377-413) with its
     signature and call form ``raster_to_polygons(output_files, n_jobs=4)``.
 
@@ -590,6 +609,14 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     (ffa_zone_clip_u8); the confidence sums need no change since background pixels contribute nowhere.  With
     ``ignore_background=False`` there is no background value to reuse: 255 is the fill, and a raster that holds 255
     in a kept class raises ValueError.  With ``zone=None, classes=None`` nothing changes.
+
+    ``zone_crs``: the CRS the zone is given in (anything crs.parse accepts, or "auto" for GeoJSON: the legacy ``crs``
+    member, else EPSG:4326); the zone is reprojected to the raster's CRS before it is rasterised.  None: the zone is in
+    the raster's CRS.  ``target_crs``: the CRS of the result (the driver's ``clean_results_gdf.to_crs(target_crs)``).
+    The order is the driver's: polygonise, ``min_area`` and simplification in the raster's CRS, then the kept vertices
+    through one pass of the GPU transform (ops.reproject_points; edges stay straight, as to_crs leaves them) and the
+    frame's ``crs`` is the target.  class_id, confidence, pixels, polygon order and ring structure do not depend on
+    ``target_crs``.  Either argument with a raster whose CRS is unknown raises ValueError; None changes nothing.
     """
     src = _polygon_source(tiff_path)
     if src.count != 1:
@@ -616,8 +643,8 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     bg = int(background_value) if ignore_background else None
     if bg is not None and not 0 <= bg <= 255:
         bg = None  # no uint8 pixel can hold it: every value is a class
-    return _polygon_table(data, conf, left, top, xres, yres, src.crs, bg, min_pixels, simplification, n_jobs,
-                          zone=zone, classes=classes)
+    return _polygon_table(data, conf, left, top, xres, yres, getattr(src, "crs", None), bg, min_pixels, simplification,
+                          n_jobs, zone=zone, classes=classes, zone_crs=zone_crs, target_crs=target_crs)
 
 
 def logits_to_labels_and_confidence(probs):

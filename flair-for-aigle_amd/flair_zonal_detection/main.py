@@ -49,11 +49,12 @@ def _wait_for(paths, timeout_s: float, newer_than: float = 0.0) -> None:
         time.sleep(0.2)
 
 
-def run_sharded(config, rank: int, world: int, timeout_s: float = 3600.0, keep_parts: bool = False, geozone=None
-                ) -> Optional[Dict[str, str]]:
+def run_sharded(config, rank: int, world: int, timeout_s: float = 3600.0, keep_parts: bool = False, geozone=None,
+                geozone_crs=None) -> Optional[Dict[str, str]]:
     """This rank's share of a zonal run over ``world`` processes (one per GPU).  Rank 0 returns {task: merged path}
     once every rank's part file exists; the other ranks return None as soon as their own part is written.
-    ``geozone`` is passed on to run_inference (every rank slices and filters the same tile grid)."""
+    ``geozone`` and ``geozone_crs`` are passed on to run_inference (every rank slices and filters the same tile
+    grid)."""
     import torch
     from flair_zonal_detection.geotiff import WRITTEN_SUFFIX, GeoTiffWriter, merge_shard_files
     from flair_zonal_detection.inference import run_inference
@@ -63,7 +64,8 @@ def run_sharded(config, rank: int, world: int, timeout_s: float = 3600.0, keep_p
     # --keep-parts) run left under the same names must not be mistaken for this run's: every rank removes its own
     # part + mask before it starts, and rank 0 only accepts parts at least as new as its own start.
     t_start = time.time()
-    outputs = run_inference(config, geozone=geozone, shard=(rank, world), before_loop=_remove_stale_parts)
+    outputs = run_inference(config, geozone=geozone, shard=(rank, world), before_loop=_remove_stale_parts,
+                            geozone_crs=geozone_crs)
     for task, o in outputs.items():
         if not isinstance(o, GeoTiffWriter):
             raise TypeError("a sharded multi-process run needs file outputs (GeoTIFF paths), not in-memory rasters")
@@ -86,7 +88,7 @@ def run_sharded(config, rank: int, world: int, timeout_s: float = 3600.0, keep_p
     return merged
 
 
-def main(argv=None) -> None:
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Run zonal detection inference.")
     parser.add_argument("--config", type=str, required=True, help="Path to the detection config file")
     parser.add_argument("--keep-parts", action="store_true", help="sharded runs: keep the per-rank part files")
@@ -95,12 +97,35 @@ def main(argv=None) -> None:
                              "defaults) and write the polygons as a GeoPackage, with the columns confidence and pixels "
                              "when the config sets write_confidence; sharded runs: rank 0, after the merge")
     parser.add_argument("--zone", type=str, default=None, metavar="PATH.geojson",
-                        help="geozone contour (GeoJSON, in the raster's CRS): only its bounding box is sliced (and, with "
-                             "skip_tiles_outside_zone in the config, only the tiles that hold a zone pixel are inferred); "
-                             "with --polygons the polygons are clipped to the contour")
+                        help="geozone contour (GeoJSON, in the raster's CRS unless --zone-crs says otherwise): only its "
+                             "bounding box is sliced (and, with skip_tiles_outside_zone in the config, only the tiles "
+                             "that hold a zone pixel are inferred); with --polygons the polygons are clipped to the "
+                             "contour")
     parser.add_argument("--classes", type=str, default=None, metavar="ID[,ID...]",
                         help="with --polygons: polygonise these class ids only, e.g. 6,7")
+    parser.add_argument("--zone-crs", type=str, default=None, metavar="EPSG:NNNN|auto",
+                        help="CRS the --zone file is given in; it is reprojected to the raster's CRS first.  auto: the "
+                             "GeoJSON's legacy crs member, else EPSG:4326 (RFC 7946).  Default: the config key "
+                             "geozone_crs, else the raster's CRS (no reprojection)")
+    parser.add_argument("--target-crs", type=str, default=None, metavar="EPSG:NNNN",
+                        help="with --polygons: write the polygons in this CRS (e.g. EPSG:4326) instead of the raster's")
+    return parser
+
+
+def main(argv=None) -> None:
+    parser = build_parser()
     args = parser.parse_args(argv)
+    if args.zone_crs is not None and args.zone is None:
+        parser.error("--zone-crs needs --zone")
+    if args.target_crs is not None and args.polygons is None:
+        parser.error("--target-crs needs --polygons")
+    for opt, value in (("--zone-crs", args.zone_crs), ("--target-crs", args.target_crs)):
+        if value is not None and not (opt == "--zone-crs" and value.strip().lower() == "auto"):
+            from flair_zonal_detection import crs
+            try:
+                crs.parse(value)
+            except ValueError as exc:
+                parser.error(f"{opt}: {exc}")
     try:
         classes = None if args.classes is None else [int(c) for c in args.classes.split(",") if c.strip()]
     except ValueError:
@@ -109,15 +134,20 @@ def main(argv=None) -> None:
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
         outputs = run_sharded(args.config, int(os.environ.get("RANK", "0")), world, keep_parts=args.keep_parts,
-                              geozone=args.zone)
+                              geozone=args.zone, geozone_crs=args.zone_crs)
     else:
         from flair_zonal_detection.inference import run_inference
-        outputs = run_inference(args.config, geozone=args.zone)
+        outputs = run_inference(args.config, geozone=args.zone, geozone_crs=args.zone_crs)
     if args.polygons and outputs is not None:
         from flair_zonal_detection.inference import raster_to_polygons
         # a write_confidence run also returns f"{task}_confidence" rasters: the polygons then carry their mean
         with_conf = any(str(k).endswith("_confidence") for k in outputs)
-        extra = {k: v for k, v in (("zone", args.zone), ("classes", classes)) if v is not None}
+        zone_crs = args.zone_crs
+        if zone_crs is None and args.zone is not None:
+            from flair_zonal_detection.config import load_config, validate_geozone_crs
+            zone_crs = validate_geozone_crs(load_config(args.config))
+        extra = {k: v for k, v in (("zone", args.zone), ("classes", classes), ("zone_crs", zone_crs),
+                                   ("target_crs", args.target_crs)) if v is not None}
         gdf = raster_to_polygons(outputs, **({"confidence": True} if with_conf else {}), **extra)
         gdf.to_file(args.polygons, driver="GPKG")
         logger.info("wrote %d polygons to %s", len(gdf), args.polygons)

@@ -3,8 +3,8 @@
 ``FlatPolygons`` holds the polygons as flat arrays (class ids, ring offsets per polygon, vertex offsets per ring,
 float64 map coordinates, rings not closed).  ``PolygonFrame`` is the small pandas.DataFrame subclass returned when
 geopandas is not importable: columns ``class_id`` and ``geometry`` like the reference's GeoDataFrame (plus optional
-numeric attribute columns between them, e.g. ``confidence`` and ``pixels``), a ``crs`` attribute and
-``to_file(path, driver="GPKG")``.  Its geometry values are ``Polygon`` views that read the flat arrays
+numeric attribute columns between them, e.g. ``confidence`` and ``pixels``), a ``crs`` attribute,
+``to_crs(crs)`` (the flat coordinates through the GPU transform, once) and ``to_file(path, driver="GPKG")``.  Its geometry values are ``Polygon`` views that read the flat arrays
 only when asked (exterior / interiors as closed float64 [n, 2] arrays, ``area``, ``wkb``).
 """
 from __future__ import annotations
@@ -108,6 +108,34 @@ class PolygonFrame(pd.DataFrame):
         df = cls(data)
         df.crs = crs
         return df
+
+    def to_crs(self, crs) -> "PolygonFrame":
+        """A new frame in ``crs`` (anything crs.parse accepts), like GeoDataFrame.to_crs: every vertex transformed,
+        edges straight, rings, order and the other columns as they are.  The flat coordinate store behind the
+        geometries goes through ops.reproject_points once; ``area`` / ``bounds`` / ``wkb`` of the new geometries come
+        from the transformed coordinates.  A frame without a (supported) ``crs`` raises ValueError."""
+        from flairhip import ops
+        from flair_zonal_detection import crs as crs_table
+        if self.crs is None:
+            raise ValueError("PolygonFrame.to_crs: the frame has no crs to transform from")
+        src, dst = crs_table.parse(self.crs), crs_table.parse(crs)
+        out = self.copy()
+        out.crs = str(dst)
+        if crs_table.same(src, dst):
+            return out
+        stores = {}
+        geoms = np.empty(len(self), dtype=object)
+        for i, g in enumerate(self["geometry"]):
+            if not isinstance(g, Polygon):
+                raise TypeError(f"PolygonFrame.to_crs: geometry {i} is {type(g).__name__}, not a polygons.Polygon")
+            st = stores.get(id(g._store))
+            if st is None:
+                s = g._store
+                xy = ops.reproject_points(np.ascontiguousarray(s.xy, dtype=np.float64), src, dst)
+                st = stores[id(s)] = FlatPolygons(s.class_id, s.poly_ring_offsets, s.ring_vertex_offsets, xy)
+            geoms[i] = Polygon(st, g._q)
+        out["geometry"] = geoms
+        return out
 
     def to_file(self, path: str, driver: str = "GPKG", layer=None, **_ignored) -> str:
         if str(driver).upper() != "GPKG":

@@ -74,8 +74,9 @@ def slice_bounds(zone_bounds, ref_bounds, patch_size: int, margin: int, resoluti
     return ops.slice_grid(min_x, min_y, max_x, max_y, ref_bounds[0], ref_bounds[1], patch_size, margin, resolution)
 
 
-def generate_patches_from_reference(config: Dict, img_path, geozone_contour_geometries=None):
-    """Slice the reference raster (intersected with the geozone) into overlapping tiles.
+def generate_patches_from_reference(config: Dict, img_path, geozone_contour_geometries=None, geozone_crs=None):
+    """Slice the reference raster (intersected with the geozone) into overlapping tiles.  ``geozone_crs`` (None: the
+    raster's CRS) is the CRS the geozone is given in; the zone is then reprojected to the raster's CRS first.
 
     ``img_path`` is a raster path (rasterio required) or a raster-like object (flair_zonal_detection.raster).
     Returns a GeoDataFrame when geopandas is importable, else a pandas DataFrame with the same columns.
@@ -87,9 +88,12 @@ def generate_patches_from_reference(config: Dict, img_path, geozone_contour_geom
 
     src = open_raster(img_path)
     try:
+        crs = getattr(src, "crs", None)
+        if geozone_contour_geometries is not None and geozone_crs is not None:
+            from flair_zonal_detection.zone import zone_in_raster_crs
+            geozone_contour_geometries = zone_in_raster_crs(geozone_contour_geometries, geozone_crs, crs)
         zone = _zone_bounds(src, geozone_contour_geometries)
         rb = src.bounds
-        crs = getattr(src, "crs", None)
     finally:
         if isinstance(img_path, (str, bytes)):
             src.close()

@@ -7,15 +7,21 @@ rasterio.mask.mask / GDAL rasterize with all_touched=False mean by "inside") and
 (raster_to_polygons(zone=...)), and the tile loop may skip the tiles that hold no zone pixel (run_inference with
 ``skip_tiles_outside_zone``).
 
-The zone must be in the CRS of the raster: nothing here reprojects (the fork reprojects before the call too).
+A zone given in another CRS than the raster's is reprojected first, vertex by vertex with straight edges kept, exactly
+what ``gdf_geozone.to_crs(config.input_crs)`` does in the reference (inference.py:249): ``reproject_zone`` and the
+``zone_crs`` argument of ``zone_mask`` (one ffa_crs_transform_f64 pass over all vertices, crs.py for the supported
+systems).  Without a ``zone_crs`` the zone is taken to be in the CRS of the raster, as before.
 """
 from __future__ import annotations
 
 import json
+import logging
 import os
 from typing import List, Sequence, Tuple
 
 import numpy as np
+
+logger = logging.getLogger(__name__)
 
 Rings = List[np.ndarray]
 
@@ -112,16 +118,124 @@ def rings_to_pixels(rings: Rings, left: float, top: float, xres: float, yres: fl
     return pix, offsets
 
 
-def zone_mask(geozone, left: float, top: float, xres: float, yres: float, H: int, W: int):
+def _load_geojson(geozone):
+    """the GeoJSON dict behind a dict or a .geojson / .json path, else None"""
+    if isinstance(geozone, dict):
+        return geozone
+    if isinstance(geozone, (str, os.PathLike)) and str(os.fspath(geozone)).lower().endswith((".geojson", ".json")):
+        with open(os.fspath(geozone), "r", encoding="utf-8") as f:
+            return json.load(f)
+    return None
+
+
+def detect_zone_crs(geozone) -> str:
+    """'EPSG:NNNN' of a GeoJSON dict or file (``zone_crs="auto"``): the legacy ``crs`` member when there is one
+    (``urn:ogc:def:crs:EPSG::NNNN``, ``EPSG:NNNN``, ``urn:ogc:def:crs:OGC:1.3:CRS84`` = 4326), else EPSG:4326 as RFC 7946
+    defines GeoJSON.  Anything that is not GeoJSON, or a member that names no EPSG code, raises ValueError."""
+    obj = _load_geojson(geozone)
+    if obj is None:
+        raise ValueError(f"zone: zone_crs='auto' reads the CRS of a GeoJSON dict or a .geojson / .json file, not of "
+                         f"{type(geozone).__name__}; name the CRS instead")
+    member = obj.get("crs")
+    if member is None:
+        return "EPSG:4326"
+    name = member.get("properties", {}).get("name") if isinstance(member, dict) else None
+    if not isinstance(name, str):
+        raise ValueError(f"zone: cannot read a CRS name from the GeoJSON crs member {member!r}")
+    tail = name.strip().upper()
+    if tail in ("URN:OGC:DEF:CRS:OGC:1.3:CRS84", "URN:OGC:DEF:CRS:OGC::CRS84", "OGC:CRS84", "CRS84"):
+        return "EPSG:4326"
+    if tail.startswith("URN:OGC:DEF:CRS:EPSG:"):
+        tail = "EPSG:" + tail.split(":")[-1]
+    if tail.startswith("EPSG:") and tail[5:].isdigit():
+        return tail
+    raise ValueError(f"zone: the GeoJSON crs member names {name!r}, which is no EPSG code")
+
+
+def reproject_zone(geozone, src_crs, dst_crs) -> dict:
+    """The zone in ``dst_crs`` as a GeoJSON MultiPolygon dict (no ``crs`` member).  Vertices are transformed one by one
+    and edges stay straight -- what GeoDataFrame.to_crs does; ring count, ring order, vertex count and closedness are
+    kept.  All rings go through one ops.reproject_points call.  A vertex without an image (a latitude beyond 90
+    degrees, say) raises ValueError."""
+    from flairhip import ops
+    polys = zone_rings(geozone)
+    rings = [r for poly in polys for r in poly]
+    if not rings:
+        return {"type": "MultiPolygon", "coordinates": []}
+    xy = np.ascontiguousarray(np.concatenate(rings), dtype=np.float64)
+    out = np.asarray(ops.reproject_points(xy, src_crs, dst_crs))
+    if out.shape != xy.shape or not np.all(np.isfinite(out)):
+        raise ValueError(f"zone: a vertex of the zone has no image in {dst_crs} (is the zone really in {src_crs}?)")
+    coords, k = [], 0
+    for poly in polys:
+        new = []
+        for r in poly:
+            new.append(out[k:k + len(r)].tolist())
+            k += len(r)
+        coords.append(new)
+    return {"type": "MultiPolygon", "coordinates": coords}
+
+
+_lonlat_warned = False
+
+
+def _warn_if_lonlat(geozone, raster_crs) -> None:
+    """one warning per process: a zone without a CRS whose coordinates all look like degrees, on a projected raster"""
+    global _lonlat_warned
+    if _lonlat_warned or raster_crs is None:
+        return
+    from flair_zonal_detection import crs
+    try:
+        if crs.parse(raster_crs).is_geographic:
+            return
+        polys = zone_rings(geozone)
+    except ValueError:
+        return
+    if not polys:
+        return
+    pts = np.concatenate([r for rings in polys for r in rings])
+    if np.all(np.abs(pts[:, 0]) <= 180.0) and np.all(np.abs(pts[:, 1]) <= 90.0):
+        _lonlat_warned = True
+        logger.warning("the zone looks like lon/lat (all coordinates within [-180, 180] x [-90, 90]) but the raster is "
+                       "in %s; pass zone_crs (e.g. 'EPSG:4326', or 'auto' for GeoJSON) to reproject it", raster_crs)
+
+
+def zone_in_raster_crs(geozone, zone_crs, raster_crs):
+    """The geozone as the raster's CRS sees it.  ``zone_crs`` None: the zone itself (it is taken to be in the raster's
+    CRS; nothing is launched).  A CRS (anything crs.parse accepts) or "auto" (GeoJSON dicts and files, detect_zone_crs):
+    the zone reprojected to ``raster_crs``, or the zone itself when the two are the same.  A ``zone_crs`` with a raster
+    whose CRS is unknown or unsupported raises ValueError."""
+    if geozone is None:
+        return None
+    if zone_crs is None:
+        _warn_if_lonlat(geozone, raster_crs)
+        return geozone
+    from flair_zonal_detection import crs
+    from flair_zonal_detection.gpkg import epsg_code
+    if isinstance(zone_crs, str) and zone_crs.strip().lower() == "auto":
+        zone_crs = detect_zone_crs(geozone)
+    src = crs.parse(zone_crs)
+    if not isinstance(raster_crs, crs.CrsParams) and epsg_code(raster_crs) is None:
+        raise ValueError(f"zone: a zone_crs ({src}) needs a raster with a recognisable CRS to reproject to, got "
+                         f"{raster_crs!r}")
+    dst = crs.parse(raster_crs)
+    if crs.same(src, dst):
+        return geozone
+    return reproject_zone(geozone, src, dst)
+
+
+def zone_mask(geozone, left: float, top: float, xres: float, yres: float, H: int, W: int, zone_crs=None,
+              raster_crs=None):
     """Device uint8 [H, W] inside mask of the zone on the north-up grid whose pixel (r, c) has its centre at
     (left + (c + 0.5) xres, top - (r + 0.5) yres): 1 where that centre is inside the zone.  Each polygon is filled
-    even-odd over its rings (holes) and the polygons are united, like unary_union in the fork.  The zone must be in
-    the CRS of the grid."""
+    even-odd over its rings (holes) and the polygons are united, like unary_union in the fork.  ``zone_crs`` None:
+    the zone is in the CRS of the grid, as it always was.  Otherwise the zone is in ``zone_crs`` (a CRS, or "auto")
+    and is reprojected to ``raster_crs``, the CRS of the grid, first (zone_in_raster_crs)."""
     import torch
     from flairhip import ops
     if not (xres > 0 and yres > 0):
         raise ValueError(f"zone_mask: positive pixel sizes expected, got {(xres, yres)}")
-    polys = zone_rings(geozone)
+    polys = zone_rings(zone_in_raster_crs(geozone, zone_crs, raster_crs))
     mask = None
     for rings in polys:
         pix, offsets = rings_to_pixels(rings, left, top, xres, yres)

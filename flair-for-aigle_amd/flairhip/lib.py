@@ -38,6 +38,15 @@ class Window(C.Structure):
                 ("skip", C.c_int)]
 
 
+class Crs(C.Structure):
+    """FfaCrs: kind (CRS_GEOGRAPHIC / CRS_LCC2SP / CRS_TMERC), ellipsoid, origin, parallels, scale, false origin"""
+    _fields_ = [("kind", C.c_int), ("a", C.c_double), ("inv_flattening", C.c_double), ("lon0", C.c_double),
+                ("lat0", C.c_double), ("lat1", C.c_double), ("lat2", C.c_double), ("k0", C.c_double),
+                ("false_easting", C.c_double), ("false_northing", C.c_double)]
+
+
+CRS_GEOGRAPHIC, CRS_LCC2SP, CRS_TMERC = 0, 1, 2  # FFA_CRS_*
+
 _i, _ll, _p, _f, _d = C.c_int, C.c_longlong, C.c_void_p, C.c_float, C.c_double
 
 # name -> (restype, argtypes); mirrors include/flairhip.h one to one
@@ -173,6 +182,7 @@ SIGNATURES = {
     "ffa_zone_mask_u8": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _ll, _p]),
     "ffa_zone_clip_u8": (_i, [_p, _p, _p, _ll, _i, _p]),
     "ffa_zone_window_counts": (_i, [_p, _i, _i, _p, _i, _p, _p]),
+    "ffa_crs_transform_f64": (_i, [_p, _p, _ll, C.POINTER(Crs), C.POINTER(Crs), _p]),
     "ffa_probe_tr16": (_i, [_p, _p, _p]),
     "ffa_probe_mfma": (_i, [_p, _p, _p, _i, _p]),
 }

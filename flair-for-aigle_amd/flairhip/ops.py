@@ -1172,6 +1172,74 @@ def zone_window_counts(mask: torch.Tensor, windows) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------------------
+# points between coordinate reference systems (csrc/crs_transform.hip)
+
+def _ffa_crs(p) -> "_l.Crs":
+    return _l.Crs(int(p.kind), float(p.a), float(p.inv_flattening), float(p.lon0), float(p.lat0), float(p.lat1),
+                  float(p.lat2), float(p.k0), float(p.false_easting), float(p.false_northing))
+
+
+def reproject_points(xy, src, dst, out=None):
+    """Points xy (float64 [N, 2], x = easting or longitude, y = northing or latitude) from the CRS ``src`` to the CRS
+    ``dst`` (anything flair_zonal_detection.crs.parse accepts), one pass of ffa_crs_transform_f64; the definition,
+    the datum rule and the NaN rule are in include/flairhip.h.
+
+    A contiguous CUDA tensor is transformed on its device into ``out`` (same shape, dtype and device; ``out is xy``
+    transforms in place; None allocates) and a tensor is returned.  A numpy array goes to the current device, through
+    the kernel and back: a new array (or ``out``, a float64 [N, 2] array) is returned.  Anything that is not
+    contiguous float64 [N, 2] raises ValueError.  N == 0, or two CRSs crs.same calls equal, launch nothing: the input
+    is returned (copied into ``out`` when that is given)."""
+    import numpy as np
+    from flair_zonal_detection import crs as _crs
+    s, d = _crs.parse(src), _crs.parse(dst)
+    is_tensor = torch.is_tensor(xy)
+    if not is_tensor and not isinstance(xy, np.ndarray):
+        raise ValueError(f"reproject_points: a torch tensor or a numpy array expected, got {type(xy).__name__}")
+
+    def ok(t):
+        contiguous = t.is_contiguous() if torch.is_tensor(t) else t.flags["C_CONTIGUOUS"]
+        f64 = t.dtype == (torch.float64 if torch.is_tensor(t) else np.float64)
+        return f64 and t.ndim == 2 and t.shape[1] == 2 and contiguous
+
+    if not ok(xy):
+        raise ValueError(f"reproject_points: contiguous float64 [N, 2] points expected, got {xy.dtype} "
+                         f"{tuple(xy.shape)}")
+    if out is not None:
+        if torch.is_tensor(out) != is_tensor or not ok(out) or tuple(out.shape) != tuple(xy.shape):
+            raise ValueError(f"reproject_points: out must be contiguous float64 {tuple(xy.shape)} of the kind of xy")
+        if is_tensor and out.device != xy.device:
+            raise ValueError("reproject_points: out must be on the device of xy")
+    if is_tensor and not xy.is_cuda:
+        raise ValueError("reproject_points: a CUDA tensor (or a numpy array) expected")
+    if xy.shape[0] == 0 or _crs.same(s, d):
+        if out is None or out is xy:
+            return xy
+        if is_tensor:
+            out.copy_(xy)
+        else:
+            out[...] = xy
+        return out
+    lib = _l.load()
+    if is_tensor:
+        src_d = xy
+        dst_d = torch.empty_like(xy) if out is None else out
+    else:
+        src_d = dst_d = torch.from_numpy(xy).to(torch.device("cuda", torch.cuda.current_device()))
+    if src_d.data_ptr() % 16 or dst_d.data_ptr() % 16:
+        raise ValueError("reproject_points: the points must be 16-byte aligned")
+    with torch.cuda.device(src_d.device):
+        _l.check(lib.ffa_crs_transform_f64(src_d.data_ptr(), dst_d.data_ptr(), int(xy.shape[0]), C.byref(_ffa_crs(s)),
+                                           C.byref(_ffa_crs(d)), _stream()), "crs_transform_f64")
+    if is_tensor:
+        return dst_d
+    res = dst_d.cpu().numpy()
+    if out is None:
+        return res
+    out[...] = res
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # U-TAE Sentinel branch (flair_hub/models/multitemp_model.py): small kernels around conv2d
 
 def reflect_pad1(x: torch.Tensor) -> torch.Tensor:

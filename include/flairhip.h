@@ -582,6 +582,44 @@ int ffa_zone_clip_u8(uint8_t* classes, const uint8_t* mask, const uint8_t* lut25
 int ffa_zone_window_counts(const uint8_t* mask, int H, int W, const int32_t* windows, int n_windows, int64_t* counts,
                            ffa_stream_t stream);
 
+/* ---- coordinate reference systems: points from one CRS to another (flair_zonal_detection/crs.py) ------------------ */
+/* One elementwise pass over float64 points in[n][2] = (x, y) -> out[n][2] (device memory, 16-byte aligned; in == out
+ * is allowed, partial overlap is not).  A transform is the source CRS's step to geodetic (longitude, latitude) in
+ * radians followed by the destination CRS's step from it; projected -> projected runs both in the one pass.
+ *
+ * FfaCrs (angles in degrees, lengths in metres; fields a method does not use are ignored):
+ *   FFA_CRS_GEOGRAPHIC  x = longitude, y = latitude in degrees (the always_xy order), nothing else is read
+ *   FFA_CRS_LCC2SP      Lambert conformal conic with two standard parallels lat1, lat2 (EPSG method 9802), origin
+ *                       (lon0, lat0), false easting / northing
+ *   FFA_CRS_TMERC       transverse Mercator (EPSG method 9807) by the Krueger series in the third flattening through
+ *                       n^6 (Karney 2011), origin (lon0, lat0), scale k0 on the central meridian
+ * with the ellipsoid (a, inv_flattening) of the CRS itself.
+ *
+ * Datum rule (normative).  Every supported CRS sits on GRS80 or WGS 84, and geodetic longitude and latitude are carried
+ * across unchanged between the two datums: the EPSG registry's RGF93 -> WGS 84 operation is the null transformation
+ * (as are the RGAF09 / RGR92 / RGFG95 / RGM04 / RGSPM06 ones), which is what PROJ applies for EPSG:2154 -> EPSG:4326.
+ * Each projection uses the ellipsoid of its own CRS.  Hence geographic -> geographic is the identity.
+ *
+ * The inverse latitude is the fixed point sin(lat) = tanh(psi + e atanh(e sin(lat))) of the isometric latitude psi,
+ * iterated a fixed 8 times (no data-dependent exit).  A point with a non-finite coordinate, a geographic latitude
+ * beyond +-90 degrees, a conic radius of 0 or a non-finite result comes out as (NaN, NaN); a thread reads and writes
+ * its own point only.  No atomics: equal inputs give equal bytes.  The constants derived from FfaCrs (eccentricity,
+ * cone constant, rectifying radius, series coefficients) are computed once per call on the host in float64. */
+#define FFA_CRS_GEOGRAPHIC 0
+#define FFA_CRS_LCC2SP 1
+#define FFA_CRS_TMERC 2
+typedef struct {
+  int kind;              /* FFA_CRS_* */
+  double a;              /* semi-major axis */
+  double inv_flattening; /* 298.257222101 (GRS80), 298.257223563 (WGS 84) */
+  double lon0, lat0;     /* origin: central meridian, latitude of origin */
+  double lat1, lat2;     /* standard parallels (LCC2SP) */
+  double k0;             /* scale factor on the central meridian (TMERC) */
+  double false_easting, false_northing;
+} FfaCrs;
+int ffa_crs_transform_f64(const double* in, double* out, long long n, const FfaCrs* src, const FfaCrs* dst,
+                          ffa_stream_t stream);
+
 /* ---- hardware layout probes (tests only) ---------------------------------------------------------- */
 int ffa_probe_tr16(const uint16_t* src, uint16_t* dst, ffa_stream_t stream);
 int ffa_probe_mfma(const float* A, const float* B, float* D, int use_f32, ffa_stream_t stream);

@@ -1,6 +1,6 @@
 """Polygonisation timings on synthetic class maps (GPU required).
 
-    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3] [--confidence] [--zone]
+    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3] [--confidence] [--zone] [--target-crs EPSG:4326]
 
 Maps: 'voronoi' (blocky nearest-seed map of 19 classes with 2 % label noise), 'checker' (checkerboard: every pixel a
 component, four boundary edges per pixel -- the worst case for edges), 'uniform' (one class: a single component over
@@ -18,6 +18,11 @@ map is rasterised (ffa_zone_mask_u8) and applied (ffa_zone_clip_u8), hip-event t
 next to the time the unavoidable traffic would take at the HBM rate (H W bytes of mask written, H W / 8 bytes of toggles
 written and read; 3 H W bytes for the clip), and the polygon count and host time (objects + GeoPackage) of the
 clipped map and of the whole one.
+With --target-crs one JSON line per --vertices count (default 4 M and 43 M, the range the maps above emit): Lambert-93
+vertices on a 0.2 m grid are reprojected to that CRS (ffa_crs_transform_f64, device resident, out of place):
+"reproject_ms" (hip events, best of --reps after a warm-up) next to the time the 32 bytes per vertex take at the HBM
+rate, the same for the inverse direction and for Lambert-93 -> UTM 31N (both projections in the one pass), and
+"reproject_host_ms", what ops.reproject_points costs for a numpy array (H2D, kernel, D2H; wall clock).
 Per-kernel times (count_kernel, the labelling kernels and zonal_sum_kernel of the same run side by side): run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_polygonize.py --confidence --device-only`.
 """
@@ -221,6 +226,48 @@ def run_zone(cls: np.ndarray, reps: int, device_only: bool = False) -> dict:
     return res
 
 
+def run_reproject(n: int, target_crs: str, reps: int) -> dict:
+    import torch
+    from flairhip import ops
+    dev = torch.device("cuda")
+    g = np.random.default_rng(0)
+    xy = np.empty((n, 2), np.float64)
+    xy[:, 0] = 651992.4 + 0.2 * g.integers(0, 200000, n)
+    xy[:, 1] = 6860417.8 - 0.2 * g.integers(0, 200000, n)
+    src = torch.from_numpy(xy).to(dev)
+    dst = torch.empty_like(src)
+    back = torch.empty_like(src)
+
+    def timed(a, b, s, d):
+        best = []
+        for rep in range(reps + 1):
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            ops.reproject_points(a, s, d, out=b)
+            e1.record()
+            torch.cuda.synchronize()
+            if rep:
+                best.append(e0.elapsed_time(e1))
+        return round(min(best), 4)
+
+    res = {"map": "reproject", "vertices": n, "target_crs": target_crs,
+           "reproject_ms": timed(src, dst, "EPSG:2154", target_crs),
+           "reproject_back_ms": timed(dst, back, target_crs, "EPSG:2154"),
+           "reproject_2154_to_32631_ms": timed(src, back, "EPSG:2154", "EPSG:32631"),
+           "reproject_ms_at_hbm_rate": round(32.0 * n / HBM_BYTES_PER_S * 1e3, 4)}
+    res["reproject_fraction_of_bound"] = round(res["reproject_ms_at_hbm_rate"] / res["reproject_ms"], 4)
+    ops.reproject_points(dst, target_crs, "EPSG:2154", out=back)
+    res["round_trip_max_m"] = float((back - src).abs().max())
+    host = []
+    for rep in range(reps + 1):
+        t0 = time.perf_counter()
+        ops.reproject_points(xy, "EPSG:2154", target_crs)
+        if rep:
+            host.append((time.perf_counter() - t0) * 1e3)
+    res["reproject_host_ms"] = round(min(host), 3)
+    return res
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[5000, 16384])
@@ -232,10 +279,17 @@ def main() -> None:
                     help="skip the host stages (simplifier, objects, GeoPackage: minutes on the checkerboard)")
     ap.add_argument("--zone", action="store_true",
                     help="voronoi maps only: time the zone mask + clip and the host stages with and without the zone")
+    ap.add_argument("--target-crs", type=str, default=None, metavar="EPSG:NNNN",
+                    help="time the reprojection of --vertices Lambert-93 vertices to this CRS instead of the maps")
+    ap.add_argument("--vertices", type=int, nargs="+", default=[4_000_000, 43_000_000])
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_polygonize needs an MI355X")
+    if args.target_crs:
+        for n in args.vertices:
+            print(json.dumps(run_reproject(n, args.target_crs, args.reps)), flush=True)
+        return
     if args.zone:
         for n in args.sizes:
             print(json.dumps(run_zone(voronoi(n), args.reps, args.device_only)), flush=True)
