@@ -532,7 +532,8 @@ extern "C" int ffa_ltae_attention_train(int dtype, const void* k, const void* v,
 // backward: one thread per (b, pixel, head).  a = prob * drop, out = sum_t a v:
 //   da[t] = <dout, v[t]> + dattn_ext[t] (what the aggregators send back to the returned masks), dv[t] = a[t] dout,
 //   dp = da * drop, ds[t] = prob[t] (dp[t] - sum prob dp), padded dates: score was replaced by a constant -> ds = 0,
-//   dk[t] = ds[t] Q[h] / temp, dQ[h] += sum ds[t] k[t] / temp  (per-block partial rows, summed by the caller)
+//   dk[t] = ds[t] Q[h] / temp, dQ[h] += sum ds[t] k[t] / temp  (per-block partial rows of n_head * d_k columns rounded up
+//   to a multiple of 8, summed by the caller)
 template <typename T>
 __global__ void __launch_bounds__(128) ltae_attention_bwd_kernel(
     const T* __restrict__ k, const T* __restrict__ v, const float* __restrict__ Q, const unsigned char* __restrict__ pad,
@@ -585,7 +586,9 @@ __global__ void __launch_bounds__(128) ltae_attention_bwd_kernel(
     for (int j = 0; j < DK; ++j) unsafeAtomicAdd(&sdq[h * DK + j], dqh[j]);  // ds_add_f32
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < NH * DK; i += blockDim.x) dq_partial[(long long)blockIdx.x * NH * DK + i] = sdq[i];
+  const int pitch = (NH * DK + 7) & ~7;  // rows padded with zeros to the 8 columns ffa_column_sums works in
+  for (int i = threadIdx.x; i < pitch; i += blockDim.x)
+    dq_partial[(long long)blockIdx.x * pitch + i] = i < NH * DK ? sdq[i] : 0.f;
 }
 
 extern "C" int ffa_ltae_attention_bwd_blocks(int B, int P, int n_head) {

@@ -1241,6 +1241,84 @@ def reproject_points(xy, src, dst, out=None):
 
 # --------------------------------------------------------------------------------------------------
 # U-TAE Sentinel branch (flair_hub/models/multitemp_model.py): small kernels around conv2d
+# The kernels index their small operands (pad flags, affine vectors, attention masks) without bounds of their own, so the
+# wrappers refuse what would make them read past the end.
+
+def _chk_pad(pad: torch.Tensor, n: int, ref: torch.Tensor, op: str) -> None:
+    if not (pad.dtype == torch.uint8 and pad.is_contiguous() and pad.numel() == n and pad.device == ref.device):
+        raise ValueError(f"{op}: pad must be a contiguous uint8 tensor of B * T = {n} elements on {ref.device}, got "
+                         f"{pad.dtype} {tuple(pad.shape)} on {pad.device}")
+
+
+def _chk_f32_vec(t: torch.Tensor, n: int, ref: torch.Tensor, op: str, name: str) -> None:
+    if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == ref.device):
+        raise ValueError(f"{op}: {name} must be contiguous f32 of {n} elements on {ref.device}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+
+
+def _chk_masks(t: Optional[torch.Tensor], shape, ref: torch.Tensor, op: str, name: str) -> None:
+    if t is None:
+        return
+    if not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and
+            t.device == ref.device):
+        raise ValueError(f"{op}: {name} must be contiguous f32 [n_head, B, T, h*w] = {list(shape)} on {ref.device}, got "
+                         f"{t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _chk_like(t: Optional[torch.Tensor], shape, ref: torch.Tensor, op: str, name: str) -> None:
+    if t is None:
+        return
+    if not (t.dtype == ref.dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == ref.device):
+        raise ValueError(f"{op}: {name} must be contiguous {ref.dtype} {list(shape)} on {ref.device}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+
+
+def _chk_group_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, op: str) -> int:
+    _chk_nhwc(x, f"{op} input")
+    C = x.shape[-1]
+    if groups <= 0 or C % groups:
+        raise ValueError(f"{op}: {C} channels do not split into {groups} groups")
+    _chk_f32_vec(gamma, C, x, op, "gamma")
+    _chk_f32_vec(beta, C, x, op, "beta")
+    return C
+
+
+def _chk_ltae(k: torch.Tensor, v: torch.Tensor, Q: torch.Tensor, pad: torch.Tensor, B: int, T: int, op: str):
+    _chk_nhwc(k, "ltae keys")
+    _chk_nhwc(v, "ltae values")
+    N, h, w, KC = k.shape
+    if Q.dim() != 2:
+        raise ValueError(f"{op}: Q must be [n_head, d_k], got {tuple(Q.shape)}")
+    n_head, d_k = Q.shape
+    _chk_f32_vec(Q, n_head * d_k, k, op, "Q")
+    if N != B * T:
+        raise ValueError(f"{op}: leading size {N} is not B * T = {B * T}")
+    if KC != n_head * d_k or v.shape[-1] % n_head or v.shape[:3] != k.shape[:3] or v.dtype != k.dtype:
+        raise ValueError(f"{op}: inconsistent shapes: keys {tuple(k.shape)} {k.dtype}, values {tuple(v.shape)} {v.dtype}, "
+                         f"Q {tuple(Q.shape)} (keys need n_head * d_k channels, values a multiple of n_head)")
+    _chk_pad(pad, N, k, op)
+    return h, w, n_head, d_k, v.shape[-1] // n_head
+
+
+def _chk_ltae_train(d_k: int, d_v: int, op: str) -> None:
+    if d_k > 8 or d_v > 32:
+        raise ValueError(f"{op}: d_k = {d_k}, d_v = {d_v} exceed the kernel's register arrays (d_k <= 8, d_v <= 32)")
+
+
+def _chk_aggregate(x: torch.Tensor, attn: torch.Tensor, pad: torch.Tensor, B: int, T: int, op: str) -> int:
+    _chk_nhwc(x, f"{op} input")
+    N, H, W, C = x.shape
+    if N != B * T:
+        raise ValueError(f"{op}: leading size {N} is not B * T = {B * T}")
+    if attn.dim() != 4:
+        raise ValueError(f"{op}: attn must be [n_head, B, T, h*w], got {tuple(attn.shape)}")
+    n_head = attn.shape[0]
+    if C % n_head:
+        raise ValueError(f"{op}: {C} channels do not split into {n_head} heads")
+    _chk_masks(attn, (n_head, B, T, H * W), x, op, "attn")
+    _chk_pad(pad, N, x, op)
+    return n_head
+
 
 def reflect_pad1(x: torch.Tensor) -> torch.Tensor:
     """[N,H,W,C] -> [N,H+2,W+2,C], reflect padding by one pixel (nn.Conv2d(padding_mode='reflect'))"""
@@ -1254,7 +1332,8 @@ def reflect_pad1(x: torch.Tensor) -> torch.Tensor:
 def group_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, relu: bool = False,
                residual: Optional[torch.Tensor] = None, eps: float = 1e-5) -> torch.Tensor:
     """nn.GroupNorm over each image of an NHWC tensor: y = [residual +] relu?(gn(x))"""
-    _chk_nhwc(x, "group_norm input")
+    _chk_group_norm(x, gamma, beta, groups, "group_norm")
+    _chk_like(residual, x.shape, x, "group_norm", "residual")
     N, H, W, C = x.shape
     y = torch.empty_like(x)
     _l.check(_l.load().ffa_group_norm(_dt(x), x.data_ptr(), _ptr(residual), y.data_ptr(), gamma.data_ptr(),
@@ -1267,10 +1346,10 @@ def group_norm_seq(x: torch.Tensor, B: int, T: int, gamma: torch.Tensor, beta: t
                    eps: float = 1e-5) -> torch.Tensor:
     """nn.GroupNorm over the T dates of every pixel: x is [B*T, h, w, C] (image n = b*T + t); statistics per
     (b, pixel, group) over T x C/groups values (LTAE2d.in_norm / out_norm with T = 1)"""
-    _chk_nhwc(x, "group_norm_seq input")
+    _chk_group_norm(x, gamma, beta, groups, "group_norm_seq")
     N, h, w, C = x.shape
     if N != B * T:
-        raise ValueError("group_norm_seq: leading size is not B * T")
+        raise ValueError(f"group_norm_seq: leading size {N} is not B * T = {B * T}")
     y = torch.empty_like(x)
     P = h * w
     _l.check(_l.load().ffa_group_norm(_dt(x), x.data_ptr(), None, y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
@@ -1299,13 +1378,7 @@ def add_rowvec_(x: torch.Tensor, vec: torch.Tensor) -> torch.Tensor:
 
 def ltae_attention(k: torch.Tensor, v: torch.Tensor, Q: torch.Tensor, pad: torch.Tensor, B: int, T: int):
     """-> (out [B,h,w,n_head*d_v], attn f32 [n_head,B,T,h*w]); k / v are [B*T,h,w,n_head*d_k / n_head*d_v]"""
-    _chk_nhwc(k, "ltae keys")
-    _chk_nhwc(v, "ltae values")
-    N, h, w, KC = k.shape
-    n_head, d_k = Q.shape
-    d_v = v.shape[-1] // n_head
-    if N != B * T or KC != n_head * d_k or v.shape[:3] != k.shape[:3]:
-        raise ValueError("ltae_attention: inconsistent shapes")
+    h, w, n_head, d_k, d_v = _chk_ltae(k, v, Q, pad, B, T, "ltae_attention")
     out = torch.empty((B, h, w, n_head * d_v), dtype=v.dtype, device=v.device)
     attn = torch.empty((n_head, B, T, h * w), dtype=torch.float32, device=v.device)
     _l.check(_l.load().ffa_ltae_attention(_dt(v), k.data_ptr(), v.data_ptr(), Q.data_ptr(), pad.data_ptr(),
@@ -1317,11 +1390,11 @@ def ltae_attention(k: torch.Tensor, v: torch.Tensor, Q: torch.Tensor, pad: torch
 def temporal_aggregate(x: torch.Tensor, attn: torch.Tensor, pad: torch.Tensor, B: int, T: int, use_pad: bool
                        ) -> torch.Tensor:
     """x [B*T,H,W,C], attn f32 [n_head,B,T,H*W] -> [B,H,W,C] (Temporal_Aggregator 'att_group')"""
-    _chk_nhwc(x, "aggregate input")
+    n_head = _chk_aggregate(x, attn, pad, B, T, "temporal_aggregate")
     N, H, W, C = x.shape
     out = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device)
     _l.check(_l.load().ffa_temporal_aggregate(_dt(x), x.data_ptr(), attn.data_ptr(), pad.data_ptr(), out.data_ptr(), B,
-                                              T, H * W, C, attn.shape[0], 1 if use_pad else 0, _stream()),
+                                              T, H * W, C, n_head, 1 if use_pad else 0, _stream()),
              "temporal_aggregate")
     return out
 
@@ -1337,7 +1410,11 @@ def detect_pad_images(x: torch.Tensor, value: float = 0.0) -> torch.Tensor:
 
 
 def mask_images_(x: torch.Tensor, pad: torch.Tensor, value: float = 0.0) -> torch.Tensor:
+    """x[n] = value in place for every image n with pad[n] != 0"""
+    if not (x.is_cuda and x.dim() >= 1 and x.is_contiguous()):
+        raise ValueError("mask_images: input must be a contiguous CUDA tensor [N, ...]")
     N = x.shape[0]
+    _chk_pad(pad, N, x, "mask_images")
     _l.check(_l.load().ffa_mask_images(_dt(x), x.data_ptr(), pad.data_ptr(), N, x.numel() // N, value, _stream()),
              "mask_images")
     return x
@@ -1627,26 +1704,32 @@ def _group_norm_bwd(x, dy, gamma, beta, groups, relu, geom, samples, eps):
 def group_norm_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int,
                    relu: bool = False, eps: float = 1e-5):
     """backward of group_norm (per image): -> (dx, dgamma, dbeta); a residual's gradient is dy itself"""
+    _chk_group_norm(x, gamma, beta, groups, "group_norm_bwd")
+    dy = dy.contiguous()
+    _chk_like(dy, x.shape, x, "group_norm_bwd", "dy")
     N, H, W, C = x.shape
-    return _group_norm_bwd(x, dy.contiguous(), gamma, beta, groups, relu, (1, H * W * C, 0, H * W, C), N, eps)
+    return _group_norm_bwd(x, dy, gamma, beta, groups, relu, (1, H * W * C, 0, H * W, C), N, eps)
 
 
 def group_norm_seq_bwd(x: torch.Tensor, dy: torch.Tensor, B: int, T: int, gamma: torch.Tensor, beta: torch.Tensor,
                        groups: int, eps: float = 1e-5):
     """backward of group_norm_seq (per pixel over the T dates)"""
+    _chk_group_norm(x, gamma, beta, groups, "group_norm_seq_bwd")
+    dy = dy.contiguous()
+    _chk_like(dy, x.shape, x, "group_norm_seq_bwd", "dy")
     N, h, w, C = x.shape
+    if N != B * T:
+        raise ValueError(f"group_norm_seq_bwd: leading size {N} is not B * T = {B * T}")
     P = h * w
-    return _group_norm_bwd(x, dy.contiguous(), gamma, beta, groups, False, (P, T * P * C, C, T, P * C), B * P, eps)
+    return _group_norm_bwd(x, dy, gamma, beta, groups, False, (P, T * P * C, C, T, P * C), B * P, eps)
 
 
 def ltae_attention_train(k: torch.Tensor, v: torch.Tensor, Q: torch.Tensor, pad: torch.Tensor, B: int, T: int,
                          drop: Optional[torch.Tensor] = None):
     """-> (out [B,h,w,n_head*d_v], attn f32 [n_head,B,T,h*w] after the attention dropout, prob: the clean softmax)"""
-    _chk_nhwc(k, "ltae keys")
-    _chk_nhwc(v, "ltae values")
-    N, h, w, KC = k.shape
-    n_head, d_k = Q.shape
-    d_v = v.shape[-1] // n_head
+    h, w, n_head, d_k, d_v = _chk_ltae(k, v, Q, pad, B, T, "ltae_attention_train")
+    _chk_ltae_train(d_k, d_v, "ltae_attention_train")
+    _chk_masks(drop, (n_head, B, T, h * w), k, "ltae_attention_train", "drop")
     out = torch.empty((B, h, w, n_head * d_v), dtype=v.dtype, device=v.device)
     attn = torch.empty((n_head, B, T, h * w), dtype=torch.float32, device=v.device)
     prob = torch.empty_like(attn)
@@ -1659,27 +1742,34 @@ def ltae_attention_train(k: torch.Tensor, v: torch.Tensor, Q: torch.Tensor, pad:
 def ltae_attention_bwd(k, v, Q, pad, drop, prob, dout, dattn_ext, B: int, T: int):
     """-> (dk, dv, dQ f32 [n_head, d_k])"""
     lib = _l.load()
-    N, h, w, KC = k.shape
-    n_head, d_k = Q.shape
-    d_v = v.shape[-1] // n_head
+    h, w, n_head, d_k, d_v = _chk_ltae(k, v, Q, pad, B, T, "ltae_attention_bwd")
+    _chk_ltae_train(d_k, d_v, "ltae_attention_bwd")
+    masks = (n_head, B, T, h * w)
+    _chk_masks(drop, masks, k, "ltae_attention_bwd", "drop")
+    _chk_masks(prob, masks, k, "ltae_attention_bwd", "prob")
+    _chk_masks(dattn_ext, masks, k, "ltae_attention_bwd", "dattn_ext")
+    _chk_like(dout, (B, h, w, n_head * d_v), v, "ltae_attention_bwd", "dout")
     dk, dv = torch.empty_like(k), torch.empty_like(v)
     nblk = lib.ffa_ltae_attention_bwd_blocks(B, h * w, n_head)
-    part = torch.empty((nblk, n_head * d_k), dtype=torch.float32, device=k.device)
+    pitch = (n_head * d_k + 7) // 8 * 8  # the kernel pads its rows with zeros to column_sums' 8 columns
+    part = torch.empty((nblk, pitch), dtype=torch.float32, device=k.device)
     _l.check(lib.ffa_ltae_attention_bwd(_dt(v), k.data_ptr(), v.data_ptr(), Q.data_ptr(), pad.data_ptr(), _ptr(drop),
                                         prob.data_ptr(), dout.data_ptr(), _ptr(dattn_ext), dk.data_ptr(), dv.data_ptr(),
                                         part.data_ptr(), B, T, h * w, n_head, d_k, d_v, _stream()), "ltae_attention_bwd")
-    dq = column_sums(part).view(n_head, d_k)
+    dq = column_sums(part)[:n_head * d_k].view(n_head, d_k)
     return dk, dv, dq
 
 
 def temporal_aggregate_bwd(x: torch.Tensor, attn: torch.Tensor, pad: torch.Tensor, dout: torch.Tensor, B: int, T: int,
                            use_pad: bool):
     """-> (dx like x, dattn f32 like attn)"""
+    n_head = _chk_aggregate(x, attn, pad, B, T, "temporal_aggregate_bwd")
     N, H, W, C = x.shape
+    _chk_like(dout, (B, H, W, C), x, "temporal_aggregate_bwd", "dout")
     dx = torch.empty_like(x)
     dattn = torch.empty_like(attn)
     _l.check(_l.load().ffa_temporal_aggregate_bwd(_dt(x), x.data_ptr(), attn.data_ptr(), pad.data_ptr(), dout.data_ptr(),
-                                                  dx.data_ptr(), dattn.data_ptr(), B, T, H * W, C, attn.shape[0],
+                                                  dx.data_ptr(), dattn.data_ptr(), B, T, H * W, C, n_head,
                                                   1 if use_pad else 0, _stream()), "temporal_aggregate_bwd")
     return dx, dattn
 

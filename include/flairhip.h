@@ -233,7 +233,8 @@ int ffa_ltae_attention_train(int dtype, const void* k, const void* v, const floa
                              const float* drop, void* out, float* attn, float* prob, int B, int T, int P, int n_head,
                              int d_k, int d_v, ffa_stream_t stream);
 /* its backward: dout [B][P][n_head*d_v], dattn_ext f32 [n_head][B][T][P] (nullable: gradient the aggregators send to the
- * returned masks) -> dk, dv (layouts of k, v) and dq_partial f32 [ffa_ltae_attention_bwd_blocks()][n_head*d_k] (rows to sum) */
+ * returned masks) -> dk, dv (layouts of k, v) and dq_partial f32 [ffa_ltae_attention_bwd_blocks()][n_head*d_k rounded up to a
+ * multiple of 8, zero-filled] (rows to sum, e.g. with ffa_column_sums) */
 int ffa_ltae_attention_bwd_blocks(int B, int P, int n_head);
 int ffa_ltae_attention_bwd(int dtype, const void* k, const void* v, const float* Q, const unsigned char* pad,
                            const float* drop, const float* prob, const void* dout, const float* dattn_ext, void* dk,
