@@ -55,6 +55,24 @@ def validate_geozone_crs(config: dict):
     return geozone_crs
 
 
+def validate_sieve_area(config: dict) -> float:
+    """The optional key sieve_area (default 0: off), in map units squared: before polygonisation, regions of the class
+    raster below that area are merged into their largest neighbour (raster_to_polygons(sieve_area=...)).  A number
+    >= 0 (or a string that reads as one), else ValueError."""
+    sieve_area = config.get("sieve_area", 0.0)
+    if sieve_area is None:
+        return 0.0
+    if isinstance(sieve_area, bool) or not isinstance(sieve_area, (int, float, str)):
+        raise ValueError(f"sieve_area must be a number >= 0, got {sieve_area!r}")
+    try:
+        value = float(sieve_area)
+    except ValueError:
+        raise ValueError(f"sieve_area must be a number >= 0, got {sieve_area!r}") from None
+    if not (value >= 0.0 and value != float("inf")):
+        raise ValueError(f"sieve_area must be a number >= 0, got {sieve_area!r}")
+    return value
+
+
 def validate_config(config: dict) -> None:
     for key in REQUIRED_KEYS:
         if key not in config:
@@ -62,6 +80,7 @@ def validate_config(config: dict) -> None:
     validate_write_confidence(config)
     validate_skip_tiles_outside_zone(config)
     validate_geozone_crs(config)
+    validate_sieve_area(config)
     if not os.path.isfile(config["model_weights"]):
         raise FileNotFoundError(f"Model weights not found at: {config['model_weights']}")
     os.makedirs(config["output_path"], exist_ok=True)

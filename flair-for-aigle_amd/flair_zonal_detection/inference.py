@@ -488,6 +488,15 @@ def min_pixels_for_area(min_area: float, pixel_area: float) -> int:
     return k
 
 
+def sieve_pixels_for_area(sieve_area, pixel_area: float) -> int:
+    """The sieve's pixel threshold for ``sieve_area`` (map units squared): components of fewer pixels are small.
+    0 (off) for an area of 0; a negative or non-finite area raises ValueError."""
+    area = float(sieve_area)
+    if not 0.0 <= area < float("inf"):
+        raise ValueError(f"sieve_area must be a number >= 0, got {sieve_area!r}")
+    return min_pixels_for_area(area, pixel_area) if area > 0 else 0
+
+
 def _bounds4(raster):
     b = raster.bounds
     return tuple(float(v) for v in ((b.left, b.bottom, b.right, b.top) if hasattr(b, "left") else tuple(b)[:4]))
@@ -510,15 +519,21 @@ def _confidence_source(tiff_path, confidence):
 
 def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, top: float, xres: float, yres: float,
                    crs, bg: Optional[int], min_pixels: int, simplification: float, n_jobs: Optional[int],
-                   zone=None, classes=None, zone_crs=None, target_crs=None):
-    """Shared tail of raster_to_polygons / vectorize_segmentation_parallel: zone clip and class filter on the device
-    copy of the raster (one ffa_zone_clip_u8 pass, only when asked for), GPU polygonisation (+ zonal sums of the
+                   zone=None, classes=None, zone_crs=None, target_crs=None, sieve_pixels: int = 0):
+    """Shared tail of raster_to_polygons / vectorize_segmentation_parallel: on the device copy of the raster the
+    sieve (ops.sieve_, only when ``sieve_pixels`` > 1), then zone clip and class filter (one ffa_zone_clip_u8 pass,
+    only when asked for), GPU polygonisation (+ zonal sums of the
     uint8 confidence plane), map coordinates, host simplification, reprojection of the kept vertices to
     ``target_crs`` (one ffa_crs_transform_f64 pass, only when asked for), frame."""
     from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
     dev = torch.device("cuda")
     values = None if conf is None else torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
     cls_dev = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+    if sieve_pixels > 1:
+        stats = ops.sieve_(cls_dev, int(sieve_pixels), background=bg)
+        logger.info("sieve: %d regions (%d pixels) below %d pixels merged into a neighbour in %d rounds, %d remain",
+                    stats["relabelled_components"], stats["relabelled_pixels"], int(sieve_pixels), stats["rounds"],
+                    stats["remaining_small"])
     if zone is not None or classes is not None:
         keep = None if classes is None else sorted({int(c) for c in classes})
         if keep is not None and not all(0 <= c <= 255 for c in keep):
@@ -572,7 +587,7 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
 
 def raster_to_polygons(tiff_path, ignore_background: bool = True, background_value: int = 18, min_area: float = 1.0,
                        simplification: float = 0.1, n_jobs: Optional[int] = None, confidence=None, zone=None,
-                       classes=None, zone_crs=None, target_crs=None):
+                       classes=None, zone_crs=None, target_crs=None, sieve_area: float = 0.0):
     """Vector polygons of a class raster -- the reference's raster_to_polygons (inference.py:377-413) with its
     signature and call form ``raster_to_polygons(output_files, n_jobs=4)``.
 
@@ -617,6 +632,16 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     through one pass of the GPU transform (ops.reproject_points; edges stay straight, as to_crs leaves them) and the
     frame's ``crs`` is the target.  class_id, confidence, pixels, polygon order and ring structure do not depend on
     ``target_crs``.  Either argument with a raster whose CRS is unknown raises ValueError; None changes nothing.
+
+    ``sieve_area`` (map units squared, default 0 = off): regions -- 4-connected components of equal class -- whose
+    area, pixel count * |xres * yres|, is below it are merged into their largest neighbour on the device copy of the
+    class plane (ops.sieve_; gdal_sieve's job) BEFORE the zone clip, the class filter and polygonisation.  ``min_area``
+    drops a small polygon and leaves its footprint as a hole of the polygon around it; the sieve makes a noise pixel of
+    class 3 inside a class-6 roof class 6, so it leaves no hole once ``classes=[6]`` is applied.  The area converts
+    to pixels as ``min_area`` does (min_pixels_for_area); ``ignore_background`` / ``background_value`` mean what they
+    mean for the polygoniser: background pixels never change and are never merged into.  The confidence raster is not
+    touched: a relabelled pixel contributes its own stored confidence to the polygon it joined.  The input raster is
+    not modified.  0 takes the code path without the sieve, with no new call.
     """
     src = _polygon_source(tiff_path)
     if src.count != 1:
@@ -644,7 +669,8 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     if bg is not None and not 0 <= bg <= 255:
         bg = None  # no uint8 pixel can hold it: every value is a class
     return _polygon_table(data, conf, left, top, xres, yres, getattr(src, "crs", None), bg, min_pixels, simplification,
-                          n_jobs, zone=zone, classes=classes, zone_crs=zone_crs, target_crs=target_crs)
+                          n_jobs, zone=zone, classes=classes, zone_crs=zone_crs, target_crs=target_crs,
+                          sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)))
 
 
 def logits_to_labels_and_confidence(probs):
@@ -707,8 +733,8 @@ def vectorize_segmentation_parallel(labels, confidence, transform, n_jobs: int =
     One deliberate departure: the reference takes ``confidence[mask].mean()`` over ALL pixels of a class and gives
     every polygon of that class the same number (:590-598); here each polygon gets the mean over its own pixels.
 
-    The signature is the reference's and stays so: clipping to a geozone and the class filter are arguments of
-    raster_to_polygons (``zone=``, ``classes=``)."""
+    The signature is the reference's and stays so: clipping to a geozone, the class filter and the sieve are
+    arguments of raster_to_polygons (``zone=``, ``classes=``, ``sieve_area=``)."""
     if torch.is_tensor(labels):
         labels = labels.detach().cpu().numpy()
     labels = np.asarray(labels)

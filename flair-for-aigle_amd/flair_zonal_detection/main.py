@@ -96,6 +96,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="also polygonise the written class raster (raster_to_polygons with the reference's "
                              "defaults) and write the polygons as a GeoPackage, with the columns confidence and pixels "
                              "when the config sets write_confidence; sharded runs: rank 0, after the merge")
+    parser.add_argument("--sieve-area", type=float, default=None, metavar="M2",
+                        help="with --polygons: before polygonisation, merge regions of the class raster below this "
+                             "area (map units squared) into their largest neighbour, so that speckle leaves neither "
+                             "polygons nor holes.  Default: the config key sieve_area, else 0 (off)")
     parser.add_argument("--zone", type=str, default=None, metavar="PATH.geojson",
                         help="geozone contour (GeoJSON, in the raster's CRS unless --zone-crs says otherwise): only its "
                              "bounding box is sliced (and, with skip_tiles_outside_zone in the config, only the tiles "
@@ -119,6 +123,10 @@ def main(argv=None) -> None:
         parser.error("--zone-crs needs --zone")
     if args.target_crs is not None and args.polygons is None:
         parser.error("--target-crs needs --polygons")
+    if args.sieve_area is not None and args.polygons is None:
+        parser.error("--sieve-area needs --polygons")
+    if args.sieve_area is not None and not 0.0 <= args.sieve_area < float("inf"):
+        parser.error(f"--sieve-area expects a number >= 0, got {args.sieve_area}")
     for opt, value in (("--zone-crs", args.zone_crs), ("--target-crs", args.target_crs)):
         if value is not None and not (opt == "--zone-crs" and value.strip().lower() == "auto"):
             from flair_zonal_detection import crs
@@ -146,8 +154,12 @@ def main(argv=None) -> None:
         if zone_crs is None and args.zone is not None:
             from flair_zonal_detection.config import load_config, validate_geozone_crs
             zone_crs = validate_geozone_crs(load_config(args.config))
+        sieve_area = args.sieve_area
+        if sieve_area is None:
+            from flair_zonal_detection.config import load_config, validate_sieve_area
+            sieve_area = validate_sieve_area(load_config(args.config))
         extra = {k: v for k, v in (("zone", args.zone), ("classes", classes), ("zone_crs", zone_crs),
-                                   ("target_crs", args.target_crs)) if v is not None}
+                                   ("target_crs", args.target_crs), ("sieve_area", sieve_area or None)) if v is not None}
         gdf = raster_to_polygons(outputs, **({"confidence": True} if with_conf else {}), **extra)
         gdf.to_file(args.polygons, driver="GPKG")
         logger.info("wrote %d polygons to %s", len(gdf), args.polygons)

@@ -6,6 +6,7 @@ every function launches on ``torch.cuda.current_stream()`` and returns immediate
 """
 from __future__ import annotations
 
+import logging
 import os
 
 import ctypes as C
@@ -15,6 +16,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import lib as _l
+
+logger = logging.getLogger(__name__)
 
 CH_ALIGN = 16
 
@@ -1076,6 +1079,68 @@ def polygon_simplify(xy, ring_vertex_offsets, poly_ring_offsets, tolerance: floa
         _l.check(lib.ffa_polygon_simplify(xy.ctypes.data, rvo.ctypes.data, pro.ctypes.data, P, float(tolerance),
                                           int(n_threads), keep.ctypes.data), "polygon_simplify")
     return keep.astype(bool)
+
+
+# --------------------------------------------------------------------------------------------------
+# sieve filter on a class raster (csrc/sieve.hip)
+
+def sieve_(classes: torch.Tensor, min_pixels: int, background: Optional[int] = None, max_rounds: int = 16) -> dict:
+    """In place over a device uint8 class map [H, W]: 4-connected components of fewer than ``min_pixels`` pixels take
+    the class of their greatest neighbour -- most pixels, at equal counts the smaller first pixel -- when that
+    neighbour is greater than they are (``background``: that value is no class, never changes and is never a target;
+    None: every value is a class).  The exact rule, one round of it, is ffa_sieve_round_u8's in include/flairhip.h;
+    rounds repeat until one relabels nothing or ``max_rounds`` have run (a warning is logged when the cap cut the
+    loop short).  The host reads four counters after each round.
+
+    Returns {"rounds": rounds run (the last, idle one included), "relabelled_components", "relabelled_pixels": sums
+    over the rounds, "remaining_small": small components in the raster as it is left -- at convergence those without
+    a greater neighbour}.  ``min_pixels`` <= 1 and an empty raster launch nothing."""
+    lib = _l.load()
+    if not (torch.is_tensor(classes) and classes.is_cuda and classes.dtype == torch.uint8 and classes.dim() == 2
+            and classes.is_contiguous()):
+        raise ValueError("sieve_: a contiguous CUDA uint8 [H, W] class map expected")
+    if int(min_pixels) < 0:
+        raise ValueError(f"sieve_: min_pixels {min_pixels} is negative")
+    if int(max_rounds) < 1:
+        raise ValueError(f"sieve_: max_rounds {max_rounds} is below 1")
+    if background is not None and not 0 <= int(background) <= 255:
+        raise ValueError(f"sieve_: background {background} is not a uint8 value")
+    H, W = classes.shape
+    if 4 * H * W >= 1 << 31:
+        raise ValueError(f"sieve_: a {H} x {W} raster exceeds the limit 4 * H * W < 2^31 (about 536 Mpx per call)")
+    out = {"rounds": 0, "relabelled_components": 0, "relabelled_pixels": 0, "remaining_small": 0}
+    if int(min_pixels) <= 1 or classes.numel() == 0:
+        return out
+    nbytes = lib.ffa_sieve_workspace_bytes(H, W)
+    if nbytes < 0:
+        _l.check(int(nbytes), "sieve_")
+    dev = classes.device
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    bg = -1 if background is None else int(background)
+
+    def one_round(target):
+        _l.check(lib.ffa_sieve_round_u8(target.data_ptr(), H, W, bg, int(min_pixels), ws.data_ptr(), int(nbytes),
+                                        counts.data_ptr(), _stream()), "sieve_round_u8")
+        return [int(v) for v in counts.cpu().tolist()]
+
+    moved = 0
+    while out["rounds"] < int(max_rounds):
+        small, comps, moved, _ = one_round(classes)
+        out["rounds"] += 1
+        out["relabelled_components"] += comps
+        out["relabelled_pixels"] += moved
+        out["remaining_small"] = small
+        if moved == 0:
+            break
+    if moved:
+        # The cap ended the loop: the small components of the raster as it is now are what one more round counts at
+        # its start.  The ABI has the one entry point, so that is a whole round (vote, decide, apply) on a throw-away
+        # copy: an extra H * W bytes and a round's time, paid only on this warning path, which is already the slow one.
+        out["remaining_small"] = one_round(classes.clone())[0]
+        logger.warning("sieve_: stopped after max_rounds = %d rounds while the last one still relabelled %d pixels; "
+                       "%d small components remain", int(max_rounds), moved, out["remaining_small"])
+    return out
 
 
 # --------------------------------------------------------------------------------------------------

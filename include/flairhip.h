@@ -547,6 +547,35 @@ int ffa_polygonize_zonal_sum_u8(const void* ws, long long ws_bytes, int H, int W
 int ffa_polygon_simplify(const double* xy, const int32_t* ring_offsets, const int32_t* poly_ring_offsets,
                          long long n_polys, double tolerance, int n_threads, uint8_t* keep);
 
+/* ---- sieve filter on a class raster (the gdal_sieve / rasterio.features.sieve companion of the polygoniser) -------- */
+/* In place over classes[H][W] (uint8, device): regions below a size are merged into their greatest neighbour, so the
+ * map stays a coverage with no gaps -- where ffa_polygonize_label(min_pixels) only drops them and leaves a hole.
+ * 4-connected like the polygoniser; exact and independent of the block schedule.
+ *
+ * Definition (normative).  A component is a 4-connected set of pixels of equal class that are not `background`
+ * (-1: every value is a class); its root is its smallest row-major pixel index (the polygoniser's label); it is small
+ * when it has fewer than min_pixels pixels.  Two components are neighbours when a pixel of one shares a side with a
+ * pixel of the other (corners do not count).  key(C) = (pixel count, -root), compared lexicographically: more pixels
+ * win, at equal counts the smaller root wins.  One call runs ONE round, every step on the state at its start:
+ *   1. label the raster, count the pixels per root;
+ *   2. for each small component S: best(S) = the neighbour of S with the greatest key (background is no neighbour);
+ *   3. S is relabelled when best(S) exists and key(best(S)) > key(S); its new class is the class best(S) had at the
+ *      start of the round, even when best(S) is small itself and relabelled in the same round;
+ *   4. all relabelled components are written at once.
+ * Background pixels never change and are never a target; a component that is not small at the start of a round keeps
+ * its class in that round.  The key travels as one unsigned 64-bit word, count << 32 | (0x7FFFFFFF - root), through a
+ * 64-bit atomicMax: the limit 4 * H * W < 2^31 keeps both fields in range, and a maximum does not depend on the order
+ * of its arguments, so equal inputs give equal bytes.
+ * counts_dev[4] (int64, device memory, written): components that were small at the start of the round, components
+ * relabelled, pixels relabelled, components in all (at the start).  The caller reads them and repeats the call until
+ * a round relabels nothing; each round that relabels something removes at least one component, so that ends.  A
+ * small component may remain at the end: one with no neighbour (alone in the raster or enclosed by background), or
+ * the greatest of its neighbourhood.  min_pixels <= 1: nothing is small, the call only labels and counts
+ * (counts_dev = 0, 0, 0, components).  Workspace contents are irrelevant on entry. */
+long long ffa_sieve_workspace_bytes(int H, int W); /* < 0 (FFA_ERR_ARG) beyond 4 * H * W < 2^31 */
+int ffa_sieve_round_u8(uint8_t* classes, int H, int W, int background, long long min_pixels, void* ws,
+                       long long ws_bytes, long long* counts_dev, ffa_stream_t stream);
+
 /* ---- geozone clipping on the pixel grid (flair_zonal_detection/zone.py, raster_to_polygons(zone=, classes=)) ------ */
 /* The reference clips its polygons to the zone contour in vector space (shapely intersection).  Here the zone is
  * rasterised on the class raster's own grid and applied before polygonisation: a pixel belongs to the zone when its

@@ -1,6 +1,7 @@
 """Polygonisation timings on synthetic class maps (GPU required).
 
-    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3] [--confidence] [--zone] [--target-crs EPSG:4326]
+    python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3] [--confidence] [--zone] [--sieve-area 0.2]
+        [--target-crs EPSG:4326]
 
 Maps: 'voronoi' (blocky nearest-seed map of 19 classes with 2 % label noise), 'checker' (checkerboard: every pixel a
 component, four boundary edges per pixel -- the worst case for edges), 'uniform' (one class: a single component over
@@ -23,6 +24,13 @@ vertices on a 0.2 m grid are reprojected to that CRS (ffa_crs_transform_f64, dev
 "reproject_ms" (hip events, best of --reps after a warm-up) next to the time the 32 bytes per vertex take at the HBM
 rate, the same for the inverse direction and for Lambert-93 -> UTM 31N (both projections in the one pass), and
 "reproject_host_ms", what ops.reproject_points costs for a numpy array (H2D, kernel, D2H; wall clock).
+With --sieve-area M2 one JSON line per voronoi size: the sieve (ffa_sieve_round_u8, regions below M2 at 0.2 m pixels
+merged into their largest neighbour) round by round, hip events around each call, per round the best of --reps after
+a warm-up: "round_ms", their number, "label_only_ms" (the same call with min_pixels = 1 on the input map: labels,
+counts and the root pass, no vote and no apply; "label_only_after_ms": on the sieved map), the round's algorithmic
+traffic (class map 1 B, labels 4 B written and three reads per pixel, best + new_class 9 B per component) and the
+rate the first round reaches on it, then polygons, rings, vertices and the host stages (objects, GeoPackage) of the
+map before and after.
 Per-kernel times (count_kernel, the labelling kernels and zonal_sum_kernel of the same run side by side): run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_polygonize.py --confidence --device-only`.
 """
@@ -226,6 +234,66 @@ def run_zone(cls: np.ndarray, reps: int, device_only: bool = False) -> dict:
     return res
 
 
+def run_sieve(cls: np.ndarray, reps: int, sieve_area: float, device_only: bool = False) -> dict:
+    import torch
+    from flairhip import lib as L
+    from flairhip import ops
+    from flair_zonal_detection.inference import sieve_pixels_for_area
+    lib = L.load()
+    H, W = cls.shape
+    dev = torch.device("cuda")
+    T = sieve_pixels_for_area(sieve_area, 0.2 * 0.2)
+    nbytes = int(lib.ffa_sieve_workspace_bytes(H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    x0 = torch.from_numpy(cls).to(dev)
+
+    def timed_round(x, min_pixels):
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+        L.check(lib.ffa_sieve_round_u8(x.data_ptr(), H, W, 18, min_pixels, ws.data_ptr(), nbytes, counts.data_ptr(), st))
+        e1.record()
+        c = counts.cpu().tolist()  # synchronises
+        return e0.elapsed_time(e1), c
+
+    per_rep, label_only, label_only_in, first = [], [], [], None
+    for rep in range(reps + 1):
+        x = x0.clone()
+        ms_in, _ = timed_round(x, 1)  # min_pixels = 1 moves nothing
+        times = []
+        while len(times) < 64:
+            ms, c = timed_round(x, T)
+            times.append(ms)
+            first = first or c
+            if c[2] == 0:
+                break
+        ms, _ = timed_round(x, 1)
+        if rep:
+            per_rep.append(times)
+            label_only.append(ms)
+            label_only_in.append(ms_in)
+    assert len({len(t) for t in per_rep}) == 1  # the same rounds every time
+    round_ms = [round(min(t[k] for t in per_rep), 4) for k in range(len(per_rep[0]))]
+    small, comps_moved, pixels_moved, comps = first
+    traffic = H * W * 17 + comps * 9
+    res = {"map": "voronoi+sieve", "H": H, "W": W, "sieve_area": sieve_area, "sieve_pixels": T,
+           "workspace_GB": round(nbytes / 1e9, 3), "rounds": len(round_ms), "round_ms": round_ms,
+           "label_only_ms": round(min(label_only_in), 4), "label_only_after_ms": round(min(label_only), 4),
+           "components": comps, "small_components": small,
+           "first_round_relabelled_components": comps_moved, "first_round_relabelled_pixels": pixels_moved,
+           "round_traffic_GB": round(traffic / 1e9, 4),
+           "first_round_TB_per_s": round(traffic / (round_ms[0] * 1e-3) / 1e12, 3),
+           "round_ms_at_hbm_rate": round(traffic / HBM_BYTES_PER_S * 1e3, 4)}
+    for name, t in (("before", x0), ("after", x)):
+        out = [a.cpu().numpy() for a in ops.polygonize(t, 18, 1)]
+        side = {"polygons": len(out[0]), "rings": len(out[3]) - 1, "vertices": len(out[4])}
+        if not device_only:
+            side.update({k: v for k, v in host_stage(out).items() if k != "polygons"})
+        res[name] = side
+    return res
+
+
 def run_reproject(n: int, target_crs: str, reps: int) -> dict:
     import torch
     from flairhip import ops
@@ -279,6 +347,8 @@ def main() -> None:
                     help="skip the host stages (simplifier, objects, GeoPackage: minutes on the checkerboard)")
     ap.add_argument("--zone", action="store_true",
                     help="voronoi maps only: time the zone mask + clip and the host stages with and without the zone")
+    ap.add_argument("--sieve-area", type=float, default=None, metavar="M2",
+                    help="voronoi maps only: time the sieve round by round and the stages after it with and without")
     ap.add_argument("--target-crs", type=str, default=None, metavar="EPSG:NNNN",
                     help="time the reprojection of --vertices Lambert-93 vertices to this CRS instead of the maps")
     ap.add_argument("--vertices", type=int, nargs="+", default=[4_000_000, 43_000_000])
@@ -289,6 +359,10 @@ def main() -> None:
     if args.target_crs:
         for n in args.vertices:
             print(json.dumps(run_reproject(n, args.target_crs, args.reps)), flush=True)
+        return
+    if args.sieve_area is not None:
+        for n in args.sizes:
+            print(json.dumps(run_sieve(voronoi(n), args.reps, args.sieve_area, args.device_only)), flush=True)
         return
     if args.zone:
         for n in args.sizes:
