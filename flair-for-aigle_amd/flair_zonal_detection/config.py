@@ -73,6 +73,33 @@ def validate_sieve_area(config: dict) -> float:
     return value
 
 
+COG_OVERVIEW_RESAMPLING = ("nearest", "mode", "average")
+
+
+def validate_cog_conversion(config: dict) -> bool:
+    """The key cog_conversion (default false) of every FLAIR-HUB zonal configuration: after the tile loop each written
+    raster ``<name>.tif`` is converted to the cloud-optimised ``<name>_COG.tif`` (overview pyramid, IFDs ahead of the
+    data) and removed."""
+    cog = config.get("cog_conversion", False)
+    if cog is None:
+        return False
+    if not isinstance(cog, bool):
+        raise ValueError(f"cog_conversion must be true or false, got {cog!r}")
+    return cog
+
+
+def validate_cog_overview_resampling(config: dict) -> str:
+    """The optional key cog_overview_resampling (default nearest, the reference's choice): how an overview pixel is
+    made from the 2 x 2 block under it.  'mode': class rasters take the most frequent class, confidence and
+    class-probability rasters the average; 'average': the rounded mean for every raster."""
+    method = config.get("cog_overview_resampling", "nearest")
+    if method is None:
+        return "nearest"
+    if not isinstance(method, str) or method.strip().lower() not in COG_OVERVIEW_RESAMPLING:
+        raise ValueError(f"cog_overview_resampling must be one of {', '.join(COG_OVERVIEW_RESAMPLING)}, got {method!r}")
+    return method.strip().lower()
+
+
 def validate_config(config: dict) -> None:
     for key in REQUIRED_KEYS:
         if key not in config:
@@ -81,6 +108,8 @@ def validate_config(config: dict) -> None:
     validate_skip_tiles_outside_zone(config)
     validate_geozone_crs(config)
     validate_sieve_area(config)
+    validate_cog_conversion(config)
+    validate_cog_overview_resampling(config)
     if not os.path.isfile(config["model_weights"]):
         raise FileNotFoundError(f"Model weights not found at: {config['model_weights']}")
     os.makedirs(config["output_path"], exist_ok=True)

@@ -16,6 +16,25 @@ surface as ``raster.ArrayRaster`` (which a real rasterio dataset also satisfies)
   ``close()`` encodes 256 x 256 blocks with the LZW codec of libflairhip on a thread pool and writes the file once
   (GDAL's own window writes re-append rewritten blocks; writing once keeps the file dense).
 
+* ``write_cog`` / ``validate_cog``: the cloud-optimised layout of the same raster with its overview pyramid (the
+  reference's ``convert_to_cog``, postprocess.py:33-52: GDAL's COG driver with LZW, blocksize 512, nearest overviews).
+
+COG layout (normative for ``write_cog``; ``validate_cog`` checks it):
+
+* the header, then ALL IFDs before any pixel data: IFD 0 for the full resolution, then one IFD per overview by
+  decreasing size, each IFD followed by its out-of-line tag values (tile offsets, byte counts, geo tags);
+* overview IFDs carry NewSubfileType (254) = 1 and no GeoTIFF tags; IFD 0 carries what ``GeoTiffWriter`` writes;
+* tiles are blocksize x blocksize, edge tiles zero-padded, multi-band rasters band-separate (PlanarConfiguration 2);
+* pixel data after the IFDs, smallest overview first, full resolution last; within an image band, then tile row, then
+  tile column.  The length of the IFD block depends on the tile counts only, so the tiles are encoded and written
+  behind it in one pass (a bounded number in flight) and the IFDs are filled in last;
+* GDAL's "ghost area" (the GDAL_STRUCTURAL_METADATA block after the header) is NOT written: it promises block leaders
+  and trailers that nothing here can check against GDAL.
+
+The file meets the layout requirements of the OGC Cloud Optimized GeoTIFF standard (tiled, overviews, IFDs ahead of the
+data); that GDAL's own validator (validate_cloud_optimized_geotiff.py) recognises it has not been verified, as GDAL is
+not available here.  ``validate_cog`` restates that validator's structural checks.
+
 The byte codecs (LZW, horizontal predictor) are C++ in csrc/tiff_codec.cpp behind ``ffa_tiff_*``.
 """
 from __future__ import annotations
@@ -38,6 +57,7 @@ Affine = namedtuple("Affine", ["a", "b", "c", "d", "e", "f"])  # x = a*col + b*r
 # tag ids
 _W, _H, _BITS, _COMP, _PHOTO, _STRIP_OFF, _SPP, _RPS, _STRIP_CNT = 256, 257, 258, 259, 262, 273, 277, 278, 279
 _PLANAR, _PREDICTOR, _TW, _TL, _TILE_OFF, _TILE_CNT, _EXTRA, _FORMAT = 284, 317, 322, 323, 324, 325, 338, 339
+_SUBFILE = 254
 _PIXSCALE, _TIEPOINT, _TRANSFORM, _GEOKEYS, _GEODOUBLES, _GEOASCII, _NODATA = 33550, 33922, 34264, 34735, 34736, 34737, 42113
 
 _TYPE = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("I", 4), 6: ("b", 1), 7: ("B", 1), 8: ("h", 2),
@@ -121,10 +141,15 @@ def _geokeys_for_epsg(epsg: int) -> Tuple[int, ...]:
 
 
 class GeoTiffRaster(RasterBase):
-    """Read-only, memory-mapped GeoTIFF (first image of the file; overviews are ignored)."""
+    """Read-only, memory-mapped GeoTIFF: the first image of the file, or with ``overview=k`` (k >= 1) its k-th
+    reduced-resolution image as a raster of its own (size of that image, resolution res * 2^k, same origin and CRS).
+    ``overview_count`` is the number of reduced-resolution images that follow the first one."""
 
-    def __init__(self, path: str, cache_bytes: int = 512 << 20):
+    def __init__(self, path: str, cache_bytes: int = 512 << 20, overview: int = 0):
         self.path = path
+        self.overview = int(overview)
+        if self.overview < 0:
+            raise GeoTiffError(f"{path}: overview={overview} is negative")
         self._cache: "OrderedDict[int, np.ndarray]" = OrderedDict()
         self._cache_bytes, self._cache_cap = 0, int(cache_bytes)
         self._f = open(path, "rb")
@@ -154,8 +179,12 @@ class GeoTiffRaster(RasterBase):
             raise GeoTiffError(f"{path}: bad TIFF magic {magic}")
         self._bo = bo
         try:
-            t, _ = _parse_ifd(mm, bo, big, ifd)
-            self._init_from_tags(t)
+            t, nxt = _parse_ifd(mm, bo, big, ifd)
+            ovr = self._overview_ifds(mm, bo, big, ifd, nxt)
+            self.overview_count = len(ovr)
+            if self.overview > len(ovr):
+                raise GeoTiffError(f"{path}: overview {self.overview} requested, the file has {len(ovr)}")
+            self._init_from_tags(ovr[self.overview - 1] if self.overview else t, t)
         except (struct.error, IndexError, KeyError) as e:  # truncated / inconsistent directory
             self.close()
             raise GeoTiffError(f"{path}: malformed TIFF directory ({type(e).__name__}: {e})") from e
@@ -163,7 +192,26 @@ class GeoTiffRaster(RasterBase):
             self.close()
             raise
 
-    def _init_from_tags(self, t: Dict[int, tuple]) -> None:
+    @staticmethod
+    def _overview_ifds(mm, bo: str, big: bool, first: int, nxt: int) -> List[Dict[int, tuple]]:
+        """tags of the reduced-resolution images (NewSubfileType bit 0 set, bit 2 clear) chained after the first IFD (a
+        plain file has none and costs nothing: its next-IFD offset is 0); the walk stops
+        at a malformed or repeated directory, which leaves the first image readable"""
+        out: List[Dict[int, tuple]] = []
+        seen = {first}
+        while nxt and nxt not in seen and len(seen) < 64:
+            seen.add(nxt)
+            try:
+                t, nxt = _parse_ifd(mm, bo, big, nxt)
+            except (struct.error, IndexError):
+                break
+            kind = int(t.get(_SUBFILE, (0,))[0])
+            if kind & 1 and not kind & 4 and _W in t and _H in t:  # bit 2: a transparency mask (GDAL's mask overviews)
+                out.append(t)
+        return out
+
+    def _init_from_tags(self, t: Dict[int, tuple], main: Optional[Dict[int, tuple]] = None) -> None:
+        """``t``: the image to read; ``main``: the first image, which carries the georeferencing of an overview"""
         path, bo = self.path, self._bo
         self.tags = t
         self.width, self.height = int(t[_W][0]), int(t[_H][0])
@@ -198,6 +246,7 @@ class GeoTiffRaster(RasterBase):
         want = self._nbx * self._nby * (self.count if self._planar == 2 else 1)
         if len(self._offs) != want or len(self._cnts) != want:
             raise GeoTiffError(f"{path}: {len(self._offs)} blocks listed, {want} expected")
+        t = main if main is not None else t
         # georeferencing: north-up only (what the tile grid of slicing.py assumes)
         if _PIXSCALE in t and _TIEPOINT in t:
             sx, sy = float(t[_PIXSCALE][0]), float(t[_PIXSCALE][1])
@@ -209,7 +258,7 @@ class GeoTiffRaster(RasterBase):
                 raise GeoTiffError(f"{path}: rotated / south-up rasters are not supported")
             self.left, self.top, self._xres, self._yres = m[3], m[7], m[0], -m[5]
         else:
-            self.left, self.top, self._xres, self._yres = 0.0, float(self.height), 1.0, 1.0  # rasterio's identity
+            self.left, self.top, self._xres, self._yres = 0.0, float(int(t[_H][0])), 1.0, 1.0  # rasterio's identity
         self.geokeys = tuple(int(v) for v in t.get(_GEOKEYS, ()))
         self.geoascii = t.get(_GEOASCII, ("",))[0]
         self.geodoubles = tuple(float(v) for v in t.get(_GEODOUBLES, ()))
@@ -220,6 +269,11 @@ class GeoTiffRaster(RasterBase):
             self.nodata = float(nd) if nd not in (None, "") else None
         except ValueError:
             self.nodata = None
+        if self.overview:  # same origin; pixels 2^k times the size when the image is ceil(size / 2^k), as write_cog's
+            # and GDAL's are, else by the ratio of the sizes (a foreign file with another decimation)
+            k, W0, H0 = self.overview, int(t[_W][0]), int(t[_H][0])
+            self._xres *= float(1 << k) if self.width == -(-W0 // (1 << k)) else W0 / self.width
+            self._yres *= float(1 << k) if self.height == -(-H0 // (1 << k)) else H0 / self.height
         self.closed = False
 
     # ---- rasterio-like attributes -------------------------------------------------------------------------
@@ -350,6 +404,120 @@ class GeoTiffRaster(RasterBase):
             self._f.close()
 
 
+# ---- writing: shared by GeoTiffWriter (IFD after the data) and write_cog (IFDs before the data) ------------------------
+
+def _needs_bigtiff(raw_bytes: int) -> bool:
+    return raw_bytes > (2 << 30)  # LZW can expand noise by 1.5x: stay clear of the 4 GB offsets
+
+
+def _check_classic_size(big: bool, end: int) -> None:
+    if not big and end > (1 << 32) - (1 << 20):
+        raise GeoTiffError("classic TIFF overflow: the compressed raster passed 4 GB")
+
+
+def _header(big: bool, first_ifd: int) -> bytes:
+    return b"II" + (struct.pack("<HHHQ", 43, 8, 0, first_ifd) if big else struct.pack("<HI", 42, first_ifd))
+
+
+def _encode_tile(job) -> bytes:
+    """(data [bands, H, W], block, compress, band, tile row, tile column) -> the encoded tile, edges zero-padded"""
+    data, B, compress, band, by, bx = job
+    blk = np.zeros((B, B), data.dtype)
+    src = data[band, by * B:(by + 1) * B, bx * B:(bx + 1) * B]
+    blk[:src.shape[0], :src.shape[1]] = src
+    if compress == "none":
+        return blk.tobytes()
+    if compress == "deflate":
+        return zlib.compress(blk.tobytes(), 6)
+    L = _codec()
+    flat = blk.reshape(-1).view(np.uint8)
+    cap = L.ffa_tiff_lzw_bound(flat.size)
+    out = np.empty(cap, np.uint8)
+    n = L.ffa_tiff_lzw_encode(flat.ctypes.data, flat.size, out.ctypes.data, cap)
+    if n <= 0:
+        raise GeoTiffError(f"LZW encode failed ({n})")
+    return out[:n].tobytes()
+
+
+def _tile_count(data, B: int) -> int:
+    return data.shape[0] * (-(-data.shape[1] // B)) * (-(-data.shape[2] // B))
+
+
+def _write_tiles(f, pos: int, data, B: int, compress: str) -> Tuple[List[int], List[int], int]:
+    """Encode the tiles of ``data`` (order: band, tile row, tile column) on the pool and write them at ``pos`` (the
+    file position of ``f``), each on an even offset; returns their offsets, byte counts and the position after them."""
+    nbx, nby = -(-data.shape[2] // B), -(-data.shape[1] // B)
+    jobs = [(data, B, compress, band, by, bx) for band in range(data.shape[0]) for by in range(nby) for bx in range(nbx)]
+    offs: List[int] = []
+    cnts: List[int] = []
+    for lo in range(0, len(jobs), 1024):  # bounded number of encoded blocks in flight
+        for enc in _pool().map(_encode_tile, jobs[lo:lo + 1024]):
+            f.write(enc)
+            offs.append(pos)
+            cnts.append(len(enc))
+            pos += len(enc)
+            if pos & 1:
+                f.write(b"\0")
+                pos += 1
+    return offs, cnts, pos
+
+
+def _image_entries(data, B: int, compress: str, offs: Sequence[int], cnts: Sequence[int], big: bool,
+                   reduced: bool = False) -> list:
+    """the (tag, type, values) entries that describe the pixels of one image"""
+    count, height, width = data.shape
+    LONGT = 16 if big else 4
+    kind = {"u": 1, "i": 2, "f": 3}[data.dtype.kind]
+    entries = [(_W, 4, (width,)), (_H, 4, (height,)), (_BITS, 3, (data.dtype.itemsize * 8,) * count),
+               (_COMP, 3, ({"none": 1, "lzw": 5, "deflate": 8}[compress],)), (_PHOTO, 3, (1,)),
+               (_SPP, 3, (count,)), (_PLANAR, 3, (2 if count > 1 else 1,)),
+               (_TW, 3, (B,)), (_TL, 3, (B,)), (_TILE_OFF, LONGT, tuple(offs)), (_TILE_CNT, LONGT, tuple(cnts)),
+               (_FORMAT, 3, (kind,) * count)]
+    if reduced:
+        entries.append((_SUBFILE, 4, (1,)))
+    if count > 1:
+        entries.append((_EXTRA, 3, (0,) * (count - 1)))
+    return entries
+
+
+def _geo_entries(xres: float, yres: float, left: float, top: float, geokeys, geodoubles, geoascii, nodata) -> list:
+    entries = [(_PIXSCALE, 12, (xres, yres, 0.0)), (_TIEPOINT, 12, (0.0, 0.0, 0.0, left, top, 0.0))]
+    if geokeys:
+        entries.append((_GEOKEYS, 3, tuple(geokeys)))
+    if geodoubles:
+        entries.append((_GEODOUBLES, 12, tuple(geodoubles)))
+    if geoascii:
+        entries.append((_GEOASCII, 2, geoascii))
+    if nodata is not None:
+        entries.append((_NODATA, 2, repr(nodata) if isinstance(nodata, float) else str(nodata)))
+    return entries
+
+
+def _pack_ifd(entries: list, ifd_off: int, big: bool, next_ifd: int = 0) -> bytes:
+    """The directory that starts at file offset ``ifd_off`` followed by its out-of-line values.  The length depends on
+    the entries' types and counts only, not on their values (so it is known before the tile offsets are)."""
+    entries = sorted(entries, key=lambda e: e[0])
+    inl, ofmt, cfmt, esz = (8, "Q", "Q", 20) if big else (4, "I", "I", 12)
+    table = 8 + len(entries) * esz + 8 if big else 2 + len(entries) * esz + 4
+    extra_pos = ifd_off + table
+    body, extra = b"", b""
+    for tag, typ, vals in entries:
+        if typ == 2:
+            payload = vals.encode("latin-1") + b"\0"
+            n = len(payload)
+        else:
+            payload = struct.pack("<" + _TYPE[typ][0] * len(vals), *vals)
+            n = len(vals)
+        if len(payload) <= inl:
+            field = payload.ljust(inl, b"\0")
+        else:
+            field = struct.pack("<" + ofmt, extra_pos + len(extra))
+            extra += payload + (b"\0" if len(payload) & 1 else b"")
+        body += struct.pack("<HH" + cfmt, tag, typ, n) + field
+    return (struct.pack("<Q", len(entries)) if big else struct.pack("<H", len(entries))) + body + \
+        struct.pack("<" + ofmt, next_ifd) + extra
+
+
 WRITTEN_SUFFIX = ".written.tif"  # sidecar mask of a sharded run's part file
 
 
@@ -408,94 +576,24 @@ class GeoTiffWriter(ArrayRaster):
                 "blockxsize": self.BLOCK, "blockysize": self.BLOCK,
                 "transform": Affine(self._res, 0.0, self.left, 0.0, -self._yres, self.top)}
 
-    def _encode(self, job) -> bytes:
-        band, by, bx = job
-        B = self.BLOCK
-        blk = np.zeros((B, B), self.data.dtype)
-        src = self.data[band, by * B:(by + 1) * B, bx * B:(bx + 1) * B]
-        blk[:src.shape[0], :src.shape[1]] = src
-        if self.compress == "none":
-            return blk.tobytes()
-        if self.compress == "deflate":
-            return zlib.compress(blk.tobytes(), 6)
-        L = _codec()
-        flat = blk.reshape(-1).view(np.uint8)
-        cap = L.ffa_tiff_lzw_bound(flat.size)
-        out = np.empty(cap, np.uint8)
-        n = L.ffa_tiff_lzw_encode(flat.ctypes.data, flat.size, out.ctypes.data, cap)
-        if n <= 0:
-            raise GeoTiffError(f"LZW encode failed ({n})")
-        return out[:n].tobytes()
-
     def close(self) -> None:
         if self.closed:
             return
         self.closed = True
         B = self.BLOCK
-        nbx, nby = -(-self.width // B), -(-self.height // B)
-        jobs = [(band, by, bx) for band in range(self.count) for by in range(nby) for bx in range(nbx)]
-        item = self.data.dtype.itemsize
-        big = self.data.nbytes > (2 << 30)  # LZW can expand noise by 1.5x: stay clear of the 4 GB offsets
-        kind = {"u": 1, "i": 2, "f": 3}[self.data.dtype.kind]
-        offs: List[int] = []
-        cnts: List[int] = []
+        big = _needs_bigtiff(self.data.nbytes)
         tmp = self.path + ".part"
         with open(tmp, "wb") as f:
-            f.write(b"II" + (struct.pack("<HHHQ", 43, 8, 0, 0) if big else struct.pack("<HI", 42, 0)))
-            pos = f.tell()
-            for lo in range(0, len(jobs), 1024):  # bounded number of encoded blocks in flight
-                for enc in _pool().map(self._encode, jobs[lo:lo + 1024]):
-                    f.write(enc)
-                    offs.append(pos)
-                    cnts.append(len(enc))
-                    pos += len(enc)
-                    if pos & 1:
-                        f.write(b"\0")
-                        pos += 1
-            if not big and pos > (1 << 32) - (1 << 20):
-                raise GeoTiffError("classic TIFF overflow: the compressed raster passed 4 GB")
+            f.write(_header(big, 0))
+            offs, cnts, pos = _write_tiles(f, f.tell(), self.data, B, self.compress)
+            _check_classic_size(big, pos)
             # ---- the IFD, after the pixel data ----
-            LONGT = 16 if big else 4
-            entries = [(_W, 4, (self.width,)), (_H, 4, (self.height,)), (_BITS, 3, (item * 8,) * self.count),
-                       (_COMP, 3, ({"none": 1, "lzw": 5, "deflate": 8}[self.compress],)), (_PHOTO, 3, (1,)),
-                       (_SPP, 3, (self.count,)), (_PLANAR, 3, (2 if self.count > 1 else 1,)),
-                       (_TW, 3, (B,)), (_TL, 3, (B,)), (_TILE_OFF, LONGT, tuple(offs)), (_TILE_CNT, LONGT, tuple(cnts)),
-                       (_FORMAT, 3, (kind,) * self.count),
-                       (_PIXSCALE, 12, (self._res, self._yres, 0.0)),
-                       (_TIEPOINT, 12, (0.0, 0.0, 0.0, self.left, self.top, 0.0))]
-            if self.count > 1:
-                entries.append((_EXTRA, 3, (0,) * (self.count - 1)))
-            if self.geokeys:
-                entries.append((_GEOKEYS, 3, self.geokeys))
-            if self.geodoubles:
-                entries.append((_GEODOUBLES, 12, self.geodoubles))
-            if self.geoascii:
-                entries.append((_GEOASCII, 2, self.geoascii))
-            if self.nodata is not None:
-                entries.append((_NODATA, 2, repr(self.nodata) if isinstance(self.nodata, float) else str(self.nodata)))
-            entries.sort(key=lambda e: e[0])
-            inl, ofmt, cfmt, esz = (8, "Q", "Q", 20) if big else (4, "I", "I", 12)
-            ifd_off = pos
-            table = 8 + len(entries) * esz + 8 if big else 2 + len(entries) * esz + 4
-            extra_pos = ifd_off + table
-            body, extra = b"", b""
-            for tag, typ, vals in entries:
-                if typ == 2:
-                    payload = vals.encode("latin-1") + b"\0"
-                    n = len(payload)
-                else:
-                    payload = struct.pack("<" + _TYPE[typ][0] * len(vals), *vals)
-                    n = len(vals)
-                if len(payload) <= inl:
-                    field = payload.ljust(inl, b"\0")
-                else:
-                    field = struct.pack("<" + ofmt, extra_pos + len(extra))
-                    extra += payload + (b"\0" if len(payload) & 1 else b"")
-                body += struct.pack("<HH" + cfmt, tag, typ, n) + field
-            f.write((struct.pack("<Q", len(entries)) if big else struct.pack("<H", len(entries))) + body +
-                    struct.pack("<" + ofmt, 0) + extra)
+            entries = _image_entries(self.data, B, self.compress, offs, cnts, big) + \
+                _geo_entries(self._res, self._yres, self.left, self.top, self.geokeys, self.geodoubles, self.geoascii,
+                             self.nodata)
+            f.write(_pack_ifd(entries, pos, big))
             f.seek(8 if big else 4)
-            f.write(struct.pack("<" + ofmt, ifd_off))
+            f.write(struct.pack("<Q" if big else "<I", pos))
         os.replace(tmp, self.path)
         if self.written is not None:  # sharded run: the pixels this rank wrote, for merge_shard_files
             m = GeoTiffWriter.like(self.path + WRITTEN_SUFFIX, self, 1)
@@ -535,3 +633,150 @@ def merge_shard_files(part_paths: Sequence[str], out_path: str, rows_per_pass: i
         for r in parts + masks:
             r.close()
     return out_path
+
+
+# ---- cloud-optimised GeoTIFF -----------------------------------------------------------------------------------------
+
+def write_cog(path: str, levels: Sequence[np.ndarray], left: float, top: float, res, crs: Optional[str] = None,
+              blocksize: int = 512, compress: Optional[str] = "lzw", geokeys: Sequence[int] = (), geoascii: str = "",
+              geodoubles: Sequence[float] = (), nodata=None) -> str:
+    """Cloud-optimised GeoTIFF of ``levels[0]`` ([bands, H, W]) with ``levels[1:]`` as its overviews (each no larger
+    than the one before, same band count and dtype); the layout is the module docstring's.  Written to ``path`` +
+    ".part" and renamed, like GeoTiffWriter."""
+    if compress not in (None, "none", "lzw", "deflate", "LZW", "DEFLATE", "NONE"):
+        raise GeoTiffError(f"compress={compress!r} is not supported (none / lzw / deflate are)")
+    compress = (compress or "none").lower()
+    B = int(blocksize)
+    if B < 16 or B % 16:
+        raise GeoTiffError(f"blocksize={blocksize} is not a positive multiple of 16 (TIFF 6.0 tiles)")
+    levels = [lv[None] if lv.ndim == 2 else lv for lv in levels]
+    if not levels or any(lv.ndim != 3 or lv.size == 0 for lv in levels):
+        raise GeoTiffError("write_cog: levels must be non-empty [bands, H, W] arrays, the full resolution first")
+    for k in range(1, len(levels)):
+        a, b = levels[k - 1], levels[k]
+        if b.shape[0] != a.shape[0] or b.dtype != a.dtype or b.shape[1] > a.shape[1] or b.shape[2] > a.shape[2]:
+            raise GeoTiffError(f"write_cog: overview {k} {b.shape} {b.dtype} does not follow {a.shape} {a.dtype}")
+    xres, yres = (res if isinstance(res, (tuple, list)) else (res, res))
+    geokeys = tuple(int(v) for v in geokeys)
+    if not geokeys and crs and str(crs).upper().startswith("EPSG:"):
+        geokeys = _geokeys_for_epsg(int(str(crs).split(":")[1]))
+    big = _needs_bigtiff(sum(lv.nbytes for lv in levels))
+
+    def entries(k: int, offs, cnts) -> list:
+        e = _image_entries(levels[k], B, compress, offs, cnts, big, reduced=k > 0)
+        if k == 0:
+            e += _geo_entries(float(xres), float(yres), float(left), float(top), geokeys, geodoubles, geoascii, nodata)
+        return e
+
+    # IFD positions: their lengths do not depend on the offsets they will hold
+    ifd_offs, pos = [], 16 if big else 8
+    for k in range(len(levels)):
+        ifd_offs.append(pos)
+        n = _tile_count(levels[k], B)
+        pos += len(_pack_ifd(entries(k, (0,) * n, (0,) * n), pos, big))
+    tmp = path + ".part"
+    with open(tmp, "wb") as f:
+        f.seek(pos)
+        tiles = {}
+        for k in reversed(range(len(levels))):  # smallest overview first, full resolution last
+            offs, cnts, pos = _write_tiles(f, pos, levels[k], B, compress)
+            tiles[k] = (offs, cnts)
+        _check_classic_size(big, pos)
+        f.seek(0)
+        f.write(_header(big, ifd_offs[0]))
+        for k in range(len(levels)):
+            nxt = ifd_offs[k + 1] if k + 1 < len(levels) else 0
+            f.write(_pack_ifd(entries(k, *tiles[k]), ifd_offs[k], big, nxt))
+    os.replace(tmp, path)
+    return path
+
+
+def _ifd_end(buf, bo: str, big: bool, off: int) -> int:
+    """first byte after the IFD at ``off`` and after its out-of-line values"""
+    n = struct.unpack_from(bo + ("Q" if big else "H"), buf, off)[0]
+    pos, esz, inl, cfmt = (off + 8, 20, 8, "Q") if big else (off + 2, 12, 4, "I")
+    end = pos + n * esz + (8 if big else 4)
+    for k in range(n):
+        e = pos + k * esz
+        _, typ = struct.unpack_from(bo + "HH", buf, e)
+        (cnt,) = struct.unpack_from(bo + cfmt, buf, e + 4)
+        nbytes = cnt * _TYPE.get(typ, ("B", 1))[1] * (2 if typ in (5, 10) else 1)
+        if nbytes > inl:
+            (voff,) = struct.unpack_from(bo + cfmt, buf, e + 4 + struct.calcsize(cfmt))
+            end = max(end, voff + nbytes)
+    return end
+
+
+def validate_cog(path: str) -> List[str]:
+    """The structural checks of GDAL's validate_cloud_optimized_geotiff.py, restated: the list of errors, empty when
+    ``path`` is a cloud-optimised GeoTIFF.  (The ghost area and the block leaders it announces are not looked at.)"""
+    errors: List[str] = []
+    with open(path, "rb") as f:
+        try:
+            mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        except ValueError:
+            return ["empty file"]
+        try:
+            if bytes(mm[:2]) not in (b"II", b"MM"):
+                return ["not a TIFF file"]
+            bo = "<" if bytes(mm[:2]) == b"II" else ">"
+            (magic,) = struct.unpack_from(bo + "H", mm, 2)
+            if magic not in (42, 43):
+                return [f"bad TIFF magic {magic}"]
+            big = magic == 43
+            (off,) = struct.unpack_from(bo + "Q", mm, 8) if big else struct.unpack_from(bo + "I", mm, 4)
+            header = 16 if big else 8
+            if off != header:
+                errors.append(f"the first IFD is at offset {off}, not directly after the {header}-byte header")
+            ifds = []  # (offset, end, tags)
+            seen = set()
+            while off and off not in seen and len(seen) < 64:
+                seen.add(off)
+                t, nxt = _parse_ifd(mm, bo, big, off)
+                ifds.append((off, _ifd_end(mm, bo, big, off), t))
+                off = nxt
+        except (struct.error, IndexError) as e:
+            return errors + [f"malformed TIFF directory ({type(e).__name__}: {e})"]
+        finally:
+            mm.close()
+    if not ifds:
+        return errors + ["the file has no image directory (first IFD offset 0)"]
+    for k, (off, _, t) in enumerate(ifds):
+        for tag, name in ((_W, "ImageWidth"), (_H, "ImageLength")):
+            if not t.get(tag):
+                errors.append(f"IFD {k} (offset {off}) has no {name}")
+    if any("has no Image" in e for e in errors):
+        return errors
+    main = ifds[0][2]
+    images = [ifds[0]] + [d for d in ifds[1:] if int(d[2].get(_SUBFILE, (0,))[0]) & 5 == 1]
+    W, H = int(main[_W][0]), int(main[_H][0])
+    if _TW not in main:
+        errors.append("the full-resolution image is not tiled")
+        bw = bh = 512
+    else:
+        bw, bh = int(main[_TW][0]), int(main[_TL][0])
+    if (W > bw or H > bh) and len(images) == 1:
+        errors.append(f"the image is {W} x {H}, larger than one {bw} x {bh} block, and has no overviews")
+    first_tile = []
+    for k, (off, end, t) in enumerate(images):
+        name = "the full-resolution image" if k == 0 else f"overview {k}"
+        if k and _TW not in t:
+            errors.append(f"{name} is not tiled")
+        if k:
+            pw, ph = int(images[k - 1][2][_W][0]), int(images[k - 1][2][_H][0])
+            if int(t[_W][0]) > pw or int(t[_H][0]) > ph:
+                errors.append(f"{name} ({t[_W][0]} x {t[_H][0]}) is larger than the image before it ({pw} x {ph})")
+            if off <= images[k - 1][0]:
+                errors.append(f"the IFD of {name} (offset {off}) does not follow the one before it ({images[k - 1][0]})")
+        offs = [int(o) for o in t.get(_TILE_OFF, t.get(_STRIP_OFF, ())) if int(o) > 0]
+        first_tile.append(min(offs) if offs else None)
+    data = [o for o in first_tile if o is not None]
+    for k, (off, end, _) in enumerate(ifds):
+        if data and end > min(data):
+            errors.append(f"IFD {k} (bytes {off} .. {end}) does not lie before the first pixel data ({min(data)})")
+    for k in range(1, len(images)):
+        a, b = first_tile[k - 1], first_tile[k]  # a: the larger image
+        if a is not None and b is not None and not a > b:
+            errors.append(f"the pixel data of overview {k} (offset {b}) does not precede that of the image before it "
+                          f"({a}): smaller overviews must come first, the full resolution last")
+    return errors

@@ -18,8 +18,9 @@ Polygonisation of the written raster (raster_to_polygons, reference :359-413) ru
 of the fork's postprocess_results happen on the pixel grid before polygonisation (``raster_to_polygons(zone=, classes=)``,
 csrc/zone_mask.hip, zone.py), and with the config key ``skip_tiles_outside_zone`` the tile loop leaves out the tiles
 that hold no zone pixel.  A zone in another CRS than the raster's (``geozone_crs`` / ``zone_crs``) and polygons wanted in
-another one (``target_crs``) are reprojected on the GPU (csrc/crs_transform.hip, crs.py).  COG conversion is product
-glue and is not provided.
+another one (``target_crs``) are reprojected on the GPU (csrc/crs_transform.hip, crs.py).  With the config key
+``cog_conversion`` the written rasters become cloud-optimised GeoTIFFs (postpro_outputs, reference :633-641): the overview
+pyramid comes from the GPU (csrc/overview.hip), the file layout from geotiff.write_cog.
 
 Per-polygon confidence (the column the fork's driver fills with random numbers, scripts/
 run_fast_aigle_segmentation.py:162-163, and its unused second path :566-630 means to compute): with the config key
@@ -41,12 +42,12 @@ import torch
 from torch.utils.data import DataLoader
 
 from flairhip import ops
-from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_config,
-                                          validate_geozone_crs, validate_skip_tiles_outside_zone,
-                                          validate_write_confidence)
+from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_cog_conversion,
+                                          validate_cog_overview_resampling, validate_config, validate_geozone_crs,
+                                          validate_skip_tiles_outside_zone, validate_write_confidence)
 from flair_zonal_detection.dataset import MultiModalSlicedDataset, TileBatcher, pad_series_collate
 from flair_zonal_detection.model_utils import build_inference_model, compute_patch_sizes
-from flair_zonal_detection.postprocess import convert  # noqa: F401  (re-exported like the reference)
+from flair_zonal_detection.postprocess import convert, convert_to_cog  # noqa: F401  (re-exported like the reference)
 from flair_zonal_detection.raster import ArrayRaster, make_window, open_raster
 from flair_zonal_detection.slicing import generate_patches_from_reference
 
@@ -394,6 +395,26 @@ def drop_tiles_outside_zone(tiles, ref_img, geozone):
     return tiles[keep].reset_index(drop=True)
 
 
+def postpro_outputs(temp_paths: Dict[str, str], config: Dict) -> Dict[str, str]:
+    """The reference's postpro_outputs (inference.py:633-641): with ``cog_conversion`` every written raster ``p`` of
+    ``temp_paths`` ({output key: path}) is converted to the cloud-optimised ``p.replace(".tif", "_COG.tif")`` and
+    removed.  Returns {output key: the path the raster now has}.  Overviews by ``cog_overview_resampling``: nearest
+    (default) or average for every raster; with mode the class rasters take the mode, the confidence and
+    class-probability rasters the average."""
+    paths = dict(temp_paths)
+    if not validate_cog_conversion(config):
+        return paths
+    method = validate_cog_overview_resampling(config)
+    for key, temp_path in temp_paths.items():
+        classes = config.get("output_type", "argmax") == "argmax" and not str(key).endswith(CONFIDENCE_SUFFIX)
+        cog_path = temp_path.replace(".tif", "_COG.tif")  # the reference's naming; convert_to_cog refuses a name it leaves as it is
+        t0 = time.time()
+        convert_to_cog(temp_path, cog_path, overview_resampling="average" if method == "mode" and not classes else method)
+        logger.info("converted to COG in %.1f s: %s", time.time() - t0, cog_path)
+        paths[key] = cog_path
+    return paths
+
+
 def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tuple[int, int]] = None,
                   before_loop=None, geozone_crs=None) -> Dict[str, object]:
     """End-to-end zonal run with upstream FLAIR-HUB's one-argument semantics (the fork's own run_inference is
@@ -441,6 +462,17 @@ def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tu
                 o.track_writes()
     inference_and_write(model, loader, tiles, config, outputs, ref_img)
     logger.info("zonal inference of %d tiles took %.1f s", len(tiles), time.time() - t0)
+    if validate_cog_conversion(config):
+        from flair_zonal_detection.geotiff import GeoTiffWriter
+        files = {k: o.path for k, o in outputs.items() if isinstance(o, GeoTiffWriter)}
+        if shard is not None:
+            logger.info("cog_conversion: the part files of a sharded run are not converted; the conversion follows "
+                        "merge_shard_files")
+        elif files:
+            for key, path in postpro_outputs(files, config).items():
+                outputs[key].path = path  # raster_to_polygons(outputs) reads the file that now exists
+        else:
+            logger.info("cog_conversion: in-memory outputs are left as they are")
     return outputs
 
 

@@ -100,6 +100,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="with --polygons: before polygonisation, merge regions of the class raster below this "
                              "area (map units squared) into their largest neighbour, so that speckle leaves neither "
                              "polygons nor holes.  Default: the config key sieve_area, else 0 (off)")
+    parser.add_argument("--cog", action="store_true",
+                        help="convert the written rasters to cloud-optimised GeoTIFFs (<name>_COG.tif: overview "
+                             "pyramid, IFDs ahead of the data), as the config key cog_conversion: true does; overviews "
+                             "by the config key cog_overview_resampling (nearest, mode or average)")
     parser.add_argument("--zone", type=str, default=None, metavar="PATH.geojson",
                         help="geozone contour (GeoJSON, in the raster's CRS unless --zone-crs says otherwise): only its "
                              "bounding box is sliced (and, with skip_tiles_outside_zone in the config, only the tiles "
@@ -140,12 +144,17 @@ def main(argv=None) -> None:
         parser.error(f"--classes expects comma-separated integers, got {args.classes!r}")
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    config = args.config
+    if args.cog:  # the key, for this run only
+        from flair_zonal_detection.config import load_config
+        config = load_config(args.config)
+        config["cog_conversion"] = True
     if world > 1:
-        outputs = run_sharded(args.config, int(os.environ.get("RANK", "0")), world, keep_parts=args.keep_parts,
+        outputs = run_sharded(config, int(os.environ.get("RANK", "0")), world, keep_parts=args.keep_parts,
                               geozone=args.zone, geozone_crs=args.zone_crs)
     else:
         from flair_zonal_detection.inference import run_inference
-        outputs = run_inference(args.config, geozone=args.zone, geozone_crs=args.zone_crs)
+        outputs = run_inference(config, geozone=args.zone, geozone_crs=args.zone_crs)
     if args.polygons and outputs is not None:
         from flair_zonal_detection.inference import raster_to_polygons
         # a write_confidence run also returns f"{task}_confidence" rasters: the polygons then carry their mean

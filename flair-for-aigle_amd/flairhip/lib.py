@@ -185,6 +185,9 @@ SIGNATURES = {
     "ffa_zone_clip_u8": (_i, [_p, _p, _p, _ll, _i, _p]),
     "ffa_zone_window_counts": (_i, [_p, _i, _i, _p, _i, _p, _p]),
     "ffa_crs_transform_f64": (_i, [_p, _p, _ll, C.POINTER(Crs), C.POINTER(Crs), _p]),
+    "ffa_overview_levels": (_i, [_i, _i, _i]),
+    "ffa_overview_pyramid_bytes": (_ll, [_i, _i, _i, _i]),
+    "ffa_overview_pyramid_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "ffa_probe_tr16": (_i, [_p, _p, _p]),
     "ffa_probe_mfma": (_i, [_p, _p, _p, _i, _p]),
 }

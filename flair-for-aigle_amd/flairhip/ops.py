@@ -1237,6 +1237,60 @@ def zone_window_counts(mask: torch.Tensor, windows) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------------------
+# overview pyramid of a uint8 raster (csrc/overview.hip)
+
+OVERVIEW_METHODS = {"nearest": 0, "mode": 1, "average": 2}
+
+
+def overview_levels(H: int, W: int, block: int = 512) -> int:
+    """Number of overviews of an H x W raster: the smallest L with max(ceil(H / 2^L), ceil(W / 2^L)) <= block."""
+    if int(H) < 1 or int(W) < 1 or int(block) < 1:
+        raise ValueError(f"overview_levels: raster {H} x {W}, block {block} outside 1 <= H, W, block")
+    return int(_l.load().ffa_overview_levels(int(H), int(W), int(block)))
+
+
+def overview_pyramid(base: torch.Tensor, block: int = 512, method: str = "nearest", ignore: Optional[int] = None):
+    """Overviews of a device uint8 raster [bands, H, W]: the list of the levels 1 .. L, level l of shape
+    [bands, ceil(H / 2^l), ceil(W / 2^l)], each halving the one before by ``method`` ("nearest", "mode", "average")
+    over 2 x 2 blocks; L = overview_levels(H, W, block).  ``ignore`` (mode only): a value
+    that does not vote.  The exact rule is ffa_overview_pyramid_u8's in include/flairhip.h.  The levels are views into
+    one allocation; a raster that fits one block gives an empty list."""
+    lib = _l.load()
+    if not (torch.is_tensor(base) and base.is_cuda and base.dtype == torch.uint8 and base.dim() == 3
+            and base.is_contiguous()):
+        raise ValueError("overview_pyramid: a contiguous CUDA uint8 [bands, H, W] raster expected")
+    if method not in OVERVIEW_METHODS:
+        raise ValueError(f"overview_pyramid: method {method!r} is not one of {sorted(OVERVIEW_METHODS)}")
+    if ignore is not None and not 0 <= int(ignore) <= 255:
+        raise ValueError(f"overview_pyramid: ignore {ignore} is not a uint8 value")
+    if ignore is not None and method == "average":
+        raise ValueError("overview_pyramid: the average has no ignore value")
+    bands, H, W = (int(v) for v in base.shape)
+    if bands < 1 or H < 1 or W < 1:
+        raise ValueError(f"overview_pyramid: empty raster {tuple(base.shape)}")
+    if bands * H * W >= 1 << 31:
+        raise ValueError(f"overview_pyramid: {bands} bands of {H} x {W} exceed the limit bands * H * W < 2^31 per call "
+                         "(bands are independent: pass them one at a time)")
+    L = overview_levels(H, W, block)
+    if L == 0:
+        return []
+    nbytes = int(lib.ffa_overview_pyramid_bytes(bands, H, W, L))
+    if nbytes < 0:
+        _l.check(nbytes, "overview_pyramid")
+    pyr = torch.empty(nbytes, dtype=torch.uint8, device=base.device)
+    with torch.cuda.device(base.device):
+        _l.check(lib.ffa_overview_pyramid_u8(base.data_ptr(), pyr.data_ptr(), bands, H, W, L, OVERVIEW_METHODS[method],
+                                             -1 if ignore is None or method != "mode" else int(ignore), _stream()),
+                 "overview_pyramid_u8")
+    out, pos = [], 0
+    for l in range(1, L + 1):
+        h, w = -(-H // (1 << l)), -(-W // (1 << l))
+        out.append(pyr[pos:pos + bands * h * w].view(bands, h, w))
+        pos += bands * h * w
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # points between coordinate reference systems (csrc/crs_transform.hip)
 
 def _ffa_crs(p) -> "_l.Crs":

@@ -650,6 +650,33 @@ typedef struct {
 int ffa_crs_transform_f64(const double* in, double* out, long long n, const FfaCrs* src, const FfaCrs* dst,
                           ffa_stream_t stream);
 
+/* ---- overview pyramid of a uint8 raster (the reduced-resolution images of a cloud-optimised GeoTIFF) --------------- */
+/* Definition (normative).  base is uint8 [bands][H][W] in device memory.
+ *   - Sizes.  Level 0 is the base; level l >= 1 has H_l = ceil(H / 2^l) rows and W_l = ceil(W / 2^l) columns.
+ *   - Storage.  pyr holds the levels 1 .. levels back to back, each [bands][H_l][W_l], dense
+ *     (ffa_overview_pyramid_bytes(bands, H, W, levels) bytes).
+ *   - Level count.  ffa_overview_levels returns the smallest L >= 0 with max(H_L, W_L) <= block: GDAL's COG driver
+ *     stops adding overviews once the smallest fits one block.
+ *   - Block structure.  Bands are independent.  Pixel (r, c) of level l is computed from the block of level l - 1 at
+ *     rows 2r .. min(2r + 1, H_{l-1} - 1) and columns 2c .. min(2c + 1, W_{l-1} - 1): n = 1, 2 or 4 pixels.
+ *   - method 0, nearest: the block's top-left pixel; level l pixel (r, c) therefore equals base (r * 2^l, c * 2^l),
+ *     which is always in range.
+ *   - method 1, mode: the value occurring most often in the block, among equally frequent values the smallest.  With
+ *     ignore >= 0 pixels equal to ignore do not vote, and a block made only of them gives ignore; ignore = -1: every
+ *     value votes.  For class rasters; the zone clip's 255 is what ignore is for.
+ *   - method 2, average: (2 s + n) / (2 n) in integer arithmetic, s the sum of the block -- the mean rounded half up,
+ *     exact.  ignore must be -1.  For class-probability and confidence rasters.
+ *   - Cascade.  Mode and average cascade: level l comes from level l - 1, not from the base.
+ *   - Determinism.  Integer arithmetic only, every output byte has one writer: equal inputs give equal bytes.
+ *   - Limits.  bands * H * W < 2^31, 0 <= levels <= 30 (levels beyond the 1 x 1 one repeat it; levels = 0 writes
+ *     nothing).  Bad arguments return FFA_ERR_ARG (the two size queries return it as their value).
+ * One launch writes up to four levels from one read of its source (csrc/overview.hip); the bytes are those of a
+ * level-by-level chain. */
+int ffa_overview_levels(int H, int W, int block);
+long long ffa_overview_pyramid_bytes(int bands, int H, int W, int levels);
+int ffa_overview_pyramid_u8(const uint8_t* base, uint8_t* pyr, int bands, int H, int W, int levels, int method,
+                            int ignore, ffa_stream_t stream);
+
 /* ---- hardware layout probes (tests only) ---------------------------------------------------------- */
 int ffa_probe_tr16(const uint16_t* src, uint16_t* dst, ffa_stream_t stream);
 int ffa_probe_mfma(const float* A, const float* B, float* D, int use_f32, ffa_stream_t stream);

@@ -11,6 +11,10 @@ config key write_confidence on: label + confidence from one kernel pass, 2 bytes
 --zone: instead of (b), the loop under a disc-shaped geozone covering about 40 % of the raster, with
 skip_tiles_outside_zone off (every tile of the zone's bounding box is inferred) and on, in one process: tiles skipped
 and the wall time of the tile loop (inference_and_write) of both.
+--cog: instead of all the above, the COG conversion of a one-band class raster of --cog-size (default 5000) squared:
+the overview pyramid alone for each method (hip events, best of 3 after a warm-up), the wall time of
+postprocess.convert_to_cog, and the plain GeoTiffWriter.close() of the same raster for comparison (the COG holds 4/3 of
+the tiles).
 """
 from __future__ import annotations
 
@@ -25,6 +29,74 @@ sys.path.insert(0, os.path.join(ROOT, "flair-for-aigle_amd"))
 import numpy as np
 import torch
 import yaml
+
+
+def bench_cog(size: int) -> None:
+    import shutil
+    import tempfile
+    from flairhip import ops
+    from flair_zonal_detection.geotiff import GeoTiffWriter, validate_cog
+    from flair_zonal_detection.postprocess import convert_to_cog
+    g = np.random.default_rng(0)
+    H = W = size
+    # label-like content: 8 x 8 blocks of one class, so that LZW has what a prediction raster gives it
+    cls = np.repeat(np.repeat(g.integers(0, 19, (1, H // 8 + 1, W // 8 + 1), dtype=np.uint8), 8, 1), 8, 2)[:, :H, :W]
+    cls = np.ascontiguousarray(cls)
+    dev = torch.from_numpy(cls).cuda()
+    L = ops.overview_levels(H, W, 512)
+    moved = cls.nbytes + sum(-(-H // 2 ** l) * -(-W // 2 ** l) for l in range(1, L + 1))
+    # the C entry point on a preallocated pyramid, queued back to back: the events then bracket kernels, not the
+    # host's per-call work (ops.overview_pyramid adds an allocation and the level views, timed separately below)
+    from flairhip import lib as _l
+    lib, reps = _l.load(), 20
+    pyr = torch.empty(int(lib.ffa_overview_pyramid_bytes(1, H, W, L)), dtype=torch.uint8, device=dev.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    for code, method in enumerate(("nearest", "mode", "average")):
+        def call():
+            _l.check(lib.ffa_overview_pyramid_u8(dev.data_ptr(), pyr.data_ptr(), 1, H, W, L, code, -1, stream))
+        call()  # warm-up
+        best = float("inf")
+        for _ in range(3):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                call()
+            b.record()
+            torch.cuda.synchronize()
+            best = min(best, a.elapsed_time(b) / reps)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        for _ in range(reps):
+            ops.overview_pyramid(dev, method=method)
+        torch.cuda.synchronize()
+        wall = (time.time() - t0) / reps
+        print(f"overview pyramid {H}x{W}, {L} levels, {method}: {best * 1e3:.1f} us per call (hip events over {reps} "
+              f"queued calls, best of 3) = {moved / best / 1e6:.0f} GB/s of {moved / 1e6:.1f} MB read + written; "
+              f"ops.overview_pyramid {wall * 1e6:.1f} us per call (host clock, synchronised)")
+    d = tempfile.mkdtemp(prefix="bench_cog_")
+    try:
+        plain, closes = os.path.join(d, "plain.tif"), []
+        for _ in range(3):  # the first pass also warms the encoder pool
+            w = GeoTiffWriter(plain, W, H, 1, 651000.0, 6865000.0, 0.2, crs="EPSG:2154")
+            w.data[...] = cls
+            t0 = time.time()
+            w.close()
+            closes.append(time.time() - t0)
+        plain_mb = os.path.getsize(plain) / 1e6
+        walls = []
+        for _ in range(2):
+            src = os.path.join(d, "pred.tif")
+            shutil.copy(plain, src)
+            t0 = time.time()
+            convert_to_cog(src, os.path.join(d, "pred_COG.tif"), overview_resampling="mode")
+            walls.append(time.time() - t0)
+        errors = validate_cog(os.path.join(d, "pred_COG.tif"))
+        print(f"GeoTiffWriter.close() {H}x{W} LZW: {min(closes[1:]):.2f} s ({plain_mb:.1f} MB); convert_to_cog (read + "
+              f"GPU pyramid + write_cog, blocksize 512): {min(walls):.2f} s "
+              f"({os.path.getsize(os.path.join(d, 'pred_COG.tif')) / 1e6:.1f} MB) = {min(walls) / min(closes[1:]):.2f} x "
+              f"the close; validate_cog: {errors or 'valid'}")
+    finally:
+        shutil.rmtree(d)
 
 
 def main():
@@ -44,7 +116,13 @@ def main():
                     help="run the tile loop with write_confidence: true (argmax output only)")
     ap.add_argument("--zone", action="store_true",
                     help="time the tile loop under a geozone with skip_tiles_outside_zone off and on")
+    ap.add_argument("--cog", action="store_true",
+                    help="time the overview pyramid and convert_to_cog against GeoTiffWriter.close(), nothing else")
+    ap.add_argument("--cog-size", type=int, default=5000, help="with --cog: raster height = width in pixels")
     args = ap.parse_args()
+    if args.cog:
+        bench_cog(args.cog_size)
+        return
     from flairhip.configs import unet_resnet34_config
     from flair_hub.models.flair_model import FLAIR_HUB_Model
     from flair_zonal_detection.inference import run_inference
