@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .operands import OperandCache, bump_state_epoch, state_epoch  # noqa: F401  (re-exported: graph.py and the tests call them here)
 
 LOGIT_PITCH = 32  # channel pitch of logits tensors (>= any class count of the reference's tasks)
 
@@ -34,9 +35,9 @@ def _dw_out(conv) -> Optional[torch.Tensor]:
     # weight gradients (the second kernel overwrites the first, autograd then sums two aliases of the last one).  The
     # state epoch moves with every optimizer step / graph replay; a second use inside it falls back to a fresh tensor,
     # which autograd accumulates onto the slot.
-    if getattr(w, "_ffa_buf_taken", None) == _STATE_EPOCH:
+    if getattr(w, "_ffa_buf_taken", None) == state_epoch():
         return None
-    w._ffa_buf_taken = _STATE_EPOCH
+    w._ffa_buf_taken = state_epoch()
     return buf.view(buf.shape)  # a fresh alias: autograd only adopts a gradient tensor nobody else holds
 
 
@@ -47,9 +48,9 @@ def _vec_out(p: torch.Tensor, n: int) -> Optional[torch.Tensor]:
     buf = getattr(p, "_ffa_grad_buf", None)
     if buf is None or p.grad is not None or buf.numel() != n or buf.dtype != torch.float32 or buf.dim() != 1:
         return None
-    if getattr(p, "_ffa_buf_taken", None) == _STATE_EPOCH:
+    if getattr(p, "_ffa_buf_taken", None) == state_epoch():
         return None
-    p._ffa_buf_taken = _STATE_EPOCH
+    p._ffa_buf_taken = state_epoch()
     return buf.view(buf.shape)
 
 
@@ -73,7 +74,7 @@ class HipConv2d(nn.Module):
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
-        self._cache = {}
+        self._cache = OperandCache()
 
     @property
     def in_pitch(self) -> int:
@@ -84,109 +85,63 @@ class HipConv2d(nn.Module):
         return LOGIT_PITCH if self.bias is not None and self.out_channels <= LOGIT_PITCH else ops.pad_channels(
             self.out_channels)
 
+    def allow(self, ring: bool = True, thin: bool = True) -> tuple:
+        """(ring, thin, stem): the layouts ffa_conv_plan may choose for an operand of this layer.  The ring and thin
+        kernels are pad-1 kernels, the stem kernel a pad-3 one; two requests that come out equal here ask the planner
+        the same question and share a cache entry."""
+        return (ring and self.padding == 1, thin and self.padding == 1, self.padding == 3)
+
     def packed(self, dtype: torch.dtype, transpose: bool = False, scale: Optional[torch.Tensor] = None,
-               tag: str = "", ring: bool = True, thin: bool = True) -> ops.PackedWeight:
+               ring: bool = True, thin: bool = True) -> ops.PackedWeight:
         """MFMA operand for the current weight values; re-packed only when the parameter changed.  ring=False keeps
         the conv_igemm layout (operands of the two-source / split-epilogue / bn-backward-epilogue kernels); thin=False
-        keeps a <= 32-channel layer off conv3x3_thin_kernel (it has no BatchNorm-backward-partials epilogue)."""
-        ring = ring and self.padding == 1  # the ring kernel is a pad-1 kernel
-        thin = thin and self.padding == 1
-        if not tag:
-            tag = "plain" if not thin else ("" if ring else "igemm")
-        key = (dtype, transpose, tag)
-        ver = (self.weight._version, self.weight.data_ptr(), None if scale is None else scale._version, _STATE_EPOCH)
-        hit = self._cache.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        w = self.weight.detach()
-        if not w.is_contiguous():
-            w = w.contiguous()
-        pitch = self.out_pitch if transpose else self.in_pitch
-        pw = ops.pack_conv_weight(w, dtype, self.stride, pitch, transpose=transpose, scale=scale, allow_ring=ring,
-                                  allow_thin=thin, allow_stem=(self.padding == 3))
-        self._cache[key] = (ver, pw)
-        return pw
+        keeps a <= 32-channel layer off conv3x3_thin_kernel (it has no BatchNorm-backward-partials epilogue).  Cached
+        per (dtype, transpose, layouts allowed)."""
+        allow = self.allow(ring, thin)
+
+        def build():
+            w = self.weight.detach()
+            if not w.is_contiguous():
+                w = w.contiguous()
+            pitch = self.out_pitch if transpose else self.in_pitch
+            return ops.pack_conv_weight(w, dtype, self.stride, pitch, transpose=transpose, scale=scale,
+                                        allow_ring=allow[0], allow_thin=allow[1], allow_stem=allow[2])
+        return self._cache.get((dtype, transpose, allow), self.weight, scale, build=build,
+                               repack=(transpose,) if scale is None else None)
 
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
                 f"padding={self.padding}, bias={self.bias is not None}")
 
 
-_STATE_EPOCH = 0
-
-
-def state_epoch() -> int:
-    return _STATE_EPOCH
-
-
-def bump_state_epoch() -> None:
-    """Parameters / buffers changed on the device without Python noticing (a hipGraph replay runs the optimizer and
-    the BatchNorm running-statistics updates in place: no tensor ``_version`` moves).  Every cache keyed on versions
-    -- packed MFMA operands, eval-mode BatchNorm folds -- carries this epoch as well and is rebuilt on next use."""
-    global _STATE_EPOCH
-    _STATE_EPOCH += 1
-
-
-def _after_optimizer_step(optimizer, args, kwargs) -> None:
-    bump_state_epoch()
-
-
-# torch's fused (single-kernel) Adam / AdamW / SGD update parameters WITHOUT moving their ``_version`` (checked on
-# torch 2.10: fused=True leaves p._version unchanged, the foreach / single-tensor paths bump it), so a cache keyed on
-# versions alone would keep feeding the convolutions the weights of the first step.  Every optimizer step in the
-# process therefore advances the state epoch.
-from torch.optim.optimizer import register_optimizer_step_post_hook as _register_step_hook  # noqa: E402
-
-_register_step_hook(_after_optimizer_step)
-
-
 class PackPlan:
     """Keeps the MFMA operands of all conv layers of a module tree current with ONE kernel launch per optimizer
-    step (93 separate pack launches cost 0.5 ms per step at batch 32).  Layers enter the plan once they have been
-    packed individually (first forward / backward), so unused layers never do."""
+    step (93 separate pack launches cost 0.5 ms per step at batch 32).  It covers every entry of the layers' operand
+    caches that is marked re-packable from the master weight alone, whatever layout request or column block it was
+    cached under.  Entries exist once they have been packed individually (first forward / backward), so unused layers
+    never enter the plan."""
 
     def __init__(self, root: nn.Module):
         self.convs = [m for m in root.modules() if isinstance(m, HipConv2d)]
         self.batch = None
-        self.sig = None       # identity of the buffers the table points at
-        self.versions = None  # parameter versions the packed operands correspond to
+        self.sig = None  # identity of the buffers the table points at
 
     def refresh(self, dtype: torch.dtype) -> None:
-        entries, sig, slots = [], [], []
-        for c in self.convs:
-            for transpose in (False, True):
-                for tag in ("", "igemm", "plain"):
-                    hit = c._cache.get((dtype, transpose, tag))
-                    if hit is None:
-                        continue
-                    entries.append((c.weight.detach(), hit[1], transpose))
-                    sig.append((c.weight.data_ptr(), hit[1].data.data_ptr()))
-                    slots.append((c, (dtype, transpose, tag)))
-            # column blocks of fusion 1x1 weights (FusionHandler.conv_f: one operand per modality and direction)
-            for key, hit in c._cache.items():
-                if isinstance(key, tuple) and key and key[0] == "fusion_slice" and key[3] == dtype:
-                    pw = hit[1]
-                    if pw.bco & (ops._l.BCO_RING | ops._l.BCO_THIN):
-                        continue
-                    entries.append((c.weight.detach(), pw, key[5], (key[1], key[2])))
-                    sig.append((c.weight.data_ptr(), pw.data.data_ptr()))
-                    slots.append((c, key))
-        if not entries:
+        todo = [e for c in self.convs for e in c._cache.entries.values()
+                if e.repack is not None and e.value.data.dtype == dtype]
+        if not todo:
             return
-        versions = [c.weight._version for c, _ in slots]
+        sig = [(e.sources[0].data_ptr(), e.value.data.data_ptr()) for e in todo]
         if self.batch is None or sig != self.sig:
-            if not all(e[0].is_contiguous() for e in entries):
+            if not all(e.sources[0].is_contiguous() for e in todo):
                 return
-            self.batch, self.sig, self.versions = ops.PackBatch(entries, dtype), sig, None
-        # cache stamps: (version, data_ptr, scale version, epoch) for whole weights, (version, data_ptr, epoch) for blocks
-        stale = [i for i, (c, key) in enumerate(slots)
-                 if c._cache[key][0][0] != versions[i] or c._cache[key][0][-1] != _STATE_EPOCH]
-        if not stale:
+            self.batch = ops.PackBatch([(e.sources[0].detach(), e.value, *e.repack) for e in todo], dtype)
+            self.sig = sig
+        if all(e.current() for e in todo):
             return
         self.batch.run()
-        for (c, key), v in zip(slots, versions):
-            stamp = (v, c.weight.data_ptr(), _STATE_EPOCH) if key[0] == "fusion_slice" else (v, c.weight.data_ptr(), None, _STATE_EPOCH)
-            c._cache[key] = (stamp, c._cache[key][1])
+        for e in todo:
+            e.restamp()
 
 
 class HipBatchNorm2d(nn.Module):
@@ -495,13 +450,9 @@ def _fusion_slice(conv: HipConv2d, w: torch.Tensor, off: int, c: int, dtype: tor
                   transpose: bool) -> ops.PackedWeight:
     """MFMA operand of the column block W[:, off:off+c] of a fusion 1x1 weight, cached until the weight changes
     (an inference loop packs each block once instead of once per batch)"""
-    key = ("fusion_slice", off, c, dtype, pitch, transpose)
-    ver = (conv.weight._version, conv.weight.data_ptr(), _STATE_EPOCH)
-    hit = conv._cache.get(key)
-    if hit is None or hit[0] != ver:
-        hit = (ver, ops.pack_conv_weight(w[:, off:off + c].contiguous(), dtype, 1, pitch, transpose=transpose))
-        conv._cache[key] = hit
-    return hit[1]
+    return conv._cache.get(("fusion_slice", off, c, dtype, pitch, transpose), conv.weight, repack=(transpose, (off, c)),
+                           build=lambda: ops.pack_conv_weight(w[:, off:off + c].contiguous(), dtype, 1, pitch,
+                                                              transpose=transpose))
 
 
 class _FusionConv1x1(torch.autograd.Function):
@@ -684,20 +635,16 @@ def conv_bn_act(x, conv: HipConv2d, bn: HipBatchNorm2d, relu: bool = True, resid
 
 def _eval_folded(conv: HipConv2d, bn: HipBatchNorm2d, dtype: torch.dtype, ring: bool = True):
     """(packed weights with the eval-mode BatchNorm scale folded in, shift vector), cached per parameter version"""
-    ver = (conv.weight._version, conv.weight.data_ptr(), bn.weight._version, bn.bias._version,
-           bn.running_mean._version, bn.running_var._version, dtype, _STATE_EPOCH, getattr(bn, "_stats_epoch", 0))
-    ck = "eval_fold" if ring else "eval_fold_igemm"
-    hit = conv._cache.get(ck)
-    if hit is None or hit[0] != ver:
+    allow = conv.allow(ring=ring)
+
+    def build():
         scale, shift = ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
                                           bn.eps)
         w = conv.weight.detach()
         pw = ops.pack_conv_weight(w if w.is_contiguous() else w.contiguous(), dtype, conv.stride, conv.in_pitch,
-                                  scale=scale, allow_ring=ring and conv.padding == 1, allow_thin=conv.padding == 1,
-                                  allow_stem=conv.padding == 3)
-        hit = (ver, pw, shift)
-        conv._cache[ck] = hit
-    return hit[1], hit[2]
+                                  scale=scale, allow_ring=allow[0], allow_thin=allow[1], allow_stem=allow[2])
+        return pw, shift
+    return conv._cache.get(("eval_folded", dtype, allow), conv.weight, bn=bn, build=build)
 
 
 def up_conv_bn_act(lo, skip, conv: HipConv2d, bn: HipBatchNorm2d):

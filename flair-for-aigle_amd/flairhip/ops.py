@@ -130,8 +130,10 @@ class PackBatch:
     """Descriptor tables for ffa_pack_conv_weights_batched / ffa_ring_pack_batched: re-packs many conv operands in one
     launch per layout.
 
-    entries: (master weight OIHW f32, PackedWeight it feeds, transpose flag[, (first column, columns)]).  The tables hold raw device
-    pointers, so they must be rebuilt when a parameter or a packed buffer is re-allocated."""
+    entries: (master weight OIHW f32, PackedWeight it feeds, transpose flag[, (first column, columns)]).  A column block
+    belongs to a 1x1 fusion weight, and ffa_conv_plan gives a 1x1 operand no other layout than conv_igemm's, so only
+    that table knows column blocks.  The tables hold raw device pointers, so they must be rebuilt when a parameter or
+    a packed buffer is re-allocated."""
 
     def __init__(self, entries, dtype: torch.dtype):
         lib = _l.load()

@@ -32,13 +32,14 @@ kernels (plain-FMA GEMMs and attention backward): a parity mode for gradient che
 from __future__ import annotations
 
 import re
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import nn as hnn
 from . import ops
+from .operands import OperandCache
 
 SWIN_VARIANTS = {
     "tiny": (96, (2, 2, 6, 2), (3, 6, 12, 24)),
@@ -129,23 +130,7 @@ class _Stage(nn.Module):
                                       for i in range(depth)])
 
 
-class _Operands:
-    """bf16 / packed-f32 copies of the parameters a forward needs, rebuilt when a parameter changes"""
-
-    def __init__(self):
-        self.cache: Dict[str, tuple] = {}
-
-    def get(self, tag: str, params: Sequence[Optional[torch.Tensor]], dtype: torch.dtype, build, extra=()):
-        ver = tuple((None if p is None else (p._version, p.data_ptr())) for p in params) + (hnn.state_epoch(), dtype) + \
-            tuple(extra)
-        hit = self.cache.get(tag)
-        if hit is None or hit[0] != ver:
-            hit = (ver, build())
-            self.cache[tag] = hit
-        return hit[1]
-
-
-def _lin_operand(ops_cache: _Operands, tag: str, weight: torch.Tensor, bias: Optional[torch.Tensor], dtype):
+def _lin_operand(ops_cache: OperandCache, tag: str, weight: torch.Tensor, bias: Optional[torch.Tensor], dtype):
     """(weight operand, f32 bias or None): bf16 [N,K] for the token GEMM, a packed 1x1 conv operand in f32 mode"""
     def build():
         w = weight.detach().float().contiguous()
@@ -156,7 +141,7 @@ def _lin_operand(ops_cache: _Operands, tag: str, weight: torch.Tensor, bias: Opt
         if bias is not None:
             b[: w.shape[0]] = bias.detach().float()
         return pw, b
-    return ops_cache.get(tag, (weight, bias), dtype, build)
+    return ops_cache.get(tag, weight, bias, build=build, extra=(dtype,))
 
 
 def _apply_linear(x: torch.Tensor, operand, n_out: int, act: int = ops.ACT_NONE,
@@ -175,13 +160,13 @@ def _apply_linear(x: torch.Tensor, operand, n_out: int, act: int = ops.ACT_NONE,
 # --------------------------------------------------------------------------------------------------
 # training: autograd nodes (bf16 on the MFMA kernels; f32 parity mode on the plain-FMA kernels of the same entry points)
 
-def _wt(cache: _Operands, tag: str, weight: torch.Tensor, dtype: torch.dtype = torch.bfloat16):
+def _wt(cache: OperandCache, tag: str, weight: torch.Tensor, dtype: torch.dtype = torch.bfloat16):
     """(W, W^T) in the compute dtype, rebuilt when the parameter changes: forward operand [N,K] and input-gradient
     operand [K,N]"""
     def build():
         w = weight.detach().to(dtype).contiguous()
         return w, w.t().contiguous()
-    return cache.get(tag + ":wt", (weight,), dtype, build)
+    return cache.get(tag + ":wt", weight, build=build, extra=(dtype,))
 
 
 def _wgrad_bias(x: torch.Tensor, dy: torch.Tensor):
@@ -423,7 +408,7 @@ class HipSwinEncoder(nn.Module):
             setattr(model, f"layers_{i}", _Stage(self.dims[i - 1] if i else dim, self.dims[i], res, depths[i], heads[i],
                                                  ws, i > 0))
         self.model = model
-        self._ops = _Operands()
+        self._ops = OperandCache()
         self._register_load_state_dict_pre_hook(self._rename_timm_keys)
 
     @staticmethod
@@ -447,7 +432,7 @@ class HipSwinEncoder(nn.Module):
             w2 = torch.zeros(dim, ps, ps, cp, dtype=torch.float32, device=w.device)
             w2[..., :cin] = w.permute(0, 2, 3, 1)
             return w2.reshape(dim, ps * ps * cp)
-        w2 = self._ops.get(f"pe_w{cp}", (pe.proj.weight,), torch.float32, build)
+        w2 = self._ops.get(f"pe_w{cp}", pe.proj.weight, build=build)
         operand = _lin_operand(self._ops, f"pe{cp}", w2, pe.proj.bias, x.dtype)
         t = _apply_linear(ops.space_to_depth(x, ps), operand, self.dims[0])
         return ops.layer_norm(t, pe.norm.weight.detach(), pe.norm.bias.detach())
@@ -541,7 +526,7 @@ class HipUPerNetDecoder(nn.Module):
         self.fpn_stages = nn.ModuleList(
             _mod(skip_conv=(_conv_bn(c, pyramid_channels, 1) if c != 0 else nn.Identity())) for c in ch[1:])
         self.fpn_bottleneck = _conv_bn((len(ch) - 1) * pyramid_channels, segmentation_channels, 3, padding=1)
-        self._fold = _Operands()
+        self._fold = OperandCache()
         for m in self.modules():  # smp initialize_decoder
             if isinstance(m, hnn.HipConv2d):
                 nn.init.kaiming_uniform_(m.weight, mode="fan_in", nonlinearity="relu")
@@ -559,9 +544,7 @@ class HipUPerNetDecoder(nn.Module):
             n = conv.out_channels
             w = conv.weight.detach().float().view(n, -1) * scale[:n, None]
             return w.to(torch.bfloat16).contiguous(), shift[:n].contiguous()
-        # the training kernels update the running statistics through raw pointers: their epoch counter is part of the key
-        w, b = self._fold.get(f"c{id(conv)}", (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var),
-                              torch.bfloat16, build, extra=(getattr(bn, "_stats_epoch", 0),))
+        w, b = self._fold.get(f"c{id(conv)}", conv.weight, bn=bn, build=build)
         return ops.linear(x, w, b, act=ops.ACT_RELU)
 
     @staticmethod

@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import nn as hnn
 from . import ops
+from .operands import OperandCache
 
 
 class _Affine(nn.Module):
@@ -365,7 +366,7 @@ class HipUTAE(nn.Module):
         te.mlp = _seq(_Weights((enc[-1], d_model), enc[-1]), hnn.HipBatchNorm2d(enc[-1]), _Slot())
         self.temporal_encoder = te
         self.out_conv = _block(conv=_conv_layer([dec[0]] + list(out_conv), "batch"))
-        self._cache = {}
+        self._cache = OperandCache()
         # training-time randomness of the reference: LTAE2d(dropout=0.2) after its MLP (:242,278),
         # ScaledDotProductAttention(attn_dropout=0.1) on the temporal attention masks (:387,399)
         self.mlp_dropout, self.attn_dropout = 0.2, 0.1
@@ -376,36 +377,31 @@ class HipUTAE(nn.Module):
                 transpose: bool = False, cols: Optional[slice] = None, with_bias: bool = True):
         """(packed operand, bias vector): conv weight as 4-D OIHW (Conv1d / Linear weights are 1x1 convolutions),
         evaluation-mode BatchNorm folded in: W' = scale * W, bias' = shift + scale * bias"""
-        ver = (holder.weight._version, holder.weight.data_ptr(), holder.bias._version, hnn.state_epoch(),
-               None if bn is None else (bn.weight._version, bn.bias._version, bn.running_mean._version,
-                                        bn.running_var._version, getattr(bn, "_stats_epoch", 0)), self.dtype)
-        hit = self._cache.get(tag)
-        if hit is not None and hit[0] == ver:
-            return hit[1], hit[2]
-        w = holder.weight.detach().float()
-        if w.dim() == 3:
-            w = w.unsqueeze(-1)
-        elif w.dim() == 2:
-            w = w[:, :, None, None]
-        if cols is not None:
-            w = w[:, cols]
-        w = w.contiguous()
-        n_out = w.shape[1] if transpose else w.shape[0]
-        scale = shift = None
-        if bn is not None:
-            scale, shift = ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                              bn.eps)
-        pw = ops.pack_conv_weight(w, self.dtype, 1, ci_pitch, transpose=transpose, scale=scale, allow_ring=False,
-                                  allow_thin=False)  # reflect-padded input, pad-0 convolution: conv_igemm only
-        out_pitch = self._pitch(n_out)
-        bias = torch.zeros(max(out_pitch, pw.rows), dtype=torch.float32, device=w.device)
-        if with_bias:
-            b = holder.bias.detach().float()
-            bias[:n_out] = b if scale is None else shift[:n_out] + scale[:n_out] * b
-        elif scale is not None:
-            raise ValueError("a folded BatchNorm needs its shift in the bias vector")
-        self._cache[tag] = (ver, pw, bias)
-        return pw, bias
+        def build():
+            w = holder.weight.detach().float()
+            if w.dim() == 3:
+                w = w.unsqueeze(-1)
+            elif w.dim() == 2:
+                w = w[:, :, None, None]
+            if cols is not None:
+                w = w[:, cols]
+            w = w.contiguous()
+            n_out = w.shape[1] if transpose else w.shape[0]
+            scale = shift = None
+            if bn is not None:
+                scale, shift = ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
+                                                  bn.eps)
+            pw = ops.pack_conv_weight(w, self.dtype, 1, ci_pitch, transpose=transpose, scale=scale, allow_ring=False,
+                                      allow_thin=False)  # reflect-padded input, pad-0 convolution: conv_igemm only
+            out_pitch = self._pitch(n_out)
+            bias = torch.zeros(max(out_pitch, pw.rows), dtype=torch.float32, device=w.device)
+            if with_bias:
+                b = holder.bias.detach().float()
+                bias[:n_out] = b if scale is None else shift[:n_out] + scale[:n_out] * b
+            elif scale is not None:
+                raise ValueError("a folded BatchNorm needs its shift in the bias vector")
+            return pw, bias
+        return self._cache.get(tag, holder.weight, holder.bias, bn=bn, build=build, extra=(self.dtype,))
 
     def _pitch(self, n: int) -> int:
         """stored channel pitch of an n-channel tensor: class-score tensors of up to LOGIT_PITCH classes use the
