@@ -527,6 +527,15 @@ static bool gemm_use_256(int M, int K, int N) {
   return blocks >= 240 && waste <= 1.15;  // one 512-thread block per CU: fewer blocks than CUs leave the chip idle
 }
 
+// Which kernel ffa_linear_ex launches for a shape: 0 gemm_f32_kernel, 1 gemm_bf16_kernel<2>, 2 gemm_bf16_kernel<4>,
+// 3 gemm256_bf16_kernel.  Host arithmetic only (nothing is launched); ffa_linear_ex dispatches on this very value.
+extern "C" int ffa_linear_plan(int dtype, int M, int K, int N) {
+  if (dtype == FFA_F32) return 0;
+  if (gemm_use_256(M, K, N)) return 3;
+  const long long blocks = (long long)((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
+  return blocks < 384 ? 1 : 2;  // fewer than 1.5 blocks per CU: 64-token tiles double the grid
+}
+
 extern "C" int ffa_linear_ex(int dtype, const void* a, long long lda, const void* w, const float* bias,
                              const void* residual, long long ldr, void* out, long long ldc, int M, int K, int N, int act,
                              void* aux, long long ldaux, const float* row_scale, int rows_per_scale,
@@ -566,7 +575,8 @@ extern "C" int ffa_linear_ex(int dtype, const void* a, long long lda, const void
   g.lda = lda; g.ldr = ldr; g.ldc = ldc; g.ldaux = ldaux;
   g.M = M; g.K = K; g.N = N; g.act = act;
   g.rows_per_scale = rows_per_scale > 0 ? rows_per_scale : 1;
-  if (gemm_use_256(M, K, N)) {
+  const int plan = ffa_linear_plan(dtype, M, K, N);
+  if (plan == 3) {
     g.nblk_n = (N + HBN_ - 1) / HBN_;
     const long long blocks = (long long)((M + HBM_ - 1) / HBM_) * g.nblk_n;
     FFA_REQUIRE(blocks < (1LL << 31), "linear: grid too large");
@@ -576,7 +586,7 @@ extern "C" int ffa_linear_ex(int dtype, const void* a, long long lda, const void
   g.nblk_n = (N + GBN - 1) / GBN;
   const long long blocks = (long long)((M + GBM - 1) / GBM) * g.nblk_n;
   FFA_REQUIRE(blocks < (1LL << 31), "linear: grid too large");
-  if (blocks < 384) {  // fewer than 1.5 blocks per CU: 64-token tiles double the grid
+  if (plan == 1) {
     const long long blocks64 = (long long)((M + 63) / 64) * g.nblk_n;
     hipLaunchKernelGGL(gemm_bf16_kernel<2>, dim3((unsigned)blocks64), dim3(256), 0, stream, g);
   } else {

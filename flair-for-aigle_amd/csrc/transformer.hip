@@ -766,6 +766,8 @@ extern "C" int ffa_window_attention(int dtype, const void* qkv, void* out, const
   FFA_REQUIRE(qkv && out && qkv_bias && table && B > 0 && H > 0 && W > 0 && heads > 0, "window_attention: bad arguments");
   FFA_REQUIRE(C == heads * 32, "window_attention: head dimension %d (only 32 is built)", heads ? C / heads : 0);
   FFA_REQUIRE(ws >= 1 && ws <= 12 && shift >= 0 && shift < ws, "window_attention: window %d / shift %d", ws, shift);
+  // win_token() undoes the cyclic shift by ONE subtraction of H (W): torch.roll only while shift <= H (W)
+  FFA_REQUIRE(shift == 0 || (shift <= H && shift <= W), "window_attention: shift %d exceeds the %d x %d map", shift, H, W);
   WinAttnArgs a;
   a.qkv = qkv;
   a.out = out;
@@ -1644,6 +1646,8 @@ extern "C" int ffa_window_attention_bwd(int dtype, const void* qkv, const void* 
               "window_attention_bwd: bad arguments");
   FFA_REQUIRE(C == heads * 32, "window_attention_bwd: head dimension %d (only 32 is built)", heads ? C / heads : 0);
   FFA_REQUIRE(ws >= 1 && ws <= 12 && shift >= 0 && shift < ws, "window_attention_bwd: window %d / shift %d", ws, shift);
+  // win_token() undoes the cyclic shift by ONE subtraction of H (W): torch.roll only while shift <= H (W)
+  FFA_REQUIRE(shift == 0 || (shift <= H && shift <= W), "window_attention_bwd: shift %d exceeds the %d x %d map", shift, H, W);
   if (!workspace || workspace_bytes < ffa_window_attention_bwd_workspace_bytes(B, H, W, C, heads, ws)) {
     ffa_set_error("window_attention_bwd: workspace of %lld bytes needed",
                   ffa_window_attention_bwd_workspace_bytes(B, H, W, C, heads, ws));

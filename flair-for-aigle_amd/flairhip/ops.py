@@ -1544,7 +1544,53 @@ def mask_images_(x: torch.Tensor, pad: torch.Tensor, value: float = 0.0) -> torc
 # --------------------------------------------------------------------------------------------------
 # Swin-Transformer / UPerNet (csrc/transformer.hip, csrc/gemm.hip)
 
+# The kernels index gamma / beta / stats / the qkv bias / the bias table / row_scale and the gradient operands without
+# bounds of their own, so the wrappers refuse what would make them read past the end (as the U-TAE block above does).
+
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_RELU = 0, 1, 2, 3
+
+
+def _chk_contig(t: torch.Tensor, op: str, name: str = "input") -> None:
+    if not t.is_contiguous():
+        raise ValueError(f"{op}: {name} must be contiguous")
+
+
+def _chk_stats(stats: Optional[torch.Tensor], rows: int, ref: torch.Tensor, op: str) -> None:
+    if stats is None:
+        return
+    if not (stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (rows, 2) and
+            stats.device == ref.device):
+        raise ValueError(f"{op}: stats must be contiguous f32 [{rows}, 2] on {ref.device}, got {stats.dtype} "
+                         f"{tuple(stats.shape)} on {stats.device}")
+
+
+def _chk_row_scale(row_scale: torch.Tensor, rows: int, rows_per_scale: int, ref: torch.Tensor, op: str) -> None:
+    need = -(-rows // rows_per_scale) if rows_per_scale > 0 else -1
+    if not (rows_per_scale > 0 and row_scale.dtype == torch.float32 and row_scale.is_contiguous() and
+            row_scale.numel() >= need and row_scale.device == ref.device):
+        raise ValueError(f"{op}: row_scale must be contiguous f32 on {ref.device} with one entry per rows_per_scale = "
+                         f"{rows_per_scale} rows (at least {need} for {rows} rows), got {row_scale.dtype} "
+                         f"{tuple(row_scale.shape)} on {row_scale.device}")
+
+
+def _chk_window_attention(qkv: torch.Tensor, qkv_bias: torch.Tensor, table: torch.Tensor, heads: int, ws: int, op: str):
+    _chk_nhwc(qkv, f"{op} input")
+    B, H, W, C3 = qkv.shape
+    if C3 % 3:
+        raise ValueError(f"{op}: {C3} channels are not q | k | v")
+    if not (table.dim() == 2 and tuple(table.shape) == ((2 * ws - 1) ** 2, heads) and table.dtype == torch.float32 and
+            table.is_contiguous() and table.device == qkv.device):
+        raise ValueError(f"{op}: relative position bias table must be contiguous f32 [(2ws-1)^2, heads] = "
+                         f"[{(2 * ws - 1) ** 2}, {heads}] on {qkv.device}, got {table.dtype} {tuple(table.shape)} on "
+                         f"{table.device}")
+    _chk_f32_vec(qkv_bias, C3, qkv, op, "qkv_bias")
+    return B, H, W, C3 // 3
+
+
+def linear_plan(dtype: torch.dtype, M: int, K: int, N: int) -> int:
+    """the kernel ``linear`` launches for [M, K] x [N, K]: 0 f32 parity kernel, 1 gemm_bf16_kernel<2> (64-token tile),
+    2 gemm_bf16_kernel<4> (128-token tile), 3 gemm256_bf16_kernel.  Launches nothing."""
+    return int(_l.load().ffa_linear_plan(_dtype_id(dtype), M, K, N))
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
@@ -1568,9 +1614,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     for name, t in (("residual", residual), ("aux", aux)):
         if t is not None and (t.shape != out.shape or not t.is_contiguous() or t.dtype != x.dtype):
             raise ValueError(f"linear: {name} must be contiguous bf16 and shaped like the output")
-    if row_scale is not None and (row_scale.dtype != torch.float32 or rows_per_scale <= 0 or
-                                  row_scale.numel() * rows_per_scale < M):
-        raise ValueError("linear: row_scale must be f32 with one entry per rows_per_scale rows")
+    if row_scale is not None:
+        _chk_row_scale(row_scale, M, rows_per_scale, x, "linear")
     _l.check(_l.load().ffa_linear_ex(_dt(x), x.data_ptr(), K, w.data_ptr(), _ptr(bias), _ptr(residual), N,
                                      out.data_ptr(), N, M, K, N, act, _ptr(aux), N, _ptr(row_scale), rows_per_scale,
                                      _stream()), "linear")
@@ -1592,9 +1637,11 @@ def space_to_depth(x: torch.Tensor, ps: int) -> torch.Tensor:
 def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5,
                stats: Optional[torch.Tensor] = None) -> torch.Tensor:
     """nn.LayerNorm over the last dimension; ``stats`` (f32 [rows, 2]) receives (mean, rstd) for layer_norm_bwd"""
-    if not x.is_contiguous():
-        raise ValueError("layer_norm: input must be contiguous")
+    _chk_contig(x, "layer_norm")
     C = x.shape[-1]
+    _chk_f32_vec(gamma, C, x, "layer_norm", "gamma")
+    _chk_f32_vec(beta, C, x, "layer_norm", "beta")
+    _chk_stats(stats, x.numel() // C, x, "layer_norm")
     out = torch.empty_like(x)
     _l.check(_l.load().ffa_layer_norm(_dt(x), x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                                       _ptr(stats), x.numel() // C, C, eps, _stream()), "layer_norm")
@@ -1604,8 +1651,13 @@ def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: fl
 def layer_norm_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, stats: torch.Tensor,
                    dres: Optional[torch.Tensor] = None):
     """-> (dx [+ dres], dgamma f32, dbeta f32)"""
+    _chk_contig(x, "layer_norm_bwd")
     C = x.shape[-1]
     rows = x.numel() // C
+    _chk_like(dy, x.shape, x, "layer_norm_bwd", "dy")
+    _chk_like(dres, x.shape, x, "layer_norm_bwd", "dres")
+    _chk_f32_vec(gamma, C, x, "layer_norm_bwd", "gamma")
+    _chk_stats(stats, rows, x, "layer_norm_bwd")
     lib = _l.load()
     dx = torch.empty_like(x)
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -1623,6 +1675,11 @@ def patch_merge_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, e
     """PatchMerging's gather + LayerNorm(4C): [B,H,W,C] -> [B,H/2,W/2,4C]"""
     _chk_nhwc(x, "patch_merge input")
     B, H, W, C = x.shape
+    if H % 2 or W % 2:
+        raise ValueError(f"patch_merge_norm: odd map {H} x {W} (the padded variant is not implemented)")
+    _chk_f32_vec(gamma, 4 * C, x, "patch_merge_norm", "gamma")
+    _chk_f32_vec(beta, 4 * C, x, "patch_merge_norm", "beta")
+    _chk_stats(stats, B * (H // 2) * (W // 2), x, "patch_merge_norm")
     out = torch.empty((B, H // 2, W // 2, 4 * C), dtype=x.dtype, device=x.device)
     _l.check(_l.load().ffa_patch_merge_norm(_dt(x), x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                                             _ptr(stats), B, H, W, C, eps, _stream()), "patch_merge_norm")
@@ -1631,8 +1688,14 @@ def patch_merge_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, e
 
 def patch_merge_norm_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, stats: torch.Tensor):
     """x [B,H,W,C] (the forward's input), dy [B,H/2,W/2,4C] -> (dx [B,H,W,C], dgamma, dbeta)"""
+    _chk_nhwc(x, "patch_merge_norm_bwd input")
     B, H, W, C = x.shape
+    if H % 2 or W % 2:
+        raise ValueError(f"patch_merge_norm_bwd: odd map {H} x {W} (the padded variant is not implemented)")
     rows = B * (H // 2) * (W // 2)
+    _chk_like(dy, (B, H // 2, W // 2, 4 * C), x, "patch_merge_norm_bwd", "dy")
+    _chk_f32_vec(gamma, 4 * C, x, "patch_merge_norm_bwd", "gamma")
+    _chk_stats(stats, rows, x, "patch_merge_norm_bwd")
     lib = _l.load()
     dx = torch.empty_like(x)
     dg = torch.empty(4 * C, dtype=torch.float32, device=x.device)
@@ -1648,13 +1711,7 @@ def patch_merge_norm_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor,
 def window_attention(qkv: torch.Tensor, qkv_bias: torch.Tensor, table: torch.Tensor, heads: int, ws: int, shift: int,
                      scale: float) -> torch.Tensor:
     """qkv [B,H,W,3C] -> [B,H,W,C]; table f32 [(2ws-1)^2, heads]"""
-    _chk_nhwc(qkv, "window_attention input")
-    B, H, W, C3 = qkv.shape
-    C = C3 // 3
-    if table.shape != ((2 * ws - 1) ** 2, heads) or table.dtype != torch.float32 or not table.is_contiguous():
-        raise ValueError("window_attention: relative position bias table must be contiguous f32 [(2ws-1)^2, heads]")
-    if qkv_bias.numel() != C3 or qkv_bias.dtype != torch.float32:
-        raise ValueError("window_attention: qkv bias must be f32 [3C]")
+    B, H, W, C = _chk_window_attention(qkv, qkv_bias, table, heads, ws, "window_attention")
     out = torch.empty((B, H, W, C), dtype=qkv.dtype, device=qkv.device)
     _l.check(_l.load().ffa_window_attention(_dt(qkv), qkv.data_ptr(), out.data_ptr(), qkv_bias.data_ptr(),
                                             table.data_ptr(), B, H, W, C, heads, ws, shift, scale, _stream()),
@@ -1663,6 +1720,7 @@ def window_attention(qkv: torch.Tensor, qkv_bias: torch.Tensor, table: torch.Ten
 
 
 def gelu(x: torch.Tensor) -> torch.Tensor:
+    _chk_contig(x, "gelu")
     out = torch.empty_like(x)
     _l.check(_l.load().ffa_gelu(_dt(x), x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "gelu")
     return out
@@ -1699,12 +1757,9 @@ def window_attention_bwd(qkv: torch.Tensor, dout: torch.Tensor, qkv_bias: torch.
                          ws: int, shift: int, scale: float):
     """-> (dqkv [B,H,W,3C], dtable f32 [(2ws-1)^2, heads], dbias_pad f32 [3C]: what reaches the qkv bias through the
     padding tokens of the window grid)"""
-    _chk_nhwc(qkv, "window_attention_bwd qkv")
-    _chk_nhwc(dout, "window_attention_bwd dout")
-    B, H, W, C3 = qkv.shape
-    C = C3 // 3
-    if dout.shape != (B, H, W, C) or dout.dtype != qkv.dtype:
-        raise ValueError("window_attention_bwd: dout must be [B,H,W,C] in the dtype of qkv")
+    B, H, W, C = _chk_window_attention(qkv, qkv_bias, table, heads, ws, "window_attention_bwd")
+    C3 = 3 * C
+    _chk_like(dout, (B, H, W, C), qkv, "window_attention_bwd", "dout")
     lib = _l.load()
     dqkv = torch.empty_like(qkv)
     dtable = torch.empty_like(table)
@@ -1723,6 +1778,8 @@ def bilinear_slice_bwd(dy: torch.Tensor, in_hw: Tuple[int, int], channels: int, 
     _chk_nhwc(dy, "bilinear_slice_bwd dy")
     B, Ho, Wo, P = dy.shape
     Hi, Wi = in_hw
+    if channels <= 0 or offset < 0 or offset + channels > P:
+        raise ValueError(f"bilinear_slice_bwd: slice [{offset}, {offset + channels}) does not fit dy's {P} channels")
     dx = torch.empty((B, Hi, Wi, channels), dtype=dy.dtype, device=dy.device)
     _l.check(_l.load().ffa_bilinear_slice_bwd(_dt(dy), dy.data_ptr(), dx.data_ptr(), B, Hi, Wi, Ho, Wo, channels, P,
                                               offset, 1 if align_corners else 0, _stream()), "bilinear_slice_bwd")
@@ -1731,7 +1788,9 @@ def bilinear_slice_bwd(dy: torch.Tensor, in_hw: Tuple[int, int], channels: int, 
 
 def adaptive_avg_pool_bwd(dy: torch.Tensor, in_hw: Tuple[int, int]) -> torch.Tensor:
     _chk_nhwc(dy, "adaptive_avg_pool_bwd dy")
-    B, S, _, C = dy.shape
+    B, S, S2, C = dy.shape
+    if S != S2:
+        raise ValueError(f"adaptive_avg_pool_bwd: dy must be [B, S, S, C], got {tuple(dy.shape)}")
     H, W = in_hw
     dx = torch.empty((B, H, W, C), dtype=dy.dtype, device=dy.device)
     _l.check(_l.load().ffa_adaptive_avg_pool_bwd(_dt(dy), dy.data_ptr(), dx.data_ptr(), B, H, W, C, S, _stream()),
@@ -1740,7 +1799,9 @@ def adaptive_avg_pool_bwd(dy: torch.Tensor, in_hw: Tuple[int, int]) -> torch.Ten
 
 
 def scale_rows(x: torch.Tensor, row_scale: torch.Tensor, rows_per_scale: int) -> torch.Tensor:
+    _chk_contig(x, "scale_rows")
     C = x.shape[-1]
+    _chk_row_scale(row_scale, x.numel() // C, rows_per_scale, x, "scale_rows")
     out = torch.empty_like(x)
     _l.check(_l.load().ffa_scale_rows(_dt(x), x.data_ptr(), out.data_ptr(), row_scale.data_ptr(), x.numel() // C, C,
                                       rows_per_scale, _stream()), "scale_rows")
@@ -1790,7 +1851,8 @@ def linear_wgrad(x: torch.Tensor, dy: torch.Tensor, out: Optional[torch.Tensor] 
     lib = _l.load()
     if out is None:
         out = torch.empty((N, K), dtype=torch.float32, device=x.device)
-    db = torch.empty(N, dtype=torch.float32, device=x.device) if with_bias else None
+    # accumulate adds to whatever dbias holds as well: a fresh db must start from 0
+    db = (torch.zeros if accumulate else torch.empty)(N, dtype=torch.float32, device=x.device) if with_bias else None
     ws = workspace(lib.ffa_linear_wgrad_workspace_bytes(M, N, K), x.device, "lin_wgrad")
     _l.check(lib.ffa_linear_wgrad(_dt(x), x.data_ptr(), K, dy.data_ptr(), N, out.data_ptr(), _ptr(db), M, K, N,
                                   1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream()), "linear_wgrad")

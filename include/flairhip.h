@@ -286,6 +286,9 @@ int ffa_linear(int dtype, const void* a, long long lda, const void* w, const flo
 int ffa_linear_ex(int dtype, const void* a, long long lda, const void* w, const float* bias, const void* residual,
                   long long ldr, void* out, long long ldc, int M, int K, int N, int act, void* aux, long long ldaux,
                   const float* row_scale, int rows_per_scale, ffa_stream_t stream);
+/* The kernel ffa_linear_ex launches for a shape (host arithmetic, nothing is launched): 0 f32 parity kernel, 1 bf16
+ * 64-token tile, 2 bf16 128-token tile, 3 bf16 256 x 256 tile */
+int ffa_linear_plan(int dtype, int M, int K, int N);
 /* nn.Linear's weight gradient dW[n][k] = sum_m dy[m][n] x[m][k] (f32 [N][K]; accumulate != 0 adds to dw): transposed-
  * operand MFMA GEMM over the tokens, split over token ranges with a fixed-order reduction (deterministic); f32 operands take
  * a plain-FMA kernel with the same slabs and reduction (parity mode) */

@@ -34,6 +34,7 @@ BCO_RING, BCO_THIN, BCO_STEM = 0x1000, 0x2000, 0x8000
 HELPERS = {
     "pad_channels", "conv_out_size", "conv_stat_rows", "workspace", "upcat_supported", "pro_supported",
     "conv_is_persistent", "pack_conv_weight", "coop_barrier_failed", "slice_grid", "write_window",
+    "linear_plan",
 }
 
 

@@ -52,10 +52,15 @@ def test_linear_matches_torch(M, K, N, act, res):
 @pytest.mark.parametrize("M,K,N,act,res", [
     (1024, 512, 512, 0, False), (2048, 2048, 512, 0, True), (1024, 512, 2048, 1, False), (512, 256, 768, 0, True),
     (300, 256, 256, 1, True), (8192, 1024, 1024, 0, False), (1000, 4096, 1024, 0, True),
+    (61340, 256, 232, 1, True), (15360, 1024, 1024, 0, True),
 ])
 def test_linear_256_tile_kernel_matches_torch(M, K, N, act, res):
-    """shapes that the dispatcher sends to gemm256_bf16_kernel (LDS-DMA ring, 256 x 256 block tile)"""
+    """MFMA-bound token GEMM shapes.  Only the last two reach gemm256_bf16_kernel (LDS-DMA ring, 256 x 256 block tile:
+    at least 240 blocks of 256 x 256, K >= 256), which ops.linear_plan asserts; the dispatcher sends the earlier ones
+    to the 128-feature tile kernels (plan 1 or 2) since it asks for a full chip of 256-tiles."""
     from flairhip import ops
+    plan = ops.linear_plan(torch.bfloat16, M, K, N)
+    assert plan == 3 if M >= 15360 else plan in (1, 2)
     g = torch.Generator().manual_seed(M + 3 * K + N)
     x = torch.randn(M, K, generator=g)
     w = torch.randn(N, K, generator=g) / math.sqrt(K)
