@@ -19,6 +19,8 @@
 #define FFA_ERR_UNSUPPORTED (-2)
 #define FFA_ERR_WORKSPACE (-3)
 
+#define FFA_CE_MAXK 32  // largest class count and logit pitch of the per-pixel softmax kernels (resample_loss.hip, tta.hip)
+
 #define FFA_BCO_RING 0x1000  // `bco` flag: operand packed for conv3x3_ring_kernel (ffa_conv_plan)
 #define FFA_BCO_THIN 0x2000  // `bco` flag: operand packed for conv3x3_thin_kernel (<= 32 input channels, <= 32 rows)
 #define FFA_BCO_THIN32 0x4000  // with FFA_BCO_THIN: the operand multiplies 32-channel pixels (8-row tiles; else 16 ch, 16-row tiles)

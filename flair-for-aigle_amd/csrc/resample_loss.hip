@@ -274,8 +274,7 @@ extern "C" int ffa_bilinear_bwd(int dtype, const void* dy, void* dx, int B, int 
 // pass B reads the logits once and writes per-block loss partials, dlogits (already divided by the
 // weight sum and multiplied by *grad_scale) and the per-pixel argmax.
 
-#define FFA_CE_MAXK 32
-#define FFA_CE_BLOCKS 1024
+#define FFA_CE_BLOCKS 1024  // FFA_CE_MAXK, the largest class count / logit pitch, is in ffa_common.h
 
 // Sum of the target weights.  vec16: the target pointer is 16-byte aligned -- a thread then takes 16 consecutive
 // targets per 16-byte load (one byte per lane per load made this 24 us for 8.4 M targets) and looks the weights up in

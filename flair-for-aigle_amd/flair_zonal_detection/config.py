@@ -30,6 +30,21 @@ def validate_write_confidence(config: dict) -> bool:
     return write_confidence
 
 
+TTA_MODES = ("none", "flips", "d4")  # the keys of flairhip.augment.TTA_VIEWS
+
+
+def validate_tta(config: dict) -> str:
+    """The optional key tta (default none): test-time augmentation of the tile loop.  'flips': every tile is predicted
+    as it is and under the three flips, 'd4': under all 8 flips / rotations of the square; the softmax probabilities
+    of the views are averaged in the tile's frame before the uint8 conversion.  Anything else raises ValueError."""
+    tta = config.get("tta", "none")
+    if tta is None:
+        return "none"
+    if not isinstance(tta, str) or tta.strip().lower() not in TTA_MODES:
+        raise ValueError(f"tta must be one of {', '.join(TTA_MODES)}, got {tta!r}")
+    return tta.strip().lower()
+
+
 def validate_skip_tiles_outside_zone(config: dict) -> bool:
     """The optional key skip_tiles_outside_zone (default false): with a geozone, run_inference drops the tiles whose
     kept area (grown by a pixel) holds no pixel centre inside the zone contour before the tile loop."""
@@ -105,6 +120,7 @@ def validate_config(config: dict) -> None:
         if key not in config:
             raise ValueError(f"Missing required config key: {key}")
     validate_write_confidence(config)
+    validate_tta(config)
     validate_skip_tiles_outside_zone(config)
     validate_geozone_crs(config)
     validate_sieve_area(config)

@@ -28,6 +28,11 @@ run_fast_aigle_segmentation.py:162-163, and its unused second path :566-630 mean
 kernel pass as the label, and ``raster_to_polygons(..., confidence=...)`` adds the columns ``confidence`` (mean over
 the polygon's pixels, from exact integer sums taken on the GPU) and ``pixels``.  ``logits_to_labels_and_confidence``
 and ``vectorize_segmentation_parallel`` carry the fork's names for that path.
+
+Test-time augmentation (config key ``tta``: none, flips or d4): every tile is predicted under 4 or 8 flips / rotations
+of the square -- the transforms the network was trained with (flairhip/augment.py) -- and the softmax probabilities of
+the views are averaged in the tile's own frame (csrc/tta.hip) before the uint8 conversion; the outputs keep their
+shapes, so everything after the conversion is shared with the plain loop.
 """
 from __future__ import annotations
 
@@ -42,9 +47,10 @@ import torch
 from torch.utils.data import DataLoader
 
 from flairhip import ops
+from flairhip.augment import tta_views
 from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_cog_conversion,
                                           validate_cog_overview_resampling, validate_config, validate_geozone_crs,
-                                          validate_skip_tiles_outside_zone, validate_write_confidence)
+                                          validate_skip_tiles_outside_zone, validate_tta, validate_write_confidence)
 from flair_zonal_detection.dataset import MultiModalSlicedDataset, TileBatcher, pad_series_collate
 from flair_zonal_detection.model_utils import build_inference_model, compute_patch_sizes
 from flair_zonal_detection.postprocess import convert, convert_to_cog  # noqa: F401  (re-exported like the reference)
@@ -276,6 +282,32 @@ def inference_and_write(model: torch.nn.Module, dataloader: DataLoader, tiles_gd
                                               crop=(margin, margin, keep, keep))
         return preds
 
+    # test-time augmentation (config key tta): one forward per view, the model's layout kernels apply the view's code to
+    # every modality (batch["AUG"]); each view's probabilities go back to the tile's frame and into an f32 accumulator
+    # (ffa_tta_accumulate), and the uint8 outputs come from the mean (ffa_tta_predict_u8): same shapes and dtypes as
+    # above, so everything downstream is shared.  The whole loop is one graph replay for a full batch.
+    views = tta_views(validate_tta(config))
+    view_codes: Dict[Tuple[int, int], torch.Tensor] = {}  # (code, batch size) -> constant device uint8 [B]
+
+    def forward_tta(inputs):
+        batch_size = next(v.shape[0] for k_, v in inputs.items() if not k_.endswith("_NORM"))
+        accs = {}
+        for v, code in enumerate(views):
+            codes_v = view_codes.get((code, batch_size))
+            if codes_v is None:
+                codes_v = view_codes[(code, batch_size)] = torch.full((batch_size,), code, dtype=torch.uint8,
+                                                                      device=device)
+            logits_tasks, _ = model({**inputs, "AUG": codes_v})
+            for task_name, logits in logits_tasks.items():
+                nhwc, classes = logits._ffa_nhwc, logits._ffa_classes
+                if v == 0:
+                    accs[task_name] = ops.tta_buffer(nhwc.shape[0], classes, keep, keep, nhwc.device, cp=nhwc.shape[3])
+                ops.tta_accumulate_(accs[task_name], nhwc, classes, code, crop=(margin, margin, keep, keep),
+                                    first=v == 0)
+        return {task_name: ops.tta_predict_u8(acc, predict_mode, len(views)) for task_name, acc in accs.items()}
+
+    forward = forward_tta if len(views) > 1 else forward_eager
+
     def write_batch(indices, host_preds):
         """host side of one batch: window placement + raster writes (reference inference.py:297-352)"""
         for task_name, (buf, done) in host_preds.items():
@@ -315,10 +347,10 @@ def inference_and_write(model: torch.nn.Module, dataloader: DataLoader, tiles_gd
         if use_graph and full and len(indices) == full:
             if graphed is None:
                 from flairhip.graph import GraphedCall
-                graphed = GraphedCall(forward_eager, inputs)
+                graphed = GraphedCall(forward, inputs)
             preds = graphed(inputs)
         else:
-            preds = forward_eager(inputs)
+            preds = forward(inputs)
         host_preds = {}
         for task_name, pred in preds.items():
             if needs_rescale:

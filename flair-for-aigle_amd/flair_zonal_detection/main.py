@@ -104,6 +104,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="convert the written rasters to cloud-optimised GeoTIFFs (<name>_COG.tif: overview "
                              "pyramid, IFDs ahead of the data), as the config key cog_conversion: true does; overviews "
                              "by the config key cog_overview_resampling (nearest, mode or average)")
+    parser.add_argument("--tta", type=str, default=None, choices=("none", "flips", "d4"),
+                        help="test-time augmentation: predict every tile under the flips (4 views) or all flips and "
+                             "rotations of the square (d4, 8 views) and average the class probabilities.  Default: the "
+                             "config key tta, else none")
     parser.add_argument("--zone", type=str, default=None, metavar="PATH.geojson",
                         help="geozone contour (GeoJSON, in the raster's CRS unless --zone-crs says otherwise): only its "
                              "bounding box is sliced (and, with skip_tiles_outside_zone in the config, only the tiles "
@@ -145,10 +149,13 @@ def main(argv=None) -> None:
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     config = args.config
-    if args.cog:  # the key, for this run only
+    if args.cog or args.tta is not None:  # the keys, for this run only
         from flair_zonal_detection.config import load_config
         config = load_config(args.config)
-        config["cog_conversion"] = True
+        if args.cog:
+            config["cog_conversion"] = True
+        if args.tta is not None:
+            config["tta"] = args.tta
     if world > 1:
         outputs = run_sharded(config, int(os.environ.get("RANK", "0")), world, keep_parts=args.keep_parts,
                               geozone=args.zone, geozone_crs=args.zone_crs)

@@ -166,6 +166,9 @@ SIGNATURES = {
     "ffa_softmax_ce_sums": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _ll, _i, _i, _p, _ll, _p]),
     "ffa_scale_inplace": (_i, [_i, _p, _ll, _p, _p]),
     "ffa_predict_u8": (_i, [_i, _i, _p, _p] + [_i] * 9 + [_p]),
+    "ffa_tta_accumulate": (_i, [_i, _p, _p] + [_i] * 11 + [_p]),
+    "ffa_tta_predict_u8": (_i, [_i, _p, _p] + [_i] * 6 + [_p]),
+    "ffa_tta_probabilities": (_i, [_p, _p] + [_i] * 6 + [_p]),
     "ffa_onehot_to_index": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "ffa_confusion_matrix": (_i, [_p, _p, _ll, _i, _p, _p]),
     "ffa_slice_grid": (_ll, [_d, _d, _d, _d, _d, _d, _i, _i, _d, C.POINTER(Tile), _ll]),

@@ -966,6 +966,98 @@ def predict_u8(logits: torch.Tensor, num_classes: int, mode: str = "argmax", cro
     return out
 
 
+def tta_buffer(B: int, K: int, h: int, w: int, device, cp: Optional[int] = None) -> torch.Tensor:
+    """The accumulator of test-time augmentation for B windows of h x w pixels and K classes: f32 [B, h, w, cp],
+    pixel-major at the logits' channel pitch ``cp`` (default pad_channels(K), the pitch of the models' logits).  K rides
+    along as ``_ffa_classes``, as on the models' logits.  The contents do not matter: the first view is accumulated
+    with ``first=True``."""
+    cp = pad_channels(K) if cp is None else int(cp)
+    if min(int(B), int(K), int(h), int(w)) < 1:
+        raise ValueError(f"tta_buffer: B, K, h, w must be >= 1, got {(B, K, h, w)}")
+    if cp % 8 or cp < K:
+        raise ValueError(f"tta_buffer: pitch {cp} must be a multiple of 8 and hold {K} classes")
+    acc = torch.empty((int(B), int(h), int(w), cp), dtype=torch.float32, device=device)
+    acc._ffa_classes = int(K)
+    return acc
+
+
+def _chk_tta_acc(acc: torch.Tensor, num_classes: Optional[int], op: str) -> int:
+    """the class count of an accumulator: ``num_classes`` when given, else what tta_buffer noted on it"""
+    if not (torch.is_tensor(acc) and acc.is_cuda and acc.dtype == torch.float32 and acc.dim() == 4
+            and acc.is_contiguous()):
+        raise ValueError(f"{op}: the accumulator must be a contiguous f32 CUDA tensor [B, h, w, cp] (ops.tta_buffer)")
+    noted = getattr(acc, "_ffa_classes", None)
+    k = noted if num_classes is None else num_classes
+    if k is None:
+        raise ValueError(f"{op}: the accumulator does not come from ops.tta_buffer: num_classes is required")
+    if noted is not None and k != noted:
+        raise ValueError(f"{op}: {k} classes, but the accumulator was made for {noted}")
+    if acc.shape[3] % 8 or isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= acc.shape[3]:
+        raise ValueError(f"{op}: pitch {acc.shape[3]} must be a multiple of 8 and hold {k!r} classes")
+    return k
+
+
+def tta_accumulate_(acc: torch.Tensor, logits_nhwc: torch.Tensor, num_classes: int, code: int,
+                    crop: Optional[Tuple[int, int, int, int]] = None, first: bool = False) -> torch.Tensor:
+    """One view of test-time augmentation into the accumulator, in place: ``logits_nhwc`` [B, n, n, cp] (bf16 / f32) are
+    the logits of the tile transformed by the forward ``code`` (flairhip.augment, 0..15), in the view's frame; their
+    softmax, taken back to the tile's frame, is stored into (``first``) or added to ``acc`` [B, h, w, cp] over the crop
+    window (y0, x0, h, w) of the tile's frame (default: the whole tile).  Views add up in call order, deterministically
+    (flairhip.augment.tta_mean_probabilities is the definition)."""
+    lib = _l.load()
+    _chk_nhwc(logits_nhwc, "tta_accumulate_ logits")
+    _chk_tta_acc(acc, num_classes, "tta_accumulate_")
+    B, H, W, cp = logits_nhwc.shape
+    if H != W:
+        raise ValueError(f"tta_accumulate_: rotations need square tiles, got {H} x {W}")
+    if isinstance(code, bool) or not isinstance(code, int) or not 0 <= code <= 15:
+        raise ValueError(f"tta_accumulate_: code must be an int in 0..15, got {code!r}")
+    y0, x0, h, w = crop if crop is not None else (0, 0, H, W)
+    if not (y0 >= 0 and x0 >= 0 and h > 0 and w > 0 and y0 + h <= H and x0 + w <= W):
+        raise ValueError(f"tta_accumulate_: crop {(y0, x0, h, w)} outside the {H} x {W} tile")
+    if tuple(acc.shape) != (B, h, w, cp) or acc.device != logits_nhwc.device:
+        raise ValueError(f"tta_accumulate_: accumulator {tuple(acc.shape)} on {acc.device} does not match "
+                         f"{(B, h, w, cp)} on {logits_nhwc.device}")
+    _l.check(lib.ffa_tta_accumulate(_dt(logits_nhwc), logits_nhwc.data_ptr(), acc.data_ptr(), B, H, W, num_classes, cp,
+                                    y0, x0, h, w, code, int(bool(first)), _stream()), "tta_accumulate_")
+    return acc
+
+
+def _chk_tta_views(views: int, op: str) -> int:
+    if isinstance(views, bool) or not isinstance(views, int) or views < 1:
+        raise ValueError(f"{op}: views must be an int >= 1, got {views!r}")
+    return views
+
+
+def tta_predict_u8(acc: torch.Tensor, mode: str, views: int, num_classes: Optional[int] = None) -> torch.Tensor:
+    """predict_u8's outputs from an accumulator of ``views`` views (on acc / views): 'argmax' -> [B, h, w], 'class_prob'
+    -> [B, K, h, w], 'argmax_conf' -> [B, 2, h, w].  ``num_classes``: K, for an accumulator that is not tta_buffer's.
+    With one identity view the outputs equal predict_u8's bit for bit."""
+    lib = _l.load()
+    if mode not in _PREDICT_MODES:
+        raise ValueError(f"Unknown output type: {mode}")
+    _chk_tta_views(views, "tta_predict_u8")
+    k = _chk_tta_acc(acc, num_classes, "tta_predict_u8")
+    B, h, w, cp = acc.shape
+    shape = {"argmax": (B, h, w), "class_prob": (B, k, h, w), "argmax_conf": (B, 2, h, w)}[mode]
+    out = torch.empty(shape, dtype=torch.uint8, device=acc.device)
+    _l.check(lib.ffa_tta_predict_u8(_PREDICT_MODES[mode], acc.data_ptr(), out.data_ptr(), B, k, cp, h, w, views,
+                                    _stream()), "tta_predict_u8")
+    return out
+
+
+def tta_probabilities(acc: torch.Tensor, views: int, num_classes: Optional[int] = None) -> torch.Tensor:
+    """the mean class probabilities of an accumulator of ``views`` views: f32 [B, K, h, w]"""
+    lib = _l.load()
+    _chk_tta_views(views, "tta_probabilities")
+    k = _chk_tta_acc(acc, num_classes, "tta_probabilities")
+    B, h, w, cp = acc.shape
+    out = torch.empty((B, k, h, w), dtype=torch.float32, device=acc.device)
+    _l.check(lib.ffa_tta_probabilities(acc.data_ptr(), out.data_ptr(), B, k, cp, h, w, views, _stream()),
+             "tta_probabilities")
+    return out
+
+
 def onehot_to_index(onehot: torch.Tensor) -> torch.Tensor:
     lib = _l.load()
     if onehot.dtype != torch.float32 or not onehot.is_contiguous():

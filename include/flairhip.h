@@ -474,6 +474,29 @@ int ffa_scale_inplace(int dtype, void* x, long long n, const float* scale, ffa_s
  * probability), bit for bit the maximum over the K bands mode 1 writes for the pixel, in one pass over the logits. */
 int ffa_predict_u8(int dtype, int mode, const void* logits, uint8_t* out, int B, int H, int W, int K, int Cp, int y0,
                    int x0, int h, int w, ffa_stream_t stream);
+/* Test-time augmentation: a tile predicted under several flips / rotations ("views", the codes of ffa_d4_nchw_to_nhwc:
+ * bit 0 horizontal flip, bit 1 vertical flip, bits 2-3 k of rot90), the softmax probabilities averaged in the tile's
+ * own frame.  `logits` is ONE view's NHWC tensor [B][H][W][Cp] (bf16 or f32, K classes, H == W, else
+ * FFA_ERR_UNSUPPORTED) in the VIEW's frame, `code` (0..15, one host int: all samples of a launch share it) the forward
+ * code that made the view.  For every pixel (y0 + y, x0 + x) of the crop window, stated in the TILE's frame, the kernel
+ * finds the pixel's position in the view (the gather of the inverse transform), takes the softmax there in the
+ * arithmetic of ffa_predict_u8 mode 1 (f32: maximum, expf(z - m), sum in class order, e / se) and stores it into the
+ * accumulator (first != 0) or adds it (first == 0).
+ * Accumulator layout: f32, pixel-major over the crop window at the logits' pitch, acc[B][h][w][Cp], 16-byte aligned;
+ * the pad channels K..Cp-1 hold 0.  One thread owns an element and views add up in call order: no atomics, equal
+ * calls give equal bytes.  Both the logits and the accumulator are moved in whole runs of consecutive bytes for every
+ * code (the transposition of odd k happens in LDS). */
+int ffa_tta_accumulate(int dtype, const void* logits, float* acc, int B, int H, int W, int K, int Cp, int y0, int x0,
+                       int h, int w, int code, int first, ffa_stream_t stream);
+/* The outputs of ffa_predict_u8 from an accumulator of `views` (>= 1) views, computed on p = acc / (float)views:
+ * mode 0: out [B][h][w] = first maximum of p; mode 1: out [B][K][h][w] = rintf(p * 255.f); mode 2: out [B][2][h][w] =
+ * the label plane of mode 0 and rintf(255 * max p), bit for bit the maximum over the mode-1 bands of the pixel.  With
+ * one identity view (code 0, first != 0, views 1) all three equal ffa_predict_u8's outputs bit for bit. */
+int ffa_tta_predict_u8(int mode, const float* acc, uint8_t* out, int B, int K, int Cp, int h, int w, int views,
+                       ffa_stream_t stream);
+/* The mean probabilities themselves: out f32 [B][K][h][w] = acc / (float)views */
+int ffa_tta_probabilities(const float* acc, float* out, int B, int K, int Cp, int h, int w, int views,
+                          ffa_stream_t stream);
 int ffa_onehot_to_index(const float* onehot, uint8_t* idx, int B, int K, int H, int W, ffa_stream_t stream);
 /* counts[target][pred] += 1 (int64, accumulating): the IoU-metric state of tasks_module.py:210-212 */
 int ffa_confusion_matrix(const uint8_t* pred, const uint8_t* target, long long n, int K, long long* counts,

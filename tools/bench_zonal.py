@@ -15,6 +15,9 @@ and the wall time of the tile loop (inference_and_write) of both.
 the overview pyramid alone for each method (hip events, best of 3 after a warm-up), the wall time of
 postprocess.convert_to_cog, and the plain GeoTiffWriter.close() of the same raster for comparison (the COG holds 4/3 of
 the tiles).
+--tta flips|d4: the tile loop with the config key tta (V forward passes per batch, probabilities averaged in the tile's
+frame), after the kernels of that path alone at the loop's shapes: ffa_tta_accumulate for an even-k and an odd-k view
+and ffa_tta_predict_u8 (hip events over queued calls, best of 3 after a warm-up), with the bytes each moves per second.
 """
 from __future__ import annotations
 
@@ -99,6 +102,52 @@ def bench_cog(size: int) -> None:
         shutil.rmtree(d)
 
 
+HBM_COPY_TBS = 6.29  # measured float4 copy rate of the MI355X, TB/s: the yardstick of the streaming kernels
+
+
+def bench_tta_kernels(batch: int, precision: str, mode: str, patch: int = 512, margin: int = 40, K: int = 19) -> None:
+    """ffa_tta_accumulate (code 0: rows stay rows; code 4: a destination row is a column of the view) and
+    ffa_tta_predict_u8 at the tile loop's shapes.  Bytes: the logits window read once, the accumulator written (first
+    view) or read and written (later views); predict reads the accumulator and writes its uint8 planes."""
+    from flairhip import ops
+    dev = torch.device("cuda:0")
+    dtype = torch.bfloat16 if precision == "bf16" else torch.float32
+    cp, keep = ops.pad_channels(K), patch - 2 * margin
+    logits = torch.randn(batch, patch, patch, cp, device=dev).to(dtype)
+    acc = ops.tta_buffer(batch, K, keep, keep, dev, cp=cp)
+    crop = (margin, margin, keep, keep)
+    window_bytes = batch * keep * keep * cp * logits.element_size()
+    acc_bytes = acc.numel() * 4
+    planes = {"argmax": 1, "class_prob": K, "argmax_conf": 2}[mode]
+    reps = 20
+
+    def timed(call):
+        call()  # warm-up
+        best = float("inf")
+        for _ in range(3):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                call()
+            b.record()
+            torch.cuda.synchronize()
+            best = min(best, a.elapsed_time(b) / reps)
+        return best  # ms
+
+    rows = [(f"tta_accumulate code {code} (k = {code >> 2}) {'store' if first else 'add'}",
+             lambda code=code, first=first: ops.tta_accumulate_(acc, logits, K, code, crop=crop, first=first),
+             window_bytes + acc_bytes * (1 if first else 2))
+            for code in (0, 4) for first in (True, False)]
+    rows.append((f"tta_predict_u8 {mode}", lambda: ops.tta_predict_u8(acc, mode, 8),
+                 acc_bytes + batch * keep * keep * planes))
+    for name, call, moved in rows:
+        ms = timed(call)
+        tbs = moved / ms / 1e9
+        print(f"{name}: {ms * 1e3:.1f} us per call (batch {batch}, {keep} x {keep} of {patch} x {patch}, pitch {cp}, "
+              f"{precision}; hip events over {reps} queued calls, best of 3) = {tbs:.2f} TB/s of {moved / 1e6:.1f} MB "
+              f"= {100 * tbs / HBM_COPY_TBS:.0f} % of the {HBM_COPY_TBS} TB/s copy rate")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=6048, help="raster height = width in pixels")
@@ -114,6 +163,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--write-confidence", action="store_true",
                     help="run the tile loop with write_confidence: true (argmax output only)")
+    ap.add_argument("--tta", default=None, choices=["flips", "d4"],
+                    help="run the tile loop with the config key tta, after timing the kernels of that path alone")
     ap.add_argument("--zone", action="store_true",
                     help="time the tile loop under a geozone with skip_tiles_outside_zone off and on")
     ap.add_argument("--cog", action="store_true",
@@ -163,6 +214,10 @@ def main():
                "monotemp_arch": args.arch})
     if args.write_confidence:
         zc["write_confidence"] = True
+    if args.tta:
+        bench_tta_kernels(args.batch, args.precision,
+                          "argmax_conf" if args.write_confidence else args.output_type)
+        zc["tta"] = args.tta
     torch.save({"state_dict": {"model." + k: v.cpu() for k, v in model.state_dict().items()}}, zc["model_weights"])
     zc["modalities"][MOD].update({"input_img_path": ras, "channels": list(range(1, C + 1)),
                                   "normalization": {"type": "custom", "means": [110.0] * C, "stds": [50.0] * C}})
@@ -200,7 +255,8 @@ def main():
     torch.cuda.synchronize()
     dt = time.time() - t0
     ntiles = ((H + 80 + 431) // 432) ** 2
-    print(f"run_inference on {H}x{W} px ({ntiles} tiles of 512, batch {args.batch}): {dt:.2f} s = {ntiles / dt:.1f} tiles/s, "
+    what = f"run_inference with tta {args.tta}" if args.tta else "run_inference"
+    print(f"{what} on {H}x{W} px ({ntiles} tiles of 512, batch {args.batch}): {dt:.2f} s = {ntiles / dt:.1f} tiles/s, "
           f"{H * W / dt / 1e6:.1f} Mpx/s; output {out[TASK].data.shape}")
 
     # the same run split into its stages (second pass: kernels and workspaces are warm)
