@@ -25,8 +25,7 @@
 //             bit 3 of the row is set  -> conflict-free ds_read_b128, linear (lane-order) DMA destination
 //   halo      [k-step plane][halo pixel][32 B], halves swapped when bit 3 of the pixel's x is set; plane stride
 //             = 64 mod 128 bytes -> conflict-free ds_read_b128 for 32 pixels of a row and conflict-free ds_write_b128
-#include "ffa_common.h"
-#include <hip/hip_ext.h>
+#include "ffa_gfx950.h"
 
 #include <stdlib.h>
 
@@ -66,27 +65,6 @@ struct Ring3Args {
   long long cb64_stride;  // bytes between the operands of consecutive 64-row groups
 };
 
-template <typename T>
-struct RingMma;
-template <>
-struct RingMma<ffa_bf16> {
-  static constexpr int PER = 1;
-  static __device__ __forceinline__ void run(const ffa_u32x4& a, const ffa_u32x4& b, ffa_f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ffa_bf16x8, a), __builtin_bit_cast(ffa_bf16x8, b),
-                                                c, 0, 0, 0);
-  }
-};
-template <>
-struct RingMma<float> {
-  static constexpr int PER = 4;
-  static __device__ __forceinline__ void run(const ffa_u32x4& a, const ffa_u32x4& b, ffa_f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-  }
-};
-
 template <int WCO, int WPX, int NT, int TH, int TW>
 struct RingGeom {
   static constexpr int MT = 2;
@@ -123,36 +101,8 @@ struct RingGeom {
 
 // phase-end synchronisation: this wave's DMA of the NEXT phase has landed when at most its newest NWI vector-memory
 // operations (the DMA of the phase after that, issued at the top of this phase) are outstanding; its halo stores
-// are in LDS (lgkmcnt); then the block meets.  One asm statement with a memory clobber: neither the compiler's own
-// LDS accesses nor its loads move across it.
-// One LDS-DMA instruction: 64 lanes x 16 bytes from per-lane global addresses to LDS at lds_base + lane * 16
-// (lds_base wave-uniform).  Inline asm on purpose: with __builtin_amdgcn_global_load_lds in the kernel hipcc
-// (ROCm 7.2) stops counting lgkmcnt and drains it to 0 in front of every MFMA step (532 of 789 waits were
-// lgkmcnt(0); without the builtin they are counted), which stalls every step on the fragment reads just issued for
-// two steps later.  The DMA is invisible to the compiler: its completion is waited for by hand (ring_phase_sync),
-// the compiler's own vmcnt waits can only become stricter through the extra entries in the queue.  M0 (the LDS
-// destination base) is written and restored inside the statement.
-__device__ __forceinline__ void ring_dma16(const unsigned char* src, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_base)
-      : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void ring_phase_sync() {
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
-}
-// the same without the LDS wait: fragment reads requested for later steps stay in flight across the barrier
-template <int N>
-__device__ __forceinline__ void ring_phase_sync_nolgkm() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(N) : "memory");
-}
-__device__ __forceinline__ void ring_lds_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
+// are in LDS (lgkmcnt); then the block meets: ffa_wait_vm_lgkm_barrier<NWI>, or ffa_wait_vm_barrier where no halo
+// stores are pending, so that fragment reads requested for later steps stay in flight across the barrier.
 
 template <typename T, int WCO, int WPX, int NT, int TH, int TW, int OCC, bool PRO>
 __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3Args a) {
@@ -245,7 +195,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3
       const int g64 = ii / (G::SLAB64 / 1024), pi = ii % (G::SLAB64 / 1024);
       const unsigned char* src = w_all + (long long)(cb * WCO + g64) * a.cb64_stride + (long long)ph * G::SLAB64 +
                                  pi * 1024 + lane * 16;
-      ring_dma16(src, (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + G::RING_OFF + slot * G::SLOT +
+      ffa_lds_dma16(src, (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + G::RING_OFF + slot * G::SLOT +
                                                                                   ii * 1024));
     }
   };
@@ -311,7 +261,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3
   issue_w(cur.cb, 0, 0);
   issue_w(cur.cb, 1, 1);
   store_h(0);
-  ring_phase_sync<0>();  // slabs 0 and 1 have landed, halo chunk 0 is stored
+  ffa_wait_vm_lgkm_barrier<0>();  // slabs 0 and 1 have landed, halo chunk 0 is stored
   RT_ADD(rt_pro, rt_t0);
   int hb = 0;  // halo buffer of the current chunk
   int hd = G::HBUF;  // byte distance from the current halo buffer to the other one
@@ -407,16 +357,16 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) RingMma<T>::run(fa[st % 3][mt], fb[st % 3][nt], acc[mt][nt]);
+            for (int nt = 0; nt < NT; ++nt) Mma<T>::run(fa[st % 3][mt], fb[st % 3][nt], acc[mt][nt]);
           {
             constexpr int NM = MT * NT;
 #if FFA_RING_SCHED == 0
             __builtin_amdgcn_sched_group_barrier(0x100, MT + NT, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, NM * RingMma<T>::PER, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, NM * Mma<T>::PER, 0);
 #else
 #pragma unroll
             for (int i = 0; i < NM; ++i) {
-              __builtin_amdgcn_sched_group_barrier(0x008, RingMma<T>::PER, 0);
+              __builtin_amdgcn_sched_group_barrier(0x008, Mma<T>::PER, 0);
               if (i < MT + NT) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
 #endif
@@ -431,8 +381,8 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3
             const long long rt_s = RT_NOW();
             ++rt_phases;
 #endif
-            if (r == 2) ring_phase_sync<0>();  // halo stores must be in LDS
-            else ring_phase_sync_nolgkm<0>();
+            if (r == 2) ffa_wait_vm_lgkm_barrier<0>();  // halo stores must be in LDS
+            else ffa_wait_vm_barrier<0>();
             RT_ADD(rt_sync, rt_s);
             issue_w(wcb_, wph_, (r + 2) % 3);
             if (r == 0 && hvalid) load_h(hchunk);
@@ -529,7 +479,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3
         float* red = reinterpret_cast<float*>(smem + G::RED_OFF);
         red[(wave * 64 + lane) * 2 + 0] = st[0];
         red[(wave * 64 + lane) * 2 + 1] = st[1];
-        ring_lds_sync();
+        ffa_wait_lgkm_barrier();
         if (tid < 128 * WCO) {
           const int wc = tid >> 7, t7 = tid & 127;
           const int j = t7 & 1;
@@ -543,7 +493,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3
           const int c = cur.cb * G::BCO + wc * 64 + 16 * (L >> 3) + 8 * hf + (L & 7);
           if (c < a.Co) a.stats[((size_t)cur.pt * 2 + which) * a.Co + c] = t;
         }
-        ring_lds_sync();  // red is reused by the next tile
+        ffa_wait_lgkm_barrier();  // red is reused by the next tile
       }
     }
     RT_ADD(rt_epi, rt_e);
@@ -565,7 +515,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3
   }
 #endif
   // the trailing DMA (re-reads of the last slab) must not outlive the block's LDS allocation
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ffa_wait_vm<0>();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -585,7 +535,6 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring_kernel(Ring3
 //     step t multiplies; the phase synchronisation sits behind step 0, the DMA of phase p+2 right behind it.
 
 // source of the padding pieces of an LDS-DMA halo fill (per-lane source addresses: a border pixel reads zeros)
-__device__ __attribute__((aligned(16))) const unsigned int ffa_ring_zero16[4] = {0u, 0u, 0u, 0u};
 
 template <int WCO, int WPX, int NT, int TH, int TW>
 struct Ring16Geom {
@@ -701,7 +650,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
       const int g64 = ii / (G::SLAB64 / 1024), pi = ii % (G::SLAB64 / 1024);
       const unsigned char* src = w_all + (long long)(cb * WCO + g64) * a.cb64_stride + (long long)ph * G::SLAB64 +
                                  pi * 1024 + lane * 16;
-      ring_dma16(src, (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + G::RING_OFF + slot * G::SLOT +
+      ffa_lds_dma16(src, (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + G::RING_OFF + slot * G::SLOT +
                                                                                   ii * 1024));
     }
   };
@@ -709,16 +658,16 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
   // instruction runs with the lanes past the last piece masked off (they would write into the other buffer).
   auto dma_h = [&](int chunk, int buf) {
     const unsigned char* base = in_b + chunk * 64;
-    const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_ring_zero16);
+    const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_zero16);
 #pragma unroll
     for (int k = 0; k < G::NHP; ++k) {
       const unsigned char* src = hoff[k] >= 0 ? base + (unsigned)hoff[k] : zero;
       const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(
           smem + G::HALO_OFF + buf * G::HBUF + (wave * 64 + k * G::NTHR) * 16);
       if (k + 1 < G::NHP || G::H_PIECES % G::NTHR == 0) {
-        ring_dma16(src, dst);
+        ffa_lds_dma16(src, dst);
       } else if (wave * 64 + k * G::NTHR < G::H_PIECES) {  // wave uniform
-        if (tid + k * G::NTHR < G::H_PIECES) ring_dma16(src, dst);
+        if (tid + k * G::NTHR < G::H_PIECES) ffa_lds_dma16(src, dst);
       }
     }
   };
@@ -768,10 +717,10 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
   issue_w(cur.cb, 0, 0);
   issue_w(cur.cb, 1, 1);
   if constexpr (PRO) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ffa_wait_vm<0>();
     fix_h(0, 0);
   }
-  ring_phase_sync<0>();  // slabs 0 and 1 and halo chunk 0 are in LDS (and normalised)
+  ffa_wait_vm_lgkm_barrier<0>();  // slabs 0 and 1 and halo chunk 0 are in LDS (and normalised)
   int hb = 0;
   int hd = G::HBUF;  // byte distance from the current halo buffer to the other one
 
@@ -859,15 +808,15 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
               // exact count per wave: the tail instruction of the halo fill exists only in the waves that own pieces
               // of it (a wave that waited for one operation too few would publish a weight slab still in flight)
               constexpr bool TAIL = G::H_PIECES % G::NTHR != 0;
-              if (!TAIL || wave * 64 + (G::NHP - 1) * G::NTHR < G::H_PIECES) ring_phase_sync_nolgkm<G::NHP>();
-              else ring_phase_sync_nolgkm<G::NHP - 1>();
+              if (!TAIL || wave * 64 + (G::NHP - 1) * G::NTHR < G::H_PIECES) ffa_wait_vm_barrier<G::NHP>();
+              else ffa_wait_vm_barrier<G::NHP - 1>();
             } else if (PRO && r == 2) {
-              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+              ffa_wait_vm<0>();
               // the tile whose halo this is: hoff[] already describes it (the next chunk of `cur`, or chunk 0 of `nxt`)
               if (hvalid) fix_h(hchunk, hb ^ 1);
-              ring_phase_sync<0>();  // the rewritten pieces must be in LDS before the block meets
+              ffa_wait_vm_lgkm_barrier<0>();  // the rewritten pieces must be in LDS before the block meets
             } else {
-              ring_phase_sync_nolgkm<0>();
+              ffa_wait_vm_barrier<0>();
             }
             issue_w(wcb_, wph_, (r + 2) % 3);
             if (r == 0 && hvalid) dma_h(hchunk, hb ^ 1);
@@ -967,7 +916,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
         float* red = reinterpret_cast<float*>(smem + G::RED_OFF);
         red[(wave * 64 + lane) * 2 + 0] = st[0];
         red[(wave * 64 + lane) * 2 + 1] = st[1];
-        ring_lds_sync();
+        ffa_wait_lgkm_barrier();
         if (tid < 128 * WCO) {
           const int wc = tid >> 7, t7 = tid & 127;
           const int j = t7 & 1;
@@ -980,7 +929,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
           const int ch = cur.cb * G::BCO + wc * 64 + 16 * kq + (cl & 7) * 2 + j;
           if (ch < a.Co) a.stats[((size_t)cur.pt * 2 + which) * a.Co + ch] = t;
         }
-        ring_lds_sync();  // red is reused by the next tile
+        ffa_wait_lgkm_barrier();  // red is reused by the next tile
       }
     }
     if (!has_next) break;
@@ -988,7 +937,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
     cur = nxt;
   }
   // the trailing DMA (re-reads of the last slab) must not outlive the block's LDS allocation
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ffa_wait_vm<0>();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1029,17 +978,11 @@ static RingPlan ring_plan(int B, int H, int W, int co_rows) {
 
 template <int WCO, int WPX, int NT, int TH, int TW, int OCC>
 static int ring16_launch(const Ring3Args& a, int grid, hipStream_t stream) {
-  hipEvent_t ts, te;  // measurement session open (bench.py): the kernel's own duration from launch-attached events
-  if (!a.pro_sc && ffa_ktime_next(WCO == 2 ? FFA_KT_RING16_128CO : (TW == 32 ? FFA_KT_RING16_8x32 : FFA_KT_RING16_16x16), &ts, &te)) {
-    hipExtLaunchKernelGGL((conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, false>), dim3(grid), dim3(64 * WCO * WPX), 0,
-                          stream, ts, te, 0, a);
-    return ffa_check_launch("conv3x3_ring16");
-  }
-  if (a.pro_sc)
-    hipLaunchKernelGGL((conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, true>), dim3(grid), dim3(64 * WCO * WPX), 0,
-                       stream, a);
+  if (!a.pro_sc)  // measurement session open (bench.py): the kernel's own duration from launch-attached events
+    ffa_launch_timed(WCO == 2 ? FFA_KT_RING16_128CO : (TW == 32 ? FFA_KT_RING16_8x32 : FFA_KT_RING16_16x16),
+                     conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, false>, dim3(grid), dim3(64 * WCO * WPX), stream, a);
   else
-    hipLaunchKernelGGL((conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, false>), dim3(grid), dim3(64 * WCO * WPX), 0,
+    hipLaunchKernelGGL((conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, true>), dim3(grid), dim3(64 * WCO * WPX), 0,
                        stream, a);
   return ffa_check_launch("conv3x3_ring16");
 }

@@ -23,7 +23,7 @@
 // Accumulator tile (mt, nt): lane (col = lane & 15, kg = lane >> 4) holds rows 4*kg .. 4*kg+3 of pixel col.  The pack
 // puts output channel 8*kg + 4*mt + i (two tiles) or 4*kg + i (one tile) into tile row 4*kg + i, so a lane stores 16
 // (or 8) contiguous bytes per pixel.
-#include "ffa_common.h"
+#include "ffa_gfx950.h"
 
 #include <stdlib.h>
 
@@ -41,23 +41,6 @@ struct ThinArgs {
   int relu;
   int tiles_x, tiles_y, ntiles;
 };
-
-__device__ __attribute__((aligned(16))) const unsigned int ffa_thin_zero16[4] = {0u, 0u, 0u, 0u};
-
-// one LDS-DMA instruction: 64 lanes x 16 bytes from per-lane global addresses to LDS at lds_base + lane * 16
-// (M0 written and restored inside the statement; completion is waited for by hand: see conv3x3_ring.hip)
-__device__ __forceinline__ void thin_dma16(const unsigned char* src, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_base)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void thin_wait_and_meet() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(N) : "memory");
-}
 
 template <int CI, int MT>
 struct ThinGeom {
@@ -119,7 +102,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_kernel(ThinArgs a) {
     hyx[k] = (p < G::H_PIECES) ? ((((hy << 8) | hx) << 4) | slot) : -1;
   }
   const unsigned char* in_b = static_cast<const unsigned char*>(a.in);
-  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_thin_zero16);
+  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_zero16);
   const int Hs = UP ? (a.H >> 1) : a.H, Ws = UP ? (a.W >> 1) : a.W;  // stored source size
   // the tail instruction exists only in the waves that own pieces of it (exact vmcnt arithmetic per wave)
   const bool has_tail = (G::H_PIECES % G::NTHR == 0) || (wave * 64 + (G::NHW - 1) * G::NTHR < G::H_PIECES);
@@ -144,16 +127,16 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_kernel(ThinArgs a) {
       const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(
           smem + slot * G::SLOT + (wave * 64 + k * G::NTHR) * 16);
       if (k + 1 < G::NHW || G::H_PIECES % G::NTHR == 0) {
-        thin_dma16(src, dst);
+        ffa_lds_dma16(src, dst);
       } else if (has_tail) {  // wave uniform
-        if (hyx[k] >= 0) thin_dma16(src, dst);
+        if (hyx[k] >= 0) ffa_lds_dma16(src, dst);
       }
     }
   };
   // this wave's DMA of the tile two fills ago has landed when at most its newest fill is outstanding
   auto wait_tile = [&]() {
-    if (has_tail) thin_wait_and_meet<G::NHW>();
-    else thin_wait_and_meet<G::NHW - 1>();
+    if (has_tail) ffa_wait_vm_barrier<G::NHW>();
+    else ffa_wait_vm_barrier<G::NHW - 1>();
   };
   // PRO ("normalise on load"): once this wave's own pieces of the tile have landed, thread t rewrites in LDS the
   // pieces of LOGICAL 16-byte slot t % PPX of its pixels -- always the same 8 channels, whose scale / shift it keeps in
@@ -228,10 +211,10 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_kernel(ThinArgs a) {
 
   for (; t < a.ntiles; t += gridDim.x) {
     if constexpr (PRO) {
-      if (has_tail) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(G::NHW) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"i"(G::NHW - 1) : "memory");
+      if (has_tail) ffa_wait_vm<G::NHW>();
+      else ffa_wait_vm<G::NHW - 1>();
       fix_tile(t, slot);
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      ffa_wait_lgkm_barrier();
     } else {
       wait_tile();  // halo of tile t is in LDS for every wave; every wave is done with the slot of the tile before it
     }
@@ -382,7 +365,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_kernel(ThinArgs a) {
       // entry index of st[0] in [sums (CPL) | squares (CPL)]: NV == 16: col (bits high to low); NV == 8: col >> 1
       float* red = reinterpret_cast<float*>(smem + G::RED_OFF);
       red[wave * 64 + lane] = st[0];
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      ffa_wait_lgkm_barrier();
       if (tid < 64) {
         const float tot = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid];
         const int cl = tid & 15, kq = tid >> 4;
@@ -395,7 +378,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_kernel(ThinArgs a) {
     slot = (slot + 1) % 3;
   }
   // trailing DMA (fills for tiles that do not exist) must not outlive the block's LDS allocation
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ffa_wait_vm<0>();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -450,10 +433,6 @@ extern "C" long long ffa_thin_stat_rows(int B, int H, int W, int ci_pitch) {
 // co_rows = 16 or 32 (the packed operand's rows).  up: the input is nearest_x2 of `in`; pool: the output is 2x2
 // sum-pooled (no bias / residual / relu / statistics then).
 // pro_scale / pro_shift (both or neither, [Ci] f32): the convolution reads relu(in * scale[c] + shift[c]).
-extern "C" int ffa_thin_conv3x3_pro(const void* in, const void* w_thin, const float* bias, const void* residual,
-                                    void* out, float* stat_partials, const float* pro_scale, const float* pro_shift, int B,
-                                    int H, int W, int Ci, int Co, int co_rows, int relu, int up, int pool,
-                                    hipStream_t stream);
 extern "C" int ffa_thin_conv3x3(const void* in, const void* w_thin, const float* bias, const void* residual, void* out,
                                 float* stat_partials, int B, int H, int W, int Ci, int Co, int co_rows, int relu, int up,
                                 int pool, hipStream_t stream) {

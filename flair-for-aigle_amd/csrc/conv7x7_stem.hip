@@ -16,8 +16,7 @@
 //     arrives while the current one is multiplied;
 //   * epilogue as conv3x3_ring16_kernel's: a lane owns 16 consecutive channels of its pixel, optional bias / ReLU,
 //     BatchNorm batch statistics of the stored values (per-tile partial rows for ffa_bn_finalize).
-#include "ffa_common.h"
-#include "ffa_common_host.h"
+#include "ffa_gfx950.h"
 
 struct StemArgs {
   const void* in;   // [B][Hi][Wi][16] bf16
@@ -48,17 +47,6 @@ struct StemGeom {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
-__device__ __attribute__((aligned(16))) const unsigned int ffa_stem_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void stem_dma16(const unsigned char* src, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_base)
-      : "memory");
-}
-
 __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
   using G = StemGeom;
   __shared__ __align__(16) unsigned char smem[G::LDS_BYTES];
@@ -73,7 +61,7 @@ __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
 #pragma unroll
     for (int k = 0; k < G::WP / G::NTHR; ++k) {
       const int p = tid + k * G::NTHR;
-      stem_dma16(wsrc + (size_t)p * 16,
+      ffa_lds_dma16(wsrc + (size_t)p * 16,
                  (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + G::W_OFF + (wave * 64 + k * G::NTHR) * 16));
     }
   }
@@ -91,7 +79,7 @@ __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
     poff[k] = (hy * a.Wi + hx) * 32;
   }
   const unsigned char* in_b = static_cast<const unsigned char*>(a.in);
-  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_stem_zero16);
+  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_zero16);
 
   auto tile_origin = [&](int t, int& b, int& oy0, int& ox0) {
     const int tx = t % a.tiles_x;
@@ -114,9 +102,9 @@ __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
       const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(
           smem + G::H_OFF + buf * G::HBYTES + (wave * 64 + k * G::NTHR) * 16);
       if (k + 1 < G::NHW || G::HP % G::NTHR == 0) {
-        stem_dma16(src, dst);
+        ffa_lds_dma16(src, dst);
       } else if (wave * 64 + k * G::NTHR < G::HP) {      // wave uniform
-        if (tid + k * G::NTHR < G::HP) stem_dma16(src, dst);  // (lanes past the last piece would write into the next buffer)
+        if (tid + k * G::NTHR < G::HP) ffa_lds_dma16(src, dst);  // (lanes past the last piece would write into the next buffer)
       }
     }
   };
@@ -138,7 +126,7 @@ __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
   if (t < a.npt) issue_halo(t, 0);
   int buf = 0;
   for (; t < a.npt; t += gridDim.x) {
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // this tile's halo (and the weights) landed; other buffer free
+    ffa_wait_vm_barrier<0>();  // this tile's halo (and the weights) landed; other buffer free
     const int tn = t + gridDim.x;
     if (tn < a.npt) issue_halo(tn, buf ^ 1);
     const unsigned char* sH = smem + buf * G::HBYTES;
@@ -264,7 +252,7 @@ __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
     }
     buf ^= 1;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing of this block may still be writing its LDS
+  ffa_wait_vm<0>();  // nothing of this block may still be writing its LDS
 }
 
 // ---- weight packing: dst[k-step = r * 2 + half][LDS row rho][slot'][8 channels] (bf16), LDS row rho = mt * 16 + 4 * q + i

@@ -18,7 +18,7 @@
 // LDS images:  halo  [IH*IW pixels][32 B + 16 B pad]  (pitch 48 B: conflict-free ds_read_b128
 //                     for 16 consecutive pixels, 3 is coprime with the 16 slots of a bank row)
 //              weight [BCO rows][TAPS*32 B + 16 B pad] (odd number of 16-B slots per row)
-#include "ffa_common.h"
+#include "ffa_gfx950.h"
 
 #include <stdlib.h>
 
@@ -66,25 +66,6 @@ struct ConvArgs {
   int pad, dil, relu;
   int nchunks;  // Ci * sizeof(T) / 32
   int tiles_x, tiles_y, npt, ncb;
-};
-
-template <typename T>
-struct Mma;
-template <>
-struct Mma<ffa_bf16> {
-  static __device__ __forceinline__ void run(const ffa_u32x4& a, const ffa_u32x4& b, ffa_f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ffa_bf16x8, a),
-                                                __builtin_bit_cast(ffa_bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <>
-struct Mma<float> {
-  static __device__ __forceinline__ void run(const ffa_u32x4& a, const ffa_u32x4& b, ffa_f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-  }
 };
 
 // HK = 32-byte k-steps of channels staged per halo fill.  With HK = 4 every halo pixel is fetched as one whole
@@ -1189,32 +1170,6 @@ extern "C" int ffa_conv_block_co(int kh, int kw, int stride, int cout) {
   const int bco = conv_pref_bco(kh, kw, stride, cout);
   return conv_supported(kh, kw, stride, bco) ? bco : FFA_ERR_UNSUPPORTED;
 }
-
-// ring kernel entry points (conv3x3_ring.hip)
-extern "C" long long ffa_ring_stat_rows(int B, int H, int W, int co_rows);
-extern "C" int ffa_ring_conv3x3(int dtype, const void* in, const void* w_ring, const float* bias, const void* residual,
-                                void* out, float* stat_partials, const float* pro_scale, const float* pro_shift, int B,
-                                int H, int W, int Ci, int Co, int co_rows, int relu, hipStream_t stream);
-extern "C" int ffa_ring_pack(int dtype, const float* w_oihw, const float* scale, void* dst, int O, int I, int transpose,
-                             int co_rows, int ci_pitch, hipStream_t stream);
-
-// thin kernel entry points (conv3x3_thin.hip)
-extern "C" int ffa_stem_eligible(int dtype, int kh, int kw, int stride, int cout, int ci_pitch);
-extern "C" long long ffa_stem_stat_rows(int B, int Ho, int Wo);
-extern "C" int ffa_stem_pack(const float* w_oihw, const float* scale, void* dst, int O, int I, hipStream_t stream);
-extern "C" int ffa_stem_conv7x7(const void* in, const void* w_stem, const float* bias, void* out, float* stat_partials, int B,
-                                int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int relu, hipStream_t stream);
-extern "C" int ffa_thin_eligible(int dtype, int kh, int kw, int stride, int rows_real, int ci_pitch);
-extern "C" long long ffa_thin_stat_rows(int B, int H, int W, int ci_pitch);
-extern "C" int ffa_thin_conv3x3(const void* in, const void* w_thin, const float* bias, const void* residual, void* out,
-                                float* stat_partials, int B, int H, int W, int Ci, int Co, int co_rows, int relu, int up,
-                                int pool, hipStream_t stream);
-extern "C" int ffa_thin_pack(const float* w_oihw, const float* scale, void* dst, int O, int I, int transpose, int co_rows,
-                             int ci_pitch, hipStream_t stream);
-extern "C" int ffa_thin_conv3x3_pro(const void* in, const void* w_thin, const float* bias, const void* residual,
-                                    void* out, float* stat_partials, const float* pro_scale, const float* pro_shift, int B,
-                                    int H, int W, int Ci, int Co, int co_rows, int relu, int up, int pool,
-                                    hipStream_t stream);
 
 // Operand layout + block height for a layer: the value to hand to ffa_pack_conv_weight / ffa_conv2d as `bco`.
 // Bits 0..11 = rows per block (the padded row count is a multiple of it); FFA_BCO_RING set = the operand is packed

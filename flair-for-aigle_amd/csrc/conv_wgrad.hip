@@ -13,8 +13,7 @@
 // Work split: block = (co block, ci block, kernel-row group) x split; a split walks a strided
 // subset of the spatial tiles and writes its f32 partial slab; wgrad_reduce_kernel sums the
 // slabs in fixed order (deterministic, no float atomics) and writes the OIHW f32 gradient.
-#include "ffa_common.h"
-#include <hip/hip_ext.h>
+#include "ffa_gfx950.h"
 
 #include <stdlib.h>
 
@@ -89,13 +88,6 @@ struct WgradGeom {
   static_assert(KSTEPS % WK == 0, "k-steps must divide over the k-split waves");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
-
-// 4 pixels x 16 channels of bf16, transposed: lane (16-lane group member li) passes the address of
-// pixel row (li >> 2), 8-byte segment (li & 3); it receives channel li of the four pixels.
-__device__ __forceinline__ ffa_s16x4 lds_read_tr16(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) ffa_s16x4*)(const_cast<unsigned char*>(p)));
-}
 
 template <typename T, int KH, int KW, int STRIDE, int RG, int WCO, int WCI, int WK, int TH, int TW, bool PRO = false>
 __global__ void __launch_bounds__(64 * WCO * WCI * WK, (sizeof(T) == 2 ? 2 : 1)) conv_wgrad_kernel(WgradArgs a) {
@@ -323,8 +315,8 @@ __global__ void __launch_bounds__(64 * WCO * WCI * WK, (sizeof(T) == 2 ? 2 : 1))
         // A fragment: co = lane & 31, k = 8*khalf + j
         const int pa = n0 + 8 * khalf + (li >> 2);
         const unsigned char* ap = dyPlane + pa * G::ROWB + gsel * 32 + (li & 3) * 8;
-        const ffa_s16x4 a0 = lds_read_tr16(ap);
-        const ffa_s16x4 a1 = lds_read_tr16(ap + 4 * G::ROWB);
+        const ffa_s16x4 a0 = ffa_lds_read_tr16(ap);
+        const ffa_s16x4 a1 = ffa_lds_read_tr16(ap + 4 * G::ROWB);
         ffa_u32x4 af;
         af.x = __builtin_bit_cast(ffa_u32x2, a0).x;
         af.y = __builtin_bit_cast(ffa_u32x2, a0).y;
@@ -336,8 +328,8 @@ __global__ void __launch_bounds__(64 * WCO * WCI * WK, (sizeof(T) == 2 ? 2 : 1))
         // B fragments double-buffered: the two transpose reads of tap t+1 are issued before the MFMA of tap t
         auto load_b = [&](int tap) {
           const unsigned char* bp = bbase + ((tap / KW) * G::IW + (tap % KW)) * G::ROWB;
-          const ffa_s16x4 b0 = lds_read_tr16(bp);
-          const ffa_s16x4 b1 = lds_read_tr16(bp + 4 * G::LS * G::ROWB);
+          const ffa_s16x4 b0 = ffa_lds_read_tr16(bp);
+          const ffa_s16x4 b1 = ffa_lds_read_tr16(bp + 4 * G::LS * G::ROWB);
           ffa_u32x4 bf;
           bf.x = __builtin_bit_cast(ffa_u32x2, b0).x;
           bf.y = __builtin_bit_cast(ffa_u32x2, b0).y;
@@ -528,19 +520,7 @@ __global__ void __launch_bounds__(256, 1) conv_wgrad_ring_kernel(WgradArgs a) {
     const unsigned char* base = (k * 256 < G::DY_PIECES) ? dy_b : x_b;
     const unsigned lbase =
         (unsigned)__builtin_amdgcn_readfirstlane((int)(stage * STAGE_BYTES + (wave * 64 + k * 256) * 16));
-    // inline asm, not __builtin_amdgcn_global_load_lds: with the builtin in the kernel hipcc (ROCm 7.2) drains
-    // lgkmcnt to 0 in front of every MFMA step, i.e. waits for the transpose reads it has just issued for the NEXT
-    // step (found on conv3x3_ring_kernel); the DMA's completion is waited for by hand below anyway
-    {
-      const unsigned char* src_ = base + (unsigned)voff[k];
-      const unsigned dst_ = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + lbase);
-      unsigned keep_;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-          : "=&s"(keep_)
-          : "v"(src_), "s"(dst_)
-          : "memory");
-    }
+    ffa_lds_dma16(base + (unsigned)voff[k], (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + lbase));
   };
   auto issue_all = [&](int t, int stage) {
     prepare(t, stage);
@@ -556,11 +536,11 @@ __global__ void __launch_bounds__(256, 1) conv_wgrad_ring_kernel(WgradArgs a) {
     const int stage = t % NSTAGE;
     // this wave's DMA of tile t has landed when only the newer tile's NP instructions remain outstanding
     if (t + 1 < ntiles) {
-      if (NP == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-      else if (NP == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (NP == 11) ffa_wait_vm<11>();
+      else if (NP == 10) ffa_wait_vm<10>();
+      else ffa_wait_vm<0>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      ffa_wait_vm<0>();
     }
     {
       unsigned mask = stage == 0 ? okmask[0] : (stage == 1 ? okmask[1] : okmask[2]);
@@ -587,8 +567,8 @@ __global__ void __launch_bounds__(256, 1) conv_wgrad_ring_kernel(WgradArgs a) {
     ffa_u32x4 fa[2];
     ffa_u32x4 fb[2][9];
     auto tr2 = [&](const unsigned char* p0) {
-      const ffa_s16x4 v0 = lds_read_tr16(p0);
-      const ffa_s16x4 v1 = lds_read_tr16(p0 + 4 * G::ROWB);
+      const ffa_s16x4 v0 = ffa_lds_read_tr16(p0);
+      const ffa_s16x4 v1 = ffa_lds_read_tr16(p0 + 4 * G::ROWB);
       ffa_u32x4 f;
       f.x = __builtin_bit_cast(ffa_u32x2, v0).x;
       f.y = __builtin_bit_cast(ffa_u32x2, v0).y;
@@ -722,8 +702,8 @@ __global__ void __launch_bounds__(512, 2) stem_wgrad_kernel(WgradArgs a) {
     }
   };
   auto tr2 = [&](const unsigned char* p0, int step) {
-    const ffa_s16x4 v0 = lds_read_tr16(p0);
-    const ffa_s16x4 v1 = lds_read_tr16(p0 + step);
+    const ffa_s16x4 v0 = ffa_lds_read_tr16(p0);
+    const ffa_s16x4 v1 = ffa_lds_read_tr16(p0 + step);
     ffa_u32x4 f;
     f.x = __builtin_bit_cast(ffa_u32x2, v0).x;
     f.y = __builtin_bit_cast(ffa_u32x2, v0).y;
@@ -927,21 +907,6 @@ wgrad_reduce3x3_kernel(const float* __restrict__ slabs, float* __restrict__ dw, 
 //   * the four waves are summed through LDS in a fixed order and ONE f32 slab per block goes to the split-K workspace
 //     (wgrad_reduce_kernel finishes: deterministic, no float atomics).
 
-__device__ __attribute__((aligned(16))) const unsigned int ffa_wgthin_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void wgthin_dma16(const unsigned char* src, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_base)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wgthin_wait_and_meet() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(N) : "memory");
-}
-
 template <int CI, int CO>
 struct WgThinGeom {
   static constexpr int TH = 8, TW = 32;
@@ -990,7 +955,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_wgrad_kernel(WgradArgs a)
   }
   const unsigned char* x_b = static_cast<const unsigned char*>(a.x);
   const unsigned char* dy_b = static_cast<const unsigned char*>(a.dy);
-  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_wgthin_zero16);
+  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_zero16);
   const int Hs = UP ? (a.Hi >> 1) : a.Hi, Ws = UP ? (a.Wi >> 1) : a.Wi;
   const bool has_tail = (G::PIECES % 256 == 0) || (wave * 64 + (G::NHW - 1) * 256 < G::PIECES);
 
@@ -1024,9 +989,9 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_wgrad_kernel(WgradArgs a)
       const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(
           smem + slot * G::SLOT + (wave * 64 + k * 256) * 16);
       if (k + 1 < G::NHW || G::PIECES % 256 == 0) {
-        wgthin_dma16(src, dst);
+        ffa_lds_dma16(src, dst);
       } else if (has_tail) {
-        if (info >= 0) wgthin_dma16(src, dst);
+        if (info >= 0) ffa_lds_dma16(src, dst);
       }
     }
   };
@@ -1069,18 +1034,18 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_wgrad_kernel(WgradArgs a)
   auto wait_tile = [&](int t, int slot) {
     if constexpr (PRO) {
       if constexpr (G::NSLOT == 3) {
-        if (has_tail) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(G::NHW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"i"(G::NHW - 1) : "memory");
+        if (has_tail) ffa_wait_vm<G::NHW>();
+        else ffa_wait_vm<G::NHW - 1>();
       } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ffa_wait_vm<0>();
       }
       fix_tile(t, slot);
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      ffa_wait_lgkm_barrier();
     } else if constexpr (G::NSLOT == 3) {
-      if (has_tail) wgthin_wait_and_meet<G::NHW>();
-      else wgthin_wait_and_meet<G::NHW - 1>();
+      if (has_tail) ffa_wait_vm_barrier<G::NHW>();
+      else ffa_wait_vm_barrier<G::NHW - 1>();
     } else {
-      wgthin_wait_and_meet<0>();
+      ffa_wait_vm_barrier<0>();
     }
   };
 
@@ -1099,8 +1064,8 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_wgrad_kernel(WgradArgs a)
   const int bBase = ((2 * wave) * G::IW + px0) * G::XB + (li & 3) * 8;
 
   auto tr2 = [&](const unsigned char* p0, int step) {
-    const ffa_s16x4 v0 = lds_read_tr16(p0);
-    const ffa_s16x4 v1 = lds_read_tr16(p0 + step);
+    const ffa_s16x4 v0 = ffa_lds_read_tr16(p0);
+    const ffa_s16x4 v1 = ffa_lds_read_tr16(p0 + step);
     ffa_u32x4 f;
     f.x = __builtin_bit_cast(ffa_u32x2, v0).x;
     f.y = __builtin_bit_cast(ffa_u32x2, v0).y;
@@ -1144,7 +1109,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_wgrad_kernel(WgradArgs a)
     }
   }
   // every DMA (also the fills for tiles that do not exist) has landed before the slots become reduction scratch
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  ffa_wait_vm_barrier<0>();
 
   // ---- sum the four waves in a fixed order: (0 + 2) and (1 + 3), then (0 + 1) ----
   float* red = reinterpret_cast<float*>(smem);
@@ -1267,7 +1232,7 @@ __global__ void __launch_bounds__(512) conv3x3_wgrad64_kernel(WgradArgs a) {
   const unsigned char* x_b = (two && !from_lo) ? static_cast<const unsigned char*>(a.x2) + (ci0 - a.C1) * 2
                                                : static_cast<const unsigned char*>(a.x) + ci0 * 2;
   const unsigned char* dy_b = static_cast<const unsigned char*>(a.dy) + co0 * 2;
-  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_wgthin_zero16);
+  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_zero16);
   const bool has_tail = (G::PIECES % 512 == 0) || (wave * 64 + (G::NHW - 1) * 512 < G::PIECES);
 
   auto tile_origin = [&](int t, int& b, int& oy0, int& ox0) {
@@ -1299,9 +1264,9 @@ __global__ void __launch_bounds__(512) conv3x3_wgrad64_kernel(WgradArgs a) {
       const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(
           smem + slot * G::SLOT + (wave * 64 + k * 512) * 16);
       if (k + 1 < G::NHW || G::PIECES % 512 == 0) {
-        wgthin_dma16(src, dst);
+        ffa_lds_dma16(src, dst);
       } else if (has_tail) {
-        if (!(info & (1 << 11))) wgthin_dma16(src, dst);
+        if (!(info & (1 << 11))) ffa_lds_dma16(src, dst);
       }
       __builtin_amdgcn_sched_barrier(0);  // one piece's address registers at a time (144 accumulators are live)
     }
@@ -1341,8 +1306,8 @@ __global__ void __launch_bounds__(512) conv3x3_wgrad64_kernel(WgradArgs a) {
         boff[sx][nt][h] = ((kpx / G::TW) * G::IW + hx) * 128 + (((2 * (wci * 2 + nt) + hbit) ^ (2 * wg64_phi(hx))) * 16) + seg;
       }
   auto tr2 = [&](const unsigned char* p0, const unsigned char* p1) {
-    const ffa_s16x4 v0 = lds_read_tr16(p0);
-    const ffa_s16x4 v1 = lds_read_tr16(p1);
+    const ffa_s16x4 v0 = ffa_lds_read_tr16(p0);
+    const ffa_s16x4 v1 = ffa_lds_read_tr16(p1);
     ffa_u32x4 f;
     f.x = __builtin_bit_cast(ffa_u32x2, v0).x;
     f.y = __builtin_bit_cast(ffa_u32x2, v0).y;
@@ -1356,7 +1321,7 @@ __global__ void __launch_bounds__(512) conv3x3_wgrad64_kernel(WgradArgs a) {
     issue_tile(split, 0);
     int slot = 0;
     for (int it = 0; it < ntl; ++it) {
-      wgthin_wait_and_meet<0>();  // this tile's fill has landed (nothing younger is in flight); the other slot is free
+      ffa_wait_vm_barrier<0>();  // this tile's fill has landed (nothing younger is in flight); the other slot is free
       const bool more = it + 1 < ntl;
       if (more) issue_tile(split + (it + 1) * a.nsplit, slot ^ 1);
       const unsigned char* sS = smem + slot * G::SLOT;
@@ -1395,7 +1360,7 @@ __global__ void __launch_bounds__(512) conv3x3_wgrad64_kernel(WgradArgs a) {
       slot ^= 1;
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  ffa_wait_vm_barrier<0>();
 
   // ---- k group 1 -> LDS, k group 0 adds and writes the block's slab ----
   float* red = reinterpret_cast<float*>(smem) + (size_t)(wave & 3) * 144 * 64 + lane;
@@ -1489,7 +1454,7 @@ __global__ void __launch_bounds__(512) stem_wgrad8_kernel(WgradArgs a) {
   }
   const unsigned char* x_b = static_cast<const unsigned char*>(a.x);
   const unsigned char* dy_b = static_cast<const unsigned char*>(a.dy);
-  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_wgthin_zero16);
+  const unsigned char* zero = reinterpret_cast<const unsigned char*>(ffa_zero16);
   const bool has_tail = (G::PIECES % 512 == 0) || (wave * 64 + (G::NHW - 1) * 512 < G::PIECES);
   const int tiles_x = (a.Wo + G::TW - 1) / G::TW, tiles_y = (a.Ho + G::TH - 1) / G::TH;
   const int npt = a.B * tiles_x * tiles_y;
@@ -1513,9 +1478,9 @@ __global__ void __launch_bounds__(512) stem_wgrad8_kernel(WgradArgs a) {
       const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(
           smem + slot * G::SLOT + (wave * 64 + k * 512) * 16);
       if (k + 1 < G::NHW || G::PIECES % 512 == 0) {
-        wgthin_dma16(src, dst);
+        ffa_lds_dma16(src, dst);
       } else if (has_tail) {
-        if (tid + k * 512 < G::PIECES) wgthin_dma16(src, dst);
+        if (tid + k * 512 < G::PIECES) ffa_lds_dma16(src, dst);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1540,8 +1505,8 @@ __global__ void __launch_bounds__(512) stem_wgrad8_kernel(WgradArgs a) {
   const int boff = ((2 * 4 * kgp) * G::IWC + 2 * kpx + 2 * sp) * 16 + (li & 3) * 8;
 
   auto tr2 = [&](const unsigned char* p0, int step) {
-    const ffa_s16x4 v0 = lds_read_tr16(p0);
-    const ffa_s16x4 v1 = lds_read_tr16(p0 + step);
+    const ffa_s16x4 v0 = ffa_lds_read_tr16(p0);
+    const ffa_s16x4 v1 = ffa_lds_read_tr16(p0 + step);
     ffa_u32x4 f;
     f.x = __builtin_bit_cast(ffa_u32x2, v0).x;
     f.y = __builtin_bit_cast(ffa_u32x2, v0).y;
@@ -1555,7 +1520,7 @@ __global__ void __launch_bounds__(512) stem_wgrad8_kernel(WgradArgs a) {
     issue_tile(split, 0);
     int slot = 0;
     for (int it = 0; it < ntl; ++it) {
-      wgthin_wait_and_meet<0>();
+      ffa_wait_vm_barrier<0>();
       if (it + 1 < ntl) issue_tile(split + (it + 1) * a.nsplit, slot ^ 1);
       const unsigned char* sS = smem + slot * G::SLOT;
       ffa_u32x4 af[4][4];
@@ -1579,7 +1544,7 @@ __global__ void __launch_bounds__(512) stem_wgrad8_kernel(WgradArgs a) {
       slot ^= 1;
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  ffa_wait_vm_barrier<0>();
 
   // ---- k group 1 -> LDS, k group 0 adds and writes the block's slab ----
   float* red = reinterpret_cast<float*>(smem) + (size_t)(wave & 3) * 112 * 64 + lane;
@@ -1802,16 +1767,8 @@ static int launch_wgrad(const WgradArgs& a, const WgradPlan& p, int kh, int kw, 
         if (!(e64 && e64[0] == '0') && p.wco == 2 && p.wci == 2 && p.wk == 2 && p.th == (wide ? 8 : 16) && a.C1 % 64 == 0 &&
             (a.C1 == 0 || (a.Hi % 2 == 0 && a.Wi % 2 == 0)) && a.pad == 1 && a.Co % 64 == 0 && a.Ci % 64 == 0 &&
             ((long long)ih * a.Wi + iw) * 2 * (a.Ci > a.Co ? a.Ci : a.Co) < (1LL << 23)) {
-          hipEvent_t ts, te;
-          const dim3 grid(a.ncob * a.ncib, a.nsplit);
-          const bool timed = ffa_ktime_next(FFA_KT_WGRAD64, &ts, &te);
-          if (wide) {
-            if (timed) hipExtLaunchKernelGGL(conv3x3_wgrad64_kernel<32>, grid, dim3(512), 0, stream, ts, te, 0, a);
-            else hipLaunchKernelGGL(conv3x3_wgrad64_kernel<32>, grid, dim3(512), 0, stream, a);
-          } else {
-            if (timed) hipExtLaunchKernelGGL(conv3x3_wgrad64_kernel<16>, grid, dim3(512), 0, stream, ts, te, 0, a);
-            else hipLaunchKernelGGL(conv3x3_wgrad64_kernel<16>, grid, dim3(512), 0, stream, a);
-          }
+          ffa_launch_timed(FFA_KT_WGRAD64, wide ? conv3x3_wgrad64_kernel<32> : conv3x3_wgrad64_kernel<16>,
+                           dim3(a.ncob * a.ncib, a.nsplit), dim3(512), stream, a);
           return ffa_check_launch("conv3x3_wgrad64");
         }
       }
@@ -1966,7 +1923,7 @@ extern "C" int ffa_conv_wgrad_upcat(int dtype, const void* lo, const void* skip,
 }
 
 // ------------------------------------------------------------------------------------------------
-// hardware-layout probes used by tests/test_layout_probes.py: they pin the lane maps this file and
+// hardware-layout probes used by tests/test_kernels_gpu.py: they pin the lane maps this file and
 // conv_igemm.hip rely on (MFMA operand / accumulator layout, transpose-read semantics).
 
 __global__ void probe_tr16_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst) {
@@ -1979,7 +1936,7 @@ __global__ void probe_tr16_kernel(const uint16_t* __restrict__ src, uint16_t* __
   const int grp = lane >> 4;
   // group g reads rows 4g..4g+3, columns 16g.. : address of row (li>>2), segment (li&3)
   const unsigned char* p = buf + (4 * grp + (li >> 2)) * 128 + grp * 32 + (li & 3) * 8;
-  ffa_s16x4 v = lds_read_tr16(p);
+  ffa_s16x4 v = ffa_lds_read_tr16(p);
 #pragma unroll
   for (int e = 0; e < 4; ++e) dst[lane * 4 + e] = (uint16_t)v[e];
 }

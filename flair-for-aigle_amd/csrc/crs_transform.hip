@@ -30,8 +30,6 @@
 
 #include <cmath>
 
-#include "../../include/flairhip.h"
-
 namespace {
 
 constexpr int kT = 256;

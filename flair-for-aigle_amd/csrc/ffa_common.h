@@ -8,23 +8,20 @@
 //   * wave = 64 lanes, everywhere
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <string.h>
 
-#define FFA_BF16 0
-#define FFA_F32 1
+#include <type_traits>
 
-#define FFA_OK 0
-#define FFA_ERR_ARG (-1)
-#define FFA_ERR_UNSUPPORTED (-2)
-#define FFA_ERR_WORKSPACE (-3)
+// The C ABI is declared once, in the public header: every definition in this directory is compiled against its
+// prototype there (a drifted parameter list is "conflicting types"), and the public macros come from there too.
+#include "../../include/flairhip.h"
+static_assert(std::is_same<ffa_stream_t, hipStream_t>::value, "ffa_stream_t must be hipStream_t");
 
 #define FFA_CE_MAXK 32  // largest class count and logit pitch of the per-pixel softmax kernels (resample_loss.hip, tta.hip)
 
-#define FFA_BCO_RING 0x1000  // `bco` flag: operand packed for conv3x3_ring_kernel (ffa_conv_plan)
-#define FFA_BCO_THIN 0x2000  // `bco` flag: operand packed for conv3x3_thin_kernel (<= 32 input channels, <= 32 rows)
 #define FFA_BCO_THIN32 0x4000  // with FFA_BCO_THIN: the operand multiplies 32-channel pixels (8-row tiles; else 16 ch, 16-row tiles)
-#define FFA_BCO_STEM 0x8000   // `bco` flag: operand packed for conv7x7_stem_kernel (bf16 7x7 stride 2, <= 8 real input channels, 64 rows)
 
 void ffa_set_error(const char* fmt, ...);
 int ffa_check_launch(const char* what);
@@ -34,6 +31,13 @@ bool ffa_ktime_next(int tag, hipEvent_t* start, hipEvent_t* stop);
 #define FFA_KT_RING16_16x16 2
 #define FFA_KT_RING16_128CO 4
 #define FFA_KT_WGRAD64 16
+// Launch with the session's event pair attached when a kernel timing session is open, plainly otherwise.
+template <typename K, typename A>
+static inline void ffa_launch_timed(int tag, K kernel, dim3 grid, dim3 block, hipStream_t stream, const A& a) {
+  hipEvent_t ts, te;
+  if (ffa_ktime_next(tag, &ts, &te)) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ts, te, 0, a);
+  else hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
+}
 
 #define FFA_REQUIRE(cond, ...)                 \
   do {                                         \

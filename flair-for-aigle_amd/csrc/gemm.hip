@@ -14,13 +14,8 @@
 // 64 distinct 4-bank groups) = 72 KB, two blocks per CU.  Pipeline: chunk c+2 is in flight from HBM into registers and
 // chunk c+1 moves registers -> LDS (other image) while chunk c feeds the matrix pipe: ONE barrier per 32 MFMAs per wave.
 // Bound: HBM for the thin early stages (K = 128: 1.5 flop per byte moved at stage 1), MFMA for K >= 512.
-#include "ffa_common.h"
+#include "ffa_gfx950.h"
 #include <stdlib.h>
-
-#define FFA_ACT_NONE 0
-#define FFA_ACT_GELU 1
-#define FFA_ACT_DGELU 2  // out = acc * gelu'(aux): the input gradient of fc2 carried through Mlp's activation
-#define FFA_ACT_RELU 3   // 1x1 convolution + folded BatchNorm + ReLU of the UPerNet decoder (evaluation)
 
 struct GemmArgs {
   const ffa_bf16* a;
@@ -256,7 +251,7 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmArgs g) {
 // The same GEMM on a 256 x 256 block tile for the MFMA-bound shapes (K >= 256, N a multiple of 256 or large):
 // 8 waves as 2 (tokens) x 4 (features), 128 tokens x 64 features per wave (8 x 4 MFMA tiles, 128 accumulator VGPRs:
 // 2.7 MFMAs per ds_read_b128 instead of 2), BK = 32, operands streamed global -> LDS by LDS-DMA
-// (global_load_lds_dwordx4 from inline asm: with the builtin hipcc stops counting lgkmcnt) into a
+// (ffa_lds_dma16, ffa_gfx950.h) into a
 // four-stage ring of (256 + 256) rows x 64 bytes, three tiles ahead, counted vmcnt (never 0 in the loop), one raw
 // s_barrier per 32 MFMAs per wave.  The DMA writes linearly (16 rows x 64 bytes per wave instruction), so the
 // bank-conflict swizzle is applied on the SOURCE side and again on the read: 16-byte chunk c of row r lives at chunk
@@ -270,19 +265,6 @@ constexpr int HSTAGES = 4;
 }  // namespace
 
 __device__ __forceinline__ int gemm256_swz(int r) { return (4 - ((r >> 2) & 3)) & 3; }
-
-__device__ __forceinline__ void gemm_dma16(const unsigned char* src, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_base)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void gemm_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(N) : "memory");
-}
 
 __global__ void __launch_bounds__(512, 1) gemm256_bf16_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[HSTAGES * HSTAGE];
@@ -322,7 +304,7 @@ __global__ void __launch_bounds__(512, 1) gemm256_bf16_kernel(GemmArgs g) {
     const unsigned base = lds0 + (unsigned)((t & (HSTAGES - 1)) * HSTAGE);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      gemm_dma16(src[j] + (long long)t * (HBK * 2),
+      ffa_lds_dma16(src[j] + (long long)t * (HBK * 2),
                  (unsigned)__builtin_amdgcn_readfirstlane((int)(base + dst[j])));
   };
 
@@ -343,9 +325,9 @@ __global__ void __launch_bounds__(512, 1) gemm256_bf16_kernel(GemmArgs g) {
   for (int t = 0; t < nk; ++t) {
     // tile t has landed for every wave once each wave's own pieces are retired and the barrier is passed; the
     // barrier also says that everyone is done reading tile t - 1, whose stage tile t + 3 is about to overwrite
-    if (t + 2 < nk) gemm_wait_barrier<8>();
-    else if (t + 1 < nk) gemm_wait_barrier<4>();
-    else gemm_wait_barrier<0>();
+    if (t + 2 < nk) ffa_wait_vm_barrier<8>();
+    else if (t + 1 < nk) ffa_wait_vm_barrier<4>();
+    else ffa_wait_vm_barrier<0>();
     if (t + 3 < nk) issue(t + 3);
     const unsigned char* img = smem + (t & (HSTAGES - 1)) * HSTAGE;
     ffa_bf16x8 fw[4], ft[8];
@@ -626,11 +608,6 @@ constexpr int TPITCH = 288;        // bytes per staged row (128 columns + 32 pad
 constexpr int TIMG = 2 * TBM * TPITCH;
 }  // namespace
 
-__device__ __forceinline__ ffa_s16x4 gemm_read_tr16(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) ffa_s16x4*)(const_cast<unsigned char*>(p)));
-}
-
 __global__ void __launch_bounds__(256, 2) gemm_tn_bf16_kernel(GemmTnArgs g) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * TIMG];
   int id = blockIdx.x;
@@ -711,8 +688,8 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_bf16_kernel(GemmTnArgs g) {
       for (int i = 0; i < 4; ++i) {
         const unsigned char* py = img + yb + st * 32 * TPITCH + i * 32;
         const unsigned char* px = img + xb + st * 32 * TPITCH + i * 32;
-        const ffa_s16x4 y0 = gemm_read_tr16(py), y1 = gemm_read_tr16(py + 16 * TPITCH);
-        const ffa_s16x4 x0 = gemm_read_tr16(px), x1 = gemm_read_tr16(px + 16 * TPITCH);
+        const ffa_s16x4 y0 = ffa_lds_read_tr16(py), y1 = ffa_lds_read_tr16(py + 16 * TPITCH);
+        const ffa_s16x4 x0 = ffa_lds_read_tr16(px), x1 = ffa_lds_read_tr16(px + 16 * TPITCH);
         ffa_u32x4 vy, vx;
         vy.x = __builtin_bit_cast(ffa_u32x2, y0).x; vy.y = __builtin_bit_cast(ffa_u32x2, y0).y;
         vy.z = __builtin_bit_cast(ffa_u32x2, y1).x; vy.w = __builtin_bit_cast(ffa_u32x2, y1).y;

@@ -770,11 +770,6 @@ bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy, const T* 
 // dres from the coefficients a stage-1 call left in the SAME workspace), bit 2 = the reduction alone, bit 3 = the
 // finalize alone (1 == 4 | 8).  ffa_bn_bwd = all; the split exists so that a profiler-free harness can bracket each
 // kernel with its own events (bench.py's HBM roofline entry).
-extern "C" int ffa_bn_bwd_stages(int dtype, const void* x, const void* dy, const void* y, const float* gamma,
-                                 const float* beta, const float* mean, const float* rstd, void* dx, void* dres,
-                                 float* dgamma, float* dbeta, long long npix, int C, int relu, void* workspace,
-                                 long long workspace_bytes, int stages, hipStream_t stream);
-
 extern "C" int ffa_bn_bwd(int dtype, const void* x, const void* dy, const void* y, const float* gamma,
                           const float* beta, const float* mean, const float* rstd, void* dx, void* dres,
                           float* dgamma, float* dbeta,

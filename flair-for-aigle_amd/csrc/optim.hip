@@ -9,7 +9,6 @@
 // torch's fused kernel (ATen/native/cuda/fused_adam_utils.cuh: decoupled decay on the parameter, lerp for the first moment,
 // bias corrections formed in double, sqrt(v) / sqrt(bc2) + eps), so optimizer state is interchangeable with torch's.
 #include "ffa_common.h"
-#include "ffa_common_host.h"
 
 struct AdamTensor {
   float* p;

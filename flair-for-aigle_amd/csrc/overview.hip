@@ -17,8 +17,6 @@
 // the bytes equal those of a level-by-level chain.  Levels beyond four come from further launches on the last level.
 #include "ffa_common.h"
 
-#include "../../include/flairhip.h"
-
 namespace {
 
 constexpr int kT = 256;

@@ -28,8 +28,6 @@
 #include "ffa_common.h"
 #include "ffa_ccl.h"
 
-#include "../../include/flairhip.h"
-
 namespace {
 
 constexpr int kItems = 16;      // items per thread in scans / radix passes

@@ -638,11 +638,6 @@ extern "C" long long ffa_softmax_ce_workspace_bytes(void) {
 
 // loss[0] = weighted-mean CE; wsum_out[0] = sum of target weights; optional dlogits (scaled by
 // grad_scale[0], a device scalar, default 1 when null is not allowed -> pass a device 1.0f) and pred.
-extern "C" int ffa_softmax_ce_sums(int dtype, const void* logits, const uint8_t* targets, const float* class_weights,
-                                   const float* grad_scale, float* loss, float* wsum_out, void* dlogits, uint8_t* pred,
-                                   float* dlogit_sums, long long npix, int K, int Cp, void* workspace,
-                                   long long workspace_bytes, hipStream_t stream);
-
 extern "C" int ffa_softmax_ce(int dtype, const void* logits, const uint8_t* targets, const float* class_weights,
                               const float* grad_scale, float* loss, float* wsum_out, void* dlogits, uint8_t* pred,
                               long long npix, int K, int Cp, void* workspace, long long workspace_bytes,

@@ -15,8 +15,6 @@
 #include "ffa_common.h"
 #include "ffa_ccl.h"
 
-#include "../../include/flairhip.h"
-
 namespace {
 
 typedef unsigned long long u64;

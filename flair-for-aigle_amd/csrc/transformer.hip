@@ -15,7 +15,7 @@
 //   * adaptive_avg_pool   -- PSP module's nn.AdaptiveAvgPool2d
 //   * bilinear_slice      -- F.interpolate(bilinear) with either corner convention, written into a channel slice of a
 //                            wider tensor (the FPN concat never exists as a separate copy), optional addend (FPN top-down)
-#include "ffa_common.h"
+#include "ffa_gfx950.h"
 
 #define FFA_TF_THREADS 256
 
@@ -589,11 +589,6 @@ __global__ void __launch_bounds__(256) window_attention_f32_kernel(WinAttnArgs a
 // four lane groups of a query by two xor-shuffles, then O^T = V^T P^T with P^T taken straight from the S^T registers:
 // the k-slot order of a 32-key MFMA block is [tile 2u keys 4g..4g+3 | tile 2u+1 keys 4g..4g+3] for lane group g, which
 // is what two transposed reads of V (4 keys x 16 channels each) deliver.
-__device__ __forceinline__ ffa_s16x4 attn_read_tr16(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) ffa_s16x4*)(const_cast<unsigned char*>(p)));
-}
-
 template <int NTP, int NW>  // padded key tiles of 16 (even): 4 (ws <= 8) or 10 (ws <= 12); waves per block
 __global__ void __launch_bounds__(64 * NW) window_attention_bf16_kernel(WinAttnArgs a) {
   constexpr int NP = NTP * 16;
@@ -733,10 +728,10 @@ __global__ void __launch_bounds__(64 * NW) window_attention_bf16_kernel(WinAttnA
       }
       // lane group g: keys 32u + 4g .. +3 (tile 2u) and 32u + 16 + 4g .. +3 (tile 2u + 1), channels 0-15 / 16-31
       const unsigned char* vb = sv + (u * 32 + g * 4) * VP + tr_off;
-      const ffa_s16x4 a00 = attn_read_tr16(vb);
-      const ffa_s16x4 a01 = attn_read_tr16(vb + 16 * VP);
-      const ffa_s16x4 a10 = attn_read_tr16(vb + 32);
-      const ffa_s16x4 a11 = attn_read_tr16(vb + 16 * VP + 32);
+      const ffa_s16x4 a00 = ffa_lds_read_tr16(vb);
+      const ffa_s16x4 a01 = ffa_lds_read_tr16(vb + 16 * VP);
+      const ffa_s16x4 a10 = ffa_lds_read_tr16(vb + 32);
+      const ffa_s16x4 a11 = ffa_lds_read_tr16(vb + 16 * VP + 32);
       ffa_u32x4 v0, v1;
       v0.x = __builtin_bit_cast(ffa_u32x2, a00).x; v0.y = __builtin_bit_cast(ffa_u32x2, a00).y;
       v0.z = __builtin_bit_cast(ffa_u32x2, a01).x; v0.w = __builtin_bit_cast(ffa_u32x2, a01).y;
@@ -1246,8 +1241,8 @@ __global__ void __launch_bounds__(64 * NW) window_attention_bwd_kernel(WinAttnAr
   auto tr_frag = [&](const unsigned char* img, int u, int dhalf) -> ffa_bf16x8 {
     // transposed 16 x 32 fragment: rows (tokens) 32u + 4g .. +3 and 32u + 16 + 4g .. +3, channels 16 dhalf + lane % 16
     const unsigned char* p = img + (u * 32 + g * 4) * RP + tr_off + dhalf * 32;
-    const ffa_s16x4 lo = attn_read_tr16(p);
-    const ffa_s16x4 hi = attn_read_tr16(p + 16 * RP);
+    const ffa_s16x4 lo = ffa_lds_read_tr16(p);
+    const ffa_s16x4 hi = ffa_lds_read_tr16(p + 16 * RP);
     ffa_u32x4 v;
     v.x = __builtin_bit_cast(ffa_u32x2, lo).x; v.y = __builtin_bit_cast(ffa_u32x2, lo).y;
     v.z = __builtin_bit_cast(ffa_u32x2, hi).x; v.w = __builtin_bit_cast(ffa_u32x2, hi).y;

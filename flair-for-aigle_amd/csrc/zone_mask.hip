@@ -17,8 +17,6 @@
 // The plane is cleared at the head of every call (hipMemsetAsync), so the workspace may hold anything.
 #include "ffa_common.h"
 
-#include "../../include/flairhip.h"
-
 // xc = x0 + ((yc - y0) * (x1 - x0)) / (y1 - y0) must round every operation separately: no a * b + c -> fma
 #pragma clang fp contract(off)
 
