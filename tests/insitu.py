@@ -131,6 +131,41 @@ def upcat(lo, skip):
     return u if skip is None else torch.cat([u, skip], dim=-1)
 
 
+def bilinear_matrix(n_in: int, n_out: int, device=None) -> torch.Tensor:
+    """[n_out, n_in] float64: the bilinear resize of one axis with align_corners=False as ATen defines it -- source
+    coordinate max(0, (dst + 0.5) * n_in / n_out - 0.5) taken in float64, taps floor(src) and the next index clamped
+    to the last one, weights 1 - frac and frac.  The backward of the resize is the transpose of this matrix."""
+    dst = torch.arange(n_out, dtype=F64, device=device)
+    src = ((dst + 0.5) * (float(n_in) / float(n_out)) - 0.5).clamp_min(0.0)
+    i0 = src.floor().long().clamp(max=n_in - 1)
+    i1 = (i0 + 1).clamp(max=n_in - 1)
+    l1 = src - i0.to(F64)
+    m = torch.zeros((n_out, n_in), dtype=F64, device=device)
+    m.scatter_add_(1, i0.unsqueeze(1), (1.0 - l1).unsqueeze(1))
+    m.scatter_add_(1, i1.unsqueeze(1), l1.unsqueeze(1))
+    return m
+
+
+def resize2(t: torch.Tensor, my: torch.Tensor, mx: torch.Tensor) -> torch.Tensor:
+    """t [B,H,W,C] float64 -> [B, my.rows, mx.rows, C]: rows through my [Ho,H], columns through mx [Wo,W]"""
+    return torch.einsum("px,boxc->bopc", mx, torch.einsum("oy,byxc->boxc", my, t))
+
+
+def d4_gather(planes: torch.Tensor, code: int) -> torch.Tensor:
+    """[..., n, n] -> the flipped / rotated planes of augmentation code `code` (flairhip.augment.d4_source_index)"""
+    from flairhip.augment import d4_source_index
+    si, sj = d4_source_index(int(code), planes.shape[-1])
+    si, sj = (torch.from_numpy(v).to(planes.device) for v in (si, sj))
+    return planes[..., si, sj]
+
+
+def samples_f64(x: torch.Tensor) -> torch.Tensor:
+    """raster samples of any accepted type (uint8 / uint16 / int16 / float32) as float64"""
+    if x.dtype == torch.uint16:
+        return (x.view(torch.int16).to(torch.int32) & 0xFFFF).to(F64)
+    return x.to(F64)
+
+
 # --------------------------------------------------------------------------------------------------
 # comparison
 
@@ -218,7 +253,8 @@ def _shift(res: dict, b0: int, full_shape) -> dict:
 
 class Checker:
     """mode "full": elementwise; "proj": conv-family outputs through random projections over the channels.
-    weights: id(PackedWeight) -> dict(name, transpose, weight (f32 OIHW master at pack time))."""
+    weights: id(PackedWeight) -> dict(name, transpose, weight (f32 OIHW master at pack time)); for a column block of a
+    fusion 1x1 weight: master (the whole weight), off, c instead of weight."""
 
     def __init__(self, mode: str = "full", chunk: int = 2, seed: int = 1234, nproj: int = 2):
         assert mode in ("full", "proj")
@@ -228,6 +264,7 @@ class Checker:
         self.results: List[Result] = []
         self.calls: List[dict] = []  # one summary per checked call: op, module, layout, family flags
         self.grad_sources: List[tuple] = []  # (tag, f32 tensor) outputs that autograd hands to parameters
+        self.sum_sources: List[torch.Tensor] = []  # checked channel_sums outputs (a bias gradient is a prefix of one)
         self.ambiguous = [0, 0]  # ReLU mask: ambiguous elements, elements
 
     # ---- helpers -------------------------------------------------------------------------------
@@ -246,7 +283,7 @@ class Checker:
     def _weight(self, pw):
         info = self.weights.get(id(pw))
         if info is None:
-            raise KeyError("operand not produced by HipConv2d.packed during the recording")
+            raise KeyError("operand not produced by HipConv2d.packed or _fusion_slice during the recording")
         return info
 
     def _chunks(self, B: int):
@@ -609,6 +646,79 @@ class Checker:
         if out.shape[-1] > C:
             self._add(call, _exact_zero(out[..., C:], "pad channels"))
 
+    def nhwc_to_nchw(self, call, x, channels, out):
+        r = x[..., :channels].permute(0, 3, 1, 2).to(F64)
+        self._add(call, _compare(out, r, torch.zeros_like(r), "values"))
+
+    def bilinear(self, call, src, o, transpose):
+        """forward: o [B,Ho,Wo,C] = resize of src [B,Hi,Wi,C] (align_corners=False, float64 source index);
+        transpose: o [B,Hi,Wi,C] = the transposed map of src = dy [B,Ho,Wo,C].  The taps are non-negative, so the
+        magnitude bound a is the same map on |src|.  A channel that is zero in all of src (the pad channels) must be
+        exactly zero in o.  (The kernel, like ATen for f32 tensors, takes the source coordinate in f32: at ratios that
+        are no power of two that is a few 1e-6 of the step between two taps, far inside a bf16 ulp; the f32 bound
+        REL * a can be missed by it where the taps nearly cancel -- tests/test_kernels_gpu.py::test_bilinear.)"""
+        what = "dx" if transpose else "y"
+        if transpose:
+            my = bilinear_matrix(o.shape[1], src.shape[1], src.device).t()
+            mx = bilinear_matrix(o.shape[2], src.shape[2], src.device).t()
+        else:
+            my = bilinear_matrix(src.shape[1], o.shape[1], src.device)
+            mx = bilinear_matrix(src.shape[2], o.shape[2], src.device)
+        parts = []
+        for b0, b1 in self._chunks(src.shape[0]):
+            s = src[b0:b1].to(F64)
+            r, a = resize2(s, my, mx), resize2(s.abs(), my, mx)
+            tol = REL * a + (ulp_bf16(r) if o.dtype == torch.bfloat16 else 0.0)
+            parts.append(_shift(_compare(o[b0:b1], r, tol, what), b0, o.shape))
+        self._add(call, _merge(parts, what))
+        dead = (src == 0).reshape(-1, src.shape[-1]).all(0)
+        if bool(dead.any()):
+            self._add(call, _exact_zero(o[..., dead], what + " pad channels"))
+
+    def mean_stack(self, call, xs, divisor, o):
+        d = float(len(xs) if divisor is None else divisor)
+        r = sum(x.to(F64) for x in xs) / d
+        a = sum(x.to(F64).abs() for x in xs) / abs(d)
+        tol = REL * a + (ulp_bf16(r) if o.dtype == torch.bfloat16 else 0.0)
+        return self._add(call, _compare(o, r, tol, "sum / divisor"))
+
+    def layout_norm(self, call, x, mean, std, out, codes=None, group=1):
+        """out [B,H,W,pitch] = ((x - mean[c]) / std[c]) of the raster samples x [B,C,H,W], image b flipped / rotated by
+        codes[b // group] first; without mean / std the values themselves, rounded once to the stored type"""
+        B, C = x.shape[:2]
+        if out.shape[-1] > C:
+            self._add(call, _exact_zero(out[..., C:], "pad channels"))
+        parts = []
+        for b0, b1 in self._chunks(B):
+            xc = samples_f64(x[b0:b1])
+            if codes is not None:
+                xc = torch.stack([d4_gather(xc[i], int(codes[(b0 + i) // group])) for i in range(b1 - b0)])
+            xc = xc.permute(0, 2, 3, 1)
+            oc = out[b0:b1, ..., :C]
+            if mean is None:
+                r = xc.to(out.dtype).to(F64)
+                parts.append(_shift(_compare(oc, r, torch.zeros_like(r), "values"), b0, out.shape))
+                continue
+            m, s = mean[:C].to(F64), std[:C].to(F64)
+            r = (xc - m) / s
+            a = (xc.abs() + m.abs()) / s.abs()
+            tol = REL * a + (ulp_bf16(r) if out.dtype == torch.bfloat16 else 0.0)
+            parts.append(_shift(_compare(oc, r, tol, "(x - mean) / std"), b0, out.shape))
+        return self._add(call, _merge(parts, parts[0]["what"]))
+
+    def d4_labels(self, call, t, codes, out):
+        r = torch.stack([d4_gather(t[b], int(codes[b])) for b in range(t.shape[0])])
+        self._add(call, _exact_zero((out != r).to(torch.int8), "labels"))
+
+    def head_bias_grad(self, call, sums, abs_sums, db):
+        """db [K] f32, the bias gradient of the layer that produced the logits, handed over as the loss kernel's
+        per-class sums times the upstream gradient.  sums [Cp] float64: the column sums of the FINAL dlogits buffer
+        (after the rescale, as the consuming node saw it); abs_sums [Cp] float64: the magnitude term of the softmax_ce
+        sums check (sums of |stored dlogits|) times |upstream gradient|; one f32 rounding for the product."""
+        K = db.shape[0]
+        r = sums[:K]
+        return self._add(call, _compare(db, r, REL * abs_sums[:K] + ulp_f32(r), "bias gradient from the loss sums"))
+
     def confusion(self, call, before, after, pred, target):
         K = before.shape[0]
         idx = target.reshape(-1).long() * K + pred.reshape(-1).long()
@@ -635,6 +745,9 @@ class Recorder(Checker):
         self.counts = defaultdict(int)
         self._saved = []
         self._wcache = {}
+        self._chains = {}        # fusion conv name -> real channels of the links of its forward chain, in order
+        self._scaled = {}        # address of a rescaled dlogits buffer -> what its consumer's bias gradient must be
+        self.head_bias = {}      # module name of a head -> the entry of _scaled its dgrad call consumed
 
     # ---- patching ------------------------------------------------------------------------------
 
@@ -664,6 +777,22 @@ class Recorder(Checker):
 
         self._saved.append((hnn.HipConv2d, "packed", orig_packed))
         hnn.HipConv2d.packed = packed
+        orig_slice = hnn._fusion_slice
+
+        def fusion_slice(conv, w, off, c, dtype, pitch, transpose):
+            """the column block of a fusion 1x1 weight: the reference keeps the whole master weight and the offset the
+            product asked for; _conv_call takes the block where the chain of real channel counts puts it"""
+            pw = orig_slice(conv, w, off, c, dtype, pitch, transpose)
+            key = (id(conv), conv.weight._version, conv.weight.data_ptr(), hnn.state_epoch())
+            full = rec._wcache.get(key)
+            if full is None:
+                full = rec._wcache[key] = conv.weight.detach().clone()
+            rec.weights[id(pw)] = {"name": rec.names.get(id(conv), "?"), "transpose": bool(transpose), "master": full,
+                                   "off": int(off), "c": int(c), "stride": 1, "padding": 0}
+            return pw
+
+        self._saved.append((hnn, "_fusion_slice", orig_slice))
+        hnn._fusion_slice = fusion_slice
         return self
 
     def __exit__(self, *exc):
@@ -706,10 +835,36 @@ class Recorder(Checker):
 
     # ---- per-op adapters: (call summary, cloned inputs, live arguments, outputs) ----------------
 
+    def _fusion_block(self, call, info, residual):
+        """master columns of one link of a fusion 1x1 conv.  The offset is not taken from the product: the links of a
+        forward chain (it starts at the call without a residual) occupy the columns in call order, each as many as its
+        source has real channels, and together all of them; a dgrad link must be one of the blocks of that chain."""
+        W, off, c, name = info["master"], info["off"], info["c"], info["name"]
+        call.update(fusion=True, off=off, c=c, module=name)
+        if not info["transpose"]:
+            chain = self._chains[name] = [] if residual is None else self._chains.get(name)
+            if chain is None:
+                raise ValueError("fusion link with a residual before the first link of its chain")
+            want = sum(chain)
+            chain.append(c)
+            if sum(chain) > W.shape[1]:
+                raise ValueError(f"fusion chain of {sum(chain)} channels over a weight of {W.shape[1]} columns")
+        else:
+            chain = self._chains.get(name) or []
+            starts = {sum(chain[:m]): cm for m, cm in enumerate(chain)}
+            if sum(chain) != W.shape[1] or starts.get(off) != c:
+                raise ValueError(f"dgrad block [{off}, {off + c}) is no link of the forward chain {chain} "
+                                 f"over {W.shape[1]} columns")
+            want = off
+        blk = W[:, want:want + c]
+        if off != want:
+            raise ValueError(f"fusion block taken at column {off}, the chain of real channels puts it at {want}")
+        return blk
+
     def _conv_call(self, call, a, out, w, dil, residual, bias=None, relu=False, stats=False):
         info = self._weight(a["w"])
         pw = a["w"]
-        W = info["weight"]
+        W = self._fusion_block(call, info, residual) if "master" in info else info["weight"]
         w64 = bf16_round(W) if pw.data.dtype == torch.bfloat16 else W.to(F64)
         call.update(module=info["name"], layout=layout_of(pw), transpose=info["transpose"], kernel=f"{pw.kh}x{pw.kw}",
                     dil=dil, residual=residual is not None, stats=stats)
@@ -725,6 +880,13 @@ class Recorder(Checker):
     def _op_conv2d(self, call, a, live, out):
         if a["stats"] is not None:
             raise ValueError("conv2d with a statistics buffer outside conv2d_bn_stats")
+        # a dgrad call that reads a rescaled dlogits buffer is the backward of the head that produced those logits: its
+        # node is the one that takes the loss sums for its bias gradient
+        hit = self._scaled.pop(live["x"].data_ptr(), None)
+        if hit is not None and hit["shape"] == tuple(live["x"].shape):
+            info = self.weights.get(id(a["w"]))
+            if info is not None and info["transpose"]:
+                self.head_bias[info["name"]] = hit
         self._conv_call(call, a, out, a["w"], a["dil"], a["residual"], bias=a["bias"], relu=a["relu"])
 
     def _op_conv2d_bn_stats(self, call, a, live, out):
@@ -796,6 +958,7 @@ class Recorder(Checker):
         call.update(family="wgrad", kernel=f"{a['kh']}x{a['kw']}", stride=a["stride"],
                     layout="thin" if (a["x"].shape[-1] <= 32 and a["dy"].shape[-1] <= 32 and a["kh"] == 3
                                       and a["stride"] == 1) else "general")
+        call.update(co=out.shape[0], ci=out.shape[1], hw=tuple(a["x"].shape[1:3]))
         before = a["out"] if a["accumulate"] else None
         self.conv_wgrad(call, a["x"], a["dy"], a["kh"], a["kw"], a["stride"], a["pad"], out, before=before)
         self.grad_sources.append(("dW", out.detach().clone()))
@@ -828,6 +991,7 @@ class Recorder(Checker):
     def _op_channel_sums(self, call, a, live, out):
         call["family"] = "channel_sums"
         self.channel_sums(call, a["x"], *out)
+        self.sum_sources.append(out[0].detach().clone())
 
     def _op_maxpool3x3s2_fwd(self, call, a, live, out):
         call["family"] = "maxpool_fwd"
@@ -844,10 +1008,50 @@ class Recorder(Checker):
     def _op_scale_inplace(self, call, a, live, out):
         call["family"] = "scale_inplace"
         self.scale_inplace(call, a["x"], a["scale"], out)
+        gs = float(a["scale"].reshape(-1)[0])
+        call["scale"] = gs
+        if out.dim() == 4:  # a gradient buffer on its way to the layer that produced the logits
+            Cp = out.shape[-1]
+            ref, mag = out.new_zeros(Cp, dtype=F64), out.new_zeros(Cp, dtype=F64)
+            for b0, b1 in self._chunks(out.shape[0]):
+                ref += out[b0:b1].to(F64).reshape(-1, Cp).sum(0)
+                mag += a["x"][b0:b1].to(F64).abs().reshape(-1, Cp).sum(0) * abs(gs)
+            self._scaled[out.data_ptr()] = {"shape": tuple(out.shape), "sums": ref, "abs_sums": mag, "scale": gs,
+                                            "call": call["call"]}
 
     def _op_nchw_to_nhwc(self, call, a, live, out):
         call["family"] = "nchw_to_nhwc"
         self.nchw_to_nhwc(call, a["x"], out)
+
+    def _op_nhwc_to_nchw(self, call, a, live, out):
+        call["family"] = "nhwc_to_nchw"
+        self.nhwc_to_nchw(call, a["x"], a["channels"], out)
+
+    def _op_bilinear_fwd(self, call, a, live, out):
+        call.update(family="bilinear_fwd", ratio=a["x"].shape[1] / out.shape[1])
+        self.bilinear(call, a["x"], out, False)
+
+    def _op_bilinear_bwd(self, call, a, live, out):
+        call.update(family="bilinear_bwd", ratio=out.shape[1] / a["dy"].shape[1])
+        self.bilinear(call, a["dy"], out, True)
+
+    def _op_mean_stack(self, call, a, live, out):
+        call["family"] = "mean_stack"
+        self.mean_stack(call, list(a["xs"]), a["divisor"], out)
+
+    def _op_u8_nchw_to_nhwc(self, call, a, live, out):
+        call["family"] = "layout_norm"
+        self.layout_norm(call, a["x"], a["mean"], a["std"], out)
+
+    _op_raw_nchw_to_nhwc = _op_u8_nchw_to_nhwc
+
+    def _op_d4_layout(self, call, a, live, out):
+        call.update(family="d4_layout", codes=sorted(set(int(c) & 15 for c in a["codes"].tolist())))
+        self.layout_norm(call, a["x"], a["mean"], a["std"], out, codes=a["codes"].tolist(), group=a["group"])
+
+    def _op_d4_labels(self, call, a, live, out):
+        call["family"] = "d4_labels"
+        self.d4_labels(call, a["t"], a["codes"].tolist(), out)
 
     def _op_confusion_matrix_update(self, call, a, live, out):
         call["family"] = "confusion_matrix"
@@ -857,6 +1061,57 @@ class Recorder(Checker):
 
     def failures(self) -> List[Result]:
         return [r for r in self.results if not r.ok]
+
+    def grad_orphans(self, named_parameters) -> List[str]:
+        """names of the parameters whose gradient is not what a checked call produced.  A gradient is accounted for if
+
+        * it IS the output of a checked call, bit for bit (dW, dgamma, dbeta, the loss sums of an upstream gradient 1);
+        * (a) it is the dim=1 concatenation of checked conv_wgrad outputs that follow one another in call order (the
+          weight of a fusion 1x1 conv: one wgrad per source);
+        * (b) it is the bias gradient of a head whose dgrad call read a rescaled dlogits buffer: then it must pass
+          head_bias_grad against the final contents of THAT buffer, whatever else it may equal;
+        * it is a bias gradient cut from the front of a checked channel_sums output, bit for bit."""
+        by_shape = defaultdict(list)
+        for _, t in self.grad_sources:
+            by_shape[tuple(t.shape)].append(t)
+        dws = [t for tag, t in self.grad_sources if tag == "dW"]
+        orphans = []
+        for name, p in named_parameters:
+            if p.grad is None:
+                continue
+            g = p.grad.detach()
+            mod, _, leaf = name.rpartition(".")
+            if leaf == "bias" and mod in self.head_bias:
+                h = self.head_bias[mod]
+                res = self.head_bias_grad({"op": "head_bias_grad", "family": "head_bias_grad", "call": h["call"],
+                                           "module": mod, "scale": h["scale"]}, h["sums"], h["abs_sums"], g)
+                if not res.ok:
+                    orphans.append(name)
+                continue
+            if any(torch.equal(g, t) for t in by_shape.get(tuple(g.shape), [])):
+                continue
+            if g.dim() == 4 and self._is_concat_of_wgrads(g, dws):
+                continue
+            if g.dim() == 1 and any(t.numel() >= g.numel() and torch.equal(g, t[:g.numel()]) for t in self.sum_sources):
+                continue
+            orphans.append(name)
+        return orphans
+
+    @staticmethod
+    def _is_concat_of_wgrads(g, dws) -> bool:
+        O, I, kh, kw = g.shape
+        for i in range(len(dws)):
+            run, width = [], 0
+            for t in dws[i:]:
+                if t.shape[0] != O or tuple(t.shape[2:]) != (kh, kw) or width + t.shape[1] > I:
+                    break
+                run.append(t)
+                width += t.shape[1]
+                if width == I:
+                    break
+            if len(run) > 1 and width == I and torch.equal(g, torch.cat(run, dim=1)):
+                return True
+        return False
 
     def table(self) -> str:
         fam = defaultdict(lambda: {"calls": set(), "layouts": set(), "worst": 0.0, "checks": 0})

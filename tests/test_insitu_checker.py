@@ -271,3 +271,223 @@ def test_honest_elementwise_and_loss_results_pass():
                 sums2[3] += 1e-3 * sums2.abs().max()
             ck.softmax_ce({"op": "softmax_ce"}, logits, t, cw, K, None, (loss2.reshape(1), wsum.reshape(1), d2, pred2, sums2))
         assert any(not r.ok for r in ck.results), corrupt
+
+
+# --------------------------------------------------------------------------------------------------
+# the references of the two-modality fusion step: 1x1 conv chains over column blocks of one weight, the bilinear
+# alignment at ratio 1.5, mean_stack, the head bias gradient handed over from the loss, the layout kernels
+
+FB, FH, FW, FHO, FWO = 2, 12, 8, 18, 12   # maps 12 x 8 -> 18 x 12 (ratio 1.5)
+FC0, FC1, FO, FPITCH = 5, 6, 12, 16       # two sources of 5 and 6 real channels, 12 outputs, pitch 16
+FK = 11                                   # classes of the head (pitch 16)
+SQ = 12                                   # square planes for the flips and rotations
+
+
+def _taps(n_in, n_out, align=False, clamp=True):
+    """f32 taps of one axis as the kernel takes them; align: the align_corners=True source index"""
+    dst = torch.arange(n_out, dtype=torch.float32)
+    if align:
+        src = dst * torch.tensor((n_in - 1) / (n_out - 1), dtype=torch.float32)
+    else:
+        src = ((dst + 0.5) * torch.tensor(n_in / n_out, dtype=torch.float32) - 0.5).clamp_min(0)
+    i0 = src.floor().long().clamp(max=n_in - 1)
+    i1 = i0 + 1
+    if clamp:
+        i1 = i1.clamp(max=n_in - 1)
+    l1 = src - i0.float()
+    return i0, i1, 1 - l1, l1
+
+
+def _bilinear_f32(x, ho, wo, align=False, clamp_rows=True):
+    """gather form in f32, rows of two column-interpolated taps; clamp_rows=False: the second tap of the last row reads
+    row H, which in memory is row 0 of the next image (zeros past the last one)"""
+    Bn, H, W, C = x.shape
+    xf = x.float()
+    if not clamp_rows:
+        xf = torch.cat([xf, torch.cat([xf[1:, :1], torch.zeros(1, 1, W, C)])], dim=1)
+    y0, y1, ly0, ly1 = _taps(H, ho, align, clamp_rows)
+    x0, x1, lx0, lx1 = _taps(W, wo, align)
+
+    def row(yi):
+        r = xf[:, yi]
+        return lx0[None, None, :, None] * r[:, :, x0] + lx1[None, None, :, None] * r[:, :, x1]
+
+    return ly0[None, :, None, None] * row(y0) + ly1[None, :, None, None] * row(y1)
+
+
+def _tap_matrix(n_in, n_out):
+    i0, i1, l0, l1 = _taps(n_in, n_out)
+    m = torch.zeros(n_out, n_in)
+    m.scatter_add_(1, i0[:, None], l0[:, None])
+    m.scatter_add_(1, i1[:, None], l1[:, None])
+    return m
+
+
+@pytest.fixture(scope="module")
+def fcase():
+    g = torch.Generator().manual_seed(17)
+    c = {}
+
+    def padded(real, *shape):
+        t = torch.randn(*shape, real, generator=g)
+        return F.pad(t, (0, FPITCH - real)).to(torch.bfloat16)
+
+    c["xa"], c["xb"] = padded(FC0, FB, FH, FW), padded(FC1, FB, FH, FW)
+    c["w"] = _bf(torch.randn(FO, FC0 + FC1, 1, 1, generator=g) / 3)
+    c["bias"] = F.pad(torch.randn(FO, generator=g), (0, FPITCH - FO))
+    c["x"] = padded(10, FB, FH, FW)                   # the map the alignment resizes
+    c["dy"] = padded(10, FB, FHO, FWO)
+    c["g"] = padded(10, FB, FH, FW)
+    d = F.pad(torch.randn(FB, FH, FW, FK, generator=g) * 0.01, (0, FPITCH - FK)).to(torch.bfloat16)
+    c["dlogits"] = d
+    c["sums"] = d.float().reshape(-1, FPITCH).sum(0)  # what the loss kernel hands over: for an upstream gradient of 1
+    c["u8"] = torch.randint(0, 256, (FB, 3, SQ, SQ), generator=g).to(torch.uint8)
+    c["mean"], c["std"] = torch.tensor([105.0, 110.5, 101.25]), torch.tensor([52.0, 45.5, 44.0])
+    c["labels"] = torch.randint(0, 19, (FB, SQ, SQ), generator=g).to(torch.uint8)
+    return c
+
+
+def _link(x, w, real, extra):
+    """one link of the chain in f32: 1x1 conv of the real channels + (bias and / or the chain so far), stored bf16"""
+    y = _nhwc(F.conv2d(_nchw(x[..., :real].float()), w)) + extra
+    return F.pad(y, (0, FPITCH - FO)).to(torch.bfloat16)
+
+
+def run_fusion(ck, c, fault):
+    w, b = c["w"], c["bias"][:FO]
+    y0 = _link(c["xa"], w[:, :FC0], FC0, b)
+    w1 = w[:, FC0:FC0 + FC1]
+    if fault == "slice_padded_offset":  # the second block starts at the first source's PITCH: past the weight's columns
+        w1 = w[:, FPITCH:FPITCH + FC1]
+        w1 = F.pad(w1, (0, 0, 0, 0, 0, FC1 - w1.shape[1]))
+    y1 = _link(c["xb"], w1, FC1, y0[..., :FO].float() + (b if fault == "bias_twice" else 0.0))
+    w64 = _f64(w)
+    ck.conv_forward({"op": "conv2d", "link": 0}, c["xa"], w64[:, :FC0], 1, 0, y0, bias=c["bias"])
+    ck.conv_forward({"op": "conv2d", "link": 1}, c["xb"], w64[:, FC0:FC0 + FC1], 1, 0, y1, residual=y0)
+
+
+def run_bilinear_fwd(ck, c, fault):
+    y = _bilinear_f32(c["x"], FHO, FWO, align=fault == "align_corners", clamp_rows=fault != "no_clamp")
+    ck.bilinear({"op": "bilinear_fwd"}, c["x"], y.to(torch.bfloat16), False)
+
+
+BWD_SRC_ROW, BWD_DST_ROW = 5, 9  # destination rows 7, 8 and 9 reach source row 5 at ratio 1.5
+
+
+def run_bilinear_bwd(ck, c, fault):
+    my, mx = _tap_matrix(FH, FHO), _tap_matrix(FW, FWO)
+    if fault == "missing_row":  # the gather of one source row stops one destination row early
+        assert my[BWD_DST_ROW, BWD_SRC_ROW] > 0 and my[BWD_DST_ROW + 1, BWD_SRC_ROW] == 0
+        my[BWD_DST_ROW, BWD_SRC_ROW] = 0
+    dx = torch.einsum("px,bypc->byxc", mx, torch.einsum("oy,bopc->bypc", my, c["dy"].float()))
+    ck.bilinear({"op": "bilinear_bwd"}, c["dy"], dx.to(torch.bfloat16), True)
+
+
+def run_mean_stack(ck, c, fault):
+    ck.mean_stack({"op": "mean_stack", "dir": "fwd"}, [c["x"], c["g"]], None,
+                  ((c["g"].float() + c["x"].float()) / 2).to(torch.bfloat16))
+    gi = (c["g"].float() / (1 if fault == "divisor_one" else 2)).to(torch.bfloat16)
+    ck.mean_stack({"op": "mean_stack", "dir": "bwd"}, [c["g"]], 2, gi)
+
+
+def run_head_bias(ck, c, fault):
+    gs = 0.5
+    final = (c["dlogits"].float() * gs).to(torch.bfloat16)  # the buffer after scale_inplace
+    db = (c["sums"] * (1.0 if fault == "no_task_weight" else gs))[:FK]
+    ck.head_bias_grad({"op": "head_bias_grad"}, _f64(final).reshape(-1, FPITCH).sum(0),
+                      _f64(c["dlogits"]).abs().reshape(-1, FPITCH).sum(0) * gs, db)
+
+
+def run_layouts(ck, c, fault):
+    from flairhip.augment import VFLIP, apply_code, make_code
+    codes = [make_code(False, False, 1), make_code(True, True, 0)]  # a quarter turn (transpose + flip), both flips
+
+    def product(x, used):
+        t = torch.stack([torch.from_numpy(apply_code(x[b].numpy(), k)) for b, k in enumerate(used)])
+        v = (t.float() - c["mean"][None, :, None, None]) / c["std"][None, :, None, None]
+        return F.pad(_nhwc(v), (0, 5)).to(torch.bfloat16)
+
+    used = [VFLIP, codes[1]] if fault == "transpose_as_flip" else codes
+    ck.layout_norm({"op": "d4_layout"}, c["u8"], c["mean"], c["std"], product(c["u8"], used), codes=codes)
+    ck.layout_norm({"op": "u8_nchw_to_nhwc"}, c["u8"], c["mean"], c["std"], product(c["u8"], [0, 0]))
+    xf = torch.randn(FB, 2, SQ, SQ, generator=torch.Generator().manual_seed(3))
+    t = torch.stack([torch.from_numpy(apply_code(xf[b].numpy(), k)) for b, k in enumerate(codes)])
+    ck.layout_norm({"op": "d4_layout"}, xf, None, None, F.pad(_nhwc(t), (0, 6)).to(torch.bfloat16), codes=codes)
+    lab = torch.stack([torch.from_numpy(apply_code(c["labels"][b].numpy(), k)) for b, k in enumerate(codes)])
+    ck.d4_labels({"op": "d4_labels"}, c["labels"], codes, lab)
+    ck.nhwc_to_nchw({"op": "nhwc_to_nchw"}, c["x"], 10, _nchw(c["x"][..., :10].float()))
+
+
+FCALLS = {"fusion": run_fusion, "bilinear_fwd": run_bilinear_fwd, "bilinear_bwd": run_bilinear_bwd,
+          "mean_stack": run_mean_stack, "head_bias": run_head_bias, "layouts": run_layouts}
+# fault -> (call it lives in, modes, what the failing results must say)
+FFAULTS = {
+    "slice_padded_offset": ("fusion", ("full", "proj"), lambda r: r["link"] == 1),
+    "bias_twice": ("fusion", ("full", "proj"), lambda r: r["link"] == 1),
+    "align_corners": ("bilinear_fwd", ("full",), lambda r: r["op"] == "bilinear_fwd"),
+    "no_clamp": ("bilinear_fwd", ("full",), lambda r: r["where"][1] == FHO - 1 and r["fail"] <= FB * FWO * 10),
+    "missing_row": ("bilinear_bwd", ("full",), lambda r: r["where"][1] == BWD_SRC_ROW and r["fail"] <= FB * FW * 10),
+    "divisor_one": ("mean_stack", ("full",), lambda r: r["dir"] == "bwd"),
+    "no_task_weight": ("head_bias", ("full",), lambda r: r["what"] == "bias gradient from the loss sums"),
+    "transpose_as_flip": ("layouts", ("full",), lambda r: r["op"] == "d4_layout" and r["where"][0] == 0),
+}
+
+
+@pytest.mark.parametrize("mode", ["full", "proj"])
+@pytest.mark.parametrize("call", sorted(FCALLS))
+def test_honest_fusion_results_pass(fcase, mode, call):
+    ck = Checker(mode, chunk=1)
+    FCALLS[call](ck, fcase, None)
+    assert ck.results
+    bad = [r.line() for r in ck.results if not r.ok]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("fault,mode", [(f, m) for f in sorted(FFAULTS) for m in FFAULTS[f][1]])
+def test_planted_fusion_fault_is_flagged_in_the_right_place(fcase, mode, fault):
+    call, _, right_place = FFAULTS[fault]
+    ck = Checker(mode, chunk=1)
+    FCALLS[call](ck, fcase, fault)
+    bad = [r for r in ck.results if not r.ok]
+    assert bad, f"{fault} passed the {mode} comparator: " + "; ".join(r.line() for r in ck.results)
+    assert all(right_place(r) for r in bad), [r.line() for r in bad]
+
+
+def test_bilinear_matrix_is_the_aten_resize():
+    """the float64 taps against F.interpolate (f32) at the sizes of the fusion stages, both directions"""
+    for n_in, n_out in ((2, 3), (3, 2), (32, 48), (48, 32), (8, 12), (1, 8), (13, 40)):
+        x = torch.randn(1, 1, n_in, 1, generator=torch.Generator().manual_seed(n_in))
+        ref = F.interpolate(x, size=(n_out, 1), mode="bilinear", align_corners=False)[0, 0, :, 0]
+        got = insitu.bilinear_matrix(n_in, n_out) @ _f64(x[0, 0, :, 0])
+        # ATen takes the source coordinate in f32: a few ulps of a number up to n_in, times the step between the taps
+        assert (got - _f64(ref)).abs().max().item() <= 8 * n_in * 2.0 ** -24 * 2 * x.abs().max().item()
+        assert torch.allclose(insitu.bilinear_matrix(n_in, n_out).sum(1), torch.ones(n_out, dtype=torch.float64))
+
+
+def test_grad_source_rules():
+    """a parameter gradient is accounted for bit for bit, (a) as the dim=1 concatenation of consecutive checked wgrads
+    or (b) -- a head's bias -- against the rescaled buffer its node consumed; nothing else"""
+    g = torch.Generator().manual_seed(23)
+    rec = insitu.Recorder(torch.nn.Module(), "full")
+    a, b, other = (torch.randn(FO, n, 1, 1, generator=g) for n in (FC0, FC1, FC1))
+    rec.grad_sources += [("dW", a), ("dW", other), ("dW", b)]
+    P = torch.nn.Parameter
+
+    def with_grad(t):
+        p = P(torch.zeros_like(t))
+        p.grad = t.clone()
+        return p
+
+    assert rec.grad_orphans([("plain.weight", with_grad(a))]) == []
+    assert rec.grad_orphans([("fused.weight", with_grad(torch.cat([a, other], 1)))]) == []
+    assert rec.grad_orphans([("fused.weight", with_grad(torch.cat([a, b], 1)))]) == ["fused.weight"]  # not consecutive
+    assert rec.grad_orphans([("fused.weight", with_grad(torch.cat([other, a], 1)))]) == ["fused.weight"]  # wrong order
+    s = torch.randn(FPITCH, generator=g)
+    rec.sum_sources.append(s)
+    assert rec.grad_orphans([("conv_f.bias", with_grad(s[:FO]))]) == []
+    assert rec.grad_orphans([("conv_f.bias", with_grad(s[1:FO + 1]))]) == ["conv_f.bias"]
+    sums = torch.randn(FPITCH, generator=g, dtype=torch.float64)
+    rec.head_bias["head"] = {"call": 7, "scale": 0.5, "sums": sums * 0.5, "abs_sums": sums.abs() * 40 * 0.5}
+    assert rec.grad_orphans([("head.bias", with_grad((sums.float() * 0.5)[:FK]))]) == []
+    assert rec.grad_orphans([("head.bias", with_grad(sums.float()[:FK]))]) == ["head.bias"]
+    assert [r["module"] for r in rec.failures()] == ["head"]
