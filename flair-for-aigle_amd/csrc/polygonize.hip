@@ -68,11 +68,13 @@ __device__ __forceinline__ int compact_index(const int* L, const int* cnt, const
   return off[r * W + c] + __builtin_popcount(m & ((1 << d) - 1));
 }
 
-// eid[i] = 4 p + d, succ[i], and the min-propagation start state (nxt = succ, mn = i)
+// eid[i] = 4 p + d, succ[i], and the min-propagation start state (nxt = succ, mn = i).  Edge ids are unsigned: the
+// count-sized path takes p up to 2^30 - 1, so 4 p + d needs all 32 bits; compact indices stay below 2^31.
 __global__ __launch_bounds__(kT) void edge_build_kernel(int H, int W, const int* __restrict__ L,
                                                         const int* __restrict__ cnt, const int* __restrict__ off,
-                                                        int min_pixels, int* __restrict__ eid, int* __restrict__ succ,
-                                                        int* __restrict__ nxt, int* __restrict__ mn) {
+                                                        int min_pixels, unsigned int* __restrict__ eid,
+                                                        int* __restrict__ succ, int* __restrict__ nxt,
+                                                        int* __restrict__ mn) {
   const int p = blockIdx.x * kT + threadIdx.x;
   if (p >= H * W) return;
   const int r = p / W, c = p % W;
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(kT) void edge_build_kernel(int H, int W, const int*
       s = compact_index(L, cnt, off, H, W, ar, ac, d, min_pixels);            // straight on
     else
       s = off[p] + __builtin_popcount(m & ((1 << fd) - 1));                   // turn left, same pixel
-    eid[i] = 4 * p + d;
+    eid[i] = 4u * (unsigned int)p + (unsigned int)d;
     succ[i] = s;
     nxt[i] = s;
     mn[i] = i;
@@ -102,33 +104,39 @@ __global__ __launch_bounds__(kT) void edge_build_kernel(int H, int W, const int*
 
 // ---- 4. rings: pointer jumping ---------------------------------------------------------------------------------------
 
+// Grid-stride loops over the edges count unsigned: n may be close to 2^31, where i + gridDim.x * kT no longer fits an
+// int but, with at most 2^21 threads in a grid (grid_for), stays far below 2^32.
+__device__ __forceinline__ unsigned int grid_first() { return blockIdx.x * kT + threadIdx.x; }
+__device__ __forceinline__ unsigned int grid_step() { return gridDim.x * kT; }
+
 __global__ __launch_bounds__(kT) void jump_min_kernel(const int* __restrict__ n_dev, const int* __restrict__ nxt,
                                                       const int* __restrict__ mn, int* __restrict__ nxt2,
                                                       int* __restrict__ mn2) {
   const int n = *n_dev;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < n; i += gridDim.x * kT) {
+  for (unsigned int i = grid_first(); i < (unsigned int)n; i += grid_step()) {
     const int j = nxt[i];
     nxt2[i] = nxt[j];
     mn2[i] = min(mn[i], mn[j]);
   }
 }
 
-__device__ __forceinline__ int edge_dir(int e) { return e & 3; }
+__device__ __forceinline__ int edge_dir(unsigned int e) { return (int)(e & 3u); }
 
 // list ranking start state over predecessors, the cycle broken at the ring id: for j = succ(i), P[j] = i and D[j] =
 // 1 when the direction changes at the corner between i and j (a vertex at the start corner of j); the ring id edge
 // gets P = itself, D = 0
-__global__ __launch_bounds__(kT) void rank_init_kernel(const int* __restrict__ n_dev, const int* __restrict__ eid,
+__global__ __launch_bounds__(kT) void rank_init_kernel(const int* __restrict__ n_dev,
+                                                       const unsigned int* __restrict__ eid,
                                                        const int* __restrict__ succ, const int* __restrict__ ring,
                                                        int* __restrict__ P, int* __restrict__ D) {
   const int n = *n_dev;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < n; i += gridDim.x * kT) {
+  for (unsigned int i = grid_first(); i < (unsigned int)n; i += grid_step()) {
     const int j = succ[i];
     if (ring[j] == j) {
       P[j] = j;
       D[j] = 0;
     } else {
-      P[j] = i;
+      P[j] = (int)i;
       D[j] = edge_dir(eid[i]) != edge_dir(eid[j]) ? 1 : 0;
     }
   }
@@ -138,7 +146,7 @@ __global__ __launch_bounds__(kT) void jump_sum_kernel(const int* __restrict__ n_
                                                       const int* __restrict__ D, int* __restrict__ P2,
                                                       int* __restrict__ D2) {
   const int n = *n_dev;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < n; i += gridDim.x * kT) {
+  for (unsigned int i = grid_first(); i < (unsigned int)n; i += grid_step()) {
     const int j = P[i];
     P2[i] = P[j];
     D2[i] = D[i] + (j == i ? 0 : D[j]);
@@ -148,12 +156,12 @@ __global__ __launch_bounds__(kT) void jump_sum_kernel(const int* __restrict__ n_
 __global__ __launch_bounds__(kT) void root_flag_kernel(const int* __restrict__ n_dev, const int* __restrict__ ring,
                                                        int* __restrict__ flag) {
   const int n = *n_dev;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < n; i += gridDim.x * kT) flag[i] = ring[i] == i ? 1 : 0;
+  for (unsigned int i = grid_first(); i < (unsigned int)n; i += grid_step()) flag[i] = ring[i] == i ? 1 : 0;
 }
 
 // start corner (col, row) of edge e = 4 p + d
-__device__ __forceinline__ void edge_start(int e, int W, int* x, int* y) {
-  const int p = e >> 2, d = e & 3, r = p / W, c = p % W;
+__device__ __forceinline__ void edge_start(unsigned int e, int W, int* x, int* y) {
+  const int p = (int)(e >> 2), d = (int)(e & 3u), r = p / W, c = p % W;
   *x = c + (d == 1 || d == 2 ? 1 : 0);
   *y = r + (d == 0 || d == 1 ? 1 : 0);
 }
@@ -161,24 +169,26 @@ __device__ __forceinline__ void edge_start(int e, int W, int* x, int* y) {
 // per ring (ordinal r = ring_ord[ring id]): label, vertex count, whether the ring-id edge starts at a vertex, and
 // the doubled signed area in map orientation (sum of dx*y - x*dy over its unit edges, pixel coordinates with y down)
 __global__ __launch_bounds__(kT) void ring_info_kernel(const int* __restrict__ n_dev, int W, const int* __restrict__ L,
-                                                       const int* __restrict__ eid, const int* __restrict__ succ,
-                                                       const int* __restrict__ ring, const int* __restrict__ D,
-                                                       const int* __restrict__ ring_ord, int* __restrict__ ring_label,
-                                                       int* __restrict__ ring_nv, int* __restrict__ ring_s,
+                                                       const unsigned int* __restrict__ eid,
+                                                       const int* __restrict__ succ, const int* __restrict__ ring,
+                                                       const int* __restrict__ D, const int* __restrict__ ring_ord,
+                                                       int* __restrict__ ring_label, int* __restrict__ ring_nv,
+                                                       int* __restrict__ ring_s,
                                                        unsigned long long* __restrict__ ring_area2) {
   const int n = *n_dev;
   const int lane = lane_id();
   // grid-stride over whole waves so that every lane reaches the ballots below
-  for (int base = blockIdx.x * kT + (threadIdx.x & ~63); base < n; base += gridDim.x * kT) {
-    const int i = base + lane;
+  for (unsigned int base = blockIdx.x * kT + (threadIdx.x & ~63u); base < (unsigned int)n; base += grid_step()) {
+    const unsigned int i = base + lane;
     int r = -1;
     long long a = 0;
     if (i < n) {
-      const int e = eid[i], root = ring[i];
+      const unsigned int e = eid[i];
+      const int root = ring[i];
       r = ring_ord[root];
       int x, y;
       edge_start(e, W, &x, &y);
-      const int d = e & 3;
+      const int d = edge_dir(e);
       const int dx = d == 0 ? 1 : (d == 2 ? -1 : 0), dy = d == 3 ? 1 : (d == 1 ? -1 : 0);
       a = (long long)dx * y - (long long)x * dy;
       if (root == i) ring_label[r] = L[e >> 2];
@@ -238,18 +248,25 @@ __global__ __launch_bounds__(kT) void scan_reduce_kernel(const int* __restrict__
   if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
-// one block: exclusive scan of the block partials in place, the grand total to *total_out
-__global__ __launch_bounds__(kT) void scan_partials_kernel(int* part, int nparts, int* total_out) {
-  int carry = 0;
+// one block: exclusive scan of the block partials in place, the grand total to *total_out.  *total64_out receives the
+// same total accumulated in 64 bits (a partial of per-pixel edge counts is at most 4 * kChunk, so 256 of them fit an
+// int): when it is 2^31 or more the 32-bit offsets have wrapped and mean nothing, which the caller finds out from the
+// total before it uses them.
+__global__ __launch_bounds__(kT) void scan_partials_kernel(int* part, int nparts, int* total_out,
+                                                           long long* total64_out) {
+  unsigned int carry = 0;
+  long long carry64 = 0;
   for (int b0 = 0; b0 < nparts; b0 += kT) {
     const int i = b0 + threadIdx.x;
     const int v = i < nparts ? part[i] : 0;
     int tot;
     const int ex = block_exclusive_scan(v, &tot);
-    if (i < nparts) part[i] = carry + ex;
-    carry += tot;
+    if (i < nparts) part[i] = (int)(carry + (unsigned int)ex);
+    carry += (unsigned int)tot;
+    carry64 += tot;
   }
-  if (threadIdx.x == 0 && total_out) *total_out = carry;
+  if (threadIdx.x == 0 && total_out) *total_out = (int)carry;
+  if (threadIdx.x == 0 && total64_out) *total64_out = carry64;
 }
 
 __global__ __launch_bounds__(kT) void scan_apply_kernel(const int* in, const int* n_dev, int n_host,
@@ -352,7 +369,7 @@ __global__ __launch_bounds__(kT) void comp_list_kernel(int N, const uint8_t* __r
 __global__ __launch_bounds__(kT) void poly_index_kernel(const int* n_dev, const int* __restrict__ poly_label,
                                                         int* __restrict__ polyidx) {
   const int n = *n_dev;
-  for (int q = blockIdx.x * kT + threadIdx.x; q < n; q += gridDim.x * kT) polyidx[poly_label[q]] = q;
+  for (unsigned int q = grid_first(); q < (unsigned int)n; q += grid_step()) polyidx[poly_label[q]] = (int)q;
 }
 
 __global__ __launch_bounds__(kT) void ring_keys_kernel(const int* n_dev, const int* __restrict__ ring_label,
@@ -360,10 +377,10 @@ __global__ __launch_bounds__(kT) void ring_keys_kernel(const int* n_dev, const i
                                                        const int* __restrict__ polyidx, int* __restrict__ keys,
                                                        int* __restrict__ vals) {
   const int n = *n_dev;
-  for (int r = blockIdx.x * kT + threadIdx.x; r < n; r += gridDim.x * kT) {
+  for (unsigned int r = grid_first(); r < (unsigned int)n; r += grid_step()) {
     const long long a = (long long)ring_area2[r];
     keys[r] = 2 * polyidx[ring_label[r]] + (a > 0 ? 0 : 1);
-    vals[r] = r;
+    vals[r] = (int)r;
   }
 }
 
@@ -373,11 +390,11 @@ __global__ __launch_bounds__(kT) void ring_order_kernel(const int* n_dev, const 
                                                         int* __restrict__ ring_pos, int* __restrict__ nv_sorted,
                                                         int* __restrict__ poly_first) {
   const int n = *n_dev;
-  for (int j = blockIdx.x * kT + threadIdx.x; j < n; j += gridDim.x * kT) {
+  for (unsigned int j = grid_first(); j < (unsigned int)n; j += grid_step()) {
     const int r = rs[j];
-    ring_pos[r] = j;
+    ring_pos[r] = (int)j;
     nv_sorted[j] = ring_nv[r];
-    if (!(sk[j] & 1)) poly_first[sk[j] >> 1] = j;
+    if (!(sk[j] & 1)) poly_first[sk[j] >> 1] = (int)j;
   }
 }
 
@@ -391,6 +408,21 @@ __global__ void counts_kernel(const Counters* c, long long* out) {
     out[1] = c->rings;
     out[2] = c->verts;
     out[3] = c->edges;
+  }
+}
+
+// The count-sized path keeps its counters in the pixel workspace: the count phase leaves the edge and polygon counts
+// there, the trace phase reads them as the loop bounds and adds rings and vertices.  edges64 is the edge total in
+// 64 bits; c.edges is its low half and equal to it whenever the trace phase may run.
+struct PixelCounters {
+  Counters c;
+  long long edges64;
+};
+
+__global__ void pixel_counts_kernel(const PixelCounters* c, long long* out) {
+  if (threadIdx.x == 0) {
+    out[0] = c->edges64;
+    out[1] = c->c.polys;
   }
 }
 
@@ -420,20 +452,21 @@ __global__ __launch_bounds__(kT) void emit_ring_offsets_kernel(int R, int V, con
 }
 
 // one thread per edge i with a direction change at its end corner: that corner is the start corner of succ(i)
-__global__ __launch_bounds__(kT) void emit_vertices_kernel(const int* n_dev, int W, const int* __restrict__ eid,
+__global__ __launch_bounds__(kT) void emit_vertices_kernel(const int* n_dev, int W,
+                                                           const unsigned int* __restrict__ eid,
                                                            const int* __restrict__ succ, const int* __restrict__ ring,
                                                            const int* __restrict__ D, const int* __restrict__ ring_ord,
                                                            const int* __restrict__ ring_s,
                                                            const int* __restrict__ ring_pos,
                                                            const int* __restrict__ voff, int32_t* __restrict__ verts) {
   const int E = *n_dev;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < E; i += gridDim.x * kT) {
+  for (unsigned int i = grid_first(); i < (unsigned int)E; i += grid_step()) {
     const int j = succ[i];
-    const int ej = eid[j];
+    const unsigned int ej = eid[j];
     if (edge_dir(eid[i]) == edge_dir(ej)) continue;
     const int r = ring_ord[ring[i]];
     const int idx = D[j] - 1 + ring_s[r];
-    const int v = voff[ring_pos[r]] + idx;
+    const long long v = (long long)voff[ring_pos[r]] + idx;  // below V < 2^31, so 2 v needs 64 bits
     int x, y;
     edge_start(ej, W, &x, &y);
     verts[2 * v] = x;
@@ -505,7 +538,26 @@ __global__ __launch_bounds__(kT) void zonal_sum_kernel(int N, int P, const int* 
     if (key[s] >= 0) zonal_flush(key[s], acc[s], P, polyidx, poly_label, sums);
 }
 
-// ---- workspace ----------------------------------------------------------------------------------------------------
+// ---- workspaces ---------------------------------------------------------------------------------------------------
+// Two ways to give the stages their arrays.  The bound-sized layout (ffa_polygonize_label) sizes everything from the
+// raster before anything is known about it: 4 edges per pixel, a ring and a polygon per pixel.  The count-sized
+// layouts split the work at the one point where the sizes are known: a pixel workspace for labels, counts, edge
+// offsets and the polygon index (ffa_polygonize_count), then, once the host has read the edge and polygon counts, a
+// trace workspace sized by those two numbers alone (ffa_polygonize_trace).  Both run the same stages on an Arrays.
+
+struct Arrays {
+  long long N, e_cap, r_cap, m_cap;  // pixels; capacity of the edge arrays, the ring arrays, the polygon / radix arrays
+  int rounds, nb_r;                  // pointer-jumping rounds, blocks of a radix pass
+  int *L, *cnt, *off, *polyidx;      // per pixel
+  int* ord;                          // per pixel: scanned kept-root flags (radix buffer rk1 or polyidx, see the layouts)
+  int *poly_label, *poly_cls, *poly_first, *rk0, *rv0, *rk1, *rv1;  // m_cap + 1
+  int *ring_label, *ring_nv, *ring_s, *ring_pos, *voff;              // r_cap + 1
+  unsigned long long* ring_area2;                                    // r_cap + 1
+  unsigned int* eid;                                                 // e_cap + 1, as the six below
+  int *succ, *ring, *P0, *P1, *D0, *D1;
+  int *hist, *part;
+  Counters* ctr;
+};
 
 struct Layout {
   long long N, E, nb_n, nb_e, nb_r;  // pixels, edge bound, scan / radix block counts
@@ -517,6 +569,12 @@ struct Layout {
 
 long long align_up(long long v) { return (v + 255) & ~255ll; }
 
+int rounds_for(long long edges) {
+  int rounds = 0;
+  while ((1ll << rounds) < edges) ++rounds;
+  return rounds;
+}
+
 bool make_layout(int H, int W, Layout* lo) {
   if (H < 1 || W < 1) return false;
   const long long N = (long long)H * W;
@@ -526,9 +584,7 @@ bool make_layout(int H, int W, Layout* lo) {
   lo->nb_n = (N + 1 + kChunk - 1) / kChunk;
   lo->nb_e = (lo->E + 1 + kChunk - 1) / kChunk;
   lo->nb_r = (N + kChunk - 1) / kChunk;  // radix passes run over <= N items (components, rings)
-  int rounds = 0;
-  while ((1ll << rounds) < lo->E) ++rounds;
-  lo->rounds = rounds;
+  lo->rounds = rounds_for(lo->E);
   long long o = 0;
   auto take = [&](long long bytes) {
     const long long at = o;
@@ -572,29 +628,203 @@ T* at(void* ws, long long off) {
   return reinterpret_cast<T*>(static_cast<char*>(ws) + off);
 }
 
+Arrays bind(void* ws, const Layout& lo) {
+  Arrays a;
+  a.N = lo.N;
+  a.e_cap = lo.E;
+  a.r_cap = lo.N;
+  a.m_cap = lo.N;
+  a.rounds = lo.rounds;
+  a.nb_r = (int)lo.nb_r;
+  a.L = at<int>(ws, lo.L);
+  a.cnt = at<int>(ws, lo.cnt);
+  a.off = at<int>(ws, lo.off);
+  a.polyidx = at<int>(ws, lo.polyidx);
+  a.poly_label = at<int>(ws, lo.poly_label);
+  a.poly_cls = at<int>(ws, lo.poly_cls);
+  a.poly_first = at<int>(ws, lo.poly_first);
+  a.rk0 = at<int>(ws, lo.rk0);
+  a.rv0 = at<int>(ws, lo.rv0);
+  a.rk1 = at<int>(ws, lo.rk1);
+  a.rv1 = at<int>(ws, lo.rv1);
+  a.ord = a.rk1;  // free until the first radix sort, which runs after its only reader (comp_list_kernel)
+  a.ring_label = at<int>(ws, lo.ring_label);
+  a.ring_nv = at<int>(ws, lo.ring_nv);
+  a.ring_s = at<int>(ws, lo.ring_s);
+  a.ring_pos = at<int>(ws, lo.ring_pos);
+  a.voff = at<int>(ws, lo.voff);
+  a.ring_area2 = at<unsigned long long>(ws, lo.ring_area2);
+  a.eid = at<unsigned int>(ws, lo.eid);
+  a.succ = at<int>(ws, lo.succ);
+  a.ring = at<int>(ws, lo.ring);
+  a.P0 = at<int>(ws, lo.P0);
+  a.P1 = at<int>(ws, lo.P1);
+  a.D0 = at<int>(ws, lo.D0);
+  a.D1 = at<int>(ws, lo.D1);
+  a.hist = at<int>(ws, lo.hist);
+  a.part = at<int>(ws, lo.part);
+  a.ctr = at<Counters>(ws, lo.ctr);
+  return a;
+}
+
+// Pixel workspace of the count-sized path: four int32 arrays of N + 1, the scan partials and the counters.  With
+// N < 2^30 the partials are below 1 MiB, so the total stays within 16 N + 2 MiB.
+constexpr long long kCountedMaxPixels = 1ll << 30;
+constexpr long long kCountedMaxEdges = (1ll << 31) - 1;  // exclusive
+
+struct PixelLayout {
+  long long N, nb_n;
+  long long L, cnt, off, polyidx, part, ctr, total;
+};
+
+bool make_pixel_layout(int H, int W, PixelLayout* pl) {
+  if (H < 1 || W < 1) return false;
+  const long long N = (long long)H * W;
+  if (N >= kCountedMaxPixels) return false;
+  pl->N = N;
+  pl->nb_n = (N + 1 + kChunk - 1) / kChunk;
+  long long o = 0;
+  auto take = [&](long long bytes) {
+    const long long at = o;
+    o += align_up(bytes);
+    return at;
+  };
+  const long long n4 = 4 * (N + 1);
+  pl->L = take(n4);
+  pl->cnt = take(n4);
+  pl->off = take(n4);
+  pl->polyidx = take(n4);
+  pl->part = take(4 * (pl->nb_n + 16));
+  pl->ctr = take(sizeof(PixelCounters));
+  pl->total = o;
+  return true;
+}
+
+// Trace workspace: a function of the two counts only.  A ring has at least 4 edges, so E / 4 bounds the rings; the
+// polygon arrays double as radix buffers for the rings, hence max(P, E / 4).  28 bytes per edge for the seven edge
+// arrays, 28 per ring, 28 per polygon slot and 1 KiB of histogram per 4096 slots: with P <= E / 4 about 42 bytes
+// per edge, and never more than 48 per edge + 64 per polygon + 64 KiB.
+struct TraceLayout {
+  long long E, P, r_cap, m_cap, nb_r;
+  int rounds;
+  long long poly_label, poly_cls, poly_first, rk0, rv0, rk1, rv1, ring_label, ring_nv, ring_s, ring_pos, voff, ring_area2,
+      eid, succ, ring, P0, P1, D0, D1, hist, part, total;
+};
+
+bool make_trace_layout(long long E, long long P, TraceLayout* tl) {
+  if (E < 0 || P < 0 || E >= kCountedMaxEdges || P >= kCountedMaxPixels) return false;
+  tl->E = E;
+  tl->P = P;
+  tl->r_cap = E / 4;
+  tl->m_cap = P > tl->r_cap ? P : tl->r_cap;
+  tl->nb_r = tl->m_cap > 0 ? (tl->m_cap + kChunk - 1) / kChunk : 1;
+  tl->rounds = rounds_for(E > 2 ? E : 2);
+  const long long nb_e = (E + 1 + kChunk - 1) / kChunk, nb_h = (256 * tl->nb_r + 1 + kChunk - 1) / kChunk;
+  long long o = 0;
+  auto take = [&](long long bytes) {
+    const long long at = o;
+    o += align_up(bytes);
+    return at;
+  };
+  const long long m4 = 4 * (tl->m_cap + 1), r4 = 4 * (tl->r_cap + 1), e4 = 4 * (E + 1);
+  tl->poly_label = take(m4);
+  tl->poly_cls = take(m4);
+  tl->poly_first = take(m4);
+  tl->rk0 = take(m4);
+  tl->rv0 = take(m4);
+  tl->rk1 = take(m4);
+  tl->rv1 = take(m4);
+  tl->ring_label = take(r4);
+  tl->ring_nv = take(r4);
+  tl->ring_s = take(r4);
+  tl->ring_pos = take(r4);
+  tl->voff = take(r4);
+  tl->ring_area2 = take(2 * r4);
+  tl->eid = take(e4);
+  tl->succ = take(e4);
+  tl->ring = take(e4);
+  tl->P0 = take(e4);
+  tl->P1 = take(e4);
+  tl->D0 = take(e4);
+  tl->D1 = take(e4);
+  tl->hist = take(4ll * 256 * tl->nb_r + 4);
+  tl->part = take(4 * (nb_e + nb_h + 16));
+  tl->total = o;
+  return true;
+}
+
+// the pixel arrays alone (count phase); part is the pixel workspace's
+Arrays bind_pixels(void* ws_px, const PixelLayout& pl) {
+  Arrays a = {};
+  a.N = pl.N;
+  a.L = at<int>(ws_px, pl.L);
+  a.cnt = at<int>(ws_px, pl.cnt);
+  a.off = at<int>(ws_px, pl.off);
+  a.polyidx = at<int>(ws_px, pl.polyidx);
+  // comp_list_kernel reads the ordinals of the kept roots before poly_index_kernel writes the polygon index over
+  // them; what stays at the roots of dropped components is at most P and fails zonal_flush's check like any stale
+  // value
+  a.ord = a.polyidx;
+  a.part = at<int>(ws_px, pl.part);
+  a.ctr = &at<PixelCounters>(ws_px, pl.ctr)->c;
+  return a;
+}
+
+Arrays bind_counted(void* ws_px, const PixelLayout& pl, void* ws_tr, const TraceLayout& tl) {
+  Arrays a = bind_pixels(ws_px, pl);
+  a.e_cap = tl.E;
+  a.r_cap = tl.r_cap;
+  a.m_cap = tl.m_cap;
+  a.rounds = tl.rounds;
+  a.nb_r = (int)tl.nb_r;
+  a.poly_label = at<int>(ws_tr, tl.poly_label);
+  a.poly_cls = at<int>(ws_tr, tl.poly_cls);
+  a.poly_first = at<int>(ws_tr, tl.poly_first);
+  a.rk0 = at<int>(ws_tr, tl.rk0);
+  a.rv0 = at<int>(ws_tr, tl.rv0);
+  a.rk1 = at<int>(ws_tr, tl.rk1);
+  a.rv1 = at<int>(ws_tr, tl.rv1);
+  a.ring_label = at<int>(ws_tr, tl.ring_label);
+  a.ring_nv = at<int>(ws_tr, tl.ring_nv);
+  a.ring_s = at<int>(ws_tr, tl.ring_s);
+  a.ring_pos = at<int>(ws_tr, tl.ring_pos);
+  a.voff = at<int>(ws_tr, tl.voff);
+  a.ring_area2 = at<unsigned long long>(ws_tr, tl.ring_area2);
+  a.eid = at<unsigned int>(ws_tr, tl.eid);
+  a.succ = at<int>(ws_tr, tl.succ);
+  a.ring = at<int>(ws_tr, tl.ring);
+  a.P0 = at<int>(ws_tr, tl.P0);
+  a.P1 = at<int>(ws_tr, tl.P1);
+  a.D0 = at<int>(ws_tr, tl.D0);
+  a.D1 = at<int>(ws_tr, tl.D1);
+  a.hist = at<int>(ws_tr, tl.hist);
+  a.part = at<int>(ws_tr, tl.part);
+  return a;
+}
+
 // exclusive scan of n items (n_dev on the device, else n_host, in which case out[n_host] = total as well)
-void scan(const int* in, int* out, const int* n_dev, long long n_max, int* part, int* total_dev, hipStream_t st) {
+void scan(const int* in, int* out, const int* n_dev, long long n_max, int* part, int* total_dev, long long* total64_dev,
+          hipStream_t st) {
   const int nb = (int)((n_max + 1 + kChunk - 1) / kChunk);
   const int n_host = n_dev ? 0 : (int)n_max;
   hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(kT), 0, st, in, n_dev, n_host, part);
-  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kT), 0, st, part, nb, total_dev);
+  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kT), 0, st, part, nb, total_dev, total64_dev);
   hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(kT), 0, st, in, n_dev, n_host, part, out);
 }
 
 // stable LSD radix sort of (key, value) pairs by the low `bits` key bits; result in (k0, v0)
-void radix_sort(int* k0, int* v0, int* k1, int* v1, const int* n_dev, const Layout& lo, int bits, int* hist,
-                int* part, hipStream_t st) {
-  const int nb = (int)lo.nb_r;
+void radix_sort(int* k0, int* v0, int* k1, int* v1, const int* n_dev, const Arrays& a, int bits, hipStream_t st) {
+  const int nb = a.nb_r;
   for (int shift = 0; shift < bits; shift += 8) {
-    hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(kT), 0, st, k0, n_dev, shift, nb, hist);
-    scan(hist, hist, nullptr, 256ll * nb, part, nullptr, st);
-    hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(kT), 0, st, k0, v0, n_dev, shift, nb, hist, k1, v1);
+    hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(kT), 0, st, k0, n_dev, shift, nb, a.hist);
+    scan(a.hist, a.hist, nullptr, 256ll * nb, a.part, nullptr, nullptr, st);
+    hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(kT), 0, st, k0, v0, n_dev, shift, nb, a.hist, k1, v1);
     int* t = k0; k0 = k1; k1 = t;
     t = v0; v0 = v1; v1 = t;
   }
   if ((bits + 7) / 8 % 2 == 1) {  // an odd number of passes left the result in the second buffers
-    (void)hipMemcpyAsync(k1, k0, 4 * lo.N, hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(v1, v0, 4 * lo.N, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(k1, k0, 4 * a.m_cap, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(v1, v0, 4 * a.m_cap, hipMemcpyDeviceToDevice, st);
   }
 }
 
@@ -602,6 +832,111 @@ int bits_for(long long v) {
   int b = 1;
   while ((1ll << b) <= v) ++b;
   return b;
+}
+
+int clamp_min_pixels(long long min_pixels, long long N) {
+  return (int)(min_pixels < 1 ? 1 : (min_pixels > N + 1 ? N + 1 : min_pixels));
+}
+
+// The stages come in four groups.  The bound-sized path runs them as label_stages, ring_stages, kept_root_stage,
+// order_stages (the kept roots late: edge_build_kernel finds the edge offsets, and comp_list_kernel the ordinals,
+// still in the last-level cache); the count-sized path needs both counts first: label_stages and kept_root_stage in
+// the count phase, ring_stages and order_stages in the trace phase.
+
+// Stages 1 to 3a: labels, pixel counts, per-pixel edge counts with their exclusive scan (total -> ctr->edges, and in
+// 64 bits -> *edges64 when given).
+void label_stages(const Arrays& a, const uint8_t* classes, int H, int W, int background, int minp, long long* edges64,
+                  hipStream_t st) {
+  const int N = (int)a.N, gN = (N + kT - 1) / kT;
+  (void)hipMemsetAsync(a.ctr, 0, sizeof(Counters), st);
+  (void)hipMemsetAsync(a.cnt, 0, 4ll * N, st);
+  // 1. labels, 2. counts (ffa_ccl.h)
+  ccl_label_and_count(classes, H, W, background, a.L, a.cnt, st);
+  // 3. edges: off = exclusive scan of per-pixel edge counts
+  hipLaunchKernelGGL(edge_count_kernel, dim3(gN), dim3(kT), 0, st, H, W, a.L, a.cnt, minp, a.off);
+  scan(a.off, a.off, nullptr, N, a.part, &a.ctr->edges, edges64, st);
+}
+
+// head of stage 5: ordinals of the kept roots in label order, their number -> ctr->polys
+void kept_root_stage(const Arrays& a, int minp, hipStream_t st) {
+  const int N = (int)a.N, gN = (N + kT - 1) / kT;
+  hipLaunchKernelGGL(kept_root_flag_kernel, dim3(gN), dim3(kT), 0, st, N, a.L, a.cnt, minp, a.ord);
+  scan(a.ord, a.ord, nullptr, N, a.part, &a.ctr->polys, nullptr, st);
+}
+
+// ring_info_kernel accumulates the ring areas: zeroed before ring_stages, on the same stream
+void zero_ring_areas(const Arrays& a, hipStream_t st) {
+  (void)hipMemsetAsync(a.ring_area2, 0, 8ll * (a.r_cap + 1), st);
+}
+
+// Stages 3b and 4 on e_cap >= ctr->edges edge slots: successors, ring ids, vertex ranks, per-ring facts.
+void ring_stages(const Arrays& a, int H, int W, int minp, hipStream_t st) {
+  const int N = (int)a.N, gN = (N + kT - 1) / kT, gE = grid_for(a.e_cap);
+  Counters* ctr = a.ctr;
+  hipLaunchKernelGGL(edge_build_kernel, dim3(gN), dim3(kT), 0, st, H, W, a.L, a.cnt, a.off, minp, a.eid, a.succ, a.P0,
+                     a.D0);
+  // 4a. ring id = min compact index on the cycle (P = next pointer, D = running minimum)
+  int *pa = a.P0, *pb = a.P1, *da = a.D0, *db = a.D1;
+  for (int k = 0; k < a.rounds; ++k) {
+    hipLaunchKernelGGL(jump_min_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, pa, da, pb, db);
+    int* t = pa; pa = pb; pb = t;
+    t = da; da = db; db = t;
+  }
+  (void)hipMemcpyAsync(a.ring, da, 4 * a.e_cap, hipMemcpyDeviceToDevice, st);
+  // 4b. vertex ranks: D[i] = direction changes on the ring between the ring id edge and edge i
+  hipLaunchKernelGGL(rank_init_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, a.eid, a.succ, a.ring, a.P0, a.D0);
+  pa = a.P0; pb = a.P1; da = a.D0; db = a.D1;
+  for (int k = 0; k < a.rounds; ++k) {
+    hipLaunchKernelGGL(jump_sum_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, pa, da, pb, db);
+    int* t = pa; pa = pb; pb = t;
+    t = da; da = db; db = t;
+  }
+  if (da != a.D0) (void)hipMemcpyAsync(a.D0, da, 4 * a.e_cap, hipMemcpyDeviceToDevice, st);  // final ranks live in D0
+  // ring ordinals (ring id order) in P0, R -> ctr->rings
+  hipLaunchKernelGGL(root_flag_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, a.ring, a.P1);
+  scan(a.P1, a.P0, &ctr->edges, a.e_cap, a.part, &ctr->rings, nullptr, st);
+  hipLaunchKernelGGL(ring_info_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, W, a.L, a.eid, a.succ, a.ring, a.D0,
+                     a.P0, a.ring_label, a.ring_nv, a.ring_s, a.ring_area2);
+}
+
+// Stage 5 after the kept roots: polygons and rings in output order; counts_dev[4] = polygons, rings, vertices, edges.
+void order_stages(const Arrays& a, const uint8_t* classes, int minp, long long* counts_dev, hipStream_t st) {
+  const int N = (int)a.N, gN = (N + kT - 1) / kT, gM = grid_for(a.m_cap);
+  Counters* ctr = a.ctr;
+  // polygons sorted by (class, label)
+  hipLaunchKernelGGL(comp_list_kernel, dim3(gN), dim3(kT), 0, st, N, classes, a.L, a.cnt, minp, a.ord, a.rk0, a.rv0);
+  radix_sort(a.rk0, a.rv0, a.rk1, a.rv1, &ctr->polys, a, 8, st);
+  (void)hipMemcpyAsync(a.poly_label, a.rv0, 4 * a.m_cap, hipMemcpyDeviceToDevice, st);
+  (void)hipMemcpyAsync(a.poly_cls, a.rk0, 4 * a.m_cap, hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(poly_index_kernel, dim3(gM), dim3(kT), 0, st, &ctr->polys, a.poly_label, a.polyidx);
+  // rings sorted by (polygon, hole, ring id); key bits above those of 2 * m_cap are zero in both layouts
+  hipLaunchKernelGGL(ring_keys_kernel, dim3(gM), dim3(kT), 0, st, &ctr->rings, a.ring_label, a.ring_area2, a.polyidx,
+                     a.rk0, a.rv0);
+  radix_sort(a.rk0, a.rv0, a.rk1, a.rv1, &ctr->rings, a, bits_for(2 * a.m_cap), st);
+  hipLaunchKernelGGL(ring_order_kernel, dim3(gM), dim3(kT), 0, st, &ctr->rings, a.rk0, a.rv0, a.ring_nv, a.ring_pos,
+                     a.rk1, a.poly_first);
+  scan(a.rk1, a.voff, &ctr->rings, a.r_cap, a.part, &ctr->verts, nullptr, st);
+  hipLaunchKernelGGL(counts_kernel, dim3(1), dim3(64), 0, st, ctr, counts_dev);
+}
+
+void emit_stages(const Arrays& a, int W, long long n_polys, long long n_rings, long long n_vertices,
+                 int32_t* poly_class, int64_t* poly_pixels, int32_t* poly_ring_offsets, int32_t* ring_vertex_offsets,
+                 int32_t* vertices, hipStream_t st) {
+  const int P = (int)n_polys, R = (int)n_rings;
+  // thread q < P writes polygon q, thread P writes poly_ring_offsets[P] = R
+  hipLaunchKernelGGL(emit_polys_kernel, dim3((P + 1 + kT - 1) / kT), dim3(kT), 0, st, P, R, a.poly_cls, a.cnt,
+                     a.poly_label, a.poly_first, poly_class, poly_pixels, poly_ring_offsets);
+  hipLaunchKernelGGL(emit_ring_offsets_kernel, dim3((R + 1 + kT - 1) / kT), dim3(kT), 0, st, R, (int)n_vertices, a.voff,
+                     ring_vertex_offsets);
+  if (n_vertices > 0)
+    hipLaunchKernelGGL(emit_vertices_kernel, dim3(grid_for(a.e_cap)), dim3(kT), 0, st, &a.ctr->edges, W, a.eid, a.succ,
+                       a.ring, a.D0, a.P0, a.ring_s, a.ring_pos, a.voff, vertices);
+}
+
+void zonal_stage(const Arrays& a, const uint8_t* values, long long n_polys, int64_t* sums, hipStream_t st) {
+  (void)hipMemsetAsync(sums, 0, 8 * n_polys, st);
+  hipLaunchKernelGGL(zonal_sum_kernel, dim3((unsigned int)((a.N + kChunk - 1) / kChunk)), dim3(kT), 0, st, (int)a.N,
+                     (int)n_polys, a.L, values, a.polyidx, a.poly_label, reinterpret_cast<unsigned long long*>(sums));
 }
 
 }  // namespace
@@ -625,82 +960,13 @@ extern "C" int ffa_polygonize_label(const uint8_t* classes, int H, int W, int ba
     ffa_set_error("polygonize_label: workspace %lld bytes < %lld", ws_bytes, lo.total);
     return FFA_ERR_WORKSPACE;
   }
-  const int N = (int)lo.N;
-  const int minp = (int)(min_pixels < 1 ? 1 : (min_pixels > lo.N + 1 ? lo.N + 1 : min_pixels));
-  int* L = at<int>(ws, lo.L);
-  int* cnt = at<int>(ws, lo.cnt);
-  int* off = at<int>(ws, lo.off);
-  int* eid = at<int>(ws, lo.eid);
-  int* succ = at<int>(ws, lo.succ);
-  int* ring = at<int>(ws, lo.ring);
-  int* P0 = at<int>(ws, lo.P0);
-  int* P1 = at<int>(ws, lo.P1);
-  int* D0 = at<int>(ws, lo.D0);
-  int* D1 = at<int>(ws, lo.D1);
-  int* part = at<int>(ws, lo.part);
-  int* hist = at<int>(ws, lo.hist);
-  Counters* ctr = at<Counters>(ws, lo.ctr);
-  const int gN = (N + kT - 1) / kT, gE = grid_for(lo.E);
-
-  (void)hipMemsetAsync(ctr, 0, sizeof(Counters), st);
-  (void)hipMemsetAsync(cnt, 0, 4ll * N, st);
-  (void)hipMemsetAsync(at<void>(ws, lo.ring_area2), 0, 8ll * (N + 1), st);
-  // 1. labels, 2. counts (ffa_ccl.h)
-  ccl_label_and_count(classes, H, W, background, L, cnt, st);
-  // 3. edges: off = exclusive scan of per-pixel edge counts, total -> ctr->edges
-  hipLaunchKernelGGL(edge_count_kernel, dim3(gN), dim3(kT), 0, st, H, W, L, cnt, minp, off);
-  scan(off, off, nullptr, N, part, &ctr->edges, st);
-  hipLaunchKernelGGL(edge_build_kernel, dim3(gN), dim3(kT), 0, st, H, W, L, cnt, off, minp, eid, succ, P0, D0);
-  // 4a. ring id = min compact index on the cycle (P = next pointer, D = running minimum)
-  int *pa = P0, *pb = P1, *da = D0, *db = D1;
-  for (int k = 0; k < lo.rounds; ++k) {
-    hipLaunchKernelGGL(jump_min_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, pa, da, pb, db);
-    int* t = pa; pa = pb; pb = t;
-    t = da; da = db; db = t;
-  }
-  (void)hipMemcpyAsync(ring, da, 4 * lo.E, hipMemcpyDeviceToDevice, st);
-  // 4b. vertex ranks: D[i] = direction changes on the ring between the ring id edge and edge i
-  hipLaunchKernelGGL(rank_init_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, eid, succ, ring, P0, D0);
-  pa = P0; pb = P1; da = D0; db = D1;
-  for (int k = 0; k < lo.rounds; ++k) {
-    hipLaunchKernelGGL(jump_sum_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, pa, da, pb, db);
-    int* t = pa; pa = pb; pb = t;
-    t = da; da = db; db = t;
-  }
-  if (da != D0) (void)hipMemcpyAsync(D0, da, 4 * lo.E, hipMemcpyDeviceToDevice, st);  // final ranks live in D0
-  // ring ordinals (ring id order) in P0, R -> ctr->rings
-  hipLaunchKernelGGL(root_flag_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, ring, P1);
-  scan(P1, P0, &ctr->edges, lo.E, part, &ctr->rings, st);
-  int* ring_label = at<int>(ws, lo.ring_label);
-  int* ring_nv = at<int>(ws, lo.ring_nv);
-  int* ring_s = at<int>(ws, lo.ring_s);
-  unsigned long long* area2 = at<unsigned long long>(ws, lo.ring_area2);
-  hipLaunchKernelGGL(ring_info_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, W, L, eid, succ, ring, D0, P0,
-                     ring_label, ring_nv, ring_s, area2);
-  // 5. polygons sorted by (class, label)
-  int* rk0 = at<int>(ws, lo.rk0);
-  int* rv0 = at<int>(ws, lo.rv0);
-  int* rk1 = at<int>(ws, lo.rk1);
-  int* rv1 = at<int>(ws, lo.rv1);
-  int* polyidx = at<int>(ws, lo.polyidx);
-  int* poly_label = at<int>(ws, lo.poly_label);
-  hipLaunchKernelGGL(kept_root_flag_kernel, dim3(gN), dim3(kT), 0, st, N, L, cnt, minp, rk1);
-  scan(rk1, rk1, nullptr, N, part, &ctr->polys, st);
-  hipLaunchKernelGGL(comp_list_kernel, dim3(gN), dim3(kT), 0, st, N, classes, L, cnt, minp, rk1, rk0, rv0);
-  radix_sort(rk0, rv0, rk1, rv1, &ctr->polys, lo, 8, hist, part, st);
-  (void)hipMemcpyAsync(poly_label, rv0, 4 * lo.N, hipMemcpyDeviceToDevice, st);
-  (void)hipMemcpyAsync(at<int>(ws, lo.poly_cls), rk0, 4 * lo.N, hipMemcpyDeviceToDevice, st);
-  hipLaunchKernelGGL(poly_index_kernel, dim3(grid_for(N)), dim3(kT), 0, st, &ctr->polys, poly_label, polyidx);
-  // rings sorted by (polygon, hole, ring id)
-  hipLaunchKernelGGL(ring_keys_kernel, dim3(grid_for(N)), dim3(kT), 0, st, &ctr->rings, ring_label, area2, polyidx,
-                     rk0, rv0);
-  radix_sort(rk0, rv0, rk1, rv1, &ctr->rings, lo, bits_for(2 * lo.N), hist, part, st);
-  int* ring_pos = at<int>(ws, lo.ring_pos);
-  int* voff = at<int>(ws, lo.voff);
-  hipLaunchKernelGGL(ring_order_kernel, dim3(grid_for(N)), dim3(kT), 0, st, &ctr->rings, rk0, rv0, ring_nv, ring_pos,
-                     rk1, at<int>(ws, lo.poly_first));
-  scan(rk1, voff, &ctr->rings, lo.N, part, &ctr->verts, st);
-  hipLaunchKernelGGL(counts_kernel, dim3(1), dim3(64), 0, st, ctr, counts_dev);
+  const Arrays a = bind(ws, lo);
+  const int minp = clamp_min_pixels(min_pixels, lo.N);
+  zero_ring_areas(a, st);
+  label_stages(a, classes, H, W, background, minp, nullptr, st);
+  ring_stages(a, H, W, minp, st);
+  kept_root_stage(a, minp, st);
+  order_stages(a, classes, minp, counts_dev, st);
   return ffa_check_launch("polygonize_label");
 }
 
@@ -717,20 +983,8 @@ extern "C" int ffa_polygonize_emit(const void* ws_c, long long ws_bytes, int H, 
               n_vertices);
   FFA_REQUIRE(poly_ring_offsets && ring_vertex_offsets && (n_polys == 0 || (poly_class && poly_pixels && vertices)),
               "polygonize_emit: null output pointer");
-  void* ws = const_cast<void*>(ws_c);
-  const int P = (int)n_polys, R = (int)n_rings;
-  // thread q < P writes polygon q, thread P writes poly_ring_offsets[P] = R
-  hipLaunchKernelGGL(emit_polys_kernel, dim3((P + 1 + kT - 1) / kT), dim3(kT), 0, st, P, R, at<int>(ws, lo.poly_cls),
-                     at<int>(ws, lo.cnt), at<int>(ws, lo.poly_label), at<int>(ws, lo.poly_first), poly_class,
-                     poly_pixels, poly_ring_offsets);
-  hipLaunchKernelGGL(emit_ring_offsets_kernel, dim3((R + 1 + kT - 1) / kT), dim3(kT), 0, st, R, (int)n_vertices,
-                     at<int>(ws, lo.voff), ring_vertex_offsets);
-  if (n_vertices > 0) {
-    const Counters* ctr = at<Counters>(ws, lo.ctr);
-    hipLaunchKernelGGL(emit_vertices_kernel, dim3(grid_for(lo.E)), dim3(kT), 0, st, &ctr->edges, W, at<int>(ws, lo.eid),
-                       at<int>(ws, lo.succ), at<int>(ws, lo.ring), at<int>(ws, lo.D0), at<int>(ws, lo.P0),
-                       at<int>(ws, lo.ring_s), at<int>(ws, lo.ring_pos), at<int>(ws, lo.voff), vertices);
-  }
+  emit_stages(bind(const_cast<void*>(ws_c), lo), W, n_polys, n_rings, n_vertices, poly_class, poly_pixels,
+              poly_ring_offsets, ring_vertex_offsets, vertices, st);
   return ffa_check_launch("polygonize_emit");
 }
 
@@ -745,11 +999,124 @@ extern "C" int ffa_polygonize_zonal_sum_u8(const void* ws_c, long long ws_bytes,
               "ffa_polygonize_label", n_polys);
   FFA_REQUIRE(values && (n_polys == 0 || sums), "polygonize_zonal_sum_u8: null pointer");
   if (n_polys == 0) return FFA_OK;
-  void* ws = const_cast<void*>(ws_c);
-  (void)hipMemsetAsync(sums, 0, 8 * n_polys, st);
-  const int N = (int)lo.N;
-  hipLaunchKernelGGL(zonal_sum_kernel, dim3((unsigned int)((lo.N + kChunk - 1) / kChunk)), dim3(kT), 0, st, N,
-                     (int)n_polys, at<int>(ws, lo.L), values, at<int>(ws, lo.polyidx), at<int>(ws, lo.poly_label),
-                     reinterpret_cast<unsigned long long*>(sums));
+  zonal_stage(bind(const_cast<void*>(ws_c), lo), values, n_polys, sums, st);
   return ffa_check_launch("polygonize_zonal_sum_u8");
 }
+
+// ---- the count-sized path ---------------------------------------------------------------------------------------------
+
+extern "C" long long ffa_polygonize_count_bytes(int H, int W) {
+  PixelLayout pl;
+  if (!make_pixel_layout(H, W, &pl)) {
+    ffa_set_error("polygonize_count: raster %d x %d = %lld pixels outside 1 <= H, W and H * W < 2^30", H, W,
+                  (long long)H * W);
+    return FFA_ERR_ARG;
+  }
+  return pl.total;
+}
+
+extern "C" int ffa_polygonize_count(const uint8_t* classes, int H, int W, int background, long long min_pixels,
+                                    void* ws_px, long long ws_px_bytes, long long* counts_dev, hipStream_t st) {
+  PixelLayout pl;
+  FFA_REQUIRE(make_pixel_layout(H, W, &pl), "polygonize_count: raster %d x %d = %lld pixels outside 1 <= H, W and "
+              "H * W < 2^30", H, W, (long long)H * W);
+  FFA_REQUIRE(classes && ws_px && counts_dev, "polygonize_count: null pointer");
+  FFA_REQUIRE(background >= -1 && background <= 255, "polygonize_count: background must be -1 (none) or 0..255");
+  if (ws_px_bytes < pl.total) {
+    ffa_set_error("polygonize_count: workspace %lld bytes < %lld", ws_px_bytes, pl.total);
+    return FFA_ERR_WORKSPACE;
+  }
+  PixelCounters* pc = at<PixelCounters>(ws_px, pl.ctr);
+  (void)hipMemsetAsync(pc, 0, sizeof(PixelCounters), st);
+  const Arrays a = bind_pixels(ws_px, pl);
+  const int minp = clamp_min_pixels(min_pixels, pl.N);
+  label_stages(a, classes, H, W, background, minp, &pc->edges64, st);
+  kept_root_stage(a, minp, st);
+  hipLaunchKernelGGL(pixel_counts_kernel, dim3(1), dim3(64), 0, st, pc, counts_dev);
+  return ffa_check_launch("polygonize_count");
+}
+
+extern "C" long long ffa_polygonize_trace_bytes(long long n_edges, long long n_polys) {
+  TraceLayout tl;
+  if (!make_trace_layout(n_edges, n_polys, &tl)) {
+    ffa_set_error("polygonize_trace: %lld boundary edges and %lld polygons outside 0 <= edges < 2^31 - 1 (which also "
+                  "keeps vertices < 2^31) and 0 <= polygons < 2^30", n_edges, n_polys);
+    return FFA_ERR_ARG;
+  }
+  return tl.total;
+}
+
+namespace {
+
+// the checks the three calls after the count phase share; fills both layouts
+int counted_layouts(const char* what, const void* ws_px, long long ws_px_bytes, int H, int W, const void* ws_tr,
+                    long long ws_tr_bytes, long long n_edges, long long n_polys, PixelLayout* pl, TraceLayout* tl) {
+  FFA_REQUIRE(make_pixel_layout(H, W, pl), "%s: raster %d x %d = %lld pixels outside 1 <= H, W and H * W < 2^30", what,
+              H, W, (long long)H * W);
+  FFA_REQUIRE(make_trace_layout(n_edges, n_polys, tl), "%s: %lld boundary edges and %lld polygons outside 0 <= edges "
+              "< 2^31 - 1 and 0 <= polygons < 2^30", what, n_edges, n_polys);
+  FFA_REQUIRE(n_edges >= 4 && n_polys >= 1 && 4 * n_polys <= n_edges && n_edges <= 4 * pl->N,
+              "%s: %lld edges and %lld polygons are not counts of ffa_polygonize_count on %d x %d (nothing to trace "
+              "when either is 0)", what, n_edges, n_polys, H, W);
+  FFA_REQUIRE(ws_px && ws_tr, "%s: null workspace", what);
+  if (ws_px_bytes < pl->total || ws_tr_bytes < tl->total) {
+    ffa_set_error("%s: workspaces of %lld and %lld bytes < %lld and %lld", what, ws_px_bytes, ws_tr_bytes, pl->total,
+                  tl->total);
+    return FFA_ERR_WORKSPACE;
+  }
+  return FFA_OK;
+}
+
+}  // namespace
+
+extern "C" int ffa_polygonize_trace(const uint8_t* classes, int H, int W, long long min_pixels, void* ws_px,
+                                    long long ws_px_bytes, long long n_edges, long long n_polys, void* ws_tr,
+                                    long long ws_tr_bytes, long long* counts_dev, hipStream_t st) {
+  PixelLayout pl;
+  TraceLayout tl;
+  const int rc = counted_layouts("polygonize_trace", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes, n_edges, n_polys,
+                                 &pl, &tl);
+  if (rc != FFA_OK) return rc;
+  FFA_REQUIRE(classes && counts_dev, "polygonize_trace: null pointer");
+  const Arrays a = bind_counted(ws_px, pl, ws_tr, tl);
+  const int minp = clamp_min_pixels(min_pixels, pl.N);
+  zero_ring_areas(a, st);
+  ring_stages(a, H, W, minp, st);
+  order_stages(a, classes, minp, counts_dev, st);
+  return ffa_check_launch("polygonize_trace");
+}
+
+extern "C" int ffa_polygonize_counted_emit(const void* ws_px, long long ws_px_bytes, int H, int W, const void* ws_tr,
+                                           long long ws_tr_bytes, long long n_edges, long long n_polys,
+                                           long long n_rings, long long n_vertices, int32_t* poly_class,
+                                           int64_t* poly_pixels, int32_t* poly_ring_offsets,
+                                           int32_t* ring_vertex_offsets, int32_t* vertices, hipStream_t st) {
+  PixelLayout pl;
+  TraceLayout tl;
+  const int rc = counted_layouts("polygonize_counted_emit", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes, n_edges,
+                                 n_polys, &pl, &tl);
+  if (rc != FFA_OK) return rc;
+  FFA_REQUIRE(n_rings >= n_polys && n_rings <= tl.r_cap && n_vertices >= 4 * n_rings && n_vertices <= n_edges,
+              "polygonize_counted_emit: counts (%lld, %lld, %lld) are not those of ffa_polygonize_trace", n_polys,
+              n_rings, n_vertices);
+  FFA_REQUIRE(poly_class && poly_pixels && poly_ring_offsets && ring_vertex_offsets && vertices,
+              "polygonize_counted_emit: null output pointer");
+  emit_stages(bind_counted(const_cast<void*>(ws_px), pl, const_cast<void*>(ws_tr), tl), W, n_polys, n_rings,
+              n_vertices, poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices, st);
+  return ffa_check_launch("polygonize_counted_emit");
+}
+
+extern "C" int ffa_polygonize_counted_zonal_sum_u8(const void* ws_px, long long ws_px_bytes, int H, int W,
+                                                   const void* ws_tr, long long ws_tr_bytes, long long n_edges,
+                                                   const uint8_t* values, long long n_polys, int64_t* sums,
+                                                   hipStream_t st) {
+  PixelLayout pl;
+  TraceLayout tl;
+  const int rc = counted_layouts("polygonize_counted_zonal_sum_u8", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes,
+                                 n_edges, n_polys, &pl, &tl);
+  if (rc != FFA_OK) return rc;
+  FFA_REQUIRE(values && sums, "polygonize_counted_zonal_sum_u8: null pointer");
+  zonal_stage(bind_counted(const_cast<void*>(ws_px), pl, const_cast<void*>(ws_tr), tl), values, n_polys, sums, st);
+  return ffa_check_launch("polygonize_counted_zonal_sum_u8");
+}
+

@@ -583,16 +583,28 @@ def _confidence_source(tiff_path, confidence):
 
 def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, top: float, xres: float, yres: float,
                    crs, bg: Optional[int], min_pixels: int, simplification: float, n_jobs: Optional[int],
-                   zone=None, classes=None, zone_crs=None, target_crs=None, sieve_pixels: int = 0):
-    """Shared tail of raster_to_polygons / vectorize_segmentation_parallel: on the device copy of the raster the
+                   zone=None, classes=None, zone_crs=None, target_crs=None, sieve_pixels: int = 0,
+                   workspace: str = "auto"):
+    """Shared tail of raster_to_polygons / rasters_to_polygons / vectorize_segmentation_parallel: on the device copy
+    of the raster the
     sieve (ops.sieve_, only when ``sieve_pixels`` > 1), then zone clip and class filter (one ffa_zone_clip_u8 pass,
     only when asked for), GPU polygonisation (+ zonal sums of the
     uint8 confidence plane), map coordinates, host simplification, reprojection of the kept vertices to
-    ``target_crs`` (one ffa_crs_transform_f64 pass, only when asked for), frame."""
+    ``target_crs`` (one ffa_crs_transform_f64 pass, only when asked for), frame.  ``data`` / ``conf`` are host arrays,
+    or device tensors this call may change (the mosaic of rasters_to_polygons).  ``workspace``: "bound"
+    (ops.polygonize), "counted" (ops.polygonize_counted) or "auto" = bound where 4 * H * W < 2^31, else counted."""
     from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
+    if workspace not in ("auto", "bound", "counted"):
+        raise ValueError(f"raster_to_polygons: workspace must be 'auto', 'bound' or 'counted', got {workspace!r}")
+    if workspace == "auto":
+        workspace = "bound" if 4 * int(data.shape[0]) * int(data.shape[1]) < 1 << 31 else "counted"
+    polygonize = ops.polygonize if workspace == "bound" else ops.polygonize_counted
     dev = torch.device("cuda")
-    values = None if conf is None else torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
-    cls_dev = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+    if torch.is_tensor(data):
+        cls_dev, values = data, conf
+    else:
+        values = None if conf is None else torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
+        cls_dev = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
     if sieve_pixels > 1:
         stats = ops.sieve_(cls_dev, int(sieve_pixels), background=bg)
         logger.info("sieve: %d regions (%d pixels) below %d pixels merged into a neighbour in %d rounds, %d remain",
@@ -614,8 +626,8 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
             mask = zone_mask(zone, left, top, xres, yres, data.shape[0], data.shape[1], zone_crs=zone_crs,
                              raster_crs=crs)
         ops.zone_clip_(cls_dev, mask, keep_classes=keep, fill=bg)
-    res = [t.cpu().numpy() for t in ops.polygonize(cls_dev, bg, min_pixels,
-                                                   **({} if values is None else {"values": values}))]
+    res = [t.cpu().numpy() for t in polygonize(cls_dev, bg, min_pixels,
+                                               **({} if values is None else {"values": values}))]
     pc, pix, pro, rvo, verts = res[:5]
     xy = np.empty(verts.shape, dtype=np.float64)
     xy[:, 0] = left + verts[:, 0] * xres
@@ -651,7 +663,8 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
 
 def raster_to_polygons(tiff_path, ignore_background: bool = True, background_value: int = 18, min_area: float = 1.0,
                        simplification: float = 0.1, n_jobs: Optional[int] = None, confidence=None, zone=None,
-                       classes=None, zone_crs=None, target_crs=None, sieve_area: float = 0.0):
+                       classes=None, zone_crs=None, target_crs=None, sieve_area: float = 0.0,
+                       workspace: str = "auto"):
     """Vector polygons of a class raster -- the reference's raster_to_polygons (inference.py:377-413) with its
     signature and call form ``raster_to_polygons(output_files, n_jobs=4)``.
 
@@ -706,6 +719,14 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     mean for the polygoniser: background pixels never change and are never merged into.  The confidence raster is not
     touched: a relabelled pixel contributes its own stored confidence to the polygon it joined.  The input raster is
     not modified.  0 takes the code path without the sieve, with no new call.
+
+    ``workspace``: how the polygoniser's device workspace is sized.  "bound" is ops.polygonize: 184 bytes per pixel
+    whatever the raster holds, rasters of 4 * H * W < 2^31 (about 536 Mpx) only.  "counted" is
+    ops.polygonize_counted: 16 bytes per pixel, then about 42 bytes per boundary edge once the edges are counted, one
+    host synchronisation more, rasters of H * W < 2^30 -- a 25 000 x 25 000 BD ORTHO dalle included.  Both give the
+    same polygons, byte for byte.  "auto" (the default) is "bound" wherever it can run, else "counted", so no call
+    that worked before changes.  ``sieve_area`` > 0 on a raster beyond 4 * H * W < 2^31 still raises from ops.sieve_,
+    whose limit is its own, as a ``zone`` does from the zone mask's.
     """
     src = _polygon_source(tiff_path)
     if src.count != 1:
@@ -734,7 +755,157 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
         bg = None  # no uint8 pixel can hold it: every value is a class
     return _polygon_table(data, conf, left, top, xres, yres, getattr(src, "crs", None), bg, min_pixels, simplification,
                           n_jobs, zone=zone, classes=classes, zone_crs=zone_crs, target_crs=target_crs,
-                          sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)))
+                          sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)), workspace=workspace)
+
+
+def mosaic_grid(bounds_list, res, names=None):
+    """The common pixel grid of rasters with bounds (left, bottom, right, top) and one resolution ``res`` = (xres,
+    yres): ``(H, W, left, top, [(row0, col0, h, w), ...])``, the union's size and origin and each raster's window in
+    it, in input order.  Host arithmetic only.  Every origin must differ from the first raster's by whole pixels to
+    within 1e-6 of a pixel, every extent must be a whole number of pixels, no two windows may share a pixel and the
+    union must hold fewer than 2^30 pixels; else ValueError naming the source (``names[i]``, default "source i").
+    The origin returned is the ``left`` of the first leftmost raster and the ``top`` of the first topmost one as
+    they stand, not a sum that could round: a mosaic's map coordinates are bit for bit those of one raster with that
+    origin."""
+    xres, yres = (float(v) for v in res)
+    if not (xres > 0 and yres > 0):
+        raise ValueError(f"mosaic_grid: resolution {res!r} must be positive")
+    bounds_list = [tuple(float(v) for v in b) for b in bounds_list]
+    if not bounds_list:
+        raise ValueError("mosaic_grid: no sources")
+    names = [f"source {i}" for i in range(len(bounds_list))] if names is None else [str(n) for n in names]
+    left0, _, _, top0 = bounds_list[0]
+
+    def whole(v, what, name):
+        k = round(v)
+        if abs(v - k) > 1e-6:
+            raise ValueError(f"mosaic_grid: {name}: {what} is {v!r} pixels, not a whole number (within 1e-6)")
+        return int(k)
+
+    wins = []
+    for name, (l, b, r, t) in zip(names, bounds_list):
+        c0 = whole((l - left0) / xres, "the origin's x offset from the first source", name)
+        r0 = whole((top0 - t) / yres, "the origin's y offset from the first source", name)
+        w = whole((r - l) / xres, "the width", name)
+        h = whole((t - b) / yres, "the height", name)
+        if h < 1 or w < 1:
+            raise ValueError(f"mosaic_grid: {name}: empty extent {h} x {w}")
+        wins.append((r0, c0, h, w))
+    rmin, cmin = min(w[0] for w in wins), min(w[1] for w in wins)
+    H = max(w[0] + w[2] for w in wins) - rmin
+    W = max(w[1] + w[3] for w in wins) - cmin
+    if H * W >= 1 << 30:
+        raise ValueError(f"mosaic_grid: the mosaic of {len(wins)} sources is {H} x {W} pixels, beyond the limit "
+                         f"H * W < 2^30 (its last source: {names[-1]})")
+    wins = [(r0 - rmin, c0 - cmin, h, w) for r0, c0, h, w in wins]
+    order = sorted(range(len(wins)), key=lambda i: wins[i])
+    for n, i in enumerate(order):  # sorted by first row: only windows that start before this one ends can meet it
+        r0, c0, h, w = wins[i]
+        for j in order[n + 1:]:
+            s0, d0, g, v = wins[j]
+            if s0 >= r0 + h:
+                break
+            if d0 < c0 + w and c0 < d0 + v:
+                raise ValueError(f"mosaic_grid: {names[j]} and {names[i]} share pixels (windows {wins[j]} and "
+                                 f"{wins[i]} as (row0, col0, h, w))")
+    left = next(b[0] for b, w in zip(bounds_list, wins) if w[1] == 0)
+    top = next(b[3] for b, w in zip(bounds_list, wins) if w[0] == 0)
+    return H, W, left, top, wins
+
+
+def _same_crs(a, b) -> bool:
+    if a is None or b is None:
+        return a is None and b is None
+    from flair_zonal_detection import crs as crs_table
+    ca, cb = crs_table.epsg_code(a), crs_table.epsg_code(b)
+    return ca == cb if ca is not None and cb is not None else str(a) == str(b)
+
+
+def rasters_to_polygons(sources, confidence=None, ignore_background: bool = True, background_value: int = 18,
+                        min_area: float = 1.0, simplification: float = 0.1, n_jobs: Optional[int] = None, zone=None,
+                        classes=None, zone_crs=None, target_crs=None, sieve_area: float = 0.0,
+                        workspace: str = "auto"):
+    """``raster_to_polygons`` of several rasters of one grid as ONE raster: an object lying across two dalles comes
+    out as one polygon with its whole pixel count and one confidence, where polygonising each raster on its own and
+    concatenating the frames (the driver's loop) cuts it at the seam and lets ``min_area`` drop the halves.
+
+    ``sources``: a sequence of anything raster_to_polygons accepts (outputs dicts, paths, raster objects), in any
+    order.  ``confidence``: None, True (each outputs dict's own confidence entry) or a sequence of confidence rasters
+    of the same length.  The other keywords mean what they mean for raster_to_polygons.  All sources must be one-band
+    uint8 rasters of one resolution and CRS whose origins differ by whole pixels (within 1e-6 of a pixel), and no two
+    may share a pixel; the mosaic must hold fewer than 2^30 pixels: each violation is a ValueError naming the source.
+    Pixels of the union's bounding box that no source covers take ``background_value``, which needs
+    ``ignore_background=True`` (ValueError otherwise), and confidence 0, which no polygon sees.
+
+    The mosaic is assembled on the device -- a uint8 plane filled with the background, each source uploaded once and
+    copied into its window -- and goes through raster_to_polygons' own tail with the mosaic's origin: the result
+    equals raster_to_polygons of a single raster holding the same pixels."""
+    sources = list(sources)
+    if not sources:
+        raise ValueError("rasters_to_polygons: no sources")
+    if confidence is None or confidence is False:
+        conf_args = [None] * len(sources)
+    elif confidence is True:
+        conf_args = [True] * len(sources)
+    else:
+        conf_args = list(confidence)
+        if len(conf_args) != len(sources):
+            raise ValueError(f"rasters_to_polygons: {len(conf_args)} confidence rasters for {len(sources)} sources")
+        missing = [i for i, c in enumerate(conf_args) if c is None]
+        if missing and len(missing) != len(conf_args):
+            raise ValueError(f"rasters_to_polygons: source {missing[0]} has no confidence raster, others have one")
+    rasters, names = [], []
+    for i, s in enumerate(sources):
+        src = _polygon_source(s)
+        name = f"source {i} ({getattr(src, 'path', None) or getattr(src, 'name', None) or type(src).__name__})"
+        if src.count != 1:
+            raise ValueError(f"rasters_to_polygons: {name}: a one-band class raster expected, got {src.count} bands")
+        if rasters and tuple(float(v) for v in src.res) != tuple(float(v) for v in rasters[0].res):
+            raise ValueError(f"rasters_to_polygons: {name}: resolution {tuple(src.res)} differs from the first "
+                             f"source's {tuple(rasters[0].res)}")
+        if rasters and not _same_crs(getattr(src, "crs", None), getattr(rasters[0], "crs", None)):
+            raise ValueError(f"rasters_to_polygons: {name}: CRS {getattr(src, 'crs', None)!r} differs from the first "
+                             f"source's {getattr(rasters[0], 'crs', None)!r}")
+        rasters.append(src)
+        names.append(name)
+    xres, yres = (float(v) for v in rasters[0].res)
+    H, W, left, top, wins = mosaic_grid([_bounds4(r) for r in rasters], (xres, yres), names)
+    bg = int(background_value) if ignore_background else None
+    if bg is not None and not 0 <= bg <= 255:
+        bg = None
+    covered = sum(h * w for _, _, h, w in wins)
+    if covered != H * W and bg is None:
+        raise ValueError(f"rasters_to_polygons: the {len(rasters)} sources leave {H * W - covered} pixels of their "
+                         f"{H} x {W} bounding box uncovered (first gap next to {names[0]}); filling a gap needs "
+                         "ignore_background=True and a uint8 background_value")
+    dev = torch.device("cuda")
+    plane = torch.full((H, W), bg if bg is not None else 0, dtype=torch.uint8, device=dev)
+    cplane = torch.zeros((H, W), dtype=torch.uint8, device=dev) if conf_args[0] is not None else None
+    for s, src, name, carg, (r0, c0, h, w) in zip(sources, rasters, names, conf_args, wins):
+        data = np.asarray(src.read(1))
+        if data.dtype != np.uint8:
+            raise ValueError(f"rasters_to_polygons: {name}: uint8 class raster expected, got {data.dtype}")
+        if data.shape != (h, w):
+            raise ValueError(f"rasters_to_polygons: {name}: {data.shape} pixels, but its bounds and resolution give "
+                             f"{(h, w)}")
+        plane[r0:r0 + h, c0:c0 + w] = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+        if cplane is None:
+            continue
+        if carg is None:
+            raise ValueError(f"rasters_to_polygons: {name}: no confidence raster, the other sources have one")
+        csrc = _confidence_source(s, carg)
+        conf = np.asarray(csrc.read(1)) if csrc.count == 1 else None
+        if conf is None or conf.dtype != np.uint8 or conf.shape != data.shape:
+            raise ValueError(f"rasters_to_polygons: {name}: the confidence raster must be one uint8 band of shape "
+                             f"{data.shape}")
+        if tuple(float(v) for v in csrc.res) != (xres, yres) or _bounds4(csrc) != _bounds4(src):
+            raise ValueError(f"rasters_to_polygons: {name}: the confidence raster's bounds / resolution differ from "
+                             "the class raster's")
+        cplane[r0:r0 + h, c0:c0 + w] = torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
+    min_pixels = min_pixels_for_area(float(min_area), abs(xres * yres))
+    return _polygon_table(plane, cplane, left, top, xres, yres, getattr(rasters[0], "crs", None), bg, min_pixels,
+                          simplification, n_jobs, zone=zone, classes=classes, zone_crs=zone_crs, target_crs=target_crs,
+                          sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)), workspace=workspace)
 
 
 def logits_to_labels_and_confidence(probs):

@@ -181,6 +181,12 @@ SIGNATURES = {
     "ffa_polygonize_label": (_i, [_p, _i, _i, _i, _ll, _p, _ll, _p, _p]),
     "ffa_polygonize_emit": (_i, [_p, _ll, _i, _i, _ll, _ll, _ll, _p, _p, _p, _p, _p, _p]),
     "ffa_polygonize_zonal_sum_u8": (_i, [_p, _ll, _i, _i, _p, _ll, _p, _p]),
+    "ffa_polygonize_count_bytes": (_ll, [_i, _i]),
+    "ffa_polygonize_count": (_i, [_p, _i, _i, _i, _ll, _p, _ll, _p, _p]),
+    "ffa_polygonize_trace_bytes": (_ll, [_ll, _ll]),
+    "ffa_polygonize_trace": (_i, [_p, _i, _i, _ll, _p, _ll, _ll, _ll, _p, _ll, _p, _p]),
+    "ffa_polygonize_counted_emit": (_i, [_p, _ll, _i, _i, _p, _ll, _ll, _ll, _ll, _ll, _p, _p, _p, _p, _p, _p]),
+    "ffa_polygonize_counted_zonal_sum_u8": (_i, [_p, _ll, _i, _i, _p, _ll, _ll, _p, _ll, _p, _p]),
     "ffa_sieve_workspace_bytes": (_ll, [_i, _i]),
     "ffa_sieve_round_u8": (_i, [_p, _i, _i, _i, _ll, _p, _ll, _p, _p]),
     "ffa_polygon_simplify": (_i, [_p, _p, _p, _ll, _d, _i, _p]),

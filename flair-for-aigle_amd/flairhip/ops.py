@@ -1159,6 +1159,85 @@ def polygonize(classes: torch.Tensor, background: Optional[int] = None, min_pixe
     return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices, sums
 
 
+def _polygonize_size(nbytes: int) -> int:
+    """a size function's answer, its FFA_ERR_ARG (a limit of the count-sized path) as ValueError"""
+    if nbytes < 0:
+        raise ValueError(_l.load().ffa_last_error().decode("utf-8", "replace"))
+    return int(nbytes)
+
+
+def polygonize_counted(classes: torch.Tensor, background: Optional[int] = None, min_pixels: int = 1,
+                       values: Optional[torch.Tensor] = None):
+    """``polygonize`` with workspaces sized by what the raster holds: same arguments, same returns, byte for byte.
+
+    A count phase (labels, pixel counts, boundary edges E and polygons P; at most 16 bytes per pixel) is followed by
+    one more host synchronisation, the read of E and P, and a trace phase whose workspace depends on E and P alone
+    (about 42 bytes per edge).  Limits: H * W < 2^30 and E < 2^31 - 1, each a ValueError that names the numbers, raised
+    before anything sized by E is allocated; a trace workspace beyond the device's free memory is a ValueError as
+    well.  With E == 0 or P == 0 no trace is launched and the empty tensors are returned."""
+    lib = _l.load()
+    if not (classes.is_cuda and classes.dtype == torch.uint8 and classes.dim() == 2):
+        raise ValueError("polygonize_counted: a CUDA uint8 [H, W] class map expected")
+    if background is not None and not 0 <= int(background) <= 255:
+        raise ValueError(f"polygonize_counted: background {background} is not a uint8 value")
+    H, W = classes.shape
+    if values is not None:
+        if not (values.is_cuda and values.dtype == torch.uint8 and tuple(values.shape) == (H, W)
+                and values.device == classes.device):
+            raise ValueError(f"polygonize_counted: values must be a CUDA uint8 [{H}, {W}] tensor on the device of "
+                             "classes")
+        values = values.contiguous()
+    if H * W >= 1 << 30:
+        raise ValueError(f"polygonize_counted: a {H} x {W} raster exceeds the limit H * W < 2^30 (about 1074 Mpx per "
+                         "call)")
+    px_bytes = _polygonize_size(lib.ffa_polygonize_count_bytes(H, W))
+    classes = classes.contiguous()
+    dev = classes.device
+    minp = int(max(min_pixels, 0))
+    ws_px = torch.empty(px_bytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    st = _stream()
+    _l.check(lib.ffa_polygonize_count(classes.data_ptr(), H, W, -1 if background is None else int(background), minp,
+                                      ws_px.data_ptr(), px_bytes, counts.data_ptr(), st), "polygonize_count")
+    E, P = (int(v) for v in counts[:2].cpu().tolist())
+    if E == 0 or P == 0:
+        empty = (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                 torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
+                 torch.empty((0, 2), dtype=torch.int32, device=dev))
+        return empty if values is None else empty + (torch.empty(0, dtype=torch.int64, device=dev),)
+    if E >= (1 << 31) - 1:
+        raise ValueError(f"polygonize_counted: the {H} x {W} raster has {E} boundary edges, beyond the limit "
+                         "E < 2^31 - 1")
+    tr_bytes = _polygonize_size(lib.ffa_polygonize_trace_bytes(E, P))
+    free = torch.cuda.mem_get_info(dev)[0]
+    if tr_bytes > free:
+        raise ValueError(f"polygonize_counted: the trace workspace for {E} boundary edges and {P} polygons takes "
+                         f"{tr_bytes} bytes, the device has {free} free")
+    ws_tr = torch.empty(tr_bytes, dtype=torch.uint8, device=dev)
+    _l.check(lib.ffa_polygonize_trace(classes.data_ptr(), H, W, minp, ws_px.data_ptr(), px_bytes, E, P,
+                                      ws_tr.data_ptr(), tr_bytes, counts.data_ptr(), st), "polygonize_trace")
+    P2, R, V, E2 = (int(v) for v in counts.cpu().tolist())
+    if (P2, E2) != (P, E):
+        raise _l.FlairHipError(f"polygonize_counted: the trace phase counted ({P2}, {E2}) polygons and edges, the "
+                               f"count phase ({P}, {E})")
+    poly_class = torch.empty(P, dtype=torch.int32, device=dev)
+    poly_pixels = torch.empty(P, dtype=torch.int64, device=dev)
+    poly_ring_offsets = torch.empty(P + 1, dtype=torch.int32, device=dev)
+    ring_vertex_offsets = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    vertices = torch.empty((V, 2), dtype=torch.int32, device=dev)
+    _l.check(lib.ffa_polygonize_counted_emit(ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(), tr_bytes, E, P, R, V,
+                                             poly_class.data_ptr(), poly_pixels.data_ptr(),
+                                             poly_ring_offsets.data_ptr(), ring_vertex_offsets.data_ptr(),
+                                             vertices.data_ptr(), st), "polygonize_counted_emit")
+    if values is None:
+        return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices
+    sums = torch.empty(P, dtype=torch.int64, device=dev)
+    _l.check(lib.ffa_polygonize_counted_zonal_sum_u8(ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(), tr_bytes, E,
+                                                     values.data_ptr(), P, sums.data_ptr(), st),
+             "polygonize_counted_zonal_sum_u8")
+    return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices, sums
+
+
 def polygon_simplify(xy, ring_vertex_offsets, poly_ring_offsets, tolerance: float, n_threads: int = 1):
     """Host: keep mask (numpy bool [V]) of topology-preserving Douglas-Peucker over float64 coordinates xy [V, 2] in
     the flat polygon layout of ``polygonize`` (csrc/polygon_simplify.cpp)."""

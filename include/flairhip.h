@@ -567,6 +567,44 @@ int ffa_polygonize_emit(const void* ws, long long ws_bytes, int H, int W, long l
  * n_polys = counts_dev[0]; with n_polys == 0 nothing is written. */
 int ffa_polygonize_zonal_sum_u8(const void* ws, long long ws_bytes, int H, int W, const uint8_t* values,
                                 long long n_polys, int64_t* sums, ffa_stream_t stream);
+/* The count-sized path: the same polygons from workspaces sized by what the raster holds, for rasters beyond
+ * 4 * H * W < 2^31 and for the many below it where a workspace of 184 bytes per pixel is mostly never touched.
+ * Normative: for every input both paths accept, poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets,
+ * vertices and the zonal sums are byte-identical to those of ffa_polygonize_label / _emit / _zonal_sum_u8 (same
+ * order, ring starts and winding; everything said above holds).  Four steps, one host synchronisation more:
+ *   1. ffa_polygonize_count labels the raster and counts: counts_dev[2] (int64, device) = boundary edges E (a side of
+ *      a pixel of a kept component whose other side is outside the raster or in another component; accumulated in
+ *      64 bits, so a value of 2^31 or more is reported, never wrapped) and polygons P.  Its pixel workspace ws_px
+ *      holds labels, pixel counts, edge offsets and the polygon index: ffa_polygonize_count_bytes(H, W) <=
+ *      16 * H * W + 2 MiB.  Host only: no device memory is touched by either size function.
+ *   2. the caller reads E and P.  E == 0 or P == 0: there are no polygons and nothing more to call.  Else
+ *      ffa_polygonize_trace_bytes(E, P) is the size of the trace workspace ws_tr, a function of E and P only:
+ *      seven int32 arrays of E + 1, the ring arrays by the ring bound E / 4 (a ring has at least 4 edges), the polygon
+ *      arrays and radix buffers by max(P, E / 4); about 42 bytes per edge, at most 48 * E + 64 * P + 64 KiB.
+ *   3. ffa_polygonize_trace(the classes, H, W and min_pixels of step 1, ws_px untouched since, E, P, ws_tr) traces
+ *      the rings in ceil(log2 max(E, 2)) pointer-jumping rounds and writes counts_dev[4] like ffa_polygonize_label:
+ *      P, R, V, E.  E and P must be the values step 1 wrote: they size what the kernels index.
+ *   4. ffa_polygonize_counted_emit and, optionally, ffa_polygonize_counted_zonal_sum_u8 on the pair of workspaces,
+ *      with the outputs and the rules of ffa_polygonize_emit / ffa_polygonize_zonal_sum_u8.
+ * Limits: H * W < 2^30 (FFA_ERR_ARG from ffa_polygonize_count_bytes and ffa_polygonize_count); E < 2^31 - 1, which
+ * also keeps V <= E below 2^31 (FFA_ERR_ARG from ffa_polygonize_trace_bytes and every later call, with the numbers
+ * in ffa_last_error, before anything sized by E exists).  Edge ids 4 * pixel + side are unsigned 32-bit throughout;
+ * labels, compact edge indices, ring and vertex numbers are below 2^31.  All calls on one stream. */
+long long ffa_polygonize_count_bytes(int H, int W); /* < 0 (FFA_ERR_ARG) beyond the limit */
+int ffa_polygonize_count(const uint8_t* classes, int H, int W, int background, long long min_pixels, void* ws_px,
+                         long long ws_px_bytes, long long* counts_dev, ffa_stream_t stream);
+long long ffa_polygonize_trace_bytes(long long n_edges, long long n_polys); /* < 0 (FFA_ERR_ARG) beyond the limits */
+int ffa_polygonize_trace(const uint8_t* classes, int H, int W, long long min_pixels, void* ws_px,
+                         long long ws_px_bytes, long long n_edges, long long n_polys, void* ws_tr,
+                         long long ws_tr_bytes, long long* counts_dev, ffa_stream_t stream);
+int ffa_polygonize_counted_emit(const void* ws_px, long long ws_px_bytes, int H, int W, const void* ws_tr,
+                                long long ws_tr_bytes, long long n_edges, long long n_polys, long long n_rings,
+                                long long n_vertices, int32_t* poly_class, int64_t* poly_pixels,
+                                int32_t* poly_ring_offsets, int32_t* ring_vertex_offsets, int32_t* vertices,
+                                ffa_stream_t stream);
+int ffa_polygonize_counted_zonal_sum_u8(const void* ws_px, long long ws_px_bytes, int H, int W, const void* ws_tr,
+                                        long long ws_tr_bytes, long long n_edges, const uint8_t* values,
+                                        long long n_polys, int64_t* sums, ffa_stream_t stream);
 /* Host only: topology-preserving Douglas-Peucker (shapely / JTS TopologyPreservingSimplifier semantics within each
  * polygon; csrc/polygon_simplify.cpp) over float64 map coordinates xy[V][2] laid out as above; keep[V] receives 1 for
  * the vertices that stay.  tolerance 0 keeps all; n_threads (1 .. 16) splits the polygons between host threads. */

@@ -31,6 +31,10 @@ counts and the root pass, no vote and no apply; "label_only_after_ms": on the si
 traffic (class map 1 B, labels 4 B written and three reads per pixel, best + new_class 9 B per component) and the
 rate the first round reaches on it, then polygons, rings, vertices and the host stages (objects, GeoPackage) of the
 map before and after.
+With --workspace counted (or both) the count-sized path is timed: one JSON line with "count_ms", "trace_ms", their
+per-repetition sum "label_ms" (the figure to hold against the bound-sized "label_ms"; "label_ms_all" lists every
+repetition, for the spread), "emit_ms", both workspaces' sizes and the edges per pixel.  Device stages only;
+`--sizes 25000 --maps voronoi --workspace counted` is a full 5 km BD ORTHO dalle, which the bound-sized path refuses.
 Per-kernel times (count_kernel, the labelling kernels and zonal_sum_kernel of the same run side by side): run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_polygonize.py --confidence --device-only`.
 """
@@ -80,7 +84,8 @@ def checker(n: int) -> np.ndarray:
     return (np.add.outer(np.arange(n), np.arange(n)) % 2).astype(np.uint8)
 
 
-def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_only: bool = False) -> dict:
+def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_only: bool = False,
+        outputs: list = None) -> dict:
     import torch
     from flairhip import lib as L
     from flairhip import ops
@@ -129,8 +134,11 @@ def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_
             t_emit.append(e1b.elapsed_time(e2))
             t_d2h.append((t1 - t0) * 1e3)
     pc, pp, pro, rvo, verts = out
-    res.update({"polygons": P, "rings": R, "vertices": V, "edges": E,
-                "label_ms": round(min(t_label), 3), "emit_ms": round(min(t_emit), 3), "d2h_ms": round(min(t_d2h), 3)})
+    if outputs is not None:
+        outputs[:] = out
+    res.update({"polygons": P, "rings": R, "vertices": V, "edges": E, "label_ms": round(min(t_label), 3),
+                "label_ms_all": [round(t, 3) for t in t_label], "emit_ms": round(min(t_emit), 3),
+                "d2h_ms": round(min(t_d2h), 3)})
     # bytes the label phase cannot avoid: class map (1 B) + labels written, read by counts / edges (3 x 4 B) per pixel,
     # then the compacted edge arrays (eid, succ written; ~log2(E) pointer-jumping rounds read 2 x 4 B and write 2 x 4 B)
     rounds = max(1, int(np.ceil(np.log2(max(4 * H * W, 2)))))
@@ -161,6 +169,74 @@ def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_
     res.update({"coords_ms": round((t1 - t0) * 1e3, 1), "simplify_ms": round((t2 - t1) * 1e3, 1),
                 "objects_ms": round((t3 - t2) * 1e3, 1), "gpkg_ms": round((t4 - t3) * 1e3, 1),
                 "vertices_after_simplify": int(keep.sum())})
+    return res
+
+
+def run_counted(name: str, cls: np.ndarray, reps: int, confidence: bool = False, compare=None) -> dict:
+    """The count-sized path (ffa_polygonize_count / _trace / _counted_emit), device stages only: hip events around
+    each phase after a warm-up call, best of ``reps``; "label_ms" = count + trace is what ``run`` calls label_ms.
+    The trace workspace is allocated inside the loop as ops.polygonize_counted does (the caching allocator serves
+    it from the second call on).  ``compare``: the five arrays of ``run`` on the same map, checked for equal bytes."""
+    import torch
+    from flairhip import lib as L
+    lib = L.load()
+    H, W = cls.shape
+    dev = torch.device("cuda")
+    x = torch.from_numpy(cls).to(dev)
+    px_bytes = int(lib.ffa_polygonize_count_bytes(H, W))
+    ws_px = torch.empty(px_bytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    values = torch.randint(0, 256, (H, W), dtype=torch.uint8, device=dev) if confidence else None
+    t_count, t_trace, t_emit, t_zonal = [], [], [], []
+    for rep in range(reps + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(7)]
+        ev[0].record()
+        L.check(lib.ffa_polygonize_count(x.data_ptr(), H, W, 18, 1, ws_px.data_ptr(), px_bytes, counts.data_ptr(), st))
+        ev[1].record()
+        E, P = (int(v) for v in counts[:2].cpu().tolist())
+        tr_bytes = int(lib.ffa_polygonize_trace_bytes(E, P))
+        if tr_bytes < 0:
+            raise SystemExit(lib.ffa_last_error().decode())
+        ws_tr = torch.empty(tr_bytes, dtype=torch.uint8, device=dev)
+        ev[2].record()
+        L.check(lib.ffa_polygonize_trace(x.data_ptr(), H, W, 1, ws_px.data_ptr(), px_bytes, E, P, ws_tr.data_ptr(),
+                                         tr_bytes, counts.data_ptr(), st))
+        ev[3].record()
+        P, R, V, E = (int(v) for v in counts.cpu().tolist())
+        bufs = [torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int64, device=dev),
+                torch.empty(P + 1, dtype=torch.int32, device=dev), torch.empty(R + 1, dtype=torch.int32, device=dev),
+                torch.empty((V, 2), dtype=torch.int32, device=dev)]
+        ev[4].record()
+        L.check(lib.ffa_polygonize_counted_emit(ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(), tr_bytes, E, P, R,
+                                                V, *(b.data_ptr() for b in bufs), st))
+        ev[5].record()
+        if confidence:
+            sums = torch.empty(P, dtype=torch.int64, device=dev)
+            L.check(lib.ffa_polygonize_counted_zonal_sum_u8(ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(),
+                                                            tr_bytes, E, values.data_ptr(), P, sums.data_ptr(), st))
+            ev[6].record()
+        torch.cuda.synchronize()
+        if rep:
+            t_count.append(ev[0].elapsed_time(ev[1]))
+            t_trace.append(ev[2].elapsed_time(ev[3]))
+            t_emit.append(ev[4].elapsed_time(ev[5]))
+            if confidence:
+                t_zonal.append(ev[5].elapsed_time(ev[6]))
+        if rep < reps:
+            del ws_tr, bufs
+    res = {"map": name, "workspace": "counted", "H": H, "W": W, "pixel_workspace_GB": round(px_bytes / 1e9, 3),
+           "trace_workspace_GB": round(tr_bytes / 1e9, 3), "workspace_GB": round((px_bytes + tr_bytes) / 1e9, 3),
+           "polygons": P, "rings": R, "vertices": V, "edges": E, "edges_per_pixel": round(E / (H * W), 4),
+           "count_ms": round(min(t_count), 3), "trace_ms": round(min(t_trace), 3),
+           "label_ms": round(min(a + b for a, b in zip(t_count, t_trace)), 3),
+           "label_ms_all": [round(a + b, 3) for a, b in zip(t_count, t_trace)], "emit_ms": round(min(t_emit), 3),
+           "jump_rounds": max(1, int(np.ceil(np.log2(max(E, 2)))))}
+    if confidence:
+        assert int(sums.sum()) == int(values[x != 18].sum(dtype=torch.int64))
+        res["zonal_sum_ms"] = round(min(t_zonal), 3)
+    if compare is not None:
+        res["bytes_equal_to_bound_path"] = all(a.tobytes() == b.cpu().numpy().tobytes() for a, b in zip(compare, bufs))
     return res
 
 
@@ -352,6 +428,10 @@ def main() -> None:
     ap.add_argument("--target-crs", type=str, default=None, metavar="EPSG:NNNN",
                     help="time the reprojection of --vertices Lambert-93 vertices to this CRS instead of the maps")
     ap.add_argument("--vertices", type=int, nargs="+", default=[4_000_000, 43_000_000])
+    ap.add_argument("--workspace", choices=["bound", "counted", "both"], default="bound",
+                    help="bound: ffa_polygonize_label, sizes up to 23170; counted: ffa_polygonize_count / _trace, device "
+                         "stages only, sizes up to 32767 (--sizes 25000 is one BD ORTHO dalle); both: one line each, "
+                         "and the outputs compared byte for byte")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -368,14 +448,22 @@ def main() -> None:
         for n in args.sizes:
             print(json.dumps(run_zone(voronoi(n), args.reps, args.device_only)), flush=True)
         return
+    def both(name, cls):
+        old = []
+        if args.workspace in ("bound", "both"):
+            res = run(name, cls, args.reps, args.confidence, args.device_only, old)
+            print(json.dumps(dict(res, workspace="bound")), flush=True)
+        if args.workspace in ("counted", "both"):
+            print(json.dumps(run_counted(name, cls, args.reps, args.confidence, old or None)), flush=True)
+
     if "voronoi" in args.maps:
         for n in args.sizes:
-            print(json.dumps(run("voronoi", voronoi(n), args.reps, args.confidence, args.device_only)), flush=True)
+            both("voronoi", voronoi(n))
     if "uniform" in args.maps:
         for n in args.sizes:
-            print(json.dumps(run("uniform", np.full((n, n), 3, np.uint8), args.reps, args.confidence, args.device_only)), flush=True)
+            both("uniform", np.full((n, n), 3, np.uint8))
     if "checker" in args.maps:
-        print(json.dumps(run("checker", checker(args.checker_size), args.reps, args.confidence, args.device_only)), flush=True)
+        both("checker", checker(args.checker_size))
 
 
 if __name__ == "__main__":
