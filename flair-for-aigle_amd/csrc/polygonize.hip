@@ -27,6 +27,7 @@
 //   6. emit        (second ABI call) writes the flat output arrays.
 #include "ffa_common.h"
 #include "ffa_ccl.h"
+#include "ffa_workspace.h"
 
 namespace {
 
@@ -557,17 +558,8 @@ struct Arrays {
   int *succ, *ring, *P0, *P1, *D0, *D1;
   int *hist, *part;
   Counters* ctr;
+  PixelCounters* pc;  // count-sized path: where the counters live (ctr = &pc->c), else null
 };
-
-struct Layout {
-  long long N, E, nb_n, nb_e, nb_r;  // pixels, edge bound, scan / radix block counts
-  int rounds;
-  // offsets in bytes
-  long long L, cnt, off, polyidx, poly_label, poly_cls, poly_first, rk0, rv0, rk1, rv1, ring_label, ring_nv, ring_s, ring_pos,
-      voff, ring_area2, eid, succ, ring, P0, P1, D0, D1, hist, part, ctr, total;
-};
-
-long long align_up(long long v) { return (v + 255) & ~255ll; }
 
 int rounds_for(long long edges) {
   int rounds = 0;
@@ -575,231 +567,82 @@ int rounds_for(long long edges) {
   return rounds;
 }
 
-bool make_layout(int H, int W, Layout* lo) {
-  if (H < 1 || W < 1) return false;
+long long chunks(long long n) { return (n + kChunk - 1) / kChunk; }  // blocks of a scan over n items
+long long radix_blocks(long long m_cap) { return m_cap > 0 ? chunks(m_cap) : 1; }
+
+// Both layouts are carved by the same two routines (ffa_workspace.h: with a null base the walk only sizes), so an
+// array is listed once.  The per-pixel arrays: four int32 arrays of N + 1.
+void carve_pixels(ffa_carver& c, long long N, Arrays* a) {
+  a->N = N;
+  for (int** p : {&a->L, &a->cnt, &a->off, &a->polyidx}) c.take(*p, N + 1);
+}
+
+// The edge, ring and polygon arrays for e_cap edges, r_cap rings and m_cap polygon slots (the polygon arrays double
+// as radix buffers for the rings), 1 KiB of radix histogram per block of m_cap and part_ints scan partials, whose
+// number is the caller's: the layouts differ in it.
+void carve_trace(ffa_carver& c, long long e_cap, long long r_cap, long long m_cap, long long part_ints, Arrays* a) {
+  a->e_cap = e_cap;
+  a->r_cap = r_cap;
+  a->m_cap = m_cap;
+  a->rounds = rounds_for(e_cap > 2 ? e_cap : 2);
+  a->nb_r = (int)radix_blocks(m_cap);
+  for (int** p : {&a->poly_label, &a->poly_cls, &a->poly_first, &a->rk0, &a->rv0, &a->rk1, &a->rv1})
+    c.take(*p, m_cap + 1);
+  for (int** p : {&a->ring_label, &a->ring_nv, &a->ring_s, &a->ring_pos, &a->voff}) c.take(*p, r_cap + 1);
+  c.take(a->ring_area2, r_cap + 1);
+  c.take(a->eid, e_cap + 1);
+  for (int** p : {&a->succ, &a->ring, &a->P0, &a->P1, &a->D0, &a->D1}) c.take(*p, e_cap + 1);
+  c.take(a->hist, 256ll * a->nb_r + 1);
+  c.take(a->part, part_ints);
+}
+
+// Each layout below binds its arrays in ws (null: none) and returns the bytes they take, < 0 beyond its limit.
+
+// Bound-sized: both groups in one buffer, 4 edges, a ring and a polygon per pixel; 4 * H * W < 2^31.
+long long carve_bound(void* ws, int H, int W, Arrays* a) {
   const long long N = (long long)H * W;
-  if (4 * N >= (1ll << 31)) return false;
-  lo->N = N;
-  lo->E = 4 * N;
-  lo->nb_n = (N + 1 + kChunk - 1) / kChunk;
-  lo->nb_e = (lo->E + 1 + kChunk - 1) / kChunk;
-  lo->nb_r = (N + kChunk - 1) / kChunk;  // radix passes run over <= N items (components, rings)
-  lo->rounds = rounds_for(lo->E);
-  long long o = 0;
-  auto take = [&](long long bytes) {
-    const long long at = o;
-    o += align_up(bytes);
-    return at;
-  };
-  const long long n4 = 4 * (N + 1), e4 = 4 * (lo->E + 1);
-  lo->L = take(n4);
-  lo->cnt = take(n4);
-  lo->off = take(n4);
-  lo->polyidx = take(n4);
-  lo->poly_label = take(n4);
-  lo->poly_cls = take(n4);
-  lo->poly_first = take(n4);
-  lo->rk0 = take(n4);
-  lo->rv0 = take(n4);
-  lo->rk1 = take(n4);
-  lo->rv1 = take(n4);
-  lo->ring_label = take(n4);
-  lo->ring_nv = take(n4);
-  lo->ring_s = take(n4);
-  lo->ring_pos = take(n4);
-  lo->voff = take(n4);
-  lo->ring_area2 = take(8 * (N + 1));
-  lo->eid = take(e4);
-  lo->succ = take(e4);
-  lo->ring = take(e4);
-  lo->P0 = take(e4);
-  lo->P1 = take(e4);
-  lo->D0 = take(e4);
-  lo->D1 = take(e4);
-  lo->hist = take(4ll * 256 * lo->nb_r + 4);
-  lo->part = take(4ll * (lo->nb_e + lo->nb_n + 256 * lo->nb_r / kChunk + 16));
-  lo->ctr = take(sizeof(Counters));
-  lo->total = o;
-  return true;
+  if (H < 1 || W < 1 || 4 * N >= (1ll << 31)) return -1;
+  *a = {};
+  ffa_carver c{ws};
+  carve_pixels(c, N, a);
+  carve_trace(c, 4 * N, N, N, chunks(4 * N + 1) + chunks(N + 1) + 256 * radix_blocks(N) / kChunk + 16, a);
+  a->ord = a->rk1;  // free until the first radix sort, which runs after its only reader (comp_list_kernel)
+  c.take(a->ctr, 1);
+  return c.off;
 }
 
-template <typename T>
-T* at(void* ws, long long off) {
-  return reinterpret_cast<T*>(static_cast<char*>(ws) + off);
-}
-
-Arrays bind(void* ws, const Layout& lo) {
-  Arrays a;
-  a.N = lo.N;
-  a.e_cap = lo.E;
-  a.r_cap = lo.N;
-  a.m_cap = lo.N;
-  a.rounds = lo.rounds;
-  a.nb_r = (int)lo.nb_r;
-  a.L = at<int>(ws, lo.L);
-  a.cnt = at<int>(ws, lo.cnt);
-  a.off = at<int>(ws, lo.off);
-  a.polyidx = at<int>(ws, lo.polyidx);
-  a.poly_label = at<int>(ws, lo.poly_label);
-  a.poly_cls = at<int>(ws, lo.poly_cls);
-  a.poly_first = at<int>(ws, lo.poly_first);
-  a.rk0 = at<int>(ws, lo.rk0);
-  a.rv0 = at<int>(ws, lo.rv0);
-  a.rk1 = at<int>(ws, lo.rk1);
-  a.rv1 = at<int>(ws, lo.rv1);
-  a.ord = a.rk1;  // free until the first radix sort, which runs after its only reader (comp_list_kernel)
-  a.ring_label = at<int>(ws, lo.ring_label);
-  a.ring_nv = at<int>(ws, lo.ring_nv);
-  a.ring_s = at<int>(ws, lo.ring_s);
-  a.ring_pos = at<int>(ws, lo.ring_pos);
-  a.voff = at<int>(ws, lo.voff);
-  a.ring_area2 = at<unsigned long long>(ws, lo.ring_area2);
-  a.eid = at<unsigned int>(ws, lo.eid);
-  a.succ = at<int>(ws, lo.succ);
-  a.ring = at<int>(ws, lo.ring);
-  a.P0 = at<int>(ws, lo.P0);
-  a.P1 = at<int>(ws, lo.P1);
-  a.D0 = at<int>(ws, lo.D0);
-  a.D1 = at<int>(ws, lo.D1);
-  a.hist = at<int>(ws, lo.hist);
-  a.part = at<int>(ws, lo.part);
-  a.ctr = at<Counters>(ws, lo.ctr);
-  return a;
-}
-
-// Pixel workspace of the count-sized path: four int32 arrays of N + 1, the scan partials and the counters.  With
+// Pixel workspace of the count-sized path: the per-pixel arrays, the scan partials and the counters.  With
 // N < 2^30 the partials are below 1 MiB, so the total stays within 16 N + 2 MiB.
 constexpr long long kCountedMaxPixels = 1ll << 30;
 constexpr long long kCountedMaxEdges = (1ll << 31) - 1;  // exclusive
 
-struct PixelLayout {
-  long long N, nb_n;
-  long long L, cnt, off, polyidx, part, ctr, total;
-};
-
-bool make_pixel_layout(int H, int W, PixelLayout* pl) {
-  if (H < 1 || W < 1) return false;
+long long carve_count(void* ws_px, int H, int W, Arrays* a) {
   const long long N = (long long)H * W;
-  if (N >= kCountedMaxPixels) return false;
-  pl->N = N;
-  pl->nb_n = (N + 1 + kChunk - 1) / kChunk;
-  long long o = 0;
-  auto take = [&](long long bytes) {
-    const long long at = o;
-    o += align_up(bytes);
-    return at;
-  };
-  const long long n4 = 4 * (N + 1);
-  pl->L = take(n4);
-  pl->cnt = take(n4);
-  pl->off = take(n4);
-  pl->polyidx = take(n4);
-  pl->part = take(4 * (pl->nb_n + 16));
-  pl->ctr = take(sizeof(PixelCounters));
-  pl->total = o;
-  return true;
-}
-
-// Trace workspace: a function of the two counts only.  A ring has at least 4 edges, so E / 4 bounds the rings; the
-// polygon arrays double as radix buffers for the rings, hence max(P, E / 4).  28 bytes per edge for the seven edge
-// arrays, 28 per ring, 28 per polygon slot and 1 KiB of histogram per 4096 slots: with P <= E / 4 about 42 bytes
-// per edge, and never more than 48 per edge + 64 per polygon + 64 KiB.
-struct TraceLayout {
-  long long E, P, r_cap, m_cap, nb_r;
-  int rounds;
-  long long poly_label, poly_cls, poly_first, rk0, rv0, rk1, rv1, ring_label, ring_nv, ring_s, ring_pos, voff, ring_area2,
-      eid, succ, ring, P0, P1, D0, D1, hist, part, total;
-};
-
-bool make_trace_layout(long long E, long long P, TraceLayout* tl) {
-  if (E < 0 || P < 0 || E >= kCountedMaxEdges || P >= kCountedMaxPixels) return false;
-  tl->E = E;
-  tl->P = P;
-  tl->r_cap = E / 4;
-  tl->m_cap = P > tl->r_cap ? P : tl->r_cap;
-  tl->nb_r = tl->m_cap > 0 ? (tl->m_cap + kChunk - 1) / kChunk : 1;
-  tl->rounds = rounds_for(E > 2 ? E : 2);
-  const long long nb_e = (E + 1 + kChunk - 1) / kChunk, nb_h = (256 * tl->nb_r + 1 + kChunk - 1) / kChunk;
-  long long o = 0;
-  auto take = [&](long long bytes) {
-    const long long at = o;
-    o += align_up(bytes);
-    return at;
-  };
-  const long long m4 = 4 * (tl->m_cap + 1), r4 = 4 * (tl->r_cap + 1), e4 = 4 * (E + 1);
-  tl->poly_label = take(m4);
-  tl->poly_cls = take(m4);
-  tl->poly_first = take(m4);
-  tl->rk0 = take(m4);
-  tl->rv0 = take(m4);
-  tl->rk1 = take(m4);
-  tl->rv1 = take(m4);
-  tl->ring_label = take(r4);
-  tl->ring_nv = take(r4);
-  tl->ring_s = take(r4);
-  tl->ring_pos = take(r4);
-  tl->voff = take(r4);
-  tl->ring_area2 = take(2 * r4);
-  tl->eid = take(e4);
-  tl->succ = take(e4);
-  tl->ring = take(e4);
-  tl->P0 = take(e4);
-  tl->P1 = take(e4);
-  tl->D0 = take(e4);
-  tl->D1 = take(e4);
-  tl->hist = take(4ll * 256 * tl->nb_r + 4);
-  tl->part = take(4 * (nb_e + nb_h + 16));
-  tl->total = o;
-  return true;
-}
-
-// the pixel arrays alone (count phase); part is the pixel workspace's
-Arrays bind_pixels(void* ws_px, const PixelLayout& pl) {
-  Arrays a = {};
-  a.N = pl.N;
-  a.L = at<int>(ws_px, pl.L);
-  a.cnt = at<int>(ws_px, pl.cnt);
-  a.off = at<int>(ws_px, pl.off);
-  a.polyidx = at<int>(ws_px, pl.polyidx);
+  if (H < 1 || W < 1 || N >= kCountedMaxPixels) return -1;
+  *a = {};
+  ffa_carver c{ws_px};
+  carve_pixels(c, N, a);
   // comp_list_kernel reads the ordinals of the kept roots before poly_index_kernel writes the polygon index over
   // them; what stays at the roots of dropped components is at most P and fails zonal_flush's check like any stale
   // value
-  a.ord = a.polyidx;
-  a.part = at<int>(ws_px, pl.part);
-  a.ctr = &at<PixelCounters>(ws_px, pl.ctr)->c;
-  return a;
+  a->ord = a->polyidx;
+  c.take(a->part, chunks(N + 1) + 16);
+  c.take(a->pc, 1);
+  a->ctr = a->pc ? &a->pc->c : nullptr;
+  return c.off;
 }
 
-Arrays bind_counted(void* ws_px, const PixelLayout& pl, void* ws_tr, const TraceLayout& tl) {
-  Arrays a = bind_pixels(ws_px, pl);
-  a.e_cap = tl.E;
-  a.r_cap = tl.r_cap;
-  a.m_cap = tl.m_cap;
-  a.rounds = tl.rounds;
-  a.nb_r = (int)tl.nb_r;
-  a.poly_label = at<int>(ws_tr, tl.poly_label);
-  a.poly_cls = at<int>(ws_tr, tl.poly_cls);
-  a.poly_first = at<int>(ws_tr, tl.poly_first);
-  a.rk0 = at<int>(ws_tr, tl.rk0);
-  a.rv0 = at<int>(ws_tr, tl.rv0);
-  a.rk1 = at<int>(ws_tr, tl.rk1);
-  a.rv1 = at<int>(ws_tr, tl.rv1);
-  a.ring_label = at<int>(ws_tr, tl.ring_label);
-  a.ring_nv = at<int>(ws_tr, tl.ring_nv);
-  a.ring_s = at<int>(ws_tr, tl.ring_s);
-  a.ring_pos = at<int>(ws_tr, tl.ring_pos);
-  a.voff = at<int>(ws_tr, tl.voff);
-  a.ring_area2 = at<unsigned long long>(ws_tr, tl.ring_area2);
-  a.eid = at<unsigned int>(ws_tr, tl.eid);
-  a.succ = at<int>(ws_tr, tl.succ);
-  a.ring = at<int>(ws_tr, tl.ring);
-  a.P0 = at<int>(ws_tr, tl.P0);
-  a.P1 = at<int>(ws_tr, tl.P1);
-  a.D0 = at<int>(ws_tr, tl.D0);
-  a.D1 = at<int>(ws_tr, tl.D1);
-  a.hist = at<int>(ws_tr, tl.hist);
-  a.part = at<int>(ws_tr, tl.part);
-  return a;
+// Trace workspace, on top of carve_count's Arrays: a function of the two counts only.  A ring has at least 4 edges,
+// so E / 4 bounds the rings; the polygon arrays double as radix buffers for the rings, hence max(P, E / 4).  28 bytes
+// per edge for the seven edge arrays, 28 per ring, 28 per polygon slot and 1 KiB of histogram per 4096 slots: with
+// P <= E / 4 about 42 bytes per edge, and never more than 48 per edge + 64 per polygon + 64 KiB.  The scan partials
+// are the trace workspace's from here on.
+long long carve_traced(void* ws_tr, long long E, long long P, Arrays* a) {
+  if (E < 0 || P < 0 || E >= kCountedMaxEdges || P >= kCountedMaxPixels) return -1;
+  const long long r_cap = E / 4, m_cap = P > r_cap ? P : r_cap;
+  ffa_carver c{ws_tr};
+  carve_trace(c, E, r_cap, m_cap, chunks(E + 1) + chunks(256 * radix_blocks(m_cap) + 1) + 16, a);
+  return c.off;
 }
 
 // exclusive scan of n items (n_dev on the device, else n_host, in which case out[n_host] = total as well)
@@ -812,8 +655,10 @@ void scan(const int* in, int* out, const int* n_dev, long long n_max, int* part,
   hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(kT), 0, st, in, n_dev, n_host, part, out);
 }
 
+constexpr const char* kOp = "polygonize";  // names the failed clear or copy of a stage in ffa_last_error()
+
 // stable LSD radix sort of (key, value) pairs by the low `bits` key bits; result in (k0, v0)
-void radix_sort(int* k0, int* v0, int* k1, int* v1, const int* n_dev, const Arrays& a, int bits, hipStream_t st) {
+int radix_sort(int* k0, int* v0, int* k1, int* v1, const int* n_dev, const Arrays& a, int bits, hipStream_t st) {
   const int nb = a.nb_r;
   for (int shift = 0; shift < bits; shift += 8) {
     hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(kT), 0, st, k0, n_dev, shift, nb, a.hist);
@@ -823,9 +668,10 @@ void radix_sort(int* k0, int* v0, int* k1, int* v1, const int* n_dev, const Arra
     t = v0; v0 = v1; v1 = t;
   }
   if ((bits + 7) / 8 % 2 == 1) {  // an odd number of passes left the result in the second buffers
-    (void)hipMemcpyAsync(k1, k0, 4 * a.m_cap, hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(v1, v0, 4 * a.m_cap, hipMemcpyDeviceToDevice, st);
+    FFA_TRY(ffa_copy_async(k1, k0, 4 * a.m_cap, kOp, "the sorted keys", st));
+    FFA_TRY(ffa_copy_async(v1, v0, 4 * a.m_cap, kOp, "the sorted values", st));
   }
+  return 0;
 }
 
 int bits_for(long long v) {
@@ -845,16 +691,17 @@ int clamp_min_pixels(long long min_pixels, long long N) {
 
 // Stages 1 to 3a: labels, pixel counts, per-pixel edge counts with their exclusive scan (total -> ctr->edges, and in
 // 64 bits -> *edges64 when given).
-void label_stages(const Arrays& a, const uint8_t* classes, int H, int W, int background, int minp, long long* edges64,
+int label_stages(const Arrays& a, const uint8_t* classes, int H, int W, int background, int minp, long long* edges64,
                   hipStream_t st) {
   const int N = (int)a.N, gN = (N + kT - 1) / kT;
-  (void)hipMemsetAsync(a.ctr, 0, sizeof(Counters), st);
-  (void)hipMemsetAsync(a.cnt, 0, 4ll * N, st);
+  FFA_TRY(ffa_zero_async(a.ctr, sizeof(Counters), kOp, "the counters", st));
+  FFA_TRY(ffa_zero_async(a.cnt, 4ll * N, kOp, "the pixel counts", st));
   // 1. labels, 2. counts (ffa_ccl.h)
   ccl_label_and_count(classes, H, W, background, a.L, a.cnt, st);
   // 3. edges: off = exclusive scan of per-pixel edge counts
   hipLaunchKernelGGL(edge_count_kernel, dim3(gN), dim3(kT), 0, st, H, W, a.L, a.cnt, minp, a.off);
   scan(a.off, a.off, nullptr, N, a.part, &a.ctr->edges, edges64, st);
+  return 0;
 }
 
 // head of stage 5: ordinals of the kept roots in label order, their number -> ctr->polys
@@ -865,12 +712,12 @@ void kept_root_stage(const Arrays& a, int minp, hipStream_t st) {
 }
 
 // ring_info_kernel accumulates the ring areas: zeroed before ring_stages, on the same stream
-void zero_ring_areas(const Arrays& a, hipStream_t st) {
-  (void)hipMemsetAsync(a.ring_area2, 0, 8ll * (a.r_cap + 1), st);
+int zero_ring_areas(const Arrays& a, hipStream_t st) {
+  return ffa_zero_async(a.ring_area2, 8ll * (a.r_cap + 1), kOp, "the ring areas", st);
 }
 
 // Stages 3b and 4 on e_cap >= ctr->edges edge slots: successors, ring ids, vertex ranks, per-ring facts.
-void ring_stages(const Arrays& a, int H, int W, int minp, hipStream_t st) {
+int ring_stages(const Arrays& a, int H, int W, int minp, hipStream_t st) {
   const int N = (int)a.N, gN = (N + kT - 1) / kT, gE = grid_for(a.e_cap);
   Counters* ctr = a.ctr;
   hipLaunchKernelGGL(edge_build_kernel, dim3(gN), dim3(kT), 0, st, H, W, a.L, a.cnt, a.off, minp, a.eid, a.succ, a.P0,
@@ -882,7 +729,7 @@ void ring_stages(const Arrays& a, int H, int W, int minp, hipStream_t st) {
     int* t = pa; pa = pb; pb = t;
     t = da; da = db; db = t;
   }
-  (void)hipMemcpyAsync(a.ring, da, 4 * a.e_cap, hipMemcpyDeviceToDevice, st);
+  FFA_TRY(ffa_copy_async(a.ring, da, 4 * a.e_cap, kOp, "the ring ids", st));
   // 4b. vertex ranks: D[i] = direction changes on the ring between the ring id edge and edge i
   hipLaunchKernelGGL(rank_init_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, a.eid, a.succ, a.ring, a.P0, a.D0);
   pa = a.P0; pb = a.P1; da = a.D0; db = a.D1;
@@ -891,32 +738,34 @@ void ring_stages(const Arrays& a, int H, int W, int minp, hipStream_t st) {
     int* t = pa; pa = pb; pb = t;
     t = da; da = db; db = t;
   }
-  if (da != a.D0) (void)hipMemcpyAsync(a.D0, da, 4 * a.e_cap, hipMemcpyDeviceToDevice, st);  // final ranks live in D0
+  if (da != a.D0) FFA_TRY(ffa_copy_async(a.D0, da, 4 * a.e_cap, kOp, "the vertex ranks", st));  // final ranks live in D0
   // ring ordinals (ring id order) in P0, R -> ctr->rings
   hipLaunchKernelGGL(root_flag_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, a.ring, a.P1);
   scan(a.P1, a.P0, &ctr->edges, a.e_cap, a.part, &ctr->rings, nullptr, st);
   hipLaunchKernelGGL(ring_info_kernel, dim3(gE), dim3(kT), 0, st, &ctr->edges, W, a.L, a.eid, a.succ, a.ring, a.D0,
                      a.P0, a.ring_label, a.ring_nv, a.ring_s, a.ring_area2);
+  return 0;
 }
 
 // Stage 5 after the kept roots: polygons and rings in output order; counts_dev[4] = polygons, rings, vertices, edges.
-void order_stages(const Arrays& a, const uint8_t* classes, int minp, long long* counts_dev, hipStream_t st) {
+int order_stages(const Arrays& a, const uint8_t* classes, int minp, long long* counts_dev, hipStream_t st) {
   const int N = (int)a.N, gN = (N + kT - 1) / kT, gM = grid_for(a.m_cap);
   Counters* ctr = a.ctr;
   // polygons sorted by (class, label)
   hipLaunchKernelGGL(comp_list_kernel, dim3(gN), dim3(kT), 0, st, N, classes, a.L, a.cnt, minp, a.ord, a.rk0, a.rv0);
-  radix_sort(a.rk0, a.rv0, a.rk1, a.rv1, &ctr->polys, a, 8, st);
-  (void)hipMemcpyAsync(a.poly_label, a.rv0, 4 * a.m_cap, hipMemcpyDeviceToDevice, st);
-  (void)hipMemcpyAsync(a.poly_cls, a.rk0, 4 * a.m_cap, hipMemcpyDeviceToDevice, st);
+  FFA_TRY(radix_sort(a.rk0, a.rv0, a.rk1, a.rv1, &ctr->polys, a, 8, st));
+  FFA_TRY(ffa_copy_async(a.poly_label, a.rv0, 4 * a.m_cap, kOp, "the polygon labels", st));
+  FFA_TRY(ffa_copy_async(a.poly_cls, a.rk0, 4 * a.m_cap, kOp, "the polygon classes", st));
   hipLaunchKernelGGL(poly_index_kernel, dim3(gM), dim3(kT), 0, st, &ctr->polys, a.poly_label, a.polyidx);
   // rings sorted by (polygon, hole, ring id); key bits above those of 2 * m_cap are zero in both layouts
   hipLaunchKernelGGL(ring_keys_kernel, dim3(gM), dim3(kT), 0, st, &ctr->rings, a.ring_label, a.ring_area2, a.polyidx,
                      a.rk0, a.rv0);
-  radix_sort(a.rk0, a.rv0, a.rk1, a.rv1, &ctr->rings, a, bits_for(2 * a.m_cap), st);
+  FFA_TRY(radix_sort(a.rk0, a.rv0, a.rk1, a.rv1, &ctr->rings, a, bits_for(2 * a.m_cap), st));
   hipLaunchKernelGGL(ring_order_kernel, dim3(gM), dim3(kT), 0, st, &ctr->rings, a.rk0, a.rv0, a.ring_nv, a.ring_pos,
                      a.rk1, a.poly_first);
   scan(a.rk1, a.voff, &ctr->rings, a.r_cap, a.part, &ctr->verts, nullptr, st);
   hipLaunchKernelGGL(counts_kernel, dim3(1), dim3(64), 0, st, ctr, counts_dev);
+  return 0;
 }
 
 void emit_stages(const Arrays& a, int W, long long n_polys, long long n_rings, long long n_vertices,
@@ -933,135 +782,42 @@ void emit_stages(const Arrays& a, int W, long long n_polys, long long n_rings, l
                        a.ring, a.D0, a.P0, a.ring_s, a.ring_pos, a.voff, vertices);
 }
 
-void zonal_stage(const Arrays& a, const uint8_t* values, long long n_polys, int64_t* sums, hipStream_t st) {
-  (void)hipMemsetAsync(sums, 0, 8 * n_polys, st);
+int zonal_stage(const Arrays& a, const uint8_t* values, long long n_polys, int64_t* sums, hipStream_t st) {
+  FFA_TRY(ffa_zero_async(sums, 8 * n_polys, kOp, "the zonal sums", st));
   hipLaunchKernelGGL(zonal_sum_kernel, dim3((unsigned int)((a.N + kChunk - 1) / kChunk)), dim3(kT), 0, st, (int)a.N,
                      (int)n_polys, a.L, values, a.polyidx, a.poly_label, reinterpret_cast<unsigned long long*>(sums));
+  return 0;
 }
 
-}  // namespace
-
-extern "C" long long ffa_polygonize_workspace_bytes(int H, int W) {
-  Layout lo;
-  if (!make_layout(H, W, &lo)) {
-    ffa_set_error("polygonize: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
-    return FFA_ERR_ARG;
+// What the three bound-sized entry points check first: the raster against the limit, the workspace pointer and its
+// size.  A short workspace is FFA_ERR_WORKSPACE from the call that fills it and FFA_ERR_ARG from the two that read it.
+int bound_arrays(const char* what, int short_rc, const void* ws, long long ws_bytes, int H, int W, Arrays* a) {
+  const long long need = carve_bound(const_cast<void*>(ws), H, W, a);
+  FFA_REQUIRE(need >= 0, "polygonize: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
+  FFA_REQUIRE(ws, "%s: null workspace", what);
+  if (ws_bytes < need) {
+    ffa_set_error("%s: workspace %lld bytes < %lld", what, ws_bytes, need);
+    return short_rc;
   }
-  return lo.total;
+  return FFA_OK;
 }
 
-extern "C" int ffa_polygonize_label(const uint8_t* classes, int H, int W, int background, long long min_pixels,
-                                    void* ws, long long ws_bytes, long long* counts_dev, hipStream_t st) {
-  Layout lo;
-  FFA_REQUIRE(make_layout(H, W, &lo), "polygonize: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
-  FFA_REQUIRE(classes && ws && counts_dev, "polygonize_label: null pointer");
-  FFA_REQUIRE(background >= -1 && background <= 255, "polygonize_label: background must be -1 (none) or 0..255");
-  if (ws_bytes < lo.total) {
-    ffa_set_error("polygonize_label: workspace %lld bytes < %lld", ws_bytes, lo.total);
-    return FFA_ERR_WORKSPACE;
-  }
-  const Arrays a = bind(ws, lo);
-  const int minp = clamp_min_pixels(min_pixels, lo.N);
-  zero_ring_areas(a, st);
-  label_stages(a, classes, H, W, background, minp, nullptr, st);
-  ring_stages(a, H, W, minp, st);
-  kept_root_stage(a, minp, st);
-  order_stages(a, classes, minp, counts_dev, st);
-  return ffa_check_launch("polygonize_label");
-}
-
-extern "C" int ffa_polygonize_emit(const void* ws_c, long long ws_bytes, int H, int W, long long n_polys,
-                                   long long n_rings, long long n_vertices, int32_t* poly_class, int64_t* poly_pixels,
-                                   int32_t* poly_ring_offsets, int32_t* ring_vertex_offsets, int32_t* vertices,
-                                   hipStream_t st) {
-  Layout lo;
-  FFA_REQUIRE(make_layout(H, W, &lo), "polygonize: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
-  FFA_REQUIRE(ws_c && ws_bytes >= lo.total, "polygonize_emit: workspace missing or too small");
-  FFA_REQUIRE(n_polys >= 0 && n_polys <= lo.N && n_rings >= n_polys && n_rings <= lo.N && n_vertices >= 4 * n_rings &&
-                  n_vertices <= lo.E,
-              "polygonize_emit: counts (%lld, %lld, %lld) are not those of ffa_polygonize_label", n_polys, n_rings,
-              n_vertices);
-  FFA_REQUIRE(poly_ring_offsets && ring_vertex_offsets && (n_polys == 0 || (poly_class && poly_pixels && vertices)),
-              "polygonize_emit: null output pointer");
-  emit_stages(bind(const_cast<void*>(ws_c), lo), W, n_polys, n_rings, n_vertices, poly_class, poly_pixels,
-              poly_ring_offsets, ring_vertex_offsets, vertices, st);
-  return ffa_check_launch("polygonize_emit");
-}
-
-// Reads the workspace ffa_polygonize_label left (labels, polygon index) and nothing ffa_polygonize_emit writes, so it
-// may run before or after that call; it writes caller memory only.
-extern "C" int ffa_polygonize_zonal_sum_u8(const void* ws_c, long long ws_bytes, int H, int W, const uint8_t* values,
-                                           long long n_polys, int64_t* sums, hipStream_t st) {
-  Layout lo;
-  FFA_REQUIRE(make_layout(H, W, &lo), "polygonize: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
-  FFA_REQUIRE(ws_c && ws_bytes >= lo.total, "polygonize_zonal_sum_u8: workspace missing or too small");
-  FFA_REQUIRE(n_polys >= 0 && n_polys <= lo.N, "polygonize_zonal_sum_u8: %lld polygons are not those of "
-              "ffa_polygonize_label", n_polys);
-  FFA_REQUIRE(values && (n_polys == 0 || sums), "polygonize_zonal_sum_u8: null pointer");
-  if (n_polys == 0) return FFA_OK;
-  zonal_stage(bind(const_cast<void*>(ws_c), lo), values, n_polys, sums, st);
-  return ffa_check_launch("polygonize_zonal_sum_u8");
-}
-
-// ---- the count-sized path ---------------------------------------------------------------------------------------------
-
-extern "C" long long ffa_polygonize_count_bytes(int H, int W) {
-  PixelLayout pl;
-  if (!make_pixel_layout(H, W, &pl)) {
-    ffa_set_error("polygonize_count: raster %d x %d = %lld pixels outside 1 <= H, W and H * W < 2^30", H, W,
-                  (long long)H * W);
-    return FFA_ERR_ARG;
-  }
-  return pl.total;
-}
-
-extern "C" int ffa_polygonize_count(const uint8_t* classes, int H, int W, int background, long long min_pixels,
-                                    void* ws_px, long long ws_px_bytes, long long* counts_dev, hipStream_t st) {
-  PixelLayout pl;
-  FFA_REQUIRE(make_pixel_layout(H, W, &pl), "polygonize_count: raster %d x %d = %lld pixels outside 1 <= H, W and "
-              "H * W < 2^30", H, W, (long long)H * W);
-  FFA_REQUIRE(classes && ws_px && counts_dev, "polygonize_count: null pointer");
-  FFA_REQUIRE(background >= -1 && background <= 255, "polygonize_count: background must be -1 (none) or 0..255");
-  if (ws_px_bytes < pl.total) {
-    ffa_set_error("polygonize_count: workspace %lld bytes < %lld", ws_px_bytes, pl.total);
-    return FFA_ERR_WORKSPACE;
-  }
-  PixelCounters* pc = at<PixelCounters>(ws_px, pl.ctr);
-  (void)hipMemsetAsync(pc, 0, sizeof(PixelCounters), st);
-  const Arrays a = bind_pixels(ws_px, pl);
-  const int minp = clamp_min_pixels(min_pixels, pl.N);
-  label_stages(a, classes, H, W, background, minp, &pc->edges64, st);
-  kept_root_stage(a, minp, st);
-  hipLaunchKernelGGL(pixel_counts_kernel, dim3(1), dim3(64), 0, st, pc, counts_dev);
-  return ffa_check_launch("polygonize_count");
-}
-
-extern "C" long long ffa_polygonize_trace_bytes(long long n_edges, long long n_polys) {
-  TraceLayout tl;
-  if (!make_trace_layout(n_edges, n_polys, &tl)) {
-    ffa_set_error("polygonize_trace: %lld boundary edges and %lld polygons outside 0 <= edges < 2^31 - 1 (which also "
-                  "keeps vertices < 2^31) and 0 <= polygons < 2^30", n_edges, n_polys);
-    return FFA_ERR_ARG;
-  }
-  return tl.total;
-}
-
-namespace {
-
-// the checks the three calls after the count phase share; fills both layouts
-int counted_layouts(const char* what, const void* ws_px, long long ws_px_bytes, int H, int W, const void* ws_tr,
-                    long long ws_tr_bytes, long long n_edges, long long n_polys, PixelLayout* pl, TraceLayout* tl) {
-  FFA_REQUIRE(make_pixel_layout(H, W, pl), "%s: raster %d x %d = %lld pixels outside 1 <= H, W and H * W < 2^30", what,
-              H, W, (long long)H * W);
-  FFA_REQUIRE(make_trace_layout(n_edges, n_polys, tl), "%s: %lld boundary edges and %lld polygons outside 0 <= edges "
-              "< 2^31 - 1 and 0 <= polygons < 2^30", what, n_edges, n_polys);
-  FFA_REQUIRE(n_edges >= 4 && n_polys >= 1 && 4 * n_polys <= n_edges && n_edges <= 4 * pl->N,
+// the checks the three calls after the count phase share; binds both workspaces
+int counted_arrays(const char* what, const void* ws_px, long long ws_px_bytes, int H, int W, const void* ws_tr,
+                   long long ws_tr_bytes, long long n_edges, long long n_polys, Arrays* a) {
+  const long long need_px = carve_count(const_cast<void*>(ws_px), H, W, a);
+  FFA_REQUIRE(need_px >= 0, "%s: raster %d x %d = %lld pixels outside 1 <= H, W and H * W < 2^30", what, H, W,
+              (long long)H * W);
+  const long long need_tr = carve_traced(const_cast<void*>(ws_tr), n_edges, n_polys, a);
+  FFA_REQUIRE(need_tr >= 0, "%s: %lld boundary edges and %lld polygons outside 0 <= edges < 2^31 - 1 and 0 <= polygons "
+              "< 2^30", what, n_edges, n_polys);
+  FFA_REQUIRE(n_edges >= 4 && n_polys >= 1 && 4 * n_polys <= n_edges && n_edges <= 4 * a->N,
               "%s: %lld edges and %lld polygons are not counts of ffa_polygonize_count on %d x %d (nothing to trace "
               "when either is 0)", what, n_edges, n_polys, H, W);
   FFA_REQUIRE(ws_px && ws_tr, "%s: null workspace", what);
-  if (ws_px_bytes < pl->total || ws_tr_bytes < tl->total) {
-    ffa_set_error("%s: workspaces of %lld and %lld bytes < %lld and %lld", what, ws_px_bytes, ws_tr_bytes, pl->total,
-                  tl->total);
+  if (ws_px_bytes < need_px || ws_tr_bytes < need_tr) {
+    ffa_set_error("%s: workspaces of %lld and %lld bytes < %lld and %lld", what, ws_px_bytes, ws_tr_bytes, need_px,
+                  need_tr);
     return FFA_ERR_WORKSPACE;
   }
   return FFA_OK;
@@ -1069,20 +825,116 @@ int counted_layouts(const char* what, const void* ws_px, long long ws_px_bytes, 
 
 }  // namespace
 
+extern "C" long long ffa_polygonize_workspace_bytes(int H, int W) {
+  Arrays a;
+  const long long need = carve_bound(nullptr, H, W, &a);
+  if (need < 0) {
+    ffa_set_error("polygonize: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
+    return FFA_ERR_ARG;
+  }
+  return need;
+}
+
+extern "C" int ffa_polygonize_label(const uint8_t* classes, int H, int W, int background, long long min_pixels,
+                                    void* ws, long long ws_bytes, long long* counts_dev, hipStream_t st) {
+  FFA_REQUIRE(classes && counts_dev, "polygonize_label: null pointer");
+  FFA_REQUIRE(background >= -1 && background <= 255, "polygonize_label: background must be -1 (none) or 0..255");
+  Arrays a;
+  FFA_TRY(bound_arrays("polygonize_label", FFA_ERR_WORKSPACE, ws, ws_bytes, H, W, &a));
+  const int minp = clamp_min_pixels(min_pixels, a.N);
+  FFA_TRY(zero_ring_areas(a, st));
+  FFA_TRY(label_stages(a, classes, H, W, background, minp, nullptr, st));
+  FFA_TRY(ring_stages(a, H, W, minp, st));
+  kept_root_stage(a, minp, st);
+  FFA_TRY(order_stages(a, classes, minp, counts_dev, st));
+  return ffa_check_launch("polygonize_label");
+}
+
+extern "C" int ffa_polygonize_emit(const void* ws, long long ws_bytes, int H, int W, long long n_polys,
+                                   long long n_rings, long long n_vertices, int32_t* poly_class, int64_t* poly_pixels,
+                                   int32_t* poly_ring_offsets, int32_t* ring_vertex_offsets, int32_t* vertices,
+                                   hipStream_t st) {
+  Arrays a;
+  FFA_TRY(bound_arrays("polygonize_emit", FFA_ERR_ARG, ws, ws_bytes, H, W, &a));
+  FFA_REQUIRE(n_polys >= 0 && n_polys <= a.N && n_rings >= n_polys && n_rings <= a.N && n_vertices >= 4 * n_rings &&
+                  n_vertices <= a.e_cap,
+              "polygonize_emit: counts (%lld, %lld, %lld) are not those of ffa_polygonize_label", n_polys, n_rings,
+              n_vertices);
+  FFA_REQUIRE(poly_ring_offsets && ring_vertex_offsets && (n_polys == 0 || (poly_class && poly_pixels && vertices)),
+              "polygonize_emit: null output pointer");
+  emit_stages(a, W, n_polys, n_rings, n_vertices, poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets,
+              vertices, st);
+  return ffa_check_launch("polygonize_emit");
+}
+
+// Reads the workspace ffa_polygonize_label left (labels, polygon index) and nothing ffa_polygonize_emit writes, so it
+// may run before or after that call; it writes caller memory only.
+extern "C" int ffa_polygonize_zonal_sum_u8(const void* ws, long long ws_bytes, int H, int W, const uint8_t* values,
+                                           long long n_polys, int64_t* sums, hipStream_t st) {
+  Arrays a;
+  FFA_TRY(bound_arrays("polygonize_zonal_sum_u8", FFA_ERR_ARG, ws, ws_bytes, H, W, &a));
+  FFA_REQUIRE(n_polys >= 0 && n_polys <= a.N, "polygonize_zonal_sum_u8: %lld polygons are not those of "
+              "ffa_polygonize_label", n_polys);
+  FFA_REQUIRE(values && (n_polys == 0 || sums), "polygonize_zonal_sum_u8: null pointer");
+  if (n_polys == 0) return FFA_OK;
+  FFA_TRY(zonal_stage(a, values, n_polys, sums, st));
+  return ffa_check_launch("polygonize_zonal_sum_u8");
+}
+
+// ---- the count-sized path ---------------------------------------------------------------------------------------------
+
+extern "C" long long ffa_polygonize_count_bytes(int H, int W) {
+  Arrays a;
+  const long long need = carve_count(nullptr, H, W, &a);
+  if (need < 0) {
+    ffa_set_error("polygonize_count: raster %d x %d = %lld pixels outside 1 <= H, W and H * W < 2^30", H, W,
+                  (long long)H * W);
+    return FFA_ERR_ARG;
+  }
+  return need;
+}
+
+extern "C" int ffa_polygonize_count(const uint8_t* classes, int H, int W, int background, long long min_pixels,
+                                    void* ws_px, long long ws_px_bytes, long long* counts_dev, hipStream_t st) {
+  Arrays a;
+  const long long need = carve_count(ws_px, H, W, &a);
+  FFA_REQUIRE(need >= 0, "polygonize_count: raster %d x %d = %lld pixels outside 1 <= H, W and H * W < 2^30", H, W,
+              (long long)H * W);
+  FFA_REQUIRE(classes && ws_px && counts_dev, "polygonize_count: null pointer");
+  FFA_REQUIRE(background >= -1 && background <= 255, "polygonize_count: background must be -1 (none) or 0..255");
+  if (ws_px_bytes < need) {
+    ffa_set_error("polygonize_count: workspace %lld bytes < %lld", ws_px_bytes, need);
+    return FFA_ERR_WORKSPACE;
+  }
+  FFA_TRY(ffa_zero_async(a.pc, sizeof(PixelCounters), kOp, "the pixel workspace's counters", st));
+  const int minp = clamp_min_pixels(min_pixels, a.N);
+  FFA_TRY(label_stages(a, classes, H, W, background, minp, &a.pc->edges64, st));
+  kept_root_stage(a, minp, st);
+  hipLaunchKernelGGL(pixel_counts_kernel, dim3(1), dim3(64), 0, st, a.pc, counts_dev);
+  return ffa_check_launch("polygonize_count");
+}
+
+extern "C" long long ffa_polygonize_trace_bytes(long long n_edges, long long n_polys) {
+  Arrays a;
+  const long long need = carve_traced(nullptr, n_edges, n_polys, &a);
+  if (need < 0) {
+    ffa_set_error("polygonize_trace: %lld boundary edges and %lld polygons outside 0 <= edges < 2^31 - 1 (which also "
+                  "keeps vertices < 2^31) and 0 <= polygons < 2^30", n_edges, n_polys);
+    return FFA_ERR_ARG;
+  }
+  return need;
+}
+
 extern "C" int ffa_polygonize_trace(const uint8_t* classes, int H, int W, long long min_pixels, void* ws_px,
                                     long long ws_px_bytes, long long n_edges, long long n_polys, void* ws_tr,
                                     long long ws_tr_bytes, long long* counts_dev, hipStream_t st) {
-  PixelLayout pl;
-  TraceLayout tl;
-  const int rc = counted_layouts("polygonize_trace", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes, n_edges, n_polys,
-                                 &pl, &tl);
-  if (rc != FFA_OK) return rc;
+  Arrays a;
+  FFA_TRY(counted_arrays("polygonize_trace", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes, n_edges, n_polys, &a));
   FFA_REQUIRE(classes && counts_dev, "polygonize_trace: null pointer");
-  const Arrays a = bind_counted(ws_px, pl, ws_tr, tl);
-  const int minp = clamp_min_pixels(min_pixels, pl.N);
-  zero_ring_areas(a, st);
-  ring_stages(a, H, W, minp, st);
-  order_stages(a, classes, minp, counts_dev, st);
+  const int minp = clamp_min_pixels(min_pixels, a.N);
+  FFA_TRY(zero_ring_areas(a, st));
+  FFA_TRY(ring_stages(a, H, W, minp, st));
+  FFA_TRY(order_stages(a, classes, minp, counts_dev, st));
   return ffa_check_launch("polygonize_trace");
 }
 
@@ -1091,18 +943,16 @@ extern "C" int ffa_polygonize_counted_emit(const void* ws_px, long long ws_px_by
                                            long long n_rings, long long n_vertices, int32_t* poly_class,
                                            int64_t* poly_pixels, int32_t* poly_ring_offsets,
                                            int32_t* ring_vertex_offsets, int32_t* vertices, hipStream_t st) {
-  PixelLayout pl;
-  TraceLayout tl;
-  const int rc = counted_layouts("polygonize_counted_emit", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes, n_edges,
-                                 n_polys, &pl, &tl);
-  if (rc != FFA_OK) return rc;
-  FFA_REQUIRE(n_rings >= n_polys && n_rings <= tl.r_cap && n_vertices >= 4 * n_rings && n_vertices <= n_edges,
+  Arrays a;
+  FFA_TRY(counted_arrays("polygonize_counted_emit", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes, n_edges, n_polys,
+                         &a));
+  FFA_REQUIRE(n_rings >= n_polys && n_rings <= a.r_cap && n_vertices >= 4 * n_rings && n_vertices <= n_edges,
               "polygonize_counted_emit: counts (%lld, %lld, %lld) are not those of ffa_polygonize_trace", n_polys,
               n_rings, n_vertices);
   FFA_REQUIRE(poly_class && poly_pixels && poly_ring_offsets && ring_vertex_offsets && vertices,
               "polygonize_counted_emit: null output pointer");
-  emit_stages(bind_counted(const_cast<void*>(ws_px), pl, const_cast<void*>(ws_tr), tl), W, n_polys, n_rings,
-              n_vertices, poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices, st);
+  emit_stages(a, W, n_polys, n_rings, n_vertices, poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets,
+              vertices, st);
   return ffa_check_launch("polygonize_counted_emit");
 }
 
@@ -1110,13 +960,10 @@ extern "C" int ffa_polygonize_counted_zonal_sum_u8(const void* ws_px, long long 
                                                    const void* ws_tr, long long ws_tr_bytes, long long n_edges,
                                                    const uint8_t* values, long long n_polys, int64_t* sums,
                                                    hipStream_t st) {
-  PixelLayout pl;
-  TraceLayout tl;
-  const int rc = counted_layouts("polygonize_counted_zonal_sum_u8", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes,
-                                 n_edges, n_polys, &pl, &tl);
-  if (rc != FFA_OK) return rc;
+  Arrays a;
+  FFA_TRY(counted_arrays("polygonize_counted_zonal_sum_u8", ws_px, ws_px_bytes, H, W, ws_tr, ws_tr_bytes, n_edges,
+                         n_polys, &a));
   FFA_REQUIRE(values && sums, "polygonize_counted_zonal_sum_u8: null pointer");
-  zonal_stage(bind_counted(const_cast<void*>(ws_px), pl, const_cast<void*>(ws_tr), tl), values, n_polys, sums, st);
+  FFA_TRY(zonal_stage(a, values, n_polys, sums, st));
   return ffa_check_launch("polygonize_counted_zonal_sum_u8");
 }
-

@@ -14,6 +14,7 @@
 // Separate launches order the stages; no grid-wide barrier, no spinning, every loop bound fixed on the host.
 #include "ffa_common.h"
 #include "ffa_ccl.h"
+#include "ffa_workspace.h"
 
 namespace {
 
@@ -115,84 +116,63 @@ __global__ __launch_bounds__(kT) void apply_kernel(int N, uint8_t* __restrict__ 
   }
 }
 
-struct Layout {
+// The four arrays of a round, carved from ws (null: sized only); the bytes they take, < 0 beyond the limit.
+struct Arrays {
   long long N;
-  long long L, cnt, best, new_class, total;  // offsets in bytes
+  int *L, *cnt;
+  u64* best;
+  uint8_t* new_class;
 };
 
-long long align_up(long long v) { return (v + 255) & ~255ll; }
-
-bool make_layout(int H, int W, Layout* lo) {
-  if (H < 1 || W < 1) return false;
+long long carve(void* ws, int H, int W, Arrays* a) {
   const long long N = (long long)H * W;
-  if (4 * N >= (1ll << 31)) return false;
-  lo->N = N;
-  long long o = 0;
-  auto take = [&](long long bytes) {
-    const long long at = o;
-    o += align_up(bytes);
-    return at;
-  };
-  lo->L = take(4 * N);
-  lo->cnt = take(4 * N);
-  lo->best = take(8 * N);
-  lo->new_class = take(N);
-  lo->total = o;
-  return true;
-}
-
-// a failed memset would leave stale votes or counters behind: report it instead of launching on top of it
-int zero_async(void* p, long long bytes, const char* what, hipStream_t st) {
-  const hipError_t e = hipMemsetAsync(p, 0, (size_t)bytes, st);
-  if (e != hipSuccess) ffa_set_error("sieve_round_u8: clearing %s failed: %s", what, hipGetErrorString(e));
-  return (int)e;
-}
-
-template <typename T>
-T* at(void* ws, long long off) {
-  return reinterpret_cast<T*>(static_cast<char*>(ws) + off);
+  if (H < 1 || W < 1 || 4 * N >= (1ll << 31)) return -1;
+  a->N = N;
+  ffa_carver c{ws};
+  c.take(a->L, N);
+  c.take(a->cnt, N);
+  c.take(a->best, N);
+  c.take(a->new_class, N);
+  return c.off;
 }
 
 }  // namespace
 
 extern "C" long long ffa_sieve_workspace_bytes(int H, int W) {
-  Layout lo;
-  if (!make_layout(H, W, &lo)) {
+  Arrays a;
+  const long long need = carve(nullptr, H, W, &a);
+  if (need < 0) {
     ffa_set_error("sieve: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
     return FFA_ERR_ARG;
   }
-  return lo.total;
+  return need;
 }
 
 extern "C" int ffa_sieve_round_u8(uint8_t* classes, int H, int W, int background, long long min_pixels, void* ws,
                                   long long ws_bytes, long long* counts_dev, hipStream_t st) {
-  Layout lo;
-  FFA_REQUIRE(make_layout(H, W, &lo), "sieve: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
+  Arrays a;
+  const long long need = carve(ws, H, W, &a);
+  FFA_REQUIRE(need >= 0, "sieve: raster %d x %d outside 1 <= H, W and 4 * H * W < 2^31", H, W);
   FFA_REQUIRE(classes && ws && counts_dev, "sieve_round_u8: null pointer");
   FFA_REQUIRE(background >= -1 && background <= 255, "sieve_round_u8: background must be -1 (none) or 0..255");
   FFA_REQUIRE(min_pixels >= 0, "sieve_round_u8: min_pixels %lld is negative", min_pixels);
-  if (ws_bytes < lo.total) {
-    ffa_set_error("sieve_round_u8: workspace %lld bytes < %lld", ws_bytes, lo.total);
+  if (ws_bytes < need) {
+    ffa_set_error("sieve_round_u8: workspace %lld bytes < %lld", ws_bytes, need);
     return FFA_ERR_WORKSPACE;
   }
-  const int N = (int)lo.N;
-  const int T = (int)(min_pixels > lo.N + 1 ? lo.N + 1 : min_pixels);
-  int* L = at<int>(ws, lo.L);
-  int* cnt = at<int>(ws, lo.cnt);
-  u64* best = at<u64>(ws, lo.best);
-  uint8_t* new_class = at<uint8_t>(ws, lo.new_class);
+  const int N = (int)a.N;
+  const int T = (int)(min_pixels > a.N + 1 ? a.N + 1 : min_pixels);
   u64* counts = reinterpret_cast<u64*>(counts_dev);
-  const int gN = (N + kT - 1) / kT, gC = (int)((lo.N + kChunk - 1) / kChunk);
+  const int gN = (N + kT - 1) / kT, gC = (int)((a.N + kChunk - 1) / kChunk);
 
-  int rc = zero_async(counts_dev, 4 * sizeof(long long), "the counters", st);
-  if (rc == 0) rc = zero_async(cnt, 4ll * N, "the pixel counts", st);
-  if (rc == 0 && T > 1) rc = zero_async(best, 8ll * N, "the votes", st);
-  if (rc != 0) return rc;
-  ccl_label_and_count(classes, H, W, background, L, cnt, st);
+  FFA_TRY(ffa_zero_async(counts_dev, 4 * sizeof(long long), "sieve_round_u8", "the counters", st));
+  FFA_TRY(ffa_zero_async(a.cnt, 4ll * N, "sieve_round_u8", "the pixel counts", st));
+  if (T > 1) FFA_TRY(ffa_zero_async(a.best, 8ll * N, "sieve_round_u8", "the votes", st));
+  ccl_label_and_count(classes, H, W, background, a.L, a.cnt, st);
   if (T > 1) {  // a component has at least one pixel: below that nothing is small, nothing votes or moves
-    hipLaunchKernelGGL(vote_kernel, dim3(gN), dim3(kT), 0, st, H, W, L, cnt, T, best);
+    hipLaunchKernelGGL(vote_kernel, dim3(gN), dim3(kT), 0, st, H, W, a.L, a.cnt, T, a.best);
   }
-  hipLaunchKernelGGL(decide_kernel, dim3(gC), dim3(kT), 0, st, N, classes, L, cnt, T, best, new_class, counts);
-  if (T > 1) hipLaunchKernelGGL(apply_kernel, dim3(gC), dim3(kT), 0, st, N, classes, L, new_class, counts);
+  hipLaunchKernelGGL(decide_kernel, dim3(gC), dim3(kT), 0, st, N, classes, a.L, a.cnt, T, a.best, a.new_class, counts);
+  if (T > 1) hipLaunchKernelGGL(apply_kernel, dim3(gC), dim3(kT), 0, st, N, classes, a.L, a.new_class, counts);
   return ffa_check_launch("sieve_round_u8");
 }

@@ -661,6 +661,43 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
     return gpd.GeoDataFrame({"class_id": flat.class_id.astype(np.int64), **columns, "geometry": geoms}, crs=crs)
 
 
+def _class_band(src, name: str, shape=None):
+    """The one uint8 band of a class raster (``shape``: the (h, w) its bounds and resolution give, when known);
+    ValueError messages start with ``name``."""
+    if src.count != 1:
+        raise ValueError(f"{name}: a one-band class raster (argmax output) expected, got {src.count} bands")
+    data = np.asarray(src.read(1))
+    if data.dtype != np.uint8:
+        raise ValueError(f"{name}: uint8 class raster expected, got {data.dtype}")
+    if shape is not None and data.shape != tuple(shape):
+        raise ValueError(f"{name}: {data.shape} pixels, but its bounds and resolution give {tuple(shape)}")
+    return data
+
+
+def _confidence_band(csrc, src, data, name: str):
+    """The one uint8 band of the confidence raster ``csrc`` of the class raster ``src`` with band ``data``: same
+    shape, bounds and resolution, else ValueError starting with ``name``."""
+    if csrc.count != 1:
+        raise ValueError(f"{name}: the confidence raster must have one band, got {csrc.count}")
+    conf = np.asarray(csrc.read(1))
+    if conf.dtype != np.uint8:
+        raise ValueError(f"{name}: uint8 confidence raster expected, got {conf.dtype}")
+    if conf.shape != data.shape:
+        raise ValueError(f"{name}: confidence raster is {conf.shape}, the class raster {data.shape}")
+    res, cres = tuple(float(v) for v in src.res), tuple(float(v) for v in csrc.res)
+    if cres != res or _bounds4(csrc) != _bounds4(src):
+        raise ValueError(f"{name}: the confidence raster's bounds / resolution differ from the class raster's "
+                         f"({_bounds4(csrc)}, {cres} vs {_bounds4(src)}, {res})")
+    return conf
+
+
+def _background(ignore_background: bool, background_value):
+    """the polygoniser's background: ``background_value`` when it is to be ignored and a uint8 pixel can hold it,
+    else None = every value is a class"""
+    bg = int(background_value) if ignore_background else None
+    return bg if bg is not None and 0 <= bg <= 255 else None
+
+
 def raster_to_polygons(tiff_path, ignore_background: bool = True, background_value: int = 18, min_area: float = 1.0,
                        simplification: float = 0.1, n_jobs: Optional[int] = None, confidence=None, zone=None,
                        classes=None, zone_crs=None, target_crs=None, sieve_area: float = 0.0,
@@ -729,30 +766,14 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     whose limit is its own, as a ``zone`` does from the zone mask's.
     """
     src = _polygon_source(tiff_path)
-    if src.count != 1:
-        raise ValueError(f"raster_to_polygons needs a one-band class raster (argmax output), got {src.count} bands")
-    data = np.asarray(src.read(1))
-    if data.dtype != np.uint8:
-        raise ValueError(f"raster_to_polygons: uint8 class raster expected, got {data.dtype}")
+    data = _class_band(src, "raster_to_polygons")
     xres, yres = (float(v) for v in src.res)
     left, _, _, top = _bounds4(src)
     conf = None
     if confidence is not None and confidence is not False:
-        csrc = _confidence_source(tiff_path, confidence)
-        if csrc.count != 1:
-            raise ValueError(f"raster_to_polygons: the confidence raster must have one band, got {csrc.count}")
-        conf = np.asarray(csrc.read(1))
-        if conf.dtype != np.uint8:
-            raise ValueError(f"raster_to_polygons: uint8 confidence raster expected, got {conf.dtype}")
-        if conf.shape != data.shape:
-            raise ValueError(f"raster_to_polygons: confidence raster is {conf.shape}, the class raster {data.shape}")
-        if tuple(float(v) for v in csrc.res) != (xres, yres) or _bounds4(csrc) != _bounds4(src):
-            raise ValueError("raster_to_polygons: the confidence raster's bounds / resolution differ from the class "
-                             f"raster's ({_bounds4(csrc)}, {tuple(csrc.res)} vs {_bounds4(src)}, {(xres, yres)})")
+        conf = _confidence_band(_confidence_source(tiff_path, confidence), src, data, "raster_to_polygons")
     min_pixels = min_pixels_for_area(float(min_area), abs(xres * yres))
-    bg = int(background_value) if ignore_background else None
-    if bg is not None and not 0 <= bg <= 255:
-        bg = None  # no uint8 pixel can hold it: every value is a class
+    bg = _background(ignore_background, background_value)
     return _polygon_table(data, conf, left, top, xres, yres, getattr(src, "crs", None), bg, min_pixels, simplification,
                           n_jobs, zone=zone, classes=classes, zone_crs=zone_crs, target_crs=target_crs,
                           sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)), workspace=workspace)
@@ -870,9 +891,7 @@ def rasters_to_polygons(sources, confidence=None, ignore_background: bool = True
         names.append(name)
     xres, yres = (float(v) for v in rasters[0].res)
     H, W, left, top, wins = mosaic_grid([_bounds4(r) for r in rasters], (xres, yres), names)
-    bg = int(background_value) if ignore_background else None
-    if bg is not None and not 0 <= bg <= 255:
-        bg = None
+    bg = _background(ignore_background, background_value)
     covered = sum(h * w for _, _, h, w in wins)
     if covered != H * W and bg is None:
         raise ValueError(f"rasters_to_polygons: the {len(rasters)} sources leave {H * W - covered} pixels of their "
@@ -882,25 +901,13 @@ def rasters_to_polygons(sources, confidence=None, ignore_background: bool = True
     plane = torch.full((H, W), bg if bg is not None else 0, dtype=torch.uint8, device=dev)
     cplane = torch.zeros((H, W), dtype=torch.uint8, device=dev) if conf_args[0] is not None else None
     for s, src, name, carg, (r0, c0, h, w) in zip(sources, rasters, names, conf_args, wins):
-        data = np.asarray(src.read(1))
-        if data.dtype != np.uint8:
-            raise ValueError(f"rasters_to_polygons: {name}: uint8 class raster expected, got {data.dtype}")
-        if data.shape != (h, w):
-            raise ValueError(f"rasters_to_polygons: {name}: {data.shape} pixels, but its bounds and resolution give "
-                             f"{(h, w)}")
+        data = _class_band(src, f"rasters_to_polygons: {name}", (h, w))
         plane[r0:r0 + h, c0:c0 + w] = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
         if cplane is None:
             continue
         if carg is None:
             raise ValueError(f"rasters_to_polygons: {name}: no confidence raster, the other sources have one")
-        csrc = _confidence_source(s, carg)
-        conf = np.asarray(csrc.read(1)) if csrc.count == 1 else None
-        if conf is None or conf.dtype != np.uint8 or conf.shape != data.shape:
-            raise ValueError(f"rasters_to_polygons: {name}: the confidence raster must be one uint8 band of shape "
-                             f"{data.shape}")
-        if tuple(float(v) for v in csrc.res) != (xres, yres) or _bounds4(csrc) != _bounds4(src):
-            raise ValueError(f"rasters_to_polygons: {name}: the confidence raster's bounds / resolution differ from "
-                             "the class raster's")
+        conf = _confidence_band(_confidence_source(s, carg), src, data, f"rasters_to_polygons: {name}")
         cplane[r0:r0 + h, c0:c0 + w] = torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
     min_pixels = min_pixels_for_area(float(min_area), abs(xres * yres))
     return _polygon_table(plane, cplane, left, top, xres, yres, getattr(rasters[0], "crs", None), bg, min_pixels,

@@ -1107,6 +1107,42 @@ def write_window(left, top, img_bounds, out_res, pred_h: int, pred_w: int):
 # --------------------------------------------------------------------------------------------------
 # polygonisation of a class raster (csrc/polygonize.hip, csrc/polygon_simplify.cpp)
 
+def _chk_class_map(classes, background, op: str, contiguous: bool = False) -> None:
+    if not (torch.is_tensor(classes) and classes.is_cuda and classes.dtype == torch.uint8 and classes.dim() == 2
+            and (classes.is_contiguous() or not contiguous)):
+        raise ValueError(f"{op}: a {'contiguous ' if contiguous else ''}CUDA uint8 [H, W] class map expected")
+    if background is not None and not 0 <= int(background) <= 255:
+        raise ValueError(f"{op}: background {background} is not a uint8 value")
+
+
+def _chk_polygonize(classes, background, values, op: str):
+    """the argument checks of both polygonisers; returns ``values`` contiguous (or None)"""
+    _chk_class_map(classes, background, op)
+    H, W = classes.shape
+    if values is None:
+        return None
+    if not (values.is_cuda and values.dtype == torch.uint8 and tuple(values.shape) == (H, W)
+            and values.device == classes.device):
+        raise ValueError(f"{op}: values must be a CUDA uint8 [{H}, {W}] tensor on the device of classes")
+    return values.contiguous()
+
+
+def _polygon_outputs(P: int, R: int, V: int, dev):
+    """the five output tensors for P polygons, R rings and V vertices"""
+    return (torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int64, device=dev),
+            torch.empty(P + 1, dtype=torch.int32, device=dev), torch.empty(R + 1, dtype=torch.int32, device=dev),
+            torch.empty((V, 2), dtype=torch.int32, device=dev))
+
+
+def _with_zonal_sums(out, values, zonal_sum):
+    """``out``, followed when ``values`` are given by the int64 [P] sums that ``zonal_sum(values, P, sums)`` fills"""
+    if values is None:
+        return out
+    sums = torch.empty(out[0].numel(), dtype=torch.int64, device=out[0].device)
+    zonal_sum(values, sums.numel(), sums)
+    return out + (sums,)
+
+
 def polygonize(classes: torch.Tensor, background: Optional[int] = None, min_pixels: int = 1,
                values: Optional[torch.Tensor] = None):
     """Polygons of a device uint8 class map [H, W]: one per 4-connected component of equal class (``background``:
@@ -1118,16 +1154,8 @@ def polygonize(classes: torch.Tensor, background: Optional[int] = None, min_pixe
     With ``values`` (device uint8 [H, W]) a sixth tensor follows: int64 [P], the exact sum of ``values`` over the
     pixels of each polygon (ffa_polygonize_zonal_sum_u8); the first five are the same bytes either way."""
     lib = _l.load()
-    if not (classes.is_cuda and classes.dtype == torch.uint8 and classes.dim() == 2):
-        raise ValueError("polygonize: a CUDA uint8 [H, W] class map expected")
-    if background is not None and not 0 <= int(background) <= 255:
-        raise ValueError(f"polygonize: background {background} is not a uint8 value")
+    values = _chk_polygonize(classes, background, values, "polygonize")
     H, W = classes.shape
-    if values is not None:
-        if not (values.is_cuda and values.dtype == torch.uint8 and tuple(values.shape) == (H, W)
-                and values.device == classes.device):
-            raise ValueError(f"polygonize: values must be a CUDA uint8 [{H}, {W}] tensor on the device of classes")
-        values = values.contiguous()
     if 4 * H * W >= 1 << 31:
         raise ValueError(f"polygonize: a {H} x {W} raster exceeds the limit 4 * H * W < 2^31 (about 536 Mpx per call)")
     classes = classes.contiguous()
@@ -1142,21 +1170,12 @@ def polygonize(classes: torch.Tensor, background: Optional[int] = None, min_pixe
                                       int(max(min_pixels, 0)), ws.data_ptr(), int(nbytes), counts.data_ptr(), st),
              "polygonize_label")
     P, R, V, _ = (int(v) for v in counts.cpu().tolist())
-    poly_class = torch.empty(P, dtype=torch.int32, device=dev)
-    poly_pixels = torch.empty(P, dtype=torch.int64, device=dev)
-    poly_ring_offsets = torch.empty(P + 1, dtype=torch.int32, device=dev)
-    ring_vertex_offsets = torch.empty(R + 1, dtype=torch.int32, device=dev)
-    vertices = torch.empty((V, 2), dtype=torch.int32, device=dev)
-    _l.check(lib.ffa_polygonize_emit(ws.data_ptr(), int(nbytes), H, W, P, R, V, _ptr(poly_class) if P else None,
-                                     _ptr(poly_pixels) if P else None, poly_ring_offsets.data_ptr(),
-                                     ring_vertex_offsets.data_ptr(), _ptr(vertices) if V else None, st),
-             "polygonize_emit")
-    if values is None:
-        return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices
-    sums = torch.empty(P, dtype=torch.int64, device=dev)
-    _l.check(lib.ffa_polygonize_zonal_sum_u8(ws.data_ptr(), int(nbytes), H, W, values.data_ptr(), P,
-                                             _ptr(sums) if P else None, st), "polygonize_zonal_sum_u8")
-    return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices, sums
+    out = _polygon_outputs(P, R, V, dev)
+    # an empty tensor's pointer goes as NULL, which the bound-sized entry points take for "nothing to write"
+    _l.check(lib.ffa_polygonize_emit(ws.data_ptr(), int(nbytes), H, W, P, R, V,
+                                     *(t.data_ptr() if t.numel() else None for t in out), st), "polygonize_emit")
+    return _with_zonal_sums(out, values, lambda v, n, sums: _l.check(lib.ffa_polygonize_zonal_sum_u8(
+        ws.data_ptr(), int(nbytes), H, W, v.data_ptr(), n, _ptr(sums) if n else None, st), "polygonize_zonal_sum_u8"))
 
 
 def _polygonize_size(nbytes: int) -> int:
@@ -1176,17 +1195,8 @@ def polygonize_counted(classes: torch.Tensor, background: Optional[int] = None, 
     before anything sized by E is allocated; a trace workspace beyond the device's free memory is a ValueError as
     well.  With E == 0 or P == 0 no trace is launched and the empty tensors are returned."""
     lib = _l.load()
-    if not (classes.is_cuda and classes.dtype == torch.uint8 and classes.dim() == 2):
-        raise ValueError("polygonize_counted: a CUDA uint8 [H, W] class map expected")
-    if background is not None and not 0 <= int(background) <= 255:
-        raise ValueError(f"polygonize_counted: background {background} is not a uint8 value")
+    values = _chk_polygonize(classes, background, values, "polygonize_counted")
     H, W = classes.shape
-    if values is not None:
-        if not (values.is_cuda and values.dtype == torch.uint8 and tuple(values.shape) == (H, W)
-                and values.device == classes.device):
-            raise ValueError(f"polygonize_counted: values must be a CUDA uint8 [{H}, {W}] tensor on the device of "
-                             "classes")
-        values = values.contiguous()
     if H * W >= 1 << 30:
         raise ValueError(f"polygonize_counted: a {H} x {W} raster exceeds the limit H * W < 2^30 (about 1074 Mpx per "
                          "call)")
@@ -1201,10 +1211,10 @@ def polygonize_counted(classes: torch.Tensor, background: Optional[int] = None, 
                                       ws_px.data_ptr(), px_bytes, counts.data_ptr(), st), "polygonize_count")
     E, P = (int(v) for v in counts[:2].cpu().tolist())
     if E == 0 or P == 0:
-        empty = (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
-                 torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
-                 torch.empty((0, 2), dtype=torch.int32, device=dev))
-        return empty if values is None else empty + (torch.empty(0, dtype=torch.int64, device=dev),)
+        out = _polygon_outputs(0, 0, 0, dev)
+        out[2].zero_()
+        out[3].zero_()
+        return _with_zonal_sums(out, values, lambda v, n, sums: None)
     if E >= (1 << 31) - 1:
         raise ValueError(f"polygonize_counted: the {H} x {W} raster has {E} boundary edges, beyond the limit "
                          "E < 2^31 - 1")
@@ -1220,22 +1230,12 @@ def polygonize_counted(classes: torch.Tensor, background: Optional[int] = None, 
     if (P2, E2) != (P, E):
         raise _l.FlairHipError(f"polygonize_counted: the trace phase counted ({P2}, {E2}) polygons and edges, the "
                                f"count phase ({P}, {E})")
-    poly_class = torch.empty(P, dtype=torch.int32, device=dev)
-    poly_pixels = torch.empty(P, dtype=torch.int64, device=dev)
-    poly_ring_offsets = torch.empty(P + 1, dtype=torch.int32, device=dev)
-    ring_vertex_offsets = torch.empty(R + 1, dtype=torch.int32, device=dev)
-    vertices = torch.empty((V, 2), dtype=torch.int32, device=dev)
+    out = _polygon_outputs(P, R, V, dev)
     _l.check(lib.ffa_polygonize_counted_emit(ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(), tr_bytes, E, P, R, V,
-                                             poly_class.data_ptr(), poly_pixels.data_ptr(),
-                                             poly_ring_offsets.data_ptr(), ring_vertex_offsets.data_ptr(),
-                                             vertices.data_ptr(), st), "polygonize_counted_emit")
-    if values is None:
-        return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices
-    sums = torch.empty(P, dtype=torch.int64, device=dev)
-    _l.check(lib.ffa_polygonize_counted_zonal_sum_u8(ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(), tr_bytes, E,
-                                                     values.data_ptr(), P, sums.data_ptr(), st),
-             "polygonize_counted_zonal_sum_u8")
-    return poly_class, poly_pixels, poly_ring_offsets, ring_vertex_offsets, vertices, sums
+                                             *(t.data_ptr() for t in out), st), "polygonize_counted_emit")
+    return _with_zonal_sums(out, values, lambda v, n, sums: _l.check(lib.ffa_polygonize_counted_zonal_sum_u8(
+        ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(), tr_bytes, E, v.data_ptr(), n, sums.data_ptr(), st),
+        "polygonize_counted_zonal_sum_u8"))
 
 
 def polygon_simplify(xy, ring_vertex_offsets, poly_ring_offsets, tolerance: float, n_threads: int = 1):
@@ -1269,15 +1269,11 @@ def sieve_(classes: torch.Tensor, min_pixels: int, background: Optional[int] = N
     over the rounds, "remaining_small": small components in the raster as it is left -- at convergence those without
     a greater neighbour}.  ``min_pixels`` <= 1 and an empty raster launch nothing."""
     lib = _l.load()
-    if not (torch.is_tensor(classes) and classes.is_cuda and classes.dtype == torch.uint8 and classes.dim() == 2
-            and classes.is_contiguous()):
-        raise ValueError("sieve_: a contiguous CUDA uint8 [H, W] class map expected")
+    _chk_class_map(classes, background, "sieve_", contiguous=True)
     if int(min_pixels) < 0:
         raise ValueError(f"sieve_: min_pixels {min_pixels} is negative")
     if int(max_rounds) < 1:
         raise ValueError(f"sieve_: max_rounds {max_rounds} is below 1")
-    if background is not None and not 0 <= int(background) <= 255:
-        raise ValueError(f"sieve_: background {background} is not a uint8 value")
     H, W = classes.shape
     if 4 * H * W >= 1 << 31:
         raise ValueError(f"sieve_: a {H} x {W} raster exceeds the limit 4 * H * W < 2^31 (about 536 Mpx per call)")

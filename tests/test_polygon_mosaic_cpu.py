@@ -110,6 +110,21 @@ def test_trace_bytes_depends_on_the_counts_alone(lib):
     assert lib.ffa_polygonize_trace_bytes(-1, 0) < 0
 
 
+def test_workspace_bytes_are_pinned(lib):
+    """The exact answers of the four size functions: integrators allocate by them, and a workspace that shrinks under
+    a caller's buffer is not caught by the bounds above.  Numbers from the library built at e65cbdf."""
+    rasters = [(1, 1), (1, 70), (33, 65), (700, 900), (5000, 5000), (23170, 23170)]
+    assert [lib.ffa_polygonize_workspace_bytes(H, W) for H, W in rasters] == [
+        7936, 19712, 400384, 116084480, 4606381056, 98917070336]
+    assert [lib.ffa_sieve_workspace_bytes(H, W) for H, W in rasters] == [
+        1024, 2048, 37120, 10710272, 425000192, 9126432256]
+    assert [lib.ffa_polygonize_count_bytes(H, W) for H, W in rasters + [(25000, 25000), (32768, 32767)]] == [
+        1536, 2560, 35328, 10081280, 400025856, 8590108160, 10000611840, 17180395008]
+    counts = [(0, 0), (4, 1), (4096, 1024), (1_000_003, 17), (130_000_000, 5_000_000), ((1 << 31) - 2, 1 << 29)]
+    assert [lib.ffa_polygonize_trace_bytes(E, P) for E, P in counts] == [
+        6656, 6656, 178688, 42069248, 5468258304, 90330663168]
+
+
 def test_a_full_dalle_fits_sixteen_gib(lib):
     """25 000 x 25 000 pixels at the 0.2 boundary edges per pixel of real land-cover maps"""
     total = lib.ffa_polygonize_count_bytes(25000, 25000) + lib.ffa_polygonize_trace_bytes(130_000_000, 5_000_000)

@@ -84,6 +84,54 @@ def checker(n: int) -> np.ndarray:
     return (np.add.outer(np.arange(n), np.arange(n)) % 2).astype(np.uint8)
 
 
+def timed_reps(x, reps: int, confidence: bool, phases, emit, zonal):
+    """The timed loop of both paths: hip events around each device phase, ``reps`` repetitions after a warm-up one.
+    ``phases``: [(name, prepare)], the label side in order; ``prepare(counts)`` does the host work that precedes its
+    phase (reading what the phase before left in the device tensor ``counts``, allocating) and returns the call to
+    time.  ``emit((P, R, V, E), bufs)`` and ``zonal((P, R, V, E), values, sums)`` are the calls themselves; the zonal
+    sum is timed from the end of emit.  Returns (times in ms by phase name and "emit", "d2h", "zonal"; the counts
+    (P, R, V, E); the five output arrays on the host)."""
+    import torch
+    H, W = x.shape
+    dev = x.device
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    values = torch.randint(0, 256, (H, W), dtype=torch.uint8, device=dev) if confidence else None
+    times = {name: [] for name in [n for n, _ in phases] + ["emit", "d2h", "zonal"]}
+
+    def timed(call):
+        events = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        events[0].record()
+        call()
+        events[1].record()
+        return events
+
+    bufs = None
+    for rep in range(reps + 1):
+        spans = {name: timed(prepare(counts)) for name, prepare in phases}
+        n = P, R, V, E = tuple(int(v) for v in counts.cpu().tolist())
+        del bufs  # the caching allocator serves the next ones from the same blocks
+        bufs = [torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int64, device=dev),
+                torch.empty(P + 1, dtype=torch.int32, device=dev), torch.empty(R + 1, dtype=torch.int32, device=dev),
+                torch.empty((V, 2), dtype=torch.int32, device=dev)]
+        spans["emit"] = timed(lambda: emit(n, bufs))
+        if confidence:
+            sums = torch.empty(P, dtype=torch.int64, device=dev)
+            zonal(n, values, sums)
+            spans["zonal"] = [spans["emit"][1], torch.cuda.Event(enable_timing=True)]  # from the end of emit
+            spans["zonal"][1].record()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = [b.cpu().numpy() for b in bufs]
+        t1 = time.perf_counter()
+        if rep:
+            for name, (e0, e1) in spans.items():
+                times[name].append(e0.elapsed_time(e1))
+            times["d2h"].append((t1 - t0) * 1e3)
+    if confidence:
+        assert int(sums.sum()) == int(values[x != 18].sum(dtype=torch.int64))  # every non-background pixel, once
+    return times, n, out
+
+
 def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_only: bool = False,
         outputs: list = None) -> dict:
     import torch
@@ -92,53 +140,30 @@ def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_
     from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
     lib = L.load()
     H, W = cls.shape
-    dev = torch.device("cuda")
-    x = torch.from_numpy(cls).to(dev)
-    nbytes = lib.ffa_polygonize_workspace_bytes(H, W)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    x = torch.from_numpy(cls).to(torch.device("cuda"))
+    nbytes = int(lib.ffa_polygonize_workspace_bytes(H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     st = torch.cuda.current_stream().cuda_stream
-    res = {"map": name, "H": H, "W": W, "workspace_GB": round(nbytes / 1e9, 3)}
-    t_label, t_emit, t_d2h, t_zonal = [], [], [], []
-    out = None
-    values = torch.randint(0, 256, (H, W), dtype=torch.uint8, device=dev) if confidence else None
-    for rep in range(reps + 1):
-        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-        e0.record()
-        L.check(lib.ffa_polygonize_label(x.data_ptr(), H, W, 18, 1, ws.data_ptr(), int(nbytes), counts.data_ptr(), st))
-        e1.record()
-        P, R, V, E = (int(v) for v in counts.cpu().tolist())
-        bufs = [torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int64, device=dev),
-                torch.empty(P + 1, dtype=torch.int32, device=dev), torch.empty(R + 1, dtype=torch.int32, device=dev),
-                torch.empty((V, 2), dtype=torch.int32, device=dev)]
-        e1b = torch.cuda.Event(enable_timing=True)
-        e1b.record()
-        L.check(lib.ffa_polygonize_emit(ws.data_ptr(), int(nbytes), H, W, P, R, V, bufs[0].data_ptr(),
-                                        bufs[1].data_ptr(), bufs[2].data_ptr(), bufs[3].data_ptr(), bufs[4].data_ptr(),
-                                        st))
-        e2.record()
-        if confidence:
-            sums = torch.empty(P, dtype=torch.int64, device=dev)
-            e3 = torch.cuda.Event(enable_timing=True)
-            L.check(lib.ffa_polygonize_zonal_sum_u8(ws.data_ptr(), int(nbytes), H, W, values.data_ptr(), P,
-                                                    sums.data_ptr() if P else None, st))
-            e3.record()
-        torch.cuda.synchronize()
-        if confidence and rep:
-            t_zonal.append(e2.elapsed_time(e3))
-        t0 = time.perf_counter()
-        out = [b.cpu().numpy() for b in bufs]
-        t1 = time.perf_counter()
-        if rep:
-            t_label.append(e0.elapsed_time(e1))
-            t_emit.append(e1b.elapsed_time(e2))
-            t_d2h.append((t1 - t0) * 1e3)
+
+    def label(counts):
+        return lambda: L.check(lib.ffa_polygonize_label(x.data_ptr(), H, W, 18, 1, ws.data_ptr(), nbytes,
+                                                        counts.data_ptr(), st))
+
+    def emit(n, bufs):
+        L.check(lib.ffa_polygonize_emit(ws.data_ptr(), nbytes, H, W, *n[:3], *(b.data_ptr() for b in bufs), st))
+
+    def zonal(n, values, sums):
+        L.check(lib.ffa_polygonize_zonal_sum_u8(ws.data_ptr(), nbytes, H, W, values.data_ptr(), n[0],
+                                                sums.data_ptr() if n[0] else None, st))
+
+    t, (P, R, V, E), out = timed_reps(x, reps, confidence, [("label", label)], emit, zonal)
     pc, pp, pro, rvo, verts = out
     if outputs is not None:
         outputs[:] = out
-    res.update({"polygons": P, "rings": R, "vertices": V, "edges": E, "label_ms": round(min(t_label), 3),
-                "label_ms_all": [round(t, 3) for t in t_label], "emit_ms": round(min(t_emit), 3),
-                "d2h_ms": round(min(t_d2h), 3)})
+    res = {"map": name, "H": H, "W": W, "workspace_GB": round(nbytes / 1e9, 3), "polygons": P, "rings": R,
+           "vertices": V, "edges": E, "label_ms": round(min(t["label"]), 3),
+           "label_ms_all": [round(v, 3) for v in t["label"]], "emit_ms": round(min(t["emit"]), 3),
+           "d2h_ms": round(min(t["d2h"]), 3)}
     # bytes the label phase cannot avoid: class map (1 B) + labels written, read by counts / edges (3 x 4 B) per pixel,
     # then the compacted edge arrays (eid, succ written; ~log2(E) pointer-jumping rounds read 2 x 4 B and write 2 x 4 B)
     rounds = max(1, int(np.ceil(np.log2(max(4 * H * W, 2)))))
@@ -146,8 +171,7 @@ def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_
     res["label_bytes_lower_bound_GB"] = round(lb / 1e9, 3)
     res["label_ms_at_hbm_rate"] = round(lb / HBM_BYTES_PER_S * 1e3, 3)
     if confidence:
-        assert int(sums.sum()) == int(values[x != 18].sum(dtype=torch.int64))  # every non-background pixel, once
-        res["zonal_sum_ms"] = round(min(t_zonal), 3)
+        res["zonal_sum_ms"] = round(min(t["zonal"]), 3)
         res["zonal_sum_ms_at_hbm_rate"] = round(H * W * 5 / HBM_BYTES_PER_S * 1e3, 3)
     if device_only:
         return res
@@ -173,70 +197,56 @@ def run(name: str, cls: np.ndarray, reps: int, confidence: bool = False, device_
 
 
 def run_counted(name: str, cls: np.ndarray, reps: int, confidence: bool = False, compare=None) -> dict:
-    """The count-sized path (ffa_polygonize_count / _trace / _counted_emit), device stages only: hip events around
-    each phase after a warm-up call, best of ``reps``; "label_ms" = count + trace is what ``run`` calls label_ms.
-    The trace workspace is allocated inside the loop as ops.polygonize_counted does (the caching allocator serves
-    it from the second call on).  ``compare``: the five arrays of ``run`` on the same map, checked for equal bytes."""
+    """The count-sized path (ffa_polygonize_count / _trace / _counted_emit), device stages only: "label_ms" = count +
+    trace is what ``run`` calls label_ms.  The trace workspace is allocated in every repetition as
+    ops.polygonize_counted does (the caching allocator serves it from the second one on).  ``compare``: the five
+    arrays of ``run`` on the same map, checked for equal bytes."""
     import torch
     from flairhip import lib as L
     lib = L.load()
     H, W = cls.shape
-    dev = torch.device("cuda")
-    x = torch.from_numpy(cls).to(dev)
+    x = torch.from_numpy(cls).to(torch.device("cuda"))
     px_bytes = int(lib.ffa_polygonize_count_bytes(H, W))
-    ws_px = torch.empty(px_bytes, dtype=torch.uint8, device=dev)
-    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    ws_px = torch.empty(px_bytes, dtype=torch.uint8, device=x.device)
     st = torch.cuda.current_stream().cuda_stream
-    values = torch.randint(0, 256, (H, W), dtype=torch.uint8, device=dev) if confidence else None
-    t_count, t_trace, t_emit, t_zonal = [], [], [], []
-    for rep in range(reps + 1):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(7)]
-        ev[0].record()
-        L.check(lib.ffa_polygonize_count(x.data_ptr(), H, W, 18, 1, ws_px.data_ptr(), px_bytes, counts.data_ptr(), st))
-        ev[1].record()
+    tr = {}  # of the current repetition: the trace workspace, its size and the edge count it was sized for
+
+    def count(counts):
+        return lambda: L.check(lib.ffa_polygonize_count(x.data_ptr(), H, W, 18, 1, ws_px.data_ptr(), px_bytes,
+                                                        counts.data_ptr(), st))
+
+    def trace(counts):
         E, P = (int(v) for v in counts[:2].cpu().tolist())
-        tr_bytes = int(lib.ffa_polygonize_trace_bytes(E, P))
-        if tr_bytes < 0:
+        tr.clear()
+        nbytes = int(lib.ffa_polygonize_trace_bytes(E, P))
+        if nbytes < 0:
             raise SystemExit(lib.ffa_last_error().decode())
-        ws_tr = torch.empty(tr_bytes, dtype=torch.uint8, device=dev)
-        ev[2].record()
-        L.check(lib.ffa_polygonize_trace(x.data_ptr(), H, W, 1, ws_px.data_ptr(), px_bytes, E, P, ws_tr.data_ptr(),
-                                         tr_bytes, counts.data_ptr(), st))
-        ev[3].record()
-        P, R, V, E = (int(v) for v in counts.cpu().tolist())
-        bufs = [torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int64, device=dev),
-                torch.empty(P + 1, dtype=torch.int32, device=dev), torch.empty(R + 1, dtype=torch.int32, device=dev),
-                torch.empty((V, 2), dtype=torch.int32, device=dev)]
-        ev[4].record()
-        L.check(lib.ffa_polygonize_counted_emit(ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(), tr_bytes, E, P, R,
-                                                V, *(b.data_ptr() for b in bufs), st))
-        ev[5].record()
-        if confidence:
-            sums = torch.empty(P, dtype=torch.int64, device=dev)
-            L.check(lib.ffa_polygonize_counted_zonal_sum_u8(ws_px.data_ptr(), px_bytes, H, W, ws_tr.data_ptr(),
-                                                            tr_bytes, E, values.data_ptr(), P, sums.data_ptr(), st))
-            ev[6].record()
-        torch.cuda.synchronize()
-        if rep:
-            t_count.append(ev[0].elapsed_time(ev[1]))
-            t_trace.append(ev[2].elapsed_time(ev[3]))
-            t_emit.append(ev[4].elapsed_time(ev[5]))
-            if confidence:
-                t_zonal.append(ev[5].elapsed_time(ev[6]))
-        if rep < reps:
-            del ws_tr, bufs
+        tr.update(ws=torch.empty(nbytes, dtype=torch.uint8, device=x.device), bytes=nbytes, E=E)
+        return lambda: L.check(lib.ffa_polygonize_trace(x.data_ptr(), H, W, 1, ws_px.data_ptr(), px_bytes, E, P,
+                                                        tr["ws"].data_ptr(), nbytes, counts.data_ptr(), st))
+
+    def emit(n, bufs):
+        L.check(lib.ffa_polygonize_counted_emit(ws_px.data_ptr(), px_bytes, H, W, tr["ws"].data_ptr(), tr["bytes"],
+                                                tr["E"], *n[:3], *(b.data_ptr() for b in bufs), st))
+
+    def zonal(n, values, sums):
+        L.check(lib.ffa_polygonize_counted_zonal_sum_u8(ws_px.data_ptr(), px_bytes, H, W, tr["ws"].data_ptr(),
+                                                        tr["bytes"], tr["E"], values.data_ptr(), n[0],
+                                                        sums.data_ptr(), st))
+
+    t, (P, R, V, E), out = timed_reps(x, reps, confidence, [("count", count), ("trace", trace)], emit, zonal)
+    tr_bytes = tr["bytes"]
+    label = [a + b for a, b in zip(t["count"], t["trace"])]
     res = {"map": name, "workspace": "counted", "H": H, "W": W, "pixel_workspace_GB": round(px_bytes / 1e9, 3),
            "trace_workspace_GB": round(tr_bytes / 1e9, 3), "workspace_GB": round((px_bytes + tr_bytes) / 1e9, 3),
            "polygons": P, "rings": R, "vertices": V, "edges": E, "edges_per_pixel": round(E / (H * W), 4),
-           "count_ms": round(min(t_count), 3), "trace_ms": round(min(t_trace), 3),
-           "label_ms": round(min(a + b for a, b in zip(t_count, t_trace)), 3),
-           "label_ms_all": [round(a + b, 3) for a, b in zip(t_count, t_trace)], "emit_ms": round(min(t_emit), 3),
-           "jump_rounds": max(1, int(np.ceil(np.log2(max(E, 2)))))}
+           "count_ms": round(min(t["count"]), 3), "trace_ms": round(min(t["trace"]), 3),
+           "label_ms": round(min(label), 3), "label_ms_all": [round(v, 3) for v in label],
+           "emit_ms": round(min(t["emit"]), 3), "jump_rounds": max(1, int(np.ceil(np.log2(max(E, 2)))))}
     if confidence:
-        assert int(sums.sum()) == int(values[x != 18].sum(dtype=torch.int64))
-        res["zonal_sum_ms"] = round(min(t_zonal), 3)
+        res["zonal_sum_ms"] = round(min(t["zonal"]), 3)
     if compare is not None:
-        res["bytes_equal_to_bound_path"] = all(a.tobytes() == b.cpu().numpy().tobytes() for a, b in zip(compare, bufs))
+        res["bytes_equal_to_bound_path"] = all(a.tobytes() == b.tobytes() for a, b in zip(compare, out))
     return res
 
 
