@@ -50,7 +50,7 @@ __device__ long long ffa_ring_trace_buf[1024 * 8];
 
 struct Ring3Args {
   const void* in;
-  const void* w;
+  const void* w;        // ring layout (f32) / ring16 layout (bf16) of conv_pack.hip
   void* out;
   const float* bias;    // [Co] or null
   float* stats;         // [npt][2][Co] per-tile channel sums / sums of squares of the stored output, or null
@@ -1064,207 +1064,6 @@ extern "C" int ffa_ring_conv3x3(int dtype, const void* in, const void* w_ring, c
   FFA_RING_DISPATCH(float)
 #undef FFA_RING_DISPATCH
   return FFA_ERR_UNSUPPORTED;
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight packing for the ring layout:
-//   dst[cb64][chunk][kernel row r][tap s][k-step][row < 64 (fragment order)][half'][elements of 16 B]
-// half' = half ^ bit 3 of the row.  src element (row, ch, r, s) is read at src[row*s_row + ch*s_ch + r*3 + s];
-// flip mirrors the taps (dgrad operand: rows = ci, channels = co).
-
-struct RingPackArgs {
-  const float* src;
-  void* dst;
-  const float* scale;
-  long long s_row, s_ch;
-  int rows, chs;  // valid rows / channels in src
-  int nchunks, ncb64, flip;
-};
-
-template <typename T>
-__device__ __forceinline__ void ring_pack_piece(const RingPackArgs& p, long long i16) {
-  // one thread = one 16-byte piece
-  constexpr int EPF = ElemTraits<T>::kPerFrag;
-  long long t = i16;
-  const int hp = (int)(t % 2); t /= 2;
-  const int row_l = (int)(t % 64); t /= 64;
-  const int ks = (int)(t % 2); t /= 2;
-  const int s = (int)(t % 3); t /= 3;
-  const int r = (int)(t % 3); t /= 3;
-  const int cc = (int)(t % p.nchunks); t /= p.nchunks;
-  const int cb = (int)t;
-  const int mt = row_l >> 5, rho = row_l & 31;
-  const int row = cb * 64 + 16 * (rho >> 3) + 8 * ((rho >> 2) & 1) + 4 * mt + (rho & 3);
-  const int hsrc = hp ^ ((row_l >> 3) & 1);
-  const int ch0 = cc * (4 * EPF) + ks * (2 * EPF) + hsrc * EPF;
-  int rr = r, ss = s;
-  if (p.flip) {
-    rr = 2 - r;
-    ss = 2 - s;
-  }
-  float v[8];
-  const bool row_ok = row < p.rows;
-  const float sc = (row_ok && p.scale) ? p.scale[row] : 1.f;
-  const float* src = p.src + (long long)row * p.s_row + rr * 3 + ss;
-#pragma unroll
-  for (int j = 0; j < EPF; ++j) {
-    const int ch = ch0 + j;
-    v[j] = (row_ok && ch < p.chs) ? src[(long long)ch * p.s_ch] * sc : 0.f;
-  }
-  if constexpr (EPF == 8) {
-    ffa_store8<ffa_bf16>(static_cast<ffa_bf16*>(p.dst) + i16 * 8, v);
-  } else {
-    *reinterpret_cast<float4*>(static_cast<float*>(p.dst) + i16 * 4) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-}
-
-// bf16 operand of conv3x3_ring16_kernel: dst[cb64][chunk][kernel row r][tap s][row < 64][slot' < 4][8 elements],
-// LDS row mt*16 + 4*kg + i holds output channel 16*kg + 4*mt + i of the 64-row group, slot' = slot ^ 2 when bit 2 of
-// the row is set (slot = channels 8*slot .. 8*slot+7 of the 32-channel chunk).  Same bytes per (group, chunk) as the
-// 32x32 layout, so sizes and strides are shared.
-// One thread = one (row, 16-byte slot) of a chunk, all nine taps: it reads 8 channels x 9 contiguous taps of the OIHW
-// master (36-byte runs; a thread per piece touched a 32-byte sector per 4 useful bytes: 287 us per step for the
-// U-Net's operands) and writes its nine pieces, one into each tap plane.  Threads of a block run over the 64 rows first,
-// so the transposed (dgrad) operand -- whose rows are the contiguous axis of the master -- reads whole runs too.
-__device__ __forceinline__ void ring16_pack_rowslot(const RingPackArgs& p, long long idx) {
-  // lanes follow the contiguous axis of the master: (slot, chunk) = consecutive 288-byte runs of one row for the
-  // forward operand [row][ch][tap]; rows = consecutive 36-byte runs for the transposed one [ch][row][tap]
-  long long t = idx;
-  int row_l, sp, cc;
-  if (!p.flip) {
-    sp = (int)(t % 4); t /= 4;
-    cc = (int)(t % p.nchunks); t /= p.nchunks;
-    row_l = (int)(t % 64); t /= 64;
-  } else {
-    row_l = (int)(t % 64); t /= 64;
-    sp = (int)(t % 4); t /= 4;
-    cc = (int)(t % p.nchunks); t /= p.nchunks;
-  }
-  const int cb = (int)t;
-  const int mt = row_l >> 4, kg = (row_l >> 2) & 3, i = row_l & 3;
-  const int row = cb * 64 + 16 * kg + 4 * mt + i;
-  const int slot = sp ^ (((row_l >> 2) & 1) << 1);
-  const int ch0 = cc * 32 + slot * 8;
-  const bool row_ok = row < p.rows;
-  const float sc = (row_ok && p.scale) ? p.scale[row] : 1.f;
-  float v[8][9];
-  if (!p.flip && row_ok && ch0 + 8 <= p.chs && (p.s_row & 3) == 0 && ((size_t)p.src & 15) == 0) {
-    // forward operand: the 8 channels x 9 taps of this thread are 72 CONTIGUOUS floats of the master -> 18 16-byte
-    // loads (a 4-byte load per element made every wave instruction touch 64 cache lines: 171 us per step)
-    const ffa_f32x4* src4 = reinterpret_cast<const ffa_f32x4*>(p.src + (long long)row * p.s_row + (long long)ch0 * 9);
-    float f[72];
-#pragma unroll
-    for (int q = 0; q < 18; ++q) {
-      const ffa_f32x4 t4 = src4[q];
-      f[4 * q] = t4[0]; f[4 * q + 1] = t4[1]; f[4 * q + 2] = t4[2]; f[4 * q + 3] = t4[3];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-      for (int tp = 0; tp < 9; ++tp) v[j][tp] = f[j * 9 + tp] * sc;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int ch = ch0 + j;
-      const bool ok = row_ok && ch < p.chs;
-      const float* src = p.src + (long long)(ok ? row : 0) * p.s_row + (long long)(ok ? ch : 0) * p.s_ch;
-      // destination tap tp reads source tap tp, or 8 - tp for the mirrored (dgrad) operand: the choice goes into the
-      // ADDRESS -- indexing v[][] with a run-time value would send the array to scratch memory
-#pragma unroll
-      for (int tp = 0; tp < 9; ++tp) v[j][tp] = ok ? src[p.flip ? 8 - tp : tp] * sc : 0.f;
-    }
-  }
-  ffa_bf16* dst = static_cast<ffa_bf16*>(p.dst) + ((((long long)cb * p.nchunks + cc) * 9) * 256 + row_l * 4 + sp) * 8;
-#pragma unroll
-  for (int tp = 0; tp < 9; ++tp) {  // destination tap (r, s) = tp
-    float o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = v[j][tp];
-    ffa_store8<ffa_bf16>(dst + (long long)tp * 256 * 8, o);
-  }
-}
-
-__global__ void ring_pack_kernel(RingPackArgs p, int dtype) {
-  if (dtype == FFA_BF16) {
-    const long long total = (long long)p.ncb64 * p.nchunks * 64 * 4;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
-      ring16_pack_rowslot(p, i);
-    return;
-  }
-  const long long total = (long long)p.ncb64 * p.nchunks * 3 * 3 * 2 * 64 * 2;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
-    ring_pack_piece<float>(p, i);
-}
-
-__global__ void ring_pack_batched_kernel(const RingPackArgs* __restrict__ descs, int dtype) {
-  const RingPackArgs p = descs[blockIdx.y];
-  if (dtype == FFA_BF16) {
-    const long long total = (long long)p.ncb64 * p.nchunks * 64 * 4;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
-      ring16_pack_rowslot(p, i);
-    return;
-  }
-  const long long total = (long long)p.ncb64 * p.nchunks * 3 * 3 * 2 * 64 * 2;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
-    ring_pack_piece<float>(p, i);
-}
-
-static int ring_pack_fill(RingPackArgs& p, const float* w_oihw, const float* scale, void* dst, int O, int I,
-                          int transpose, int co_rows, int ci_pitch, int dtype) {
-  FFA_REQUIRE(w_oihw && dst, "ring pack: null pointer");
-  const int eb = (dtype == FFA_BF16) ? 2 : 4;
-  FFA_REQUIRE(co_rows % 64 == 0 && (ci_pitch * eb) % 64 == 0, "ring pack: rows %d / pitch %d not whole groups", co_rows,
-              ci_pitch);
-  memset(&p, 0, sizeof(p));
-  p.src = w_oihw;
-  p.dst = dst;
-  p.scale = scale;
-  if (!transpose) {
-    p.rows = O; p.chs = I;
-    p.s_row = (long long)I * 9;
-    p.s_ch = 9;
-    p.flip = 0;
-  } else {
-    p.rows = I; p.chs = O;
-    p.s_row = 9;
-    p.s_ch = (long long)I * 9;
-    p.flip = 1;
-  }
-  FFA_REQUIRE(p.rows <= co_rows && p.chs <= ci_pitch, "ring pack: padded dims smaller than the tensor");
-  p.nchunks = ci_pitch * eb / 64;
-  p.ncb64 = co_rows / 64;
-  return FFA_OK;
-}
-
-extern "C" int ffa_ring_pack(int dtype, const float* w_oihw, const float* scale, void* dst, int O, int I, int transpose,
-                  int co_rows, int ci_pitch, hipStream_t stream) {
-  RingPackArgs p;
-  const int rc = ring_pack_fill(p, w_oihw, scale, dst, O, I, transpose, co_rows, ci_pitch, dtype);
-  if (rc != FFA_OK) return rc;
-  const long long total = (long long)p.ncb64 * p.nchunks * 3 * 3 * 2 * 64 * 2;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(ring_pack_kernel, dim3(grid), dim3(256), 0, stream, p, dtype);
-  return ffa_check_launch("ring_pack");
-}
-
-extern "C" int ffa_ring_pack_desc_bytes(void) { return (int)sizeof(RingPackArgs); }
-
-extern "C" int ffa_ring_pack_desc_fill(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I,
-                            int transpose, int co_rows, int ci_pitch, int dtype) {
-  FFA_REQUIRE(host_desc, "ring pack: null descriptor");
-  RingPackArgs p;
-  const int rc = ring_pack_fill(p, w_oihw, scale, dst, O, I, transpose, co_rows, ci_pitch, dtype);
-  if (rc != FFA_OK) return rc;
-  memcpy(host_desc, &p, sizeof(p));
-  return FFA_OK;
-}
-
-extern "C" int ffa_ring_pack_batched(int dtype, const void* descs_device, int n, hipStream_t stream) {
-  FFA_REQUIRE(dtype == FFA_BF16 || dtype == FFA_F32, "ring pack: bad dtype");
-  FFA_REQUIRE(descs_device && n > 0 && n <= 65535, "ring pack: bad descriptor table");
-  hipLaunchKernelGGL(ring_pack_batched_kernel, dim3(256, n), dim3(256), 0, stream,
-                     static_cast<const RingPackArgs*>(descs_device), dtype);
-  return ffa_check_launch("ring_pack_batched");
 }
 
 #if FFA_RING_TRACE

@@ -29,7 +29,7 @@
 
 struct ThinArgs {
   const void* in;      // [B][H][W][CI] (UP: [B][H/2][W/2][CI], read at (y >> 1, x >> 1))
-  const void* w;       // thin pack: [mt][k-step][lane][16 B]
+  const void* w;       // thin layout of conv_pack.hip: [mt][k-step][lane][16 B]
   void* out;           // [B][H][W][Co]  (POOL: [B][H/2][W/2][Co], 2x2 sums)
   const float* bias;   // [Co] or null
   const void* res;     // same layout as out, or null
@@ -419,11 +419,6 @@ extern "C" int ffa_thin_eligible(int dtype, int kh, int kw, int stride, int rows
          rows_real > 0 && rows_real <= 32;
 }
 
-extern "C" long long ffa_thin_pack_bytes(int co_rows, int ci_pitch) {
-  const int mt = co_rows / 16, ks = (ci_pitch == 32) ? 9 : 5;
-  return (long long)mt * ks * 1024;
-}
-
 extern "C" long long ffa_thin_stat_rows(int B, int H, int W, int ci_pitch) {
   const int th = (ci_pitch == 32) ? 8 : 16;
   return (long long)B * ffa_cdiv(W, 32) * ffa_cdiv(H, th);
@@ -462,113 +457,4 @@ extern "C" int ffa_thin_conv3x3_pro(const void* in, const void* w_thin, const fl
   a.ntiles = B * a.tiles_x * a.tiles_y;
   if (Ci == 32) return (co_rows == 32) ? thin_launch<32, 2>(a, up, pool, stream) : thin_launch<32, 1>(a, up, pool, stream);
   return (co_rows == 32) ? thin_launch<16, 2>(a, up, pool, stream) : thin_launch<16, 1>(a, up, pool, stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight packing: dst[mt][k-step][lane][8 bf16], lane = (row = lane & 15, kg = lane >> 4)
-//   tile row 4*q + i of tile mt  <->  output channel 8*q + 4*mt + i (two tiles) / 4*q + i (one tile)
-//   32 channels: k-step = tap, elements = channels 8*kg .. 8*kg+7
-//   16 channels: k-step = taps (2*ks, 2*ks + 1); kg >> 1 picks the tap (tap 9 = zeros), kg & 1 the channel half
-// src element (row, ch, tap) at src[row * s_row + ch * s_ch + tap]; flip mirrors the taps (dgrad operand).
-
-struct ThinPackArgs {
-  const float* src;
-  void* dst;
-  const float* scale;
-  long long s_row, s_ch;
-  int rows, chs;  // valid rows / channels in src
-  int mt, ci, flip;
-};
-
-__device__ __forceinline__ void thin_pack_piece(const ThinPackArgs& p, int idx) {
-  const int ks_n = (p.ci == 32) ? 9 : 5;
-  const int lane = idx % 64;
-  const int ks = (idx / 64) % ks_n;
-  const int mt = idx / (64 * ks_n);
-  const int r = lane & 15, kg = lane >> 4;
-  const int q = r >> 2, i = r & 3;
-  const int row = (p.mt == 2) ? (8 * q + 4 * mt + i) : (4 * q + i);
-  int tap, ch0;
-  if (p.ci == 32) {
-    tap = ks;
-    ch0 = 8 * kg;
-  } else {
-    tap = 2 * ks + (kg >> 1);
-    ch0 = 8 * (kg & 1);
-  }
-  float v[8];
-  const bool ok = row < p.rows && tap < 9;
-  const float sc = (ok && p.scale) ? p.scale[row] : 1.f;
-  const int st = p.flip ? 8 - tap : tap;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int ch = ch0 + j;
-    v[j] = (ok && ch < p.chs) ? p.src[(long long)row * p.s_row + (long long)ch * p.s_ch + st] * sc : 0.f;
-  }
-  ffa_store8<ffa_bf16>(static_cast<ffa_bf16*>(p.dst) + (long long)idx * 8, v);
-}
-
-__global__ void thin_pack_kernel(ThinPackArgs p) {
-  const int total = p.mt * ((p.ci == 32) ? 9 : 5) * 64;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) thin_pack_piece(p, i);
-}
-
-__global__ void thin_pack_batched_kernel(const ThinPackArgs* __restrict__ descs) {
-  const ThinPackArgs p = descs[blockIdx.y];
-  const int total = p.mt * ((p.ci == 32) ? 9 : 5) * 64;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) thin_pack_piece(p, i);
-}
-
-static int thin_pack_fill(ThinPackArgs& p, const float* w_oihw, const float* scale, void* dst, int O, int I, int transpose,
-                          int co_rows, int ci_pitch) {
-  FFA_REQUIRE(w_oihw && dst, "thin pack: null pointer");
-  FFA_REQUIRE((co_rows == 16 || co_rows == 32) && (ci_pitch == 16 || ci_pitch == 32), "thin pack: rows %d / pitch %d",
-              co_rows, ci_pitch);
-  memset(&p, 0, sizeof(p));
-  p.src = w_oihw;
-  p.dst = dst;
-  p.scale = scale;
-  if (!transpose) {
-    p.rows = O; p.chs = I;
-    p.s_row = (long long)I * 9;
-    p.s_ch = 9;
-    p.flip = 0;
-  } else {
-    p.rows = I; p.chs = O;
-    p.s_row = 9;
-    p.s_ch = (long long)I * 9;
-    p.flip = 1;
-  }
-  FFA_REQUIRE(p.rows <= co_rows && p.chs <= ci_pitch, "thin pack: padded dims smaller than the tensor");
-  p.mt = co_rows / 16;
-  p.ci = ci_pitch;
-  return FFA_OK;
-}
-
-extern "C" int ffa_thin_pack(const float* w_oihw, const float* scale, void* dst, int O, int I, int transpose, int co_rows,
-                             int ci_pitch, hipStream_t stream) {
-  ThinPackArgs p;
-  const int rc = thin_pack_fill(p, w_oihw, scale, dst, O, I, transpose, co_rows, ci_pitch);
-  if (rc != FFA_OK) return rc;
-  hipLaunchKernelGGL(thin_pack_kernel, dim3(5), dim3(256), 0, stream, p);
-  return ffa_check_launch("thin_pack");
-}
-
-extern "C" int ffa_thin_pack_desc_bytes(void) { return (int)sizeof(ThinPackArgs); }
-
-extern "C" int ffa_thin_pack_desc_fill(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I,
-                                       int transpose, int co_rows, int ci_pitch) {
-  FFA_REQUIRE(host_desc, "thin pack: null descriptor");
-  ThinPackArgs p;
-  const int rc = thin_pack_fill(p, w_oihw, scale, dst, O, I, transpose, co_rows, ci_pitch);
-  if (rc != FFA_OK) return rc;
-  memcpy(host_desc, &p, sizeof(p));
-  return FFA_OK;
-}
-
-extern "C" int ffa_thin_pack_batched(const void* descs_device, int n, hipStream_t stream) {
-  FFA_REQUIRE(descs_device && n > 0 && n <= 65535, "thin pack: bad descriptor table");
-  hipLaunchKernelGGL(thin_pack_batched_kernel, dim3(5, n), dim3(256), 0, stream,
-                     static_cast<const ThinPackArgs*>(descs_device));
-  return ffa_check_launch("thin_pack_batched");
 }

@@ -18,33 +18,17 @@
 //     BatchNorm batch statistics of the stored values (per-tile partial rows for ffa_bn_finalize).
 #include "ffa_gfx950.h"
 
+#include "conv7x7_stem.h"
+
 struct StemArgs {
   const void* in;   // [B][Hi][Wi][16] bf16
-  const void* w;    // operand packed by ffa_stem_pack
+  const void* w;    // stem layout of conv_pack.hip
   void* out;        // [B][Ho][Wo][Co] bf16
   const float* bias;
   float* stats;     // [npt][2][Co] or null
   int B, Hi, Wi, Ho, Wo, Co;
   int relu;
   int tiles_x, tiles_y, npt;
-};
-
-struct StemGeom {
-  static constexpr int TH = 16, TW = 32, NW = 8, NTHR = 512;
-  static constexpr int IH = 2 * TH + 5;           // 37 input rows
-  static constexpr int IWH = 36;                  // pixel pairs per row and parity (2 * TW + 5 = 69 columns)
-  static constexpr int ROWP = 2 * IWH;            // 16-byte pieces per halo row: [parity][IWH]
-  static constexpr int HP = IH * ROWP;            // 2664 pieces
-  static constexpr int NHW = (HP + NTHR - 1) / NTHR;
-  static constexpr int HBYTES = HP * 16;
-  static constexpr int KSTEPS = 14;
-  static constexpr int WBYTES = KSTEPS * 4096;    // [k-step][64 rows][64 B]
-  static constexpr int WP = WBYTES / 16;
-  static constexpr int W_OFF = 0, H_OFF = WBYTES, RED_OFF = WBYTES + 2 * HBYTES;
-  static constexpr int RED_BYTES = NW * 64 * 2 * 4;
-  static constexpr int LDS_BYTES = RED_OFF + RED_BYTES;
-  static_assert(WP % NTHR == 0, "every thread issues the same number of weight pieces");
-  static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
 __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
@@ -255,53 +239,12 @@ __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
   ffa_wait_vm<0>();  // nothing of this block may still be writing its LDS
 }
 
-// ---- weight packing: dst[k-step = r * 2 + half][LDS row rho][slot'][8 channels] (bf16), LDS row rho = mt * 16 + 4 * q + i
-//      holds output channel 16 * q + 4 * mt + i (so that an accumulator lane ends up with 16 consecutive channels), slot =
-//      tap 4 * half + slot of kernel row r (tap 7: zeros), slot' = slot ^ 2 when bit 2 of rho ----
-__global__ void stem_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, unsigned short* __restrict__ dst,
-                                 int O, int I) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // one thread = one 16-byte slot
-  if (i >= StemGeom::KSTEPS * 64 * 4) return;
-  const int slotp = i & 3, rho = (i >> 2) & 63, ks = i >> 8;
-  const int slot = slotp ^ (((rho >> 2) & 1) << 1);
-  const int r = ks >> 1, s = 4 * (ks & 1) + slot;
-  const int mt = rho >> 4, q = (rho >> 2) & 3, ii = rho & 3;
-  const int co = 16 * q + 4 * mt + ii;
-  unsigned short v[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    float x = 0.f;
-    if (co < O && c < I && s < 7) {
-      x = w[((size_t)(co * I + c) * 7 + r) * 7 + s];
-      if (scale) x *= scale[co];
-    }
-    v[c] = ffa_f32_to_bf16_bits(x);
-  }
-  uint4 u;
-  u.x = v[0] | ((unsigned)v[1] << 16);
-  u.y = v[2] | ((unsigned)v[3] << 16);
-  u.z = v[4] | ((unsigned)v[5] << 16);
-  u.w = v[6] | ((unsigned)v[7] << 16);
-  reinterpret_cast<uint4*>(dst)[i] = u;
-}
-
 extern "C" int ffa_stem_eligible(int dtype, int kh, int kw, int stride, int cout, int ci_pitch) {
   return dtype == FFA_BF16 && kh == 7 && kw == 7 && stride == 2 && cout == 64 && ci_pitch == 16;
 }
 
-extern "C" long long ffa_stem_pack_bytes(void) { return StemGeom::WBYTES; }
-
 extern "C" long long ffa_stem_stat_rows(int B, int Ho, int Wo) {
   return (long long)B * ffa_cdiv(Wo, StemGeom::TW) * ffa_cdiv(Ho, StemGeom::TH);
-}
-
-// w_oihw [O = 64][I <= 8][7][7] f32 -> the kernel's operand; scale (optional, per output channel) folds an eval-mode BatchNorm
-extern "C" int ffa_stem_pack(const float* w_oihw, const float* scale, void* dst, int O, int I, hipStream_t stream) {
-  FFA_REQUIRE(w_oihw && dst && O > 0 && O <= 64 && I > 0 && I <= 8, "stem pack: 1..64 output and 1..8 input channels, got %d / %d", O, I);
-  const int n = StemGeom::KSTEPS * 64 * 4;
-  hipLaunchKernelGGL(stem_pack_kernel, dim3(ffa_cdiv(n, 256)), dim3(256), 0, stream, w_oihw, scale,
-                     static_cast<unsigned short*>(dst), O, I);
-  return ffa_check_launch("stem_pack");
 }
 
 // in [B][Hi][Wi][16] bf16 (channels >= 8 are never read; pad channels must be zero), out [B][Ho][Wo][Co] with

@@ -47,7 +47,7 @@ __device__ long long ffa_conv_trace_buf[64 * 256];
 
 struct ConvArgs {
   const void* in;
-  const void* w;
+  const void* w;      // conv_igemm layout of conv_pack.hip: [cb][cc][rg][row < BCO][tap < RG*KW][32 B]
   void* out;
   const float* bias;  // [>= co block coverage] or null
   float* stats;       // [npt][2][Co] per-tile channel sums / sums of squares of the stored output, or null
@@ -1448,250 +1448,6 @@ extern "C" int ffa_conv2d_dgrad_upcat(int dtype, const void* dy, const void* w_p
   }
   return conv2d_impl(dtype, dy, w_packed_t, nullptr, nullptr, dlo, nullptr, B, Ho, Wo, Cdy, Ho, Wo, C1 + C2, co_rows,
                      bco, 3, 3, 1, 1, 1, 0, stream, dskip, C1);
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight packing: OIHW f32 master weights -> per-(co block, chunk, row group) LDS-image slabs
-//   dst[cb][cc][rg][row < BCO][tap < RG*KW][e < 32/sizeof(T)]
-// src element (row, ch, r, s) is read at src[row*s_row + ch*s_ch + r*KW + s]; flip mirrors the taps
-// (dgrad: rows = ci, ch = co, flipped).  scale[row] (optional) folds an eval-mode BN into the weights.
-
-struct PackArgs {
-  const float* src;
-  void* dst;
-  const float* scale;
-  long long s_row, s_ch;
-  int rows, chs;  // valid rows / channels in src
-  int kh, kw, rg, bco, nchunks, ncb, flip;
-};
-
-template <typename T>
-__global__ void pack_weight_kernel(PackArgs p) {
-  constexpr int EPC = ElemTraits<T>::kPerStep;
-  const int taps = p.rg * p.kw;
-  const int nrg = p.kh / p.rg;
-  const long long total = (long long)p.ncb * p.nchunks * nrg * p.bco * taps * EPC;
-  T* dst = static_cast<T*>(p.dst);
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    long long t = i;
-    const int e = t % EPC; t /= EPC;
-    const int tap = t % taps; t /= taps;
-    const int row_l = t % p.bco; t /= p.bco;
-    const int rg = t % nrg; t /= nrg;
-    const int cc = t % p.nchunks; t /= p.nchunks;
-    const int cb = (int)t;
-    int row_in_block = row_l;
-    if (p.bco >= 64) {  // fragment order inside each 64-row wave group (see conv_igemm_kernel)
-      const int j = row_l & 63, mt = j >> 5, rho = j & 31;
-      row_in_block = (row_l & ~63) + 16 * (rho >> 3) + 8 * ((rho >> 2) & 1) + 4 * mt + (rho & 3);
-    }
-    const int row = cb * p.bco + row_in_block;
-    const int ch = cc * EPC + e;
-    int r = rg * p.rg + tap / p.kw;
-    int s = tap % p.kw;
-    float v = 0.f;
-    if (row < p.rows && ch < p.chs) {
-      if (p.flip) {
-        r = p.kh - 1 - r;
-        s = p.kw - 1 - s;
-      }
-      v = p.src[row * p.s_row + ch * p.s_ch + r * p.kw + s];
-      if (p.scale) v *= p.scale[row];
-    }
-    ffa_store_elem<T>(dst + i, v);
-  }
-}
-
-extern "C" long long ffa_pack_conv_weight_bytes(int dtype, int co_rows, int ci_pitch, int kh, int kw) {
-  const long long eb = (dtype == FFA_BF16) ? 2 : 4;
-  return (long long)co_rows * ci_pitch * kh * kw * eb;
-}
-
-// co_rows / ci_pitch: padded row count (multiple of the block size from ffa_conv_block_co) and the
-// channel pitch of the activation the conv will read.  transpose=1 builds the dgrad operand from the
-// same OIHW tensor (rows = input channels, channels = output channels, taps mirrored).
-extern "C" int ffa_pack_conv_weight(int dtype, const float* w_oihw, const float* scale, void* dst, int O, int I,
-                                    int kh, int kw, int transpose, int co_rows, int ci_pitch, int bco, int rg,
-                                    hipStream_t stream) {
-  FFA_REQUIRE(dtype == FFA_BF16 || dtype == FFA_F32, "pack: bad dtype");
-  FFA_REQUIRE(w_oihw && dst, "pack: null pointer");
-  if (bco & FFA_BCO_STEM) {
-    FFA_REQUIRE(kh == 7 && kw == 7 && dtype == FFA_BF16 && !transpose, "pack: the stem layout is for the bf16 7x7 forward operand");
-    return ffa_stem_pack(w_oihw, scale, dst, O, I, stream);
-  }
-  if (bco & FFA_BCO_THIN) {
-    FFA_REQUIRE(kh == 3 && kw == 3 && dtype == FFA_BF16, "pack: the thin layout is for bf16 3x3 kernels");
-    return ffa_thin_pack(w_oihw, scale, dst, O, I, transpose, co_rows, ci_pitch, stream);
-  }
-  if (bco & FFA_BCO_RING) {
-    FFA_REQUIRE(kh == 3 && kw == 3, "pack: the ring layout is for 3x3 kernels");
-    return ffa_ring_pack(dtype, w_oihw, scale, dst, O, I, transpose, co_rows, ci_pitch, stream);
-  }
-  FFA_REQUIRE(bco > 0 && co_rows % bco == 0, "pack: rows %d not a multiple of block %d", co_rows, bco);
-  FFA_REQUIRE(rg > 0 && kh % rg == 0, "pack: bad row group");
-  const int epc = (dtype == FFA_BF16) ? 16 : 8;
-  FFA_REQUIRE(ci_pitch % 16 == 0, "pack: channel pitch must be a multiple of 16");
-  PackArgs p;
-  p.src = w_oihw;
-  p.dst = dst;
-  p.scale = scale;
-  if (!transpose) {
-    p.rows = O; p.chs = I;
-    p.s_row = (long long)I * kh * kw;
-    p.s_ch = (long long)kh * kw;
-    p.flip = 0;
-  } else {
-    p.rows = I; p.chs = O;
-    p.s_row = (long long)kh * kw;
-    p.s_ch = (long long)I * kh * kw;
-    p.flip = 1;
-  }
-  FFA_REQUIRE(p.rows <= co_rows && p.chs <= ci_pitch, "pack: padded dims smaller than the tensor");
-  p.kh = kh; p.kw = kw; p.rg = rg; p.bco = bco;
-  p.nchunks = ci_pitch / epc;
-  p.ncb = co_rows / bco;
-  const long long total = (long long)co_rows * ci_pitch * kh * kw;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  if (dtype == FFA_BF16)
-    hipLaunchKernelGGL(pack_weight_kernel<ffa_bf16>, dim3(grid), dim3(256), 0, stream, p);
-  else
-    hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(grid), dim3(256), 0, stream, p);
-  return ffa_check_launch("pack_weight");
-}
-
-// ------------------------------------------------------------------------------------------------
-// batched packing: every conv weight of the network (forward and dgrad operands) in ONE launch per step.
-// The descriptor table lives in device memory and is built once (ffa_pack_desc_fill on the host, then copied);
-// blockIdx.y selects the descriptor, blockIdx.x strides over its elements.
-
-// one thread = eight consecutive channels of one (row, tap): the index arithmetic (seven divisions by run-time
-// values) is paid once per 16-byte store instead of once per element (201 -> ~50 us for the 186 operands of the
-// U-Net at batch time)
-__device__ __forceinline__ void pack_eight(const PackArgs& p, long long i8, int dtype) {
-  const int EPC = (dtype == FFA_BF16) ? 16 : 8;
-  const int G8 = EPC / 8;
-  const int taps = p.rg * p.kw;
-  const int nrg = p.kh / p.rg;
-  long long t = i8;
-  const int e0 = (int)(t % G8) * 8; t /= G8;
-  const int tap = t % taps; t /= taps;
-  const int row_l = t % p.bco; t /= p.bco;
-  const int rg = t % nrg; t /= nrg;
-  const int cc = t % p.nchunks; t /= p.nchunks;
-  const int cb = (int)t;
-  int row_in_block = row_l;
-  if (p.bco >= 64) {
-    const int j = row_l & 63, mt = j >> 5, rho = j & 31;
-    row_in_block = (row_l & ~63) + 16 * (rho >> 3) + 8 * ((rho >> 2) & 1) + 4 * mt + (rho & 3);
-  }
-  const int row = cb * p.bco + row_in_block;
-  const int ch0 = cc * EPC + e0;
-  int r = rg * p.rg + tap / p.kw;
-  int sx = tap % p.kw;
-  if (p.flip) {
-    r = p.kh - 1 - r;
-    sx = p.kw - 1 - sx;
-  }
-  float v[8];
-  const bool row_ok = row < p.rows;
-  const float sc = (row_ok && p.scale) ? p.scale[row] : 1.f;
-  const float* src = p.src + (long long)row * p.s_row + r * p.kw + sx;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int ch = ch0 + j;
-    v[j] = (row_ok && ch < p.chs) ? src[(long long)ch * p.s_ch] * sc : 0.f;
-  }
-  if (dtype == FFA_BF16)
-    ffa_store8<ffa_bf16>(static_cast<ffa_bf16*>(p.dst) + i8 * 8, v);
-  else
-    ffa_store8<float>(static_cast<float*>(p.dst) + i8 * 8, v);
-}
-
-__global__ void pack_weight_batched_kernel(const PackArgs* __restrict__ descs, int dtype) {
-  const PackArgs p = descs[blockIdx.y];
-  const int EPC = (dtype == FFA_BF16) ? 16 : 8;
-  const long long total8 = (long long)p.ncb * p.nchunks * (p.kh / p.rg) * p.bco * (p.rg * p.kw) * (EPC / 8);
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8;
-       i += (long long)gridDim.x * blockDim.x)
-    pack_eight(p, i, dtype);
-}
-
-extern "C" int ffa_pack_desc_bytes(void) { return (int)sizeof(PackArgs); }
-
-// Fills one HOST descriptor (same arguments as ffa_pack_conv_weight, pointers are device pointers).
-extern "C" int ffa_pack_desc_fill(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I,
-                                  int kh, int kw, int transpose, int co_rows, int ci_pitch, int bco, int rg,
-                                  int dtype) {
-  FFA_REQUIRE(host_desc && w_oihw && dst, "pack_desc_fill: null pointer");
-  FFA_REQUIRE(bco > 0 && co_rows % bco == 0 && rg > 0 && kh % rg == 0 && ci_pitch % 16 == 0,
-              "pack_desc_fill: bad geometry");
-  PackArgs p;
-  memset(&p, 0, sizeof(p));
-  p.src = w_oihw;
-  p.dst = dst;
-  p.scale = scale;
-  if (!transpose) {
-    p.rows = O; p.chs = I;
-    p.s_row = (long long)I * kh * kw;
-    p.s_ch = (long long)kh * kw;
-    p.flip = 0;
-  } else {
-    p.rows = I; p.chs = O;
-    p.s_row = (long long)kh * kw;
-    p.s_ch = (long long)I * kh * kw;
-    p.flip = 1;
-  }
-  FFA_REQUIRE(p.rows <= co_rows && p.chs <= ci_pitch, "pack_desc_fill: padded dims smaller than the tensor");
-  p.kh = kh; p.kw = kw; p.rg = rg; p.bco = bco;
-  p.nchunks = ci_pitch / ((dtype == FFA_BF16) ? 16 : 8);
-  p.ncb = co_rows / bco;
-  memcpy(host_desc, &p, sizeof(p));
-  return FFA_OK;
-}
-
-// The same descriptor for the column block W[:, col0 : col0 + ncols] of a weight with I_total input channels (one
-// modality's share of a FusionHandler 1x1 convolution, flair_hub/models/flair_model.py:470-475): the source strides
-// stay those of the whole tensor, so the slices of every stage ride in the batched pack instead of one copy + one
-// pack launch each.
-extern "C" int ffa_pack_desc_fill_cols(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O,
-                                       int I_total, int col0, int ncols, int kh, int kw, int transpose, int co_rows,
-                                       int ci_pitch, int bco, int rg, int dtype) {
-  FFA_REQUIRE(host_desc && w_oihw && dst, "pack_desc_fill_cols: null pointer");
-  FFA_REQUIRE(col0 >= 0 && ncols > 0 && col0 + ncols <= I_total, "pack_desc_fill_cols: column block outside the tensor");
-  FFA_REQUIRE(bco > 0 && co_rows % bco == 0 && rg > 0 && kh % rg == 0 && ci_pitch % 16 == 0,
-              "pack_desc_fill_cols: bad geometry");
-  PackArgs p;
-  memset(&p, 0, sizeof(p));
-  p.src = w_oihw + (long long)col0 * kh * kw;
-  p.dst = dst;
-  p.scale = scale;
-  if (!transpose) {
-    p.rows = O; p.chs = ncols;
-    p.s_row = (long long)I_total * kh * kw;
-    p.s_ch = (long long)kh * kw;
-    p.flip = 0;
-  } else {
-    p.rows = ncols; p.chs = O;
-    p.s_row = (long long)kh * kw;
-    p.s_ch = (long long)I_total * kh * kw;
-    p.flip = 1;
-  }
-  FFA_REQUIRE(p.rows <= co_rows && p.chs <= ci_pitch, "pack_desc_fill_cols: padded dims smaller than the block");
-  p.kh = kh; p.kw = kw; p.rg = rg; p.bco = bco;
-  p.nchunks = ci_pitch / ((dtype == FFA_BF16) ? 16 : 8);
-  p.ncb = co_rows / bco;
-  memcpy(host_desc, &p, sizeof(p));
-  return FFA_OK;
-}
-
-extern "C" int ffa_pack_conv_weights_batched(int dtype, const void* descs_device, int n, hipStream_t stream) {
-  FFA_REQUIRE(dtype == FFA_BF16 || dtype == FFA_F32, "pack_batched: bad dtype");
-  FFA_REQUIRE(descs_device && n > 0 && n <= 65535, "pack_batched: bad descriptor table");
-  // 256 blocks per descriptor: the largest operands (2.4 M elements) set the tail, small ones exit at once
-  hipLaunchKernelGGL(pack_weight_batched_kernel, dim3(256, n), dim3(256), 0, stream,
-                     static_cast<const PackArgs*>(descs_device), dtype);
-  return ffa_check_launch("pack_weight_batched");
 }
 
 #if FFA_CONV_TRACE

@@ -56,37 +56,25 @@ SIGNATURES = {
     "ffa_target_arch": (C.c_char_p, []),
     "ffa_conv_block_co": (_i, [_i, _i, _i, _i]),
     "ffa_conv_row_group": (_i, [_i]),
-    "ffa_pack_conv_weight_bytes": (_ll, [_i, _i, _i, _i, _i]),
+    "ffa_pack_conv_weight_bytes": (_ll, [_i] * 6),
     "ffa_pack_conv_weight": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "ffa_pack_desc_bytes": (_i, []),
-    "ffa_pack_desc_fill": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "ffa_pack_desc_fill_cols": (_i, [_p, _p, _p, _p] + [_i] * 12),
-    "ffa_pack_conv_weights_batched": (_i, [_i, _p, _i, _p]),
+    "ffa_pack_desc_fill": (_i, [_p, _p, _p, _p] + [_i] * 12),
+    "ffa_pack_conv_weights_batched": (_i, [_i, _i, _p, _i, _p]),
     "ffa_conv2d": (_i, [_i, _p, _p, _p, _p, _p] + [_i] * 15 + [_p]),
     "ffa_conv_stat_rows": (_ll, [_i, _i, _i, _i, _i]),
     "ffa_conv_plan": (_i, [_i] * 7),
     "ffa_ring_conv3x3": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 7 + [_p]),
     "ffa_ring_stat_rows": (_ll, [_i, _i, _i, _i]),
-    "ffa_ring_pack": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ffa_conv2d_pro": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 9 + [_p]),
     "ffa_conv_wgrad_pro": (_i, [_i, _p, _p, _p, _p, _p] + [_i] * 11 + [_p, _ll, _p]),
     "ffa_thin_eligible": (_i, [_i] * 6),
     "ffa_stem_eligible": (_i, [_i] * 6),
-    "ffa_stem_pack_bytes": (_ll, []),
     "ffa_stem_stat_rows": (_ll, [_i, _i, _i]),
-    "ffa_stem_pack": (_i, [_p, _p, _p, _i, _i, _p]),
     "ffa_stem_conv7x7": (_i, [_p, _p, _p, _p, _p] + [_i] * 8 + [_p]),
     "ffa_thin_stat_rows": (_ll, [_i, _i, _i, _i]),
     "ffa_thin_conv3x3": (_i, [_p, _p, _p, _p, _p, _p] + [_i] * 9 + [_p]),
     "ffa_thin_conv3x3_pro": (_i, [_p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 9 + [_p]),
-    "ffa_thin_pack": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "ffa_thin_pack_bytes": (_ll, [_i, _i]),
-    "ffa_thin_pack_desc_bytes": (_i, []),
-    "ffa_thin_pack_desc_fill": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i]),
-    "ffa_thin_pack_batched": (_i, [_p, _i, _p]),
-    "ffa_ring_pack_desc_bytes": (_i, []),
-    "ffa_ring_pack_desc_fill": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),
-    "ffa_ring_pack_batched": (_i, [_i, _p, _i, _p]),
     "ffa_conv2d_stats": (_i, [_i, _p, _p, _p, _p, _p, _p] + [_i] * 15 + [_p]),
     "ffa_conv2d_bnbwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 14 + [_p]),
     "ffa_bn_bwd_partials": (_i, [_i, _p, _p, _p, _ll, _p, _p, _p, _p, _p, _p, _p, _ll, _i, _p, _ll, _p]),

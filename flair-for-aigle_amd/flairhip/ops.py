@@ -115,11 +115,7 @@ def pack_conv_weight(w_oihw: torch.Tensor, dtype: torch.dtype, stride: int, ci_p
     blk = bco & 0xFFF
     rows = (rows_real + blk - 1) // blk * blk
     rg = lib.ffa_conv_row_group(kh)
-    nbytes = lib.ffa_pack_conv_weight_bytes(did, rows, ci_pitch, kh, kw)
-    if bco & _l.BCO_THIN:
-        nbytes = lib.ffa_thin_pack_bytes(rows, ci_pitch)
-    if bco & _l.BCO_STEM:
-        nbytes = lib.ffa_stem_pack_bytes()
+    nbytes = lib.ffa_pack_conv_weight_bytes(did, rows, ci_pitch, kh, kw, bco)
     dst = torch.empty(nbytes // (2 if dtype == torch.bfloat16 else 4), dtype=dtype, device=w_oihw.device)
     _l.check(lib.ffa_pack_conv_weight(did, w_oihw.data_ptr(), _ptr(scale), dst.data_ptr(), O, I, kh, kw,
                                       1 if transpose else 0, rows, ci_pitch, bco, rg, _stream()), "pack_conv_weight")
@@ -127,78 +123,38 @@ def pack_conv_weight(w_oihw: torch.Tensor, dtype: torch.dtype, stride: int, ci_p
 
 
 class PackBatch:
-    """Descriptor tables for ffa_pack_conv_weights_batched / ffa_ring_pack_batched: re-packs many conv operands in one
-    launch per layout.
+    """Descriptor tables for ffa_pack_conv_weights_batched: re-packs many conv operands in one launch per layout.
 
     entries: (master weight OIHW f32, PackedWeight it feeds, transpose flag[, (first column, columns)]).  A column block
-    belongs to a 1x1 fusion weight, and ffa_conv_plan gives a 1x1 operand no other layout than conv_igemm's, so only
-    that table knows column blocks.  The tables hold raw device pointers, so they must be rebuilt when a parameter or
-    a packed buffer is re-allocated."""
+    belongs to a 1x1 fusion weight, and ffa_conv_plan gives a 1x1 operand no other layout than conv_igemm's (the only
+    one ffa_pack_desc_fill takes a block for).  The tables hold raw device pointers, so they must be rebuilt when a
+    parameter or a packed buffer is re-allocated."""
 
     def __init__(self, entries, dtype: torch.dtype):
         lib = _l.load()
         self.dtype_id = _dtype_id(dtype)
         self.keep = []
-        plain = [e for e in entries if not (e[1].bco & (_l.BCO_RING | _l.BCO_THIN | _l.BCO_STEM))]
-        self.stem = [e for e in entries if e[1].bco & _l.BCO_STEM]  # one operand per encoder: packed by its own small launch
-        ring = [e for e in entries if e[1].bco & _l.BCO_RING]
-        thin = [e for e in entries if e[1].bco & _l.BCO_THIN]
-        self.n, self.table = len(plain), None
-        self.n_ring, self.table_ring = len(ring), None
-        self.n_thin, self.table_thin = len(thin), None
+        nb = lib.ffa_pack_desc_bytes()
+        desc = C.create_string_buffer(nb)
+        hosts = {}  # layout bits of bco -> the descriptors of that layout, back to back
+        for e in entries:
+            w, pw, transpose = e[:3]
+            O, I, kh, kw = w.shape
+            off, c = e[3] if len(e) > 3 else (0, I)  # column block W[:, off : off + c] of a fusion 1x1 weight
+            _l.check(lib.ffa_pack_desc_fill(C.addressof(desc), w.data_ptr(), None, pw.data.data_ptr(), O, I, off, c, kh, kw,
+                                            1 if transpose else 0, pw.rows, pw.ci_pitch, pw.bco,
+                                            lib.ffa_conv_row_group(kh), self.dtype_id), "pack_desc_fill")
+            hosts.setdefault(pw.bco & (_l.BCO_RING | _l.BCO_THIN | _l.BCO_STEM), bytearray()).extend(desc.raw)
+            self.keep.append((w, pw))
         dev = entries[0][0].device
-        if plain:
-            nb = lib.ffa_pack_desc_bytes()
-            host = C.create_string_buffer(nb * len(plain))
-            base = C.addressof(host)
-            for i, e in enumerate(plain):
-                w, pw, transpose = e[:3]
-                O, I, kh, kw = w.shape
-                if len(e) > 3:  # column block W[:, off : off + c] of a fusion 1x1 weight
-                    off, c = e[3]
-                    _l.check(lib.ffa_pack_desc_fill_cols(base + i * nb, w.data_ptr(), None, pw.data.data_ptr(), O, I, off, c,
-                                                         kh, kw, 1 if transpose else 0, pw.rows, pw.ci_pitch, pw.bco,
-                                                         lib.ffa_conv_row_group(kh), self.dtype_id), "pack_desc_fill_cols")
-                else:
-                    _l.check(lib.ffa_pack_desc_fill(base + i * nb, w.data_ptr(), None, pw.data.data_ptr(), O, I, kh, kw,
-                                                    1 if transpose else 0, pw.rows, pw.ci_pitch, pw.bco,
-                                                    lib.ffa_conv_row_group(kh), self.dtype_id), "pack_desc_fill")
-                self.keep.append((w, pw))
-            self.table = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(dev)
-        if ring:
-            nb = lib.ffa_ring_pack_desc_bytes()
-            host = C.create_string_buffer(nb * len(ring))
-            base = C.addressof(host)
-            for i, (w, pw, transpose) in enumerate(ring):
-                O, I, kh, kw = w.shape
-                _l.check(lib.ffa_ring_pack_desc_fill(base + i * nb, w.data_ptr(), None, pw.data.data_ptr(), O, I,
-                                                     1 if transpose else 0, pw.rows, pw.ci_pitch, self.dtype_id),
-                         "ring_pack_desc_fill")
-                self.keep.append((w, pw))
-            self.table_ring = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(dev)
-        if thin:
-            nb = lib.ffa_thin_pack_desc_bytes()
-            host = C.create_string_buffer(nb * len(thin))
-            base = C.addressof(host)
-            for i, (w, pw, transpose) in enumerate(thin):
-                O, I, kh, kw = w.shape
-                _l.check(lib.ffa_thin_pack_desc_fill(base + i * nb, w.data_ptr(), None, pw.data.data_ptr(), O, I,
-                                                     1 if transpose else 0, pw.rows, pw.ci_pitch), "thin_pack_desc_fill")
-                self.keep.append((w, pw))
-            self.table_thin = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(dev)
+        self.tables = [(layout, torch.frombuffer(host, dtype=torch.uint8).to(dev), len(host) // nb)
+                       for layout, host in hosts.items()]
 
     def run(self) -> None:
         lib = _l.load()
-        if self.table is not None:
-            _l.check(lib.ffa_pack_conv_weights_batched(self.dtype_id, self.table.data_ptr(), self.n, _stream()),
+        for layout, table, n in self.tables:
+            _l.check(lib.ffa_pack_conv_weights_batched(self.dtype_id, layout, table.data_ptr(), n, _stream()),
                      "pack_conv_weights_batched")
-        if self.table_ring is not None:
-            _l.check(lib.ffa_ring_pack_batched(self.dtype_id, self.table_ring.data_ptr(), self.n_ring, _stream()),
-                     "ring_pack_batched")
-        if self.table_thin is not None:
-            _l.check(lib.ffa_thin_pack_batched(self.table_thin.data_ptr(), self.n_thin, _stream()), "thin_pack_batched")
-        for w, pw, transpose in self.stem:
-            _l.check(lib.ffa_stem_pack(w.data_ptr(), None, pw.data.data_ptr(), w.shape[0], w.shape[1], _stream()), "stem_pack")
 
 
 def conv_out_size(h: int, k: int, stride: int, pad: int) -> int:

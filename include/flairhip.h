@@ -45,9 +45,9 @@ const char* ffa_target_arch(void);
 
 /* preferred block height (output channels per workgroup) for a layer; weights are packed for it */
 int ffa_conv_block_co(int kh, int kw, int stride, int cout);
-/* Operand layout + block height of a layer: the `bco` value for ffa_pack_conv_weight / ffa_pack_desc_fill /
- * ffa_conv2d / ffa_conv2d_stats / ffa_conv_stat_rows.  Bits 0..11 = rows per block (pad the row count to a multiple
- * of it); FFA_BCO_RING set = the operand is packed for the LDS-DMA ring kernels (bf16: conv3x3_ring16_kernel, the default
+/* Operand layout + block height of a layer: the `bco` value for ffa_pack_conv_weight_bytes / ffa_pack_conv_weight /
+ * ffa_pack_desc_fill / ffa_pack_conv_weights_batched / ffa_conv2d / ffa_conv2d_stats / ffa_conv_stat_rows.
+ * Bits 0..11 = rows per block (pad the row count to a multiple of it); FFA_BCO_RING set = the operand is packed for the LDS-DMA ring kernels (bf16: conv3x3_ring16_kernel, the default
  * for 3x3 stride 1 pad 1 layers with >= 64 output channels and whole 64-byte groups of input channels -- FFA_RING=0 in the
  * environment restores the conv_igemm kernels; f32: conv3x3_ring_kernel, FFA_RING=1); bit 13 (0x2000) = the
  * register-resident operand of the thin layers (ffa_thin_*; FFA_THIN=0 disables).  `allow`: bit 0 admits the ring
@@ -64,13 +64,6 @@ int ffa_ring_conv3x3(int dtype, const void* in, const void* w_ring, const float*
                      float* stat_partials, const float* pro_scale, const float* pro_shift, int B, int H, int W, int Ci,
                      int Co, int co_rows, int relu, ffa_stream_t stream);
 long long ffa_ring_stat_rows(int B, int H, int W, int co_rows);
-int ffa_ring_pack(int dtype, const float* w_oihw, const float* scale, void* dst, int O, int I, int transpose,
-                  int co_rows, int ci_pitch, ffa_stream_t stream);
-/* batched packing of ring operands (the ring layout has its own descriptor type) */
-int ffa_ring_pack_desc_bytes(void);
-int ffa_ring_pack_desc_fill(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I,
-                            int transpose, int co_rows, int ci_pitch, int dtype);
-int ffa_ring_pack_batched(int dtype, const void* descs_device, int n, ffa_stream_t stream);
 /* Thin 3x3 stride-1 pad-1 layers (bf16, <= 32 real output rows, input pitch 16 or 32: the decoder's last two blocks and the
  * segmentation head; csrc/conv3x3_thin.hip): the whole weight operand lives in registers, the input halo arrives by
  * LDS-DMA three tiles deep.  Replaces the same F.conv2d as ffa_conv2d for those shapes; `up` reads nearest_x2(in)
@@ -78,7 +71,6 @@ int ffa_ring_pack_batched(int dtype, const void* descs_device, int n, ffa_stream
  * adjoint, for the transposed operand), `_pro` evaluates relu(in * scale + shift) on the staged halo.  ffa_conv2d /
  * ffa_conv2d_upcat / ffa_conv2d_dgrad_upcat dispatch here when the operand was packed for it (ffa_conv_plan bit 13). */
 int ffa_thin_eligible(int dtype, int kh, int kw, int stride, int rows_real, int ci_pitch);
-long long ffa_thin_pack_bytes(int co_rows, int ci_pitch);
 long long ffa_thin_stat_rows(int B, int H, int W, int ci_pitch);
 int ffa_thin_conv3x3(const void* in, const void* w_thin, const float* bias, const void* residual, void* out,
                      float* stat_partials, int B, int H, int W, int Ci, int Co, int co_rows, int relu, int up, int pool,
@@ -86,40 +78,31 @@ int ffa_thin_conv3x3(const void* in, const void* w_thin, const float* bias, cons
 int ffa_thin_conv3x3_pro(const void* in, const void* w_thin, const float* bias, const void* residual, void* out,
                          float* stat_partials, const float* pro_scale, const float* pro_shift, int B, int H, int W, int Ci,
                          int Co, int co_rows, int relu, int up, int pool, ffa_stream_t stream);
-int ffa_thin_pack(const float* w_oihw, const float* scale, void* dst, int O, int I, int transpose, int co_rows,
-                  int ci_pitch, ffa_stream_t stream);
-int ffa_thin_pack_desc_bytes(void);
-int ffa_thin_pack_desc_fill(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I,
-                            int transpose, int co_rows, int ci_pitch);
-int ffa_thin_pack_batched(const void* descs_device, int n, ffa_stream_t stream);
 /* The ResNet stem (bf16 7x7 stride-2 pad-3 convolution of a <= 8-channel tile stored at pitch 16 into 64 channels;
  * csrc/conv7x7_stem.hip; torchvision's conv1 as smp's ResNetEncoder keeps it): four adjacent taps x 8 channels per
  * K = 32 MFMA step, only the first 16 bytes of every input pixel are staged.  ffa_conv2d / ffa_conv2d_stats dispatch here
  * when the operand was packed for it (ffa_conv_plan with bit 2 of `allow`; bit 15 of the returned code). */
 #define FFA_BCO_STEM 0x8000
 int ffa_stem_eligible(int dtype, int kh, int kw, int stride, int cout, int ci_pitch);
-long long ffa_stem_pack_bytes(void);
 long long ffa_stem_stat_rows(int B, int Ho, int Wo);
-int ffa_stem_pack(const float* w_oihw, const float* scale, void* dst, int O, int I, ffa_stream_t stream);
 int ffa_stem_conv7x7(const void* in, const void* w_stem, const float* bias, void* out, float* stat_partials, int B, int Hi,
                      int Wi, int Ci, int Ho, int Wo, int Co, int relu, ffa_stream_t stream);
 int ffa_conv_row_group(int kh);
-long long ffa_pack_conv_weight_bytes(int dtype, int co_rows, int ci_pitch, int kh, int kw);
-/* OIHW f32 master weight -> kernel operand.  transpose=1 builds the dgrad operand (rows = input
- * channels, taps mirrored).  scale (optional, per row) folds an eval-mode BatchNorm. */
+/* Weight packing (csrc/conv_pack.hip): OIHW f32 master weight -> the operand of the layout in `bco` (ffa_conv_plan),
+ * whose size in bytes the first call returns.  transpose=1 builds the dgrad operand (rows = input channels, taps
+ * mirrored).  scale (optional, per row) folds an eval-mode BatchNorm. */
+long long ffa_pack_conv_weight_bytes(int dtype, int co_rows, int ci_pitch, int kh, int kw, int bco);
 int ffa_pack_conv_weight(int dtype, const float* w_oihw, const float* scale, void* dst, int O, int I, int kh, int kw,
                          int transpose, int co_rows, int ci_pitch, int bco, int rg, ffa_stream_t stream);
-/* every conv operand of a network in one launch: descriptors are filled on the host (ffa_pack_desc_fill,
- * ffa_pack_desc_bytes each), copied to the device once, and replayed every step */
+/* Every conv operand of a network in one launch per layout: descriptors (ffa_pack_desc_bytes each, the same type for every
+ * layout) are filled on the host, copied to the device once, one table per layout, and replayed every step.  A
+ * descriptor covers the column block W[:, col0 : col0 + ncols] of a weight with I_total input channels (one modality's
+ * share of a FusionHandler 1x1 convolution, flair_hub/models/flair_model.py:470-475,533-541; conv_igemm layout only)
+ * or, with col0 = 0 and ncols = I_total, the whole tensor. */
 int ffa_pack_desc_bytes(void);
-int ffa_pack_desc_fill(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I, int kh,
-                       int kw, int transpose, int co_rows, int ci_pitch, int bco, int rg, int dtype);
-/* descriptor for the column block W[:, col0 : col0 + ncols] of a weight with I_total input channels (one modality's share
- * of a FusionHandler 1x1 convolution, flair_hub/models/flair_model.py:470-475,533-541) */
-int ffa_pack_desc_fill_cols(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I_total,
-                            int col0, int ncols, int kh, int kw, int transpose, int co_rows, int ci_pitch, int bco, int rg,
-                            int dtype);
-int ffa_pack_conv_weights_batched(int dtype, const void* descs_device, int n, ffa_stream_t stream);
+int ffa_pack_desc_fill(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I_total, int col0,
+                       int ncols, int kh, int kw, int transpose, int co_rows, int ci_pitch, int bco, int rg, int dtype);
+int ffa_pack_conv_weights_batched(int dtype, int bco, const void* descs_device, int n, ffa_stream_t stream);
 /* out = relu?( conv(in, w) + bias + residual ).  dil=2 reads `in` through a virtual zero insertion
  * (dgrad of a stride-2 layer, stride must then be 1). */
 int ffa_conv2d(int dtype, const void* in, const void* w_packed, const float* bias, const void* residual, void* out,

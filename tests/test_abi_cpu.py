@@ -74,7 +74,7 @@ def test_ctypes_table_equals_the_header():
     header = header_signatures()
     assert len(header) == len(re.findall(r"\bffa_\w+\s*\(", re.sub(r"/\*.*?\*/", "", open(
         os.path.join(ROOT, "include", "flairhip.h")).read(), flags=re.S))), "the parser missed a prototype"
-    assert len(header) >= 143
+    assert len(header) >= 137  # 149 before the twelve per-layout packing entries left the ABI
     assert mismatches(header, L.SIGNATURES) == []
 
 

@@ -73,7 +73,8 @@ def test_one_batched_repack_covers_every_repackable_entry(cuda, monkeypatch):
             p.copy_(torch.randn_like(p))
     plan = hnn.PackPlan(m)
     plan.refresh(BF)
-    assert plan.batch.n + plan.batch.n_ring + plan.batch.n_thin + len(plan.batch.stem) == len(before)
+    assert sorted(t[0] for t in plan.batch.tables) == sorted(set(kinds))  # one table per layout
+    assert sum(t[2] for t in plan.batch.tables) == len(before)
 
     fresh = []
     for c, tr, ring, thin in whole:
