@@ -12,6 +12,12 @@ a bound made of the rounding of the stored output plus an f32 summation term:
 with ``a`` the same linear operation on absolute values.  The inputs are exactly what the kernel saw, so an error in
 one layer does not avalanche into the next one's check.  Only summaries are kept.
 
+The eval step (zonal inference) is covered the same way: ``nn._eval_folded`` is hooked so that a conv call on an
+operand with the BatchNorm scale folded in is checked against ``bf16(w * scale)`` as the packer forms it, with the
+product's own scale vector -- which is itself checked, as the output of ``bn_eval_params``, against float64 -- and the
+uint8 outputs (``predict_u8``, ``tta_accumulate_``, ``tta_predict_u8``, ``tta_probabilities``) against the float64
+softmax of the call's own logits: labels exactly (first maximum), bands and confidence under the half-integer rule.
+
 The references work on any device (CPU for tests/test_insitu_checker.py, the GPU in float64 for the step).
 """
 from __future__ import annotations
@@ -34,8 +40,16 @@ BCO_RING, BCO_THIN, BCO_STEM = 0x1000, 0x2000, 0x8000
 HELPERS = {
     "pad_channels", "conv_out_size", "conv_stat_rows", "workspace", "upcat_supported", "pro_supported",
     "conv_is_persistent", "pack_conv_weight", "coop_barrier_failed", "slice_grid", "write_window",
-    "linear_plan",
+    "linear_plan", "tta_buffer",
 }
+
+# uint8 bands / confidence (rint(255 p)): a value may differ from rint(255 p64) only where 255 p64 lies within HALF_OPEN
+# of a half-integer, and then by 1 (tests/test_tta_gpu.py::test_views_against_float64); at most OPEN_MAX_SHARE of a
+# call's values may be left open like that, which is decided on the float64 reference alone
+HALF_OPEN = 1e-3
+OPEN_MAX_SHARE = 0.01
+BN_EVAL_ULPS = 6.0        # bn_eval_params: one add, sqrtf, an f32 divide and a multiply (HIP documents 1 and 2.5 ulp)
+PREDICT_MODES = ("argmax", "class_prob", "argmax_conf")
 
 
 def layout_of(pw) -> str:
@@ -166,6 +180,37 @@ def samples_f64(x: torch.Tensor) -> torch.Tensor:
     return x.to(F64)
 
 
+def folded_weight(w: torch.Tensor, scale: torch.Tensor, bf16: bool) -> torch.Tensor:
+    """the operand values of an eval-mode fold as the packer defines them (csrc/conv_pack.hip): w[co] * scale[co] in
+    f32, then the storage rounding.  Not taken in float64: rounding the exact product once differs from the packer's
+    two roundings on rare weights."""
+    wf = w.float() * scale.float()[:, None, None, None]
+    return bf16_round(wf) if bf16 else wf.to(F64)
+
+
+def first_max(z: torch.Tensor) -> torch.Tensor:
+    """index of the first maximum along the last axis, as numpy.argmax gives it (torch.argmax promises no order)"""
+    K = z.shape[-1]
+    idx = torch.arange(K, device=z.device).expand(z.shape)
+    return torch.where(z == z.max(-1, keepdim=True).values, idx, torch.full_like(idx, K)).min(-1).values
+
+
+def top_two_ties(z: torch.Tensor) -> int:
+    """number of positions whose two largest values along the last axis are equal"""
+    if z.shape[-1] < 2:
+        return 0
+    t = torch.topk(z, 2, dim=-1).values
+    return int((t[..., 0] == t[..., 1]).sum().item())
+
+
+def crop_window(t: torch.Tensor, crop) -> torch.Tensor:
+    """[B, H, W, ...] -> the window (y0, x0, h, w) of axes 1 and 2"""
+    if crop is None:
+        return t
+    y0, x0, h, w = (int(v) for v in crop)
+    return t[:, y0:y0 + h, x0:x0 + w]
+
+
 # --------------------------------------------------------------------------------------------------
 # comparison
 
@@ -266,6 +311,8 @@ class Checker:
         self.grad_sources: List[tuple] = []  # (tag, f32 tensor) outputs that autograd hands to parameters
         self.sum_sources: List[torch.Tensor] = []  # checked channel_sums outputs (a bias gradient is a prefix of one)
         self.ambiguous = [0, 0]  # ReLU mask: ambiguous elements, elements
+        self.open = defaultdict(lambda: [0, 0])  # uint8 codes, per kind: values left open by the half-integer rule, values
+        self.ties = defaultdict(int)  # per op: positions with an exact tie of the top two whose label was checked
 
     # ---- helpers -------------------------------------------------------------------------------
 
@@ -726,6 +773,94 @@ class Checker:
         self._add(call, _exact_zero((after != r).to(torch.int8), "counts"))
 
 
+    # ---- the eval step: folded BatchNorm, uint8 outputs, test-time augmentation ------------------
+
+    def bn_eval_params(self, call, gamma, beta, rm, rv, eps, scale, shift):
+        """scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, both f32 vectors"""
+        m, v = rm.to(F64), rv.to(F64)
+        g = gamma.to(F64) if gamma is not None else torch.ones_like(m)
+        bt = beta.to(F64) if beta is not None else torch.zeros_like(m)
+        sc = g / torch.sqrt(v + float(eps))
+        sh = bt - m * sc
+        self._add(call, _compare(scale, sc, BN_EVAL_ULPS * ulp_f32(sc), "scale"))
+        self._add(call, _compare(shift, sh, BN_EVAL_ULPS * ulp_f32(bt.abs() + (m * sc).abs()), "shift"))
+
+    def _labels(self, call, z, out, op):
+        """out (uint8) must be the first maximum of z [..., K] over the last axis: no exclusion, no tolerance"""
+        n = top_two_ties(z)
+        self.ties[op] += n
+        call["ties"] = n
+        if tuple(out.shape) != tuple(z.shape[:-1]):
+            raise ValueError(f"labels of shape {tuple(out.shape)} for scores {tuple(z.shape)}")
+        return self._add(call, _exact_zero((out.long() != first_max(z)).to(torch.int8), "label"))
+
+    def _u8_codes(self, call, p64, out, what, kind):
+        """out (uint8) against rint(255 p64): it may differ only where 255 p64 lies within HALF_OPEN of a half-integer,
+        and then by 1.  The share of such values is capped on p64 alone, before out is looked at."""
+        if tuple(out.shape) != tuple(p64.shape):
+            raise ValueError(f"{what} of shape {tuple(out.shape)} for probabilities {tuple(p64.shape)}")
+        scaled = 255.0 * p64
+        open_ = (scaled - scaled.floor() - 0.5).abs() <= HALF_OPEN
+        n_open, n = int(open_.sum().item()), open_.numel()
+        self.open[kind][0] += n_open
+        self.open[kind][1] += n
+        if n_open > OPEN_MAX_SHARE * n:
+            return self._add(call, {"what": what, "shape": tuple(p64.shape), "n": n, "fail": n_open, "worst": float("inf"),
+                                    "error": f"{n_open} of {n} values within {HALF_OPEN} of a half-integer: more than "
+                                             f"{OPEN_MAX_SHARE:.0%}, the reference decides too little"})
+        return self._add(call, _compare(out, torch.round(scaled), open_.to(F64), what))
+
+    def _u8_outputs(self, call, scores, p64, mode, out, op):
+        """the three uint8 outputs of predict_u8 / tta_predict_u8: scores [B,h,w,K] decide the label (their first
+        maximum), p64 [B,h,w,K] the bands; argmax_conf = the label plane and the largest band"""
+        if mode not in PREDICT_MODES:
+            raise ValueError(f"unknown output mode {mode!r}")
+        if mode == "argmax":
+            return self._labels(call, scores, out, op)
+        if mode == "class_prob":
+            return self._u8_codes(call, p64.permute(0, 3, 1, 2), out, "bands", "band")
+        if out.dim() != 4 or out.shape[1] != 2:
+            raise ValueError(f"argmax_conf output of shape {tuple(out.shape)}")
+        self._labels(call, scores, out[:, 0], op)
+        return self._u8_codes(call, p64.max(-1).values, out[:, 1], "confidence", "confidence")
+
+    def predict_u8(self, call, logits, K, mode, crop, out):
+        """out = the uint8 outputs of the window `crop` (y0, x0, h, w) of NHWC logits with K real classes"""
+        z = crop_window(logits, crop)[..., :K].to(F64)
+        return self._u8_outputs(call, z, torch.softmax(z, dim=-1), mode, out, "predict_u8")
+
+    def tta_accumulate(self, call, acc0, logits, K, code, crop, first, acc1):
+        """acc1 [B,h,w,Cp] f32 = (first ? 0 : acc0) + the float64 softmax of the view's logits [B,n,n,Cp] (made with the
+        forward `code`) taken back to the tile's frame with inverse_code, over the window `crop`;
+        flairhip.augment.tta_mean_probabilities of the one view is the definition.  csrc/tta.hip: "pad channels hold 0"."""
+        from flairhip.augment import tta_mean_probabilities
+        z = logits[..., :K].to(F64)
+        call["logit_ties"] = top_two_ties(z)
+        p = tta_mean_probabilities([z.permute(0, 3, 1, 2).cpu().numpy()], [int(code)])
+        p = crop_window(torch.from_numpy(p).to(logits.device).permute(0, 2, 3, 1), crop)
+        if tuple(acc1.shape[:3]) != tuple(p.shape[:3]):
+            raise ValueError(f"accumulator {tuple(acc1.shape)} for a window of {tuple(p.shape[1:3])}")
+        if first:
+            r, mag = p, p
+        else:
+            before = acc0[..., :K].to(F64)
+            r, mag = before + p, before.abs() + p
+        self._add(call, _compare(acc1[..., :K], r, ulp_f32(r) + REL * mag, "accumulator"))
+        if acc1.shape[-1] > K:
+            self._add(call, _exact_zero(acc1[..., K:], "pad channels"))
+
+    def tta_predict_u8(self, call, acc, mode, views, K, out):
+        """the uint8 outputs of an accumulator of `views` views: labels from the accumulator itself, bands from acc / views"""
+        a = acc[..., :K].to(F64)
+        return self._u8_outputs(call, a, a / float(views), mode, out, "tta_predict_u8")
+
+    def tta_probabilities(self, call, acc, views, K, out):
+        r = (acc[..., :K].to(F64) / float(views)).permute(0, 3, 1, 2)
+        if tuple(out.shape) != tuple(r.shape):
+            raise ValueError(f"probabilities of shape {tuple(out.shape)} for an accumulator {tuple(acc.shape)}")
+        return self._add(call, _compare(out, r, 2 * ulp_f32(r), "mean probabilities"))
+
+
 # --------------------------------------------------------------------------------------------------
 # the recorder: patches flairhip.ops and dispatches every outermost call to the Checker
 
@@ -736,10 +871,11 @@ def _clone(v):
 class Recorder(Checker):
     """with Recorder(model, mode) as rec: <training step>  -- then rec.results / rec.calls / rec.unchecked"""
 
-    def __init__(self, model, mode="full", chunk=2, seed=1234):
+    def __init__(self, model=None, mode="full", chunk=2, seed=1234):
         super().__init__(mode, chunk, seed)
-        self.model = model
-        self.names = {id(m): n for n, m in model.named_modules()}
+        self.names = {}
+        self._fold_params = None  # (scale, shift) of the bn_eval_params call inside the running _eval_folded, if any
+        self.adopt(model)
         self.depth = 0
         self.unchecked = defaultdict(int)
         self.counts = defaultdict(int)
@@ -748,6 +884,12 @@ class Recorder(Checker):
         self._chains = {}        # fusion conv name -> real channels of the links of its forward chain, in order
         self._scaled = {}        # address of a rescaled dlogits buffer -> what its consumer's bias gradient must be
         self.head_bias = {}      # module name of a head -> the entry of _scaled its dgrad call consumed
+
+    def adopt(self, model):
+        """take the module names of `model` (a program that builds its model inside the recording hands it over here)"""
+        self.model = model
+        if model is not None:
+            self.names.update({id(m): n for n, m in model.named_modules()})
 
     # ---- patching ------------------------------------------------------------------------------
 
@@ -793,6 +935,31 @@ class Recorder(Checker):
 
         self._saved.append((hnn, "_fusion_slice", orig_slice))
         hnn._fusion_slice = fusion_slice
+        orig_fold = hnn._eval_folded
+
+        def eval_folded(conv, bn, dtype, *a, **kw):
+            """the eval-mode operand: master weight, the product's own f32 scale vector (checked as bn_eval_params'
+            output) and the shift the conv call must carry as its bias.  An operand the cache built before the
+            recording gets its scale from a bn_eval_params call of the same state, recorded and checked like any other."""
+            rec._fold_params = None
+            pw, shift = orig_fold(conv, bn, dtype, *a, **kw)
+            params, rec._fold_params = rec._fold_params, None
+            known = rec.weights.get(id(pw))
+            if params is None and (known is None or known.get("operand") is not pw):
+                params = rec._ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
+                                                 bn.eps)
+            if params is not None:
+                key = (id(conv), conv.weight._version, conv.weight.data_ptr(), hnn.state_epoch())
+                w = rec._wcache.get(key)
+                if w is None:
+                    w = rec._wcache[key] = conv.weight.detach().clone()
+                rec.weights[id(pw)] = {"name": rec.names.get(id(conv), "?"), "transpose": False, "weight": w,
+                                       "scale": params[0].detach().clone(), "shift": shift, "operand": pw,
+                                       "stride": conv.stride, "padding": conv.padding}
+            return pw, shift
+
+        self._saved.append((hnn, "_eval_folded", orig_fold))
+        hnn._eval_folded = eval_folded
         return self
 
     def __exit__(self, *exc):
@@ -861,13 +1028,29 @@ class Recorder(Checker):
             raise ValueError(f"fusion block taken at column {off}, the chain of real channels puts it at {want}")
         return blk
 
+    @staticmethod
+    def _operand_values(call, info, pw, W, bias):
+        """float64 values of the packed operand: the master weight rounded to the storage type, for an eval-mode operand
+        with the product's scale folded in as the packer does it (folded_weight).  Such an operand must be called with
+        the shift of its own fold as the bias, bit for bit."""
+        bf16 = pw.data.dtype == torch.bfloat16
+        call["folded"] = "scale" in info
+        if not call["folded"]:
+            return bf16_round(W) if bf16 else W.to(F64)
+        if info["transpose"]:
+            raise ValueError("eval-mode fold on a dgrad operand")
+        if bias is None or not torch.equal(bias, info["shift"]):
+            raise ValueError("eval-mode operand called without the shift of its fold as the bias")
+        return folded_weight(W, info["scale"], bf16)
+
     def _conv_call(self, call, a, out, w, dil, residual, bias=None, relu=False, stats=False):
         info = self._weight(a["w"])
         pw = a["w"]
         W = self._fusion_block(call, info, residual) if "master" in info else info["weight"]
-        w64 = bf16_round(W) if pw.data.dtype == torch.bfloat16 else W.to(F64)
+        w64 = self._operand_values(call, info, pw, W, bias)
         call.update(module=info["name"], layout=layout_of(pw), transpose=info["transpose"], kernel=f"{pw.kh}x{pw.kw}",
-                    dil=dil, residual=residual is not None, stats=stats)
+                    stride=pw.stride, dil=dil, residual=residual is not None, stats=stats, bias=bias is not None,
+                    relu=bool(relu))
         x = a["x"]
         if not info["transpose"]:
             call["family"] = "fwd"
@@ -895,17 +1078,17 @@ class Recorder(Checker):
         self.bn_stats(dict(call, family="bn_stats", layout=None), y0, a["gamma"], a["beta"], a["running_mean"], a["running_var"], live["running_mean"],
                       live["running_var"], a["momentum"], a["eps"], scale, shift, mean, rstd)
 
-    def _upcat_weight(self, call, pw):
+    def _upcat_weight(self, call, pw, bias=None):
         info = self._weight(pw)
-        W = info["weight"]
         call.update(module=info["name"], layout=layout_of(pw), transpose=info["transpose"], kernel="3x3")
-        return bf16_round(W) if pw.data.dtype == torch.bfloat16 else W.to(F64)
+        return self._operand_values(call, info, pw, info["weight"], bias)
 
     def _op_conv2d_upcat(self, call, a, live, out, stats=False):
         if out is None:
             return
-        w64 = self._upcat_weight(call, a["w"])
-        call.update(family="upcat_fwd", stats=stats)
+        w64 = self._upcat_weight(call, a["w"], a.get("bias"))
+        call.update(family="upcat_fwd", stats=stats, bias=a.get("bias") is not None, relu=bool(a.get("relu", False)),
+                    residual=False)
         lo, skip = a["lo"], a["skip"]
         c1, c2 = lo.shape[-1], (0 if skip is None else skip.shape[-1])
         if w64.shape[1] != c1 + c2:
@@ -1057,6 +1240,34 @@ class Recorder(Checker):
         call["family"] = "confusion_matrix"
         self.confusion(call, a["counts"], live["counts"], a["pred"], a["target"])
 
+    def _op_bn_eval_params(self, call, a, live, out):
+        call["family"] = "bn_eval_params"
+        self._fold_params = out
+        self.bn_eval_params(call, a["gamma"], a["beta"], a["running_mean"], a["running_var"], a["eps"], *out)
+
+    def _op_predict_u8(self, call, a, live, out):
+        call.update(family="predict_u8", mode=a["mode"], crop=a["crop"])
+        self.predict_u8(call, a["logits"], a["num_classes"], a["mode"], a["crop"], out)
+
+    def _op_tta_accumulate_(self, call, a, live, out):
+        call.update(family="tta_accumulate_", code=int(a["code"]), first=bool(a["first"]), crop=a["crop"])
+        self.tta_accumulate(call, a["acc"], a["logits_nhwc"], a["num_classes"], a["code"], a["crop"], a["first"], out)
+
+    @staticmethod
+    def _tta_classes(a, live):
+        k = a["num_classes"] if a["num_classes"] is not None else getattr(live["acc"], "_ffa_classes", None)
+        if k is None:
+            raise ValueError("accumulator without a class count")
+        return int(k)
+
+    def _op_tta_predict_u8(self, call, a, live, out):
+        call.update(family="tta_predict_u8", mode=a["mode"], views=a["views"])
+        self.tta_predict_u8(call, a["acc"], a["mode"], a["views"], self._tta_classes(a, live), out)
+
+    def _op_tta_probabilities(self, call, a, live, out):
+        call.update(family="tta_probabilities", views=a["views"])
+        self.tta_probabilities(call, a["acc"], a["views"], self._tta_classes(a, live), out)
+
     # ---- report --------------------------------------------------------------------------------
 
     def failures(self) -> List[Result]:
@@ -1127,4 +1338,10 @@ class Recorder(Checker):
             f = fam[k]
             lines.append(f"{k:<24}{len(f['calls']):>6}{f['checks']:>8}  {f['worst']:>16.4g}  {','.join(sorted(f['layouts']))}")
         lines.append(f"ambiguous ReLU masks (bn_bwd mode 2): {self.ambiguous[0]} of {self.ambiguous[1]} elements")
+        for kind in sorted(self.open):
+            n_open, n = self.open[kind]
+            lines.append(f"{kind} values within {HALF_OPEN} of a half-integer (may differ by 1): {n_open} of {n} "
+                         f"({n_open / max(n, 1):.4%}, cap {OPEN_MAX_SHARE:.0%} per call)")
+        for op in sorted(self.ties):
+            lines.append(f"{op}: {self.ties[op]} labels checked at an exact tie of the top two")
         return "\n".join(lines)

@@ -6,6 +6,12 @@ must pass these honest results and flag each planted fault that applies to the m
 training step goes wrong in situ: a halo shift of one tile, a channel block with its neighbour's weights, a dropped
 split-K partial, a lost tile of a BatchNorm reduction, swapped parity planes of a stride-2 dgrad, a nonzero pad
 channel, a max-pool gradient routed to the wrong tap, a biased running variance.
+
+The references of the eval step (zonal inference) follow at the end of the file, with the ways that path goes wrong: a
+BatchNorm scale folded along the wrong axis or in another precision than the packer's, a shift left out, a residual
+added after the ReLU, a zeroed row of a ragged tile, the higher label at an exact tie, a band off by one, a crop origin
+off by one, a quarter-turn view taken back with the forward code, a first view added where it should overwrite, a view
+count off by one.
 """
 import pytest
 import torch
@@ -491,3 +497,282 @@ def test_grad_source_rules():
     assert rec.grad_orphans([("head.bias", with_grad((sums.float() * 0.5)[:FK]))]) == []
     assert rec.grad_orphans([("head.bias", with_grad(sums.float()[:FK]))]) == ["head.bias"]
     assert [r["module"] for r in rec.failures()] == ["head"]
+
+
+# --------------------------------------------------------------------------------------------------
+# the references of the eval step (zonal inference): convs on operands with the BatchNorm scale folded in, shift as the
+# bias, residual + ReLU in the epilogue; bn_eval_params; the uint8 outputs with and without test-time augmentation
+
+EB, EH, EW, EC = 2, 20, 24, 48           # 20 x 24: ragged against 16 x 16 and 8 x 32 tiles; 48 -> 48 so that a fold over
+                                          # the input channels has the shape of the right one
+PK, PCP, PN = 19, 24, 40                  # classes, logit pitch, square tile
+PCROP = (3, 5, 17, 30)                    # y0, x0, h, w
+TIE = (0, 4, 9)                           # image, row, column (tile frame, inside the crop) of the planted exact tie
+VIEWS = 8
+
+
+def _bf16_once(t64):
+    """float64 -> the nearest bf16 value (ties to even) in ONE rounding (a cast goes through f32 first)"""
+    m, e = torch.frexp(t64)
+    return torch.ldexp(torch.round(m * 256.0) / 256.0, e)
+
+
+def _double_rounding_pairs(g, want):
+    """(w, s) f32 pairs whose product rounds to another bf16 value in one step (float64) than in two (f32, then bf16):
+    the exact product lies just beside a bf16 tie and the f32 rounding lands on it"""
+    w = torch.randn(1 << 22, generator=g) / 20
+    s = torch.rand(1 << 22, generator=g) * 0.5 + 0.75
+    two = (w * s).to(torch.bfloat16).double()
+    hit = torch.nonzero(two != _bf16_once(w.double() * s.double())).flatten()[:want]
+    assert hit.numel() == want, f"only {hit.numel()} double-rounding pairs among {w.numel()}"
+    return w[hit], s[hit]
+
+
+@pytest.fixture(scope="module")
+def ecase():
+    g = torch.Generator().manual_seed(29)
+    c = {}
+    x = _bf(torch.randn(EB, EC, EH, EW, generator=g))
+    w = torch.randn(EC, EC, 3, 3, generator=g) / 20                      # f32 master weight: not bf16 values
+    gamma, beta = torch.rand(EC, generator=g) * 0.5 + 0.75, torch.randn(EC, generator=g) * 0.1
+    rm, rv = torch.randn(EC, generator=g) * 0.1, torch.rand(EC, generator=g) * 0.5 + 0.75
+    scale = gamma * (1.0 / torch.sqrt(rv + EPS))                         # f32, the kernel's operation order
+    shift = beta - rm * scale
+    # the conv case folds a scale vector of its own: 16 output channels get a (weight, scale) pair on which the
+    # float64 fold rounds differently
+    pw_, ps_ = _double_rounding_pairs(g, 16)
+    w[:16, 0, 0, 0] = pw_
+    fscale = scale.clone()
+    fscale[:16] = ps_
+    res = torch.randn(EB, EH, EW, EC, generator=g).to(torch.bfloat16)
+    c.update(x=x, w=w, gamma=gamma, beta=beta, rm=rm, rv=rv, scale=scale, shift=shift, fscale=fscale, res=res)
+    # uint8 outputs: logits N(0, 2) in bf16 values at pitch 24 (garbage in the pad channels), one exact tie of the top two
+    z = (torch.randn(EB, PN, PN, PCP, generator=g) * 2).to(torch.bfloat16)
+    b, i, j = TIE
+    z[b, i, j, :PK] = z[b, i, j, :PK].clamp(max=3.0)
+    z[b, i, j, 3] = z[b, i, j, 7] = 4.0
+    c["logits"] = z
+    # an accumulator of VIEWS views
+    p = torch.softmax(torch.randn(VIEWS, EB, PCROP[2], PCROP[3], PK, generator=g) * 2, dim=-1)
+    acc = torch.zeros(EB, PCROP[2], PCROP[3], PCP)
+    for v in range(VIEWS):
+        acc[..., :PK] += p[v]
+    acc[b, 1, 4, 5] = acc[b, 1, 4, 2] = acc[b, 1, 4, :PK].max() + 0.5     # an exact tie of the top two sums
+    c["acc"] = acc
+    return c
+
+
+def _eval_conv(c, wq, fault=None):
+    """the epilogue in f32 on the bf16 operand wq: relu(conv + shift + residual), stored bf16"""
+    y = _nhwc(F.conv2d(c["x"], wq, padding=1))
+    if fault != "no_shift":
+        y = y + c["shift"]
+    if fault == "residual_after_relu":
+        return (torch.relu(y) + c["res"].float()).to(torch.bfloat16)
+    return torch.relu(y + c["res"].float()).to(torch.bfloat16)
+
+
+def run_eval_conv(ck, c, fault):
+    w, s = c["w"], c["fscale"]
+    wq = _bf(w * s[:, None, None, None])                                 # the packer: f32 product, then bf16
+    if fault == "scale_over_inputs":
+        wq = _bf(w * s[None, :, None, None])
+    elif fault == "fold_in_f64":
+        wq = _bf16_once(w.double() * s.double()[:, None, None, None]).float()
+        c["fold_f64_differs"] = int((wq != _bf(w * s[:, None, None, None])).sum())
+    y = _eval_conv(c, wq, fault)
+    if fault == "last_row":  # the last row of the last (ragged) tile of the last image
+        y[-1, EH - 1, 16:, :] = 0
+    ck.conv_forward({"op": "conv2d"}, _nhwc(c["x"]).to(torch.bfloat16), insitu.folded_weight(w, s, True), 1, 1, y,
+                    bias=c["shift"], residual=c["res"], relu=True)
+
+
+def run_bn_eval(ck, c, fault):
+    scale, shift = c["scale"], c["shift"]
+    if fault == "no_eps":
+        scale = c["gamma"] / torch.sqrt(c["rv"])
+    elif fault == "shift_sign":
+        shift = c["beta"] + c["rm"] * c["scale"]
+    ck.bn_eval_params({"op": "bn_eval_params"}, c["gamma"], c["beta"], c["rm"], c["rv"], EPS, scale, shift)
+
+
+def _u8_product(scores, p, mode, fault=None):
+    """the kernels' outputs in f32: strict '>' keeps the lowest index, bands rint(p * 255)"""
+    label = insitu.first_max(scores)
+    bands = torch.round(p * 255.0)
+    if fault == "tie_higher":
+        b, i, j = TIE[0], TIE[1] - PCROP[0], TIE[2] - PCROP[1]
+        assert label[b, i, j] == 3
+        label[b, i, j] = 7
+    if fault == "band_off":
+        frac = (255.0 * p.double()) % 1.0
+        far = torch.nonzero(((frac - 0.5).abs() > 0.3) & (bands < 255))[0]
+        bands[tuple(far)] += 1
+        if mode == "argmax_conf":  # the confidence of that pixel
+            top = p.max(-1).values
+            k = tuple(torch.nonzero((((255.0 * top.double()) % 1.0 - 0.5).abs() > 0.3) & (top < 0.99))[0])
+            out = torch.stack([label.float(), torch.round(top * 255.0)], dim=1)
+            out[k[0], 1, k[1], k[2]] += 1
+            return out.to(torch.uint8)
+    if mode == "argmax":
+        return label.to(torch.uint8)
+    if mode == "class_prob":
+        return bands.permute(0, 3, 1, 2).to(torch.uint8)
+    return torch.stack([label.float(), bands.max(-1).values], dim=1).to(torch.uint8)
+
+
+def run_predict(mode):
+    def run(ck, c, fault):
+        y0, x0, h, w = PCROP
+        if fault == "crop_shift":
+            y0 += 1
+        z = c["logits"][:, y0:y0 + h, x0:x0 + w, :PK].float()
+        out = _u8_product(z, torch.softmax(z, dim=-1), mode, fault)
+        ck.predict_u8({"op": "predict_u8"}, c["logits"], PK, mode, PCROP, out)
+    return run
+
+
+QUARTER = 4  # the forward code of a quarter turn; its inverse is code 7
+
+
+def run_tta_accumulate(first):
+    def run(ck, c, fault):
+        from flairhip.augment import apply_code, inverse_code
+        assert inverse_code(QUARTER) != QUARTER
+        y0, x0, h, w = PCROP
+        p = torch.softmax(c["logits"][..., :PK].float(), dim=-1).permute(0, 3, 1, 2)           # the view's frame
+        back = QUARTER if fault == "forward_code" else inverse_code(QUARTER)
+        p = torch.from_numpy(apply_code(p.numpy(), back)).permute(0, 2, 3, 1)[:, y0:y0 + h, x0:x0 + w]
+        before = c["acc"].clone()
+        after = torch.zeros_like(before)
+        after[..., :PK] = p if (first and fault != "first_adds") else before[..., :PK] + p
+        if fault == "pad_channel":
+            after[0, 2, 3, PK] = 1e-6
+        ck.tta_accumulate({"op": "tta_accumulate_"}, before, c["logits"], PK, QUARTER, PCROP, first, after)
+    return run
+
+
+def run_tta_predict(mode):
+    def run(ck, c, fault):
+        views = VIEWS - 1 if fault == "views_off_by_one" else VIEWS
+        a = c["acc"][..., :PK]
+        out = _u8_product(a / float(views), a / float(views), mode)
+        if fault == "tie_higher":
+            assert out[TIE[0], 1, 4] == 2
+            out[TIE[0], 1, 4] = 5
+        ck.tta_predict_u8({"op": "tta_predict_u8"}, c["acc"], mode, VIEWS, PK, out)
+    return run
+
+
+def run_tta_probabilities(ck, c, fault):
+    views = VIEWS - 1 if fault == "views_off_by_one" else VIEWS
+    out = (c["acc"][..., :PK] / float(views)).permute(0, 3, 1, 2)
+    ck.tta_probabilities({"op": "tta_probabilities"}, c["acc"], VIEWS, PK, out)
+
+
+ECALLS = {"eval_conv": run_eval_conv, "bn_eval": run_bn_eval, "predict_argmax": run_predict("argmax"),
+          "predict_class_prob": run_predict("class_prob"), "predict_argmax_conf": run_predict("argmax_conf"),
+          "tta_first": run_tta_accumulate(True), "tta_add": run_tta_accumulate(False),
+          "tta_predict_argmax": run_tta_predict("argmax"), "tta_predict_class_prob": run_tta_predict("class_prob"),
+          "tta_predict_argmax_conf": run_tta_predict("argmax_conf"), "tta_probabilities": run_tta_probabilities}
+# (fault, call it lives in, what every failing result must be about)
+EFAULTS = [
+    ("scale_over_inputs", "eval_conv", "out"),       # scale folded over the input channels
+    ("no_shift", "eval_conv", "out"),                # shift omitted
+    ("residual_after_relu", "eval_conv", "out"),     # residual added after the ReLU
+    ("last_row", "eval_conv", "out"),                # one output row of the last tile zeroed
+    ("no_eps", "bn_eval", "scale"),
+    ("shift_sign", "bn_eval", "shift"),
+    ("tie_higher", "predict_argmax", "label"),       # the higher index at an exact tie
+    ("tie_higher", "predict_argmax_conf", "label"),
+    ("tie_higher", "tta_predict_argmax", "label"),
+    ("band_off", "predict_class_prob", "bands"),     # a band off by one away from any half-integer
+    ("band_off", "predict_argmax_conf", "confidence"),
+    ("crop_shift", "predict_argmax", "label"),       # crop origin shifted by one pixel
+    ("crop_shift", "predict_class_prob", "bands"),
+    ("crop_shift", "predict_argmax_conf", None),
+    ("forward_code", "tta_first", "accumulator"),    # a quarter turn taken back with the forward code
+    ("forward_code", "tta_add", "accumulator"),
+    ("first_adds", "tta_first", "accumulator"),      # first=True adding where it should overwrite
+    ("pad_channel", "tta_add", "pad channels"),
+    ("views_off_by_one", "tta_predict_class_prob", "bands"),
+    ("views_off_by_one", "tta_predict_argmax_conf", "confidence"),
+    ("views_off_by_one", "tta_probabilities", "mean probabilities"),
+]
+
+
+@pytest.mark.parametrize("call", sorted(ECALLS))
+def test_honest_eval_results_pass(ecase, call):
+    ck = Checker("full", chunk=1)
+    ECALLS[call](ck, ecase, None)
+    assert ck.results
+    bad = [r.line() for r in ck.results if not r.ok]
+    assert not bad, bad
+    if call.startswith("predict") and "class_prob" not in call:
+        assert ck.ties["predict_u8"] >= 1       # the planted tie was seen, and its label checked
+    if call.startswith("tta_predict") and "class_prob" not in call:
+        assert ck.ties["tta_predict_u8"] >= 1
+
+
+@pytest.mark.parametrize("fault,call,what", EFAULTS, ids=[f"{f}-{c}" for f, c, _ in EFAULTS])
+def test_planted_eval_fault_is_flagged(ecase, fault, call, what):
+    ck = Checker("full", chunk=1)
+    ECALLS[call](ck, ecase, fault)
+    bad = [r for r in ck.results if not r.ok]
+    assert bad, f"{fault} passed: " + "; ".join(r.line() for r in ck.results)
+    if what is not None:
+        assert all(r["what"] == what for r in bad), [r.line() for r in bad]
+    if fault == "last_row":
+        assert all(r["where"][:2] == (EB - 1, EH - 1) and r["where"][2] >= 16 for r in bad), [r.line() for r in bad]
+    if fault in ("tie_higher", "band_off", "pad_channel"):
+        assert sum(r["fail"] for r in bad) == 1, [r.line() for r in bad]
+
+
+def test_a_fold_taken_in_float64_fails_the_bound_where_it_matters(ecase):
+    """Scale folded in float64 and rounded once, where the packer rounds twice (f32 product, then bf16).  On the 16
+    planted (weight, scale) pairs the operand then differs by one bf16 ulp of that weight, 2^-8 |w| or more, and the
+    output by that times the tap's |x|.  The bound dictates: this FAILS, but only on the few outputs of those channels
+    that are small against the sum of their terms -- there ulp_bf16(r) gives no room, and 2^-16 a is about 2^-8 of one
+    average term for this layer's 432 taps, so a tap with an above-average |x| exceeds it (37 of 46080 outputs for this
+    seed).  Where r is of the size of a, one bf16 ulp of one weight stays far inside the half ulp of r that the bound
+    leaves beside the output's own rounding.  A reference that folded in float64 would therefore flag the product on
+    such weights: the reference folds as the packer does (insitu.folded_weight)."""
+    ck = Checker("full", chunk=1)
+    run_eval_conv(ck, ecase, "fold_in_f64")
+    assert ecase["fold_f64_differs"] == 16
+    bad = [r for r in ck.results if not r.ok]
+    assert bad and all(r["what"] == "out" and r["where"][3] < 16 for r in bad), [r.line() for r in ck.results]
+    assert sum(r["fail"] for r in bad) <= 0.01 * EB * EH * EW * 16, [r.line() for r in bad]
+
+
+def test_a_folded_operand_must_carry_its_shift():
+    """Recorder._operand_values: the reference weight of an eval-mode operand is the packer's fold, and a call on it
+    without the shift of that fold as its bias is a failed check (the conv reference alone would accept it: it sees
+    what the kernel saw)"""
+    g = torch.Generator().manual_seed(31)
+    w, scale, shift = torch.randn(8, 4, 3, 3, generator=g), torch.rand(8, generator=g) + 0.5, torch.randn(8, generator=g)
+
+    class Operand:
+        data = torch.zeros(1, dtype=torch.bfloat16)
+
+    info = {"name": "m", "transpose": False, "weight": w, "scale": scale, "shift": shift}
+    call = {}
+    got = insitu.Recorder._operand_values(call, info, Operand, w, shift.clone())
+    assert call["folded"] and torch.equal(got, (w * scale[:, None, None, None]).to(torch.bfloat16).double())
+    for bias in (None, torch.zeros(8), shift + 2.0 ** -20):
+        with pytest.raises(ValueError, match="shift"):
+            insitu.Recorder._operand_values({}, info, Operand, w, bias)
+    plain = insitu.Recorder._operand_values(call, {"name": "m", "transpose": False, "weight": w}, Operand, w, None)
+    assert not call["folded"] and torch.equal(plain, w.to(torch.bfloat16).double())
+
+
+def test_too_many_open_values_is_a_failed_check():
+    """two equal logits: every band is 127.5 exactly, the float64 reference decides nothing -- a failed check, whatever
+    the product wrote"""
+    z = torch.zeros(1, 8, 8, 8, dtype=torch.bfloat16)
+    ck = Checker("full", chunk=1)
+    ck.predict_u8({"op": "predict_u8"}, z, 2, "class_prob", None, torch.full((1, 2, 8, 8), 128, dtype=torch.uint8))
+    assert [r.ok for r in ck.results] == [False] and "half-integer" in ck.results[0]["error"]
+    ck = Checker("full", chunk=1)  # the label is decided all the same: the lowest index
+    ck.predict_u8({"op": "predict_u8"}, z, 2, "argmax", None, torch.zeros(1, 8, 8, dtype=torch.uint8))
+    assert [r.ok for r in ck.results] == [True] and ck.ties["predict_u8"] == 64
