@@ -128,10 +128,13 @@ extern "C" int ffa_upsample_nearest2x_concat_bwd(int dtype, const void* dcat, vo
 // bilinear, align_corners=False.  Source index as ATen computes it (area_pixel_compute_source_index):
 //   src = max(0, scale * (dst + 0.5) - 0.5), scale = in / out in f32, i0 = (int)src,
 //   i1 = i0 + (i0 < in - 1), lambda1 = src - i0, lambda0 = 1 - lambda1
+// The multiply and the subtraction are one fma (what the compiler's default contraction made of the expression all
+// along): written out, because the float64 reference of the f32 resize (tests/insitu.py source_coordinate_f32) rounds
+// the coordinate exactly as this line does.
 
 __device__ __forceinline__ void bilinear_src(int dst, float scale, int in_size, int& i0, int& i1, float& l0,
                                              float& l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
   if (src < 0.f) src = 0.f;
   i0 = (int)src;
   if (i0 > in_size - 1) i0 = in_size - 1;

@@ -6,11 +6,16 @@ checked too) go through a float64 reference of the same operation, and the produ
 element -- or, in projection mode, through seeded random projections over the channels (a Freivalds check) -- against
 a bound made of the rounding of the stored output plus an f32 summation term:
 
-    bf16-stored outputs:  |o - r| <= ulp_bf16(r) + REL * a
-    f32 outputs:          |o - r| <= REL * a
+    stored activations:          |o - r| <= ulp_stored(r) + REL * a    (ulp_bf16 or ulp_f32, by the output's own type)
+    f32 sums (dW, statistics):   |o - r| <= REL * a
 
 with ``a`` the same linear operation on absolute values.  The inputs are exactly what the kernel saw, so an error in
 one layer does not avalanche into the next one's check.  Only summaries are kept.
+
+The rounding unit follows the stored type (``ulp_stored``), so the fp32 programs (``hardware.precision: fp32``) are held
+to 2^-16 a + ulp_f32(r): two orders of magnitude above honest f32 summation, and 128 times below what a kernel that is
+f32 only in name (bf16 operands, a bf16 detour of the output) produces.  Their operands are the f32 master weights as
+they are, folded in eval mode as the packer folds them (w * scale in f32, csrc/conv_pack.hip).
 
 The eval step (zonal inference) is covered the same way: ``nn._eval_folded`` is hooked so that a conv call on an
 operand with the BatchNorm scale folded in is checked against ``bf16(w * scale)`` as the packer forms it, with the
@@ -76,6 +81,15 @@ def ulp_f32(r: torch.Tensor) -> torch.Tensor:
     _, e = torch.frexp(r.abs())
     u = torch.ldexp(torch.ones_like(r), (e - 24).to(torch.int32))
     return torch.clamp(torch.where(r == 0, torch.zeros_like(r), u), min=2.0 ** -149)
+
+
+def ulp_stored(r: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """rounding unit of a value of the magnitude of r in the type the output is stored in"""
+    if dtype == torch.bfloat16:
+        return ulp_bf16(r)
+    if dtype == torch.float32:
+        return ulp_f32(r)
+    raise TypeError(f"no rounding unit for outputs stored as {dtype}")
 
 
 def bf16_round(t: torch.Tensor) -> torch.Tensor:
@@ -145,12 +159,28 @@ def upcat(lo, skip):
     return u if skip is None else torch.cat([u, skip], dim=-1)
 
 
-def bilinear_matrix(n_in: int, n_out: int, device=None) -> torch.Tensor:
+def source_coordinate_f32(n_in: int, n_out: int, device=None) -> torch.Tensor:
+    """[n_out] float64 holding f32 values: ATen's area_pixel_compute_source_index for f32 tensors, as bilinear_src of
+    csrc/resample_loss.hip evaluates it -- scale = f32(n_in) / f32(n_out) rounded to f32, then
+    src = max(0, fmaf(scale, dst + 0.5, -0.5)): the multiply and the subtraction are ONE fma there (one rounding), as
+    GPU compilers contract ATen's expression too.  dst + 0.5 is exact in f32 and the product of two f32 numbers is
+    exact in float64, so one rounding of the float64 value is that fma.  (ATen's CPU build rounds the product first:
+    at 32 -> 48 two of the 48 coordinates then differ by one f32 ulp, which moves a tap weight by 2^-20 or so.)"""
+    scale = (torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)).to(F64)
+    dst = torch.arange(n_out, dtype=F64)
+    return (scale * (dst + 0.5) - 0.5).float().clamp_min(0.0).to(F64).to(device)
+
+
+def bilinear_matrix(n_in: int, n_out: int, device=None, f32_coordinate: bool = False) -> torch.Tensor:
     """[n_out, n_in] float64: the bilinear resize of one axis with align_corners=False as ATen defines it -- source
-    coordinate max(0, (dst + 0.5) * n_in / n_out - 0.5) taken in float64, taps floor(src) and the next index clamped
-    to the last one, weights 1 - frac and frac.  The backward of the resize is the transpose of this matrix."""
-    dst = torch.arange(n_out, dtype=F64, device=device)
-    src = ((dst + 0.5) * (float(n_in) / float(n_out)) - 0.5).clamp_min(0.0)
+    coordinate max(0, (dst + 0.5) * n_in / n_out - 0.5) taken in float64 (f32_coordinate: in f32, as ATen and the
+    kernel take it for f32 tensors, source_coordinate_f32), taps floor(src) and the next index clamped to the last one,
+    weights 1 - frac and frac in float64.  The backward of the resize is the transpose of this matrix."""
+    if f32_coordinate:
+        src = source_coordinate_f32(n_in, n_out, device)
+    else:
+        dst = torch.arange(n_out, dtype=F64, device=device)
+        src = ((dst + 0.5) * (float(n_in) / float(n_out)) - 0.5).clamp_min(0.0)
     i0 = src.floor().long().clamp(max=n_in - 1)
     i1 = (i0 + 1).clamp(max=n_in - 1)
     l1 = src - i0.to(F64)
@@ -355,7 +385,7 @@ class Checker:
                     e, ea = extra(b0, b1)
                     r, a = r + e, a + ea
                 oc = o[b0:b1, ..., :real_c]
-                parts.append(_shift(_compare(oc, r, ulp_bf16(r) + REL * a, what), b0, o.shape))
+                parts.append(_shift(_compare(oc, r, ulp_stored(r, o.dtype) + REL * a, what), b0, o.shape))
         else:
             u = self._u(real_c, o.device)
             for b0, b1 in self._chunks(B):
@@ -364,7 +394,7 @@ class Checker:
                     e, ea = extra(b0, b1)
                     r, a = r + e @ u, a + ea @ u.abs()
                 oc = o[b0:b1, ..., :real_c].to(F64)
-                tol = ulp_bf16(oc) @ u.abs() + REL * a
+                tol = ulp_stored(oc, o.dtype) @ u.abs() + REL * a
                 parts.append(_shift(_compare(oc @ u, r, tol, what), b0, o.shape))
         return self._add(call, _merge(parts, what + ("" if full else " (projected)")))
 
@@ -512,7 +542,7 @@ class Checker:
                 r, a = r + rr, a + rr.abs()
             if relu:
                 r = r.clamp_min(0)
-            parts.append(_shift(_compare(o[b0:b1], r, ulp_bf16(r) + REL * a, "y"), b0, o.shape))
+            parts.append(_shift(_compare(o[b0:b1], r, ulp_stored(r, o.dtype) + REL * a, "y"), b0, o.shape))
         return self._add(call, _merge(parts, "y"))
 
     def bn_bwd(self, call, x, dy, y, gamma, beta, mean, rstd, relu, dx, dres, dgamma, dbeta):
@@ -570,10 +600,10 @@ class Checker:
             xh = (xc - mu) * rs
             r = g64 * rs * (gm - sb / n - xh * sg / n)
             a = kg * (gm.abs() + sb.abs() / n + rs * (xc.abs() + mu.abs()) * sg.abs() / n)
-            tol = ulp_bf16(r) + REL * a + kg * (t_b / n + xh.abs() * t_g / n)
+            tol = ulp_stored(r, dx.dtype) + REL * a + kg * (t_b / n + xh.abs() * t_g / n)
             pdx.append(_shift(_compare(dx[b0:b1], r, tol, "dx", exclude=amb), b0, dx.shape))
             if dres is not None:
-                pres.append(_shift(_compare(dres[b0:b1], gm, ulp_bf16(gm) * 0, "dres", exclude=amb), b0, dx.shape))
+                pres.append(_shift(_compare(dres[b0:b1], gm, torch.zeros_like(gm), "dres", exclude=amb), b0, dx.shape))
         self._add(call, _merge(pdx, "dx"))
         if dres is not None:
             self._add(call, _merge(pres, "dres"))
@@ -619,7 +649,7 @@ class Checker:
             if add is not None:
                 ad = add[b0:b1].to(F64)
                 ref, a = ref + ad, a + ad.abs()
-            parts.append(_shift(_compare(dx[b0:b1], ref, ulp_bf16(ref) + REL * a, "dx"), b0, dx.shape))
+            parts.append(_shift(_compare(dx[b0:b1], ref, ulp_stored(ref, dx.dtype) + REL * a, "dx"), b0, dx.shape))
         return self._add(call, _merge(parts, "dx"))
 
     def softmax_ce(self, call, logits, targets, weights, K, grad_scale, out):
@@ -666,7 +696,7 @@ class Checker:
                 r = f * (p - oh)
                 a = f.abs() * (p + oh)
                 o = dlogits[b0:b1]
-                parts_d.append(_shift(_compare(o[..., :K], r, ulp_bf16(r) + REL * a, "dlogits"), b0, dlogits.shape))
+                parts_d.append(_shift(_compare(o[..., :K], r, ulp_stored(r, o.dtype) + REL * a, "dlogits"), b0, dlogits.shape))
                 if Cp > K:
                     parts_d.append(_shift(_exact_zero(o[..., K:], "dlogits pad channels"), b0, dlogits.shape))
                 parts_d.append(_shift(_exact_zero(torch.where((wp == 0).unsqueeze(-1), o, torch.zeros_like(o)),
@@ -683,7 +713,7 @@ class Checker:
     def scale_inplace(self, call, before, scale, after):
         s = float(scale.reshape(-1)[0])
         r = before.to(F64) * s
-        tol = torch.zeros_like(r) if s == 1.0 else ulp_bf16(r) if before.dtype == torch.bfloat16 else ulp_f32(r)
+        tol = torch.zeros_like(r) if s == 1.0 else ulp_stored(r, before.dtype)
         return self._add(call, _compare(after, r, tol, "x * s"))
 
     def nchw_to_nhwc(self, call, x, out):
@@ -701,16 +731,19 @@ class Checker:
         """forward: o [B,Ho,Wo,C] = resize of src [B,Hi,Wi,C] (align_corners=False, float64 source index);
         transpose: o [B,Hi,Wi,C] = the transposed map of src = dy [B,Ho,Wo,C].  The taps are non-negative, so the
         magnitude bound a is the same map on |src|.  A channel that is zero in all of src (the pad channels) must be
-        exactly zero in o.  (The kernel, like ATen for f32 tensors, takes the source coordinate in f32: at ratios that
-        are no power of two that is a few 1e-6 of the step between two taps, far inside a bf16 ulp; the f32 bound
-        REL * a can be missed by it where the taps nearly cancel -- tests/test_kernels_gpu.py::test_bilinear.)"""
+        exactly zero in o.  The kernel, like ATen for f32 tensors, takes the source coordinate in f32: at ratios that
+        are no power of two that is a few 1e-6 of the step between two taps, far inside a bf16 ulp, but up to 2.9 times
+        the f32 bound REL * a where the taps nearly cancel (tests/test_kernels_gpu.py::test_bilinear).  So f32 tensors
+        are checked against the operation the kernel defines: the taps in float64 from the coordinate evaluated in
+        f32 (source_coordinate_f32); bf16 tensors keep the float64 coordinate."""
         what = "dx" if transpose else "y"
+        f32c = o.dtype == torch.float32
         if transpose:
-            my = bilinear_matrix(o.shape[1], src.shape[1], src.device).t()
-            mx = bilinear_matrix(o.shape[2], src.shape[2], src.device).t()
+            my = bilinear_matrix(o.shape[1], src.shape[1], src.device, f32c).t()
+            mx = bilinear_matrix(o.shape[2], src.shape[2], src.device, f32c).t()
         else:
-            my = bilinear_matrix(src.shape[1], o.shape[1], src.device)
-            mx = bilinear_matrix(src.shape[2], o.shape[2], src.device)
+            my = bilinear_matrix(src.shape[1], o.shape[1], src.device, f32c)
+            mx = bilinear_matrix(src.shape[2], o.shape[2], src.device, f32c)
         parts = []
         for b0, b1 in self._chunks(src.shape[0]):
             s = src[b0:b1].to(F64)
@@ -1052,6 +1085,9 @@ class Recorder(Checker):
                     stride=pw.stride, dil=dil, residual=residual is not None, stats=stats, bias=bias is not None,
                     relu=bool(relu))
         x = a["x"]
+        # conv3x3_persist_kernel (a block walks several tiles) or one tile per block: the library's own answer
+        call.update(dtype=str(x.dtype).replace("torch.", ""),
+                    persistent=self._ops.conv_is_persistent(x.dtype, out.shape[0], out.shape[1], out.shape[2], pw, dil))
         if not info["transpose"]:
             call["family"] = "fwd"
             return self.conv_forward(call, x, w64, pw.stride, a["pad"], out, bias=bias, residual=residual, relu=relu)
@@ -1080,7 +1116,8 @@ class Recorder(Checker):
 
     def _upcat_weight(self, call, pw, bias=None):
         info = self._weight(pw)
-        call.update(module=info["name"], layout=layout_of(pw), transpose=info["transpose"], kernel="3x3")
+        call.update(module=info["name"], layout=layout_of(pw), transpose=info["transpose"], kernel="3x3",
+                    dtype=str(pw.data.dtype).replace("torch.", ""))
         return self._operand_values(call, info, pw, info["weight"], bias)
 
     def _op_conv2d_upcat(self, call, a, live, out, stats=False):
@@ -1091,6 +1128,7 @@ class Recorder(Checker):
                     residual=False)
         lo, skip = a["lo"], a["skip"]
         c1, c2 = lo.shape[-1], (0 if skip is None else skip.shape[-1])
+        call.update(c1=c1, c2=c2)
         if w64.shape[1] != c1 + c2:
             raise ValueError("two-source conv: pitch != real input channels")
 
@@ -1114,8 +1152,8 @@ class Recorder(Checker):
             return
         dlo, dskip = out
         w64 = self._upcat_weight(call, a["wt"])
-        call["family"] = "upcat_dgrad"
         c1, c2 = a["c1"], a["c2"]
+        call.update(family="upcat_dgrad", c1=c1, c2=c2)
         dy = a["dy"]
         B, H, W, _ = dy.shape
         O = w64.shape[0]
@@ -1139,8 +1177,9 @@ class Recorder(Checker):
 
     def _op_conv_wgrad(self, call, a, live, out):
         call.update(family="wgrad", kernel=f"{a['kh']}x{a['kw']}", stride=a["stride"],
-                    layout="thin" if (a["x"].shape[-1] <= 32 and a["dy"].shape[-1] <= 32 and a["kh"] == 3
-                                      and a["stride"] == 1) else "general")
+                    layout="thin" if (a["x"].dtype == torch.bfloat16 and a["x"].shape[-1] <= 32 and a["dy"].shape[-1] <= 32
+                                      and a["kh"] == 3 and a["stride"] == 1) else "general",
+                    dtype=str(a["x"].dtype).replace("torch.", ""))
         call.update(co=out.shape[0], ci=out.shape[1], hw=tuple(a["x"].shape[1:3]))
         before = a["out"] if a["accumulate"] else None
         self.conv_wgrad(call, a["x"], a["dy"], a["kh"], a["kw"], a["stride"], a["pad"], out, before=before)
@@ -1149,11 +1188,34 @@ class Recorder(Checker):
     def _op_conv_wgrad_upcat(self, call, a, live, out):
         if out is None:
             return
-        call.update(family="upcat_wgrad", kernel="3x3")
         lo, skip = a["lo"], a["skip"]
+        if lo.dtype == torch.float32:  # conv3x3_thin_wgrad_kernel is bf16-only
+            call["layout"] = "general"
+        call.update(family="upcat_wgrad", kernel="3x3", c1=lo.shape[-1], c2=0 if skip is None else skip.shape[-1],
+                    dtype=str(lo.dtype).replace("torch.", ""))
         x = upcat(lo, skip)
         self.conv_wgrad(call, x, a["dy"], 3, 3, 1, 1, out)
         self.grad_sources.append(("dW", out.detach().clone()))
+
+    def _op_upsample2x_concat_fwd(self, call, a, live, out):
+        """the materialised decoder input where no two-source kernel takes the channel split: a copy, so exact"""
+        call.update(family="upsample2x_concat_fwd", c1=a["lo"].shape[-1], c2=0 if a["skip"] is None else a["skip"].shape[-1])
+        r = upcat(a["lo"], a["skip"])
+        self._add(call, _exact_zero((out != r).to(torch.int8), "cat(nearest_x2(lo), skip)"))
+
+    def _op_upsample2x_concat_bwd(self, call, a, live, out):
+        """dlo = the 2 x 2 sums of the first c1 channels (four terms: REL * a + the stored rounding), dskip = the rest"""
+        call["family"] = "upsample2x_concat_bwd"
+        dlo, dskip = out
+        c1, dcat = a["c1"], a["dcat"]
+        parts = []
+        for b0, b1 in self._chunks(dcat.shape[0]):
+            d = dcat[b0:b1, ..., :c1].to(F64)
+            r, mag = pool2_sum(d), pool2_sum(d.abs())
+            parts.append(_shift(_compare(dlo[b0:b1], r, ulp_stored(r, dlo.dtype) + REL * mag, "dlo"), b0, dlo.shape))
+        self._add(call, _merge(parts, "dlo"))
+        if dskip is not None:
+            self._add(call, _exact_zero((dskip != dcat[..., c1:]).to(torch.int8), "dskip"))
 
     def _op_bn_apply(self, call, a, live, out):
         call["family"] = "bn_apply"
@@ -1325,18 +1387,20 @@ class Recorder(Checker):
         return False
 
     def table(self) -> str:
-        fam = defaultdict(lambda: {"calls": set(), "layouts": set(), "worst": 0.0, "checks": 0})
+        fam = defaultdict(lambda: {"calls": set(), "layouts": set(), "worst": 0.0, "checks": 0, "what": ""})
         for r in self.results:
             f = fam[r.get("family", r["op"])]
             f["calls"].add(r["call"])
             if r.get("layout"):
                 f["layouts"].add(r["layout"])
             f["checks"] += 1
-            f["worst"] = max(f["worst"], r["worst"])
-        lines = [f"{'family':<24}{'calls':>6}{'checks':>8}  {'worst err/bound':>16}  layouts"]
+            if r["worst"] > f["worst"]:
+                f["worst"], f["what"] = r["worst"], f"{r['what']} [{r.get('module') or ''}]"
+        lines = [f"{'family':<24}{'calls':>6}{'checks':>8}  {'worst err/bound':>16}  {'layouts':<14}  worst check"]
         for k in sorted(fam):
             f = fam[k]
-            lines.append(f"{k:<24}{len(f['calls']):>6}{f['checks']:>8}  {f['worst']:>16.4g}  {','.join(sorted(f['layouts']))}")
+            lines.append(f"{k:<24}{len(f['calls']):>6}{f['checks']:>8}  {f['worst']:>16.4g}  "
+                         f"{','.join(sorted(f['layouts'])):<14}  {f['what']}")
         lines.append(f"ambiguous ReLU masks (bn_bwd mode 2): {self.ambiguous[0]} of {self.ambiguous[1]} elements")
         for kind in sorted(self.open):
             n_open, n = self.open[kind]

@@ -7,6 +7,11 @@ training step goes wrong in situ: a halo shift of one tile, a channel block with
 split-K partial, a lost tile of a BatchNorm reduction, swapped parity planes of a stride-2 dgrad, a nonzero pad
 channel, a max-pool gradient routed to the wrong tap, a biased running variance.
 
+The same calls are made with f32 tensors for the fp32 programs, whose rounding unit is ulp_f32: there a bf16 operand, a
+bf16 detour of an output, one dropped channel group of one tap, a lost statistics tile, BatchNorm-backward sums from
+bf16-rounded gradients and a one-tap shift of the resize must be flagged as well, and one test recomputes the rule
+that was applied to every activation before (ulp_bf16) to show what it let through.
+
 The references of the eval step (zonal inference) follow at the end of the file, with the ways that path goes wrong: a
 BatchNorm scale folded along the wrong axis or in another precision than the packer's, a shift left out, a residual
 added after the ReLU, a zeroed row of a ragged tile, the higher label at an exact tie, a band off by one, a crop origin
@@ -38,26 +43,28 @@ def _nchw(t):
     return t.permute(0, 3, 1, 2).contiguous()
 
 
-def _store(t_nchw, pitch=None):
-    """f32 NCHW result -> bf16 NHWC stored tensor (pad channels zero)"""
-    o = _nhwc(t_nchw).to(torch.bfloat16)
+def _store(t_nchw, pitch=None, dtype=torch.bfloat16):
+    """f32 NCHW result -> NHWC tensor stored as `dtype` (pad channels zero)"""
+    o = _nhwc(t_nchw).to(dtype)
     if pitch is not None and pitch > o.shape[-1]:
         o = F.pad(o, (0, pitch - o.shape[-1]))
     return o
 
 
-@pytest.fixture(scope="module")
-def case():
-    g = torch.Generator().manual_seed(5)
-    c = {}
-    x = _bf(torch.randn(B, CI, H, W, generator=g))
-    w1 = _bf(torch.randn(CO, CI, 3, 3, generator=g) / 20)
-    w2 = _bf(torch.randn(C2, CI, 3, 3, generator=g) / 20)
+def _build_case(seed, dt):
+    """the calls of one layer with activations stored as `dt`: bf16 values throughout for torch.bfloat16 (the bf16
+    step), plain f32 values -- weights, activations and gradients -- for torch.float32 (the fp32 step)"""
+    g = torch.Generator().manual_seed(seed)
+    c = {"dt": dt}
+    q = _bf if dt == torch.bfloat16 else (lambda t: t)
+    x = q(torch.randn(B, CI, H, W, generator=g))
+    w1 = q(torch.randn(CO, CI, 3, 3, generator=g) / 20)
+    w2 = q(torch.randn(C2, CI, 3, 3, generator=g) / 20)
     c.update(x=x, w1=w1, w2=w2)
     # stride-1 forward (pitch 80 for 72 real channels)
-    c["y1"] = _store(F.conv2d(x, w1, padding=1), CO_PITCH)
+    c["y1"] = _store(F.conv2d(x, w1, padding=1), CO_PITCH, dt)
     # stride-2 forward + BatchNorm statistics of its stored output
-    y0 = _store(F.conv2d(x, w2, stride=2, padding=1))
+    y0 = _store(F.conv2d(x, w2, stride=2, padding=1), None, dt)
     v = y0.float().reshape(-1, C2)
     n = v.shape[0]
     mean, var = v.mean(0), v.var(0, unbiased=False)
@@ -70,40 +77,51 @@ def case():
     c.update(y0=y0, gamma=gamma, beta=beta, rm0=rm0, rv0=rv0, mean=mean, rstd=rstd, scale=scale, shift=shift,
              rm1=(1 - MOM) * rm0 + MOM * mean, rv1=(1 - MOM) * rv0 + MOM * var * n / (n - 1), var=var, n=n)
     # BatchNorm + ReLU backward, mask recomputed from the pre-activation (mode 2)
-    dy = _bf(torch.randn(B, H // 2, W // 2, C2, generator=g) * 0.1).to(torch.bfloat16)
+    dy = q(torch.randn(B, H // 2, W // 2, C2, generator=g) * 0.1).to(dt)
     xf = y0.float()
     gm = torch.where(xf * scale + shift > 0, dy.float(), torch.zeros(()))
     xh = (xf - mean) * rstd
     dbeta = gm.reshape(-1, C2).sum(0)
     dgamma = (gm * xh).reshape(-1, C2).sum(0)
-    dx = (gamma * rstd * (gm - dbeta / n - xh * dgamma / n)).to(torch.bfloat16)
+    dx = (gamma * rstd * (gm - dbeta / n - xh * dgamma / n)).to(dt)
     c.update(bdy=dy, bdx=dx, dgamma=dgamma, dbeta=dbeta, gm=gm, xh=xh)
     # stride-2 dgrad (the zero-insertion call) and stride-1 weight gradient
-    d2 = _bf(torch.randn(B, C2, H // 2, W // 2, generator=g) * 0.1)
-    c.update(d2=_nhwc(d2).to(torch.bfloat16), dx2=_store(conv2d_input((B, CI, H, W), w2, d2, stride=2, padding=1)))
-    d1 = _bf(torch.randn(B, CO, H, W, generator=g) * 0.1)
-    c.update(d1=F.pad(_nhwc(d1), (0, CO_PITCH - CO)).to(torch.bfloat16),
+    d2 = q(torch.randn(B, C2, H // 2, W // 2, generator=g) * 0.1)
+    c.update(d2=_nhwc(d2).to(dt), dx2=_store(conv2d_input((B, CI, H, W), w2, d2, stride=2, padding=1), None, dt))
+    d1 = q(torch.randn(B, CO, H, W, generator=g) * 0.1)
+    c.update(d1=F.pad(_nhwc(d1), (0, CO_PITCH - CO)).to(dt),
              dw1=conv2d_weight(x, w1.shape, d1, padding=1), d1_nchw=d1)
     # max-pool 3x3 s2 p1 forward (first maximal tap in row-major order) and backward with an `add` input
-    xp = torch.randn(B, H, W, 32, generator=g).to(torch.bfloat16)
+    xp = torch.randn(B, H, W, 32, generator=g).to(dt)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     pad = F.pad(xp.float(), (0, 0, 1, 1, 1, 1), value=float("-inf"))
     taps = torch.stack([pad[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] for r in range(3) for s in range(3)])
     best = taps.max(0).values
     idx = torch.argmax((taps == best).to(torch.int8), dim=0).to(torch.uint8)
-    pdy = torch.randn(B, Ho, Wo, 32, generator=g).to(torch.bfloat16)
-    add = torch.randn(B, H, W, 32, generator=g).to(torch.bfloat16)
-    c.update(px=xp, pidx=idx, pdy=pdy, padd=add, pdx=_route(pdy, idx, add, H, W))
+    pdy = torch.randn(B, Ho, Wo, 32, generator=g).to(dt)
+    add = torch.randn(B, H, W, 32, generator=g).to(dt)
+    c.update(px=xp, pidx=idx, pdy=pdy, padd=add, pdx=_route(pdy, idx, add, H, W).to(dt))
     return c
 
 
+@pytest.fixture(scope="module")
+def case():
+    return _build_case(5, torch.bfloat16)
+
+
+@pytest.fixture(scope="module")
+def case32():
+    return _build_case(35, torch.float32)
+
+
 def _route(dy, idx, add, H, W):
+    """the routed gradient sums + add, in f32 (the caller rounds them to the stored type)"""
     Bn, Ho, Wo, C = dy.shape
     acc = torch.zeros(Bn, 2 * Ho + 1, 2 * Wo + 1, C)
     for t in range(9):
         r, s = divmod(t, 3)
         acc[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] += torch.where(idx == t, dy.float(), torch.zeros(()))
-    return (acc[:, 1:1 + H, 1:1 + W] + add.float()).to(torch.bfloat16)
+    return acc[:, 1:1 + H, 1:1 + W] + add.float()
 
 
 def _f64(t):
@@ -114,17 +132,26 @@ def _f64(t):
 # one entry per checked kernel call: run(checker, case, fault) -> results of that call
 
 def run_fwd(ck, c, fault):
+    dt = c["dt"]
     y = c["y1"].clone()
     if fault == "halo":  # one 16x16 tile of the last image read one pixel off
-        ys = _store(F.conv2d(torch.roll(c["x"], 1, dims=3), c["w1"], padding=1), CO_PITCH)
+        ys = _store(F.conv2d(torch.roll(c["x"], 1, dims=3), c["w1"], padding=1), CO_PITCH, dt)
         y[-1, 16:32, 16:32] = ys[-1, 16:32, 16:32]
     elif fault == "channel_block":  # output channels 16..31 computed with the weights of 32..47
         w = c["w1"].clone()
         w[16:32] = w[32:48]
-        y[..., 16:32] = _store(F.conv2d(c["x"], w, padding=1), CO_PITCH)[..., 16:32]
+        y[..., 16:32] = _store(F.conv2d(c["x"], w, padding=1), CO_PITCH, dt)[..., 16:32]
     elif fault == "pad_channel":
         y[0, 3, 5, CO + 3] = 1e-3
-    ck.conv_forward({"op": "conv2d"}, _nhwc(c["x"]).to(torch.bfloat16), _f64(c["w1"]), 1, 1, y)
+    elif fault == "out_bf16":  # f32 in name only: the result takes a detour through bf16
+        y = _bf(y)
+    elif fault == "w_bf16":  # f32 in name only: the operand was packed as bf16
+        y = _store(F.conv2d(c["x"], _bf(c["w1"]), padding=1), CO_PITCH, dt)
+    elif fault == "tap_group":  # last row of the ragged tile (columns 32..47 of 48) of the last image: the 8 input
+        wz = torch.zeros_like(c["w1"])  # channels 8..15 of tap (0, 2) never reach the sum
+        wz[:, 8:16, 0, 2] = c["w1"][:, 8:16, 0, 2]
+        y[-1, H - 1, 32:, :CO] -= _nhwc(F.conv2d(c["x"], wz, padding=1))[-1, H - 1, 32:].to(dt)
+    ck.conv_forward({"op": "conv2d"}, _nhwc(c["x"]).to(dt), _f64(c["w1"]), 1, 1, y)
 
 
 def run_dgrad_s2(ck, c, fault):
@@ -136,25 +163,38 @@ def run_dgrad_s2(ck, c, fault):
 
 def run_wgrad(ck, c, fault):
     dw = c["dw1"].clone()
-    if fault == "split_k":  # image 1 missing from one 16 x 16 (out x in) channel block
+    if fault == "split_k":  # image 1 (one split-K slab) missing from one 16 x 16 (out x in) channel block
         part = conv2d_weight(c["x"][1:], c["w1"].shape, c["d1_nchw"][1:], padding=1)
         dw[0:16, 16:32] -= part[0:16, 16:32]
-    ck.conv_wgrad({"op": "conv_wgrad"}, _nhwc(c["x"]).to(torch.bfloat16), c["d1"], 3, 3, 1, 1, dw)
+    ck.conv_wgrad({"op": "conv_wgrad"}, _nhwc(c["x"]).to(c["dt"]), c["d1"], 3, 3, 1, 1, dw)
 
 
 def run_bn_stats(ck, c, fault):
-    rv1 = c["rv1"].clone()
+    k = dict(c)
     if fault == "biased_var":
-        rv1 = (1 - MOM) * c["rv0"] + MOM * c["var"]
-    ck.bn_stats({"op": "conv2d_bn_stats"}, c["y0"], c["gamma"], c["beta"], c["rm0"], c["rv0"], c["rm1"], rv1, MOM, EPS,
-                c["scale"], c["shift"], c["mean"], c["rstd"])
+        k["rv1"] = (1 - MOM) * c["rv0"] + MOM * c["var"]
+    elif fault == "lost_tile":  # channel 5: the partial sums of one 16 x 16 tile never reach the reduction
+        v, t = c["y0"].float()[..., 5], c["y0"].float()[0, 0:16, 0:16, 5]
+        n = c["n"]
+        mean, var = c["mean"].clone(), c["var"].clone()
+        mean[5] = (v.sum() - t.sum()) / n
+        var[5] = ((v * v).sum() - (t * t).sum()) / n - mean[5] ** 2
+        rstd = 1.0 / torch.sqrt(var + EPS)
+        scale = c["gamma"] * rstd
+        k.update(mean=mean, rstd=rstd, scale=scale, shift=c["beta"] - mean * scale,
+                 rm1=(1 - MOM) * c["rm0"] + MOM * mean, rv1=(1 - MOM) * c["rv0"] + MOM * var * n / (n - 1))
+    ck.bn_stats({"op": "conv2d_bn_stats"}, c["y0"], c["gamma"], c["beta"], c["rm0"], c["rv0"], k["rm1"], k["rv1"], MOM,
+                EPS, k["scale"], k["shift"], k["mean"], k["rstd"])
 
 
 def run_bn_bwd(ck, c, fault):
-    dgamma = c["dgamma"].clone()
+    dgamma, dx = c["dgamma"].clone(), c["bdx"]
     if fault == "dgamma_tile":  # channel 5 misses the partial sum of one 16 x 16 tile
         dgamma[5] -= (c["gm"][0, 0:16, 0:16, 5] * c["xh"][0, 0:16, 0:16, 5]).sum()
-    ck.bn_bwd({"op": "bn_bwd"}, c["y0"], c["bdy"], None, c["gamma"], c["beta"], c["mean"], c["rstd"], True, c["bdx"],
+    elif fault == "dbeta_from_bf16":  # the sums inside dx taken from bf16-rounded dy; the dbeta handed out is the honest one
+        low = _bf(c["gm"]).reshape(-1, C2).sum(0)
+        dx = (c["gamma"] * c["rstd"] * (c["gm"] - low / c["n"] - c["xh"] * c["dgamma"] / c["n"])).to(c["dt"])
+    ck.bn_bwd({"op": "bn_bwd"}, c["y0"], c["bdy"], None, c["gamma"], c["beta"], c["mean"], c["rstd"], True, dx,
               None, dgamma, c["dbeta"])
 
 
@@ -163,7 +203,9 @@ def run_maxpool_bwd(ck, c, fault):
     if fault == "route":  # one pixel's gradient sent to another tap of its window
         idx = c["pidx"].clone()
         idx[1, 5, 7, 3] = (int(idx[1, 5, 7, 3]) + 4) % 9
-        dx = _route(c["pdy"], idx, c["padd"], H, W)
+        dx = _route(c["pdy"], idx, c["padd"], H, W).to(c["dt"])
+    elif fault == "sum_bf16":  # the gradient sum rounded to bf16 on its way to an f32 tensor
+        dx = _bf(dx)
     ck.maxpool_bwd({"op": "maxpool3x3s2_bwd"}, c["pdy"], c["pidx"], (H, W), c["padd"], dx)
 
 
@@ -179,6 +221,19 @@ FAULTS = {
     "pad_channel": ("fwd", ("full", "proj")),
     "route": ("maxpool_bwd", ("full",)),
     "biased_var": ("bn_stats", ("full", "proj")),
+}
+# what only the f32 bounds can see (for bf16 tensors the first, second and fifth ARE the honest result), and two more
+# that the bf16 cases do not plant.  A projection sums the independent roundings of the channels: they grow with the
+# root of the channel count, the bound with the count itself, so the margin over the two bf16 detours of a forward conv
+# shrinks as the layers widen: those two are asserted for the elementwise mode, which the fp32 GPU cases run in.  The
+# projected mode is asserted on the faults that are whole terms of the sum.
+F32_FAULTS = {
+    "out_bf16": ("fwd", ("full",)),
+    "w_bf16": ("fwd", ("full",)),
+    "tap_group": ("fwd", ("full", "proj")),
+    "lost_tile": ("bn_stats", ("full", "proj")),
+    "dbeta_from_bf16": ("bn_bwd", ("full", "proj")),
+    "sum_bf16": ("maxpool_bwd", ("full",)),
 }
 
 
@@ -201,6 +256,67 @@ def test_planted_fault_is_flagged(case, mode, fault):
     CALLS[call](ck, case, fault)
     bad = [r for r in ck.results if not r.ok]
     assert bad, f"{fault} passed the {mode} comparator: " + "; ".join(r.line() for r in ck.results)
+
+
+# ---- the same calls of the fp32 programs: f32 tensors, held to ulp_f32(r) + REL * a -------------------------------------
+
+@pytest.mark.parametrize("mode", ["full", "proj"])
+@pytest.mark.parametrize("call", sorted(CALLS))
+def test_honest_f32_results_pass(case32, mode, call):
+    ck = Checker(mode, chunk=1)
+    CALLS[call](ck, case32, None)
+    assert ck.results
+    bad = [r.line() for r in ck.results if not r.ok]
+    assert not bad, bad
+    if call == "bn_bwd":
+        assert ck.ambiguous[0] <= insitu.AMBIG_MAX_FRACTION * ck.ambiguous[1]
+
+
+ALL_F32_FAULTS = dict(FAULTS, **F32_FAULTS)
+
+
+@pytest.mark.parametrize("fault,mode", [(f, m) for f in sorted(ALL_F32_FAULTS) for m in ALL_F32_FAULTS[f][1]])
+def test_planted_fault_is_flagged_in_f32(case32, mode, fault):
+    call = ALL_F32_FAULTS[fault][0]
+    ck = Checker(mode, chunk=1)
+    CALLS[call](ck, case32, fault)
+    bad = [r for r in ck.results if not r.ok]
+    assert bad, f"{fault} passed the {mode} comparator: " + "; ".join(r.line() for r in ck.results)
+    if fault == "tap_group" and mode == "full":  # nothing but the outputs that lost the terms
+        assert all(r["where"][:2] == (B - 1, H - 1) and r["where"][2] >= 32 for r in bad), [r.line() for r in bad]
+        assert sum(r["fail"] for r in bad) <= 16 * CO
+    if fault == "dbeta_from_bf16":  # dbeta and dgamma themselves are the honest ones
+        assert {r["what"] for r in bad} == {"dx"}, [r.line() for r in bad]
+
+
+def test_the_rule_for_bf16_tensors_passes_what_the_f32_rule_flags(case32):
+    """The gap the f32 rounding unit closes.  Until the unit followed the stored type, every activation was held to
+    ulp_bf16(r) + REL * a.  Recomputed here, that rule passes an f32 convolution whose output went through bf16 on
+    EVERY element: the detour's error is half a bf16 ulp of the value itself.  A weight operand rounded to bf16 it
+    passes on most elements only.  That error does not shrink with r: over K = 432 terms of size t it is about
+    sqrt(K) * 2^-9 * 0.58 t = 0.024 t, against r of about sqrt(K) t = 21 t and REL * a = 2^-16 * K * 0.64 t = 0.004 t,
+    so the old rule gives way only where ulp_bf16(r) falls below that, at |r| under a quarter of its spread: a share
+    P(|N(0, 1)| < 0.25) = 0.2 of the outputs at most, the rest passes.  ulp_f32(r) + REL * a has no such room and fails
+    both faults on more than half of the outputs."""
+    MISS_OLD, HIT_NEW = 0.2, 0.5
+    c = case32
+    x64, w64 = _f64(_nhwc(c["x"])), _f64(c["w1"])
+    r = insitu.conv_gather(x64, w64, 1, 1, H, W)
+    a = insitu.conv_gather(x64.abs(), w64.abs(), 1, 1, H, W)
+    old, new = insitu.ulp_bf16(r) + insitu.REL * a, insitu.ulp_f32(r) + insitu.REL * a
+    honest = (_f64(c["y1"][..., :CO]) - r).abs()
+    assert bool((honest <= new).all())
+    shares = {}
+    for fault in ("out_bf16", "w_bf16"):
+        y = _bf(c["y1"]) if fault == "out_bf16" else _store(F.conv2d(c["x"], _bf(c["w1"]), padding=1), CO_PITCH, c["dt"])
+        err = (_f64(y[..., :CO]) - r).abs()
+        shares[fault] = (float((err > old).double().mean()), float((err > new).double().mean()))
+        ck = Checker("full", chunk=1)
+        run_fwd(ck, c, fault)
+        assert [r_.ok for r_ in ck.results if r_["what"] == "out"] == [False]
+    print(f"\nshare of outputs outside (old rule, f32 rule): {shares}")
+    assert shares["out_bf16"][0] == 0.0 and shares["w_bf16"][0] <= MISS_OLD, shares
+    assert min(s[1] for s in shares.values()) > HIT_NEW, shares
 
 
 def test_failure_report_locates_the_fault(case):
@@ -289,30 +405,38 @@ FK = 11                                   # classes of the head (pitch 16)
 SQ = 12                                   # square planes for the flips and rotations
 
 
-def _taps(n_in, n_out, align=False, clamp=True):
-    """f32 taps of one axis as the kernel takes them; align: the align_corners=True source index"""
+def _taps(n_in, n_out, align=False, clamp=True, coord="f32", shift_from=None):
+    """f32 taps of one axis; align: the align_corners=True source index.  coord: "f32" the coordinate in plain f32
+    arithmetic, "fma" as the kernel takes it (insitu.source_coordinate_f32), "f64" taken in float64 and the weights
+    rounded to f32; shift_from: destination indices from this one on read one source index further (a one-tap shift)"""
     dst = torch.arange(n_out, dtype=torch.float32)
     if align:
         src = dst * torch.tensor((n_in - 1) / (n_out - 1), dtype=torch.float32)
+    elif coord == "fma":
+        src = insitu.source_coordinate_f32(n_in, n_out).float()
+    elif coord == "f64":
+        src = ((dst.double() + 0.5) * (n_in / n_out) - 0.5).clamp_min(0)
     else:
         src = ((dst + 0.5) * torch.tensor(n_in / n_out, dtype=torch.float32) - 0.5).clamp_min(0)
     i0 = src.floor().long().clamp(max=n_in - 1)
+    l1 = (src - i0.to(src.dtype)).float()
+    if shift_from is not None:
+        i0[shift_from:] = (i0[shift_from:] + 1).clamp(max=n_in - 1)
     i1 = i0 + 1
     if clamp:
         i1 = i1.clamp(max=n_in - 1)
-    l1 = src - i0.float()
     return i0, i1, 1 - l1, l1
 
 
-def _bilinear_f32(x, ho, wo, align=False, clamp_rows=True):
+def _bilinear_f32(x, ho, wo, align=False, clamp_rows=True, coord="f32", shift_from=None):
     """gather form in f32, rows of two column-interpolated taps; clamp_rows=False: the second tap of the last row reads
     row H, which in memory is row 0 of the next image (zeros past the last one)"""
     Bn, H, W, C = x.shape
     xf = x.float()
     if not clamp_rows:
         xf = torch.cat([xf, torch.cat([xf[1:, :1], torch.zeros(1, 1, W, C)])], dim=1)
-    y0, y1, ly0, ly1 = _taps(H, ho, align, clamp_rows)
-    x0, x1, lx0, lx1 = _taps(W, wo, align)
+    y0, y1, ly0, ly1 = _taps(H, ho, align, clamp_rows, coord, shift_from)
+    x0, x1, lx0, lx1 = _taps(W, wo, align, coord=coord)
 
     def row(yi):
         r = xf[:, yi]
@@ -321,8 +445,8 @@ def _bilinear_f32(x, ho, wo, align=False, clamp_rows=True):
     return ly0[None, :, None, None] * row(y0) + ly1[None, :, None, None] * row(y1)
 
 
-def _tap_matrix(n_in, n_out):
-    i0, i1, l0, l1 = _taps(n_in, n_out)
+def _tap_matrix(n_in, n_out, coord="f32"):
+    i0, i1, l0, l1 = _taps(n_in, n_out, coord=coord)
     m = torch.zeros(n_out, n_in)
     m.scatter_add_(1, i0[:, None], l0[:, None])
     m.scatter_add_(1, i1[:, None], l1[:, None])
@@ -468,6 +592,85 @@ def test_bilinear_matrix_is_the_aten_resize():
         # ATen takes the source coordinate in f32: a few ulps of a number up to n_in, times the step between the taps
         assert (got - _f64(ref)).abs().max().item() <= 8 * n_in * 2.0 ** -24 * 2 * x.abs().max().item()
         assert torch.allclose(insitu.bilinear_matrix(n_in, n_out).sum(1), torch.ones(n_out, dtype=torch.float64))
+
+
+# ---- f32 tensors of the fp32 programs: bilinear against the coordinate the kernel takes, bn_apply, the loss gradient ----
+
+def _f32_maps(seed):
+    g = torch.Generator().manual_seed(seed)
+    x = F.pad(torch.randn(FB, FH, FW, 10, generator=g), (0, FPITCH - 10))
+    dy = F.pad(torch.randn(FB, FHO, FWO, 10, generator=g), (0, FPITCH - 10))
+    return x, dy
+
+
+@pytest.mark.parametrize("coord", ["fma", "f64"])
+def test_f32_bilinear_passes_with_the_kernels_coordinate_and_tolerates_the_float64_one(coord):
+    """12 x 8 <-> 18 x 12, scale 2 / 3: the f32 coordinate is off the float64 one by an f32 ulp or two, and the tap
+    weights with it.  The reference takes the kernel's coordinate; a product that took the float64 one is no fault and
+    must pass too on these maps: the fractions are 1 / 6, 1 / 2 and 5 / 6, so no tap nearly cancels and a is at least a
+    sixth of |v0| + |v1|, the error at most a few 1e-7 of it."""
+    x, dy = _f32_maps(71)
+    ck = Checker("full", chunk=1)
+    ck.bilinear({"op": "bilinear_fwd"}, x, _bilinear_f32(x, FHO, FWO, coord=coord), False)
+    my, mx = _tap_matrix(FH, FHO, coord), _tap_matrix(FW, FWO, coord)
+    dx = torch.einsum("px,bypc->byxc", mx, torch.einsum("oy,bopc->bypc", my, dy))
+    ck.bilinear({"op": "bilinear_bwd"}, dy, dx, True)
+    assert len(ck.results) == 4 and all(r.ok for r in ck.results), [r.line() for r in ck.results if not r.ok]
+    assert not torch.equal(_tap_matrix(FH, FHO, "fma"), _tap_matrix(FH, FHO, "f64"))  # the two do differ here
+
+
+def test_f32_bilinear_flags_a_one_tap_shift_and_a_bf16_detour():
+    x, _ = _f32_maps(71)
+    for fault in ("shift", "bf16"):
+        y = _bilinear_f32(x, FHO, FWO, coord="fma", shift_from=FHO - 4 if fault == "shift" else None)
+        ck = Checker("full", chunk=1)
+        ck.bilinear({"op": "bilinear_fwd"}, x, _bf(y) if fault == "bf16" else y, False)
+        bad = [r for r in ck.results if not r.ok]
+        assert bad and all(r["what"] == "y" for r in bad), (fault, [r.line() for r in ck.results])
+        if fault == "shift":
+            assert bad[0]["where"][1] >= FHO - 4, bad[0].line()
+
+
+def test_f32_coordinate_matrix():
+    """rows sum to one; where the scale is an f32 number (ratios 2 and 1.5 downwards) both coordinates are the same
+    number and so are the matrices; elsewhere they differ by f32 roundings of a coordinate below n_in"""
+    for n_in, n_out in ((2, 3), (3, 2), (32, 48), (48, 32), (8, 12), (64, 32), (13, 40)):
+        m32, m64 = insitu.bilinear_matrix(n_in, n_out, f32_coordinate=True), insitu.bilinear_matrix(n_in, n_out)
+        assert torch.allclose(m32.sum(1), torch.ones(n_out, dtype=torch.float64))
+        assert (m32 - m64).abs().max().item() <= 4 * n_in * 2.0 ** -24
+        if (n_in, n_out) in ((3, 2), (48, 32), (64, 32)):
+            assert torch.equal(m32, m64)
+    c = insitu.source_coordinate_f32(32, 48)
+    assert torch.equal(c, c.float().double()) and c[0] == 0 and bool((c[1:] > c[:-1]).all())
+
+
+def test_f32_elementwise_and_loss_results():
+    """bn_apply and the loss gradient with f32 tensors: honest f32 arithmetic passes, a bf16 detour of the stored
+    values is flagged (for bf16 tensors it is the honest result)"""
+    g = torch.Generator().manual_seed(73)
+    x = torch.randn(B, H, W, 32, generator=g)
+    sc, sh = torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g)
+    res = torch.randn(B, H, W, 32, generator=g)
+    y = torch.relu(x * sc + sh + res)
+    K, Cp = 19, 32
+    logits = F.pad(torch.randn(B, H, W, K, generator=g) * 3, (0, Cp - K))
+    t = torch.randint(0, K, (B, H, W), generator=g).to(torch.uint8)
+    cw = torch.tensor([1.0] * 15 + [0.0] * 4)
+    z = logits[..., :K]
+    wp = cw[t.long()]
+    wsum = wp.sum()
+    loss = (wp * (torch.logsumexp(z, -1) - torch.gather(z, -1, t.long().unsqueeze(-1)).squeeze(-1))).sum() / wsum
+    d = F.pad((wp / wsum).unsqueeze(-1) * (torch.softmax(z, -1) - F.one_hot(t.long(), K)), (0, Cp - K))
+    pred = z.argmax(-1).to(torch.uint8)
+    for fault in (None, "y_bf16", "dlogits_bf16"):
+        ck = Checker("full", chunk=1)
+        ck.bn_apply({"op": "bn_apply"}, x, sc, sh, res, True, _bf(y) if fault == "y_bf16" else y)
+        d2 = _bf(d) if fault == "dlogits_bf16" else d
+        ck.softmax_ce({"op": "softmax_ce"}, logits, t, cw, K, None,
+                      (loss.reshape(1), wsum.reshape(1), d2, pred, d2.reshape(-1, Cp).sum(0)))
+        bad = {(r["op"], r["what"]) for r in ck.results if not r.ok}
+        want = {None: set(), "y_bf16": {("bn_apply", "y")}, "dlogits_bf16": {("softmax_ce", "dlogits")}}[fault]
+        assert bad == want, (fault, [r.line() for r in ck.results if not r.ok])
 
 
 def test_grad_source_rules():
@@ -743,6 +946,36 @@ def test_a_fold_taken_in_float64_fails_the_bound_where_it_matters(ecase):
     bad = [r for r in ck.results if not r.ok]
     assert bad and all(r["what"] == "out" and r["where"][3] < 16 for r in bad), [r.line() for r in ck.results]
     assert sum(r["fail"] for r in bad) <= 0.01 * EB * EH * EW * 16, [r.line() for r in bad]
+
+
+def test_f32_eval_conv_is_checked_against_the_packers_f32_fold(ecase):
+    """the fp32 eval operand is w * scale in f32, stored as it is (csrc/conv_pack.hip multiplies in f32 for both
+    types): honest f32 arithmetic on it passes; the operand rounded to bf16, the scale over the wrong axis and a
+    missing shift are flagged"""
+    c = ecase
+    w, s = c["w"], c["fscale"]
+    x = c["x"] * 1.0009765625 + 2.0 ** -12       # f32 values that are no bf16 values
+    res = c["res"].float() * 1.00048828125
+    for fault in (None, "fold_bf16", "scale_over_inputs", "no_shift"):
+        wq = w * (s[None, :, None, None] if fault == "scale_over_inputs" else s[:, None, None, None])
+        if fault == "fold_bf16":
+            wq = _bf(wq)
+        y = _nhwc(F.conv2d(x, wq, padding=1)) + (0.0 if fault == "no_shift" else c["shift"])
+        y = torch.relu(y + res)
+        ck = Checker("full", chunk=1)
+        ck.conv_forward({"op": "conv2d"}, _nhwc(x), insitu.folded_weight(w, s, False), 1, 1, y, bias=c["shift"],
+                        residual=res, relu=True)
+        assert [r.ok for r in ck.results] == [fault is None], (fault, [r.line() for r in ck.results])
+    call = {}
+
+    class Operand:
+        data = torch.zeros(1, dtype=torch.float32)
+
+    info = {"name": "m", "transpose": False, "weight": w, "scale": s, "shift": c["shift"]}
+    got = insitu.Recorder._operand_values(call, info, Operand, w, c["shift"].clone())
+    assert call["folded"] and torch.equal(got, (w * s[:, None, None, None]).double())
+    plain = insitu.Recorder._operand_values(call, {"name": "m", "transpose": False, "weight": w}, Operand, w, None)
+    assert not call["folded"] and torch.equal(plain, w.double())
 
 
 def test_a_folded_operand_must_carry_its_shift():

@@ -34,12 +34,12 @@ LPIS, DEM = "ALL_LABEL-LPIS", "DEM_ELEV"
 GOLD = os.path.join(ROOT, "tests", "golden", "fusion_two_mod.json")
 
 
-def _task(**cfg_kw):
+def _task(precision="bf16", **cfg_kw):
     from flairhip.configs import fusion_unet_config
     from flair_hub.tasks.module_setup import build_segmentation_module
     from oracle.seeded_weights import fill_state_dict
     sizes = cfg_kw.pop("sizes")
-    cfg = fusion_unet_config(precision="bf16", **cfg_kw)
+    cfg = fusion_unet_config(precision=precision, **cfg_kw)
     task = build_segmentation_module(cfg, sizes, "train")
     task.model.load_state_dict(fill_state_dict(task.model.state_dict()))
     return task.cuda()

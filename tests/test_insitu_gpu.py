@@ -26,10 +26,10 @@ REQUIRED_FAMILIES = {
 }
 
 
-def _batch(n, seed):
+def _batch(n, seed, hw=(TILE, TILE)):
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, 5, TILE, TILE, generator=g)
-    t = torch.randint(0, CLASSES, (n, TILE, TILE), generator=g).to(torch.uint8)
+    x = torch.randn(n, 5, *hw, generator=g)
+    t = torch.randint(0, CLASSES, (n, *hw), generator=g).to(torch.uint8)
     return {MOD: x.cuda(), TASK: t.cuda()}
 
 
@@ -66,16 +66,16 @@ def _families(rec):
     return fams
 
 
-def _checked_step(B, mode, seed, chunk):
+def _checked_step(B, mode, seed, chunk, precision="bf16", hw=(TILE, TILE)):
     """step 1 eager with the product's own optimizer (operands re-packed by the batched packers afterwards), step 2
     recorded and checked -> (task, recorder, loss)"""
     from flairhip.optim import HipAdamW
-    task, _, _ = make_pair(precision="bf16")
+    task, _, _ = make_pair(precision=precision)
     task.train()
     opt = task.configure_optimizers()
     opt = opt["optimizer"] if isinstance(opt, dict) else opt
     assert isinstance(opt, HipAdamW), type(opt)
-    batch = _batch(B, seed)
+    batch = _batch(B, seed, hw)
     loss = task.training_step(batch, 0)
     opt.zero_grad(set_to_none=True)
     loss.backward()
@@ -90,13 +90,13 @@ def _checked_step(B, mode, seed, chunk):
     return task, rec, loss
 
 
-def _report_and_assert(task, rec, t0):
+def _report_and_assert(task, rec, t0, required=REQUIRED_FAMILIES):
     print(f"\n{rec.table()}\nchecked calls: {len(rec.calls)}; wall time {time.perf_counter() - t0:.1f} s")
     fails = rec.failures()
     assert not rec.unchecked, f"kernel-launching ops calls without a reference: {dict(rec.unchecked)}"
     assert not fails, f"{len(fails)} checks failed:\n" + "\n".join(r.line() for r in fails[:40])
     # (b) coverage of the kernel families the step is expected to route through
-    missing = REQUIRED_FAMILIES - _families(rec)
+    missing = set(required) - _families(rec)
     assert not missing, f"the step no longer reaches {sorted(missing)} (routing moved: update the list and the checks)"
     # (c) every parameter gradient IS the output of a checked call (bit for bit)
     srcs = {}

@@ -33,11 +33,10 @@ TRAINING_OPS = {"conv2d_bn_stats", "conv2d_upcat_bn_stats", "conv2d_pro_bn_stats
 HEAD = f"main_decoders.{TASK}.seg_model.segmentation_head.0"
 
 
-@pytest.fixture(scope="module")
-def trained(cuda):
-    """the bf16 task after two eager training steps (2 x 128 x 128), in eval mode"""
+def trained_task(precision):
+    """the task after two eager training steps (2 x 128 x 128), in eval mode"""
     from flairhip.optim import HipAdamW
-    task, _, _ = make_pair(precision="bf16")
+    task, _, _ = make_pair(precision=precision)
     task.train()
     opt = task.configure_optimizers()
     opt = opt["optimizer"] if isinstance(opt, dict) else opt
@@ -60,10 +59,18 @@ def trained(cuda):
     return task
 
 
-def _eval_forward(task, B, H, W, seed):
+@pytest.fixture(scope="module")
+def trained(cuda):
+    return trained_task("bf16")
+
+
+def _eval_forward(task, B, H, W, seed, after=None):
+    """the eval forward under a Recorder; after(logits): further ops calls on the logits inside the same recording"""
     x = torch.randn(B, 5, H, W, generator=torch.Generator().manual_seed(seed)).cuda()
     with Recorder(task.model, mode="full", chunk=1) as rec, torch.no_grad():
         logits, _ = task.model({MOD: x})
+        if after is not None:
+            after(logits[TASK])
         torch.cuda.synchronize()
     assert tuple(logits[TASK].shape) == (B, CLASSES, H, W)
     return rec
@@ -78,7 +85,8 @@ def _report(rec, t0):
         assert n_open <= OPEN_MAX_SHARE * n, (kind, n_open, n)
 
 
-def _assert_eval_coverage(rec):
+def _assert_eval_coverage(rec, layouts=("ring16", "thin", "stem")):
+    """layouts: the operand layouts of the 3x3 / 7x7 convs of the step (bf16: ring16, thin and stem; f32: igemm alone)"""
     calls = rec.calls
     training = sorted({c["op"] for c in calls if c["op"] in TRAINING_OPS or c.get("stats")
                        or str(c.get("family", "")).startswith(("dgrad", "bn_bwd", "wgrad", "upcat_dgrad", "upcat_wgrad"))})
@@ -88,16 +96,15 @@ def _assert_eval_coverage(rec):
         return any(c.get("family") == family and (layout is None or c.get("layout") == layout)
                    and all(c.get(k) == v for k, v in flags.items()) for c in calls)
 
-    required = {
-        "fwd:ring16 bias+relu": seen("fwd", "ring16", folded=True, bias=True, relu=True, residual=False),
-        "fwd:ring16 residual+relu": seen("fwd", "ring16", folded=True, bias=True, relu=True, residual=True),
-        "fwd:thin bias+relu": seen("fwd", "thin", folded=True, bias=True, relu=True, residual=False),
-        "fwd:stem bias+relu": seen("fwd", "stem", folded=True, bias=True, relu=True, residual=False),
+    required = {f"fwd:{lay} bias+relu": seen("fwd", lay, folded=True, bias=True, relu=True, residual=False)
+                for lay in layouts}
+    required.update({
+        f"fwd:{layouts[0]} residual+relu": seen("fwd", layouts[0], folded=True, bias=True, relu=True, residual=True),
         "fwd:igemm 1x1 stride-2 bias, no relu": seen("fwd", "igemm", folded=True, kernel="1x1", stride=2, bias=True,
                                                      relu=False, residual=False),
         "upcat_fwd bias+relu": seen("upcat_fwd", folded=True, bias=True, relu=True),
         "bn_eval_params": seen("bn_eval_params"),
-    }
+    })
     missing = sorted(k for k, ok in required.items() if not ok)
     assert not missing, f"the eval step no longer reaches {missing} (routing moved: update the list and the checks); " \
                         f"families seen: {sorted(_families(rec))}"

@@ -333,7 +333,8 @@ def test_upsample_concat(cuda, dtype, C1, C2):
 def test_bilinear(cuda, dtype, hi, wi, ho, wo):
     """both directions against the float64 resize of tests/insitu.py (ATen's align_corners=False source index taken
     in float64; the backward is its exact transpose), element by element: ulp_bf16(r) + REL * a for the bf16 outputs, a
-    the same map on absolute values.  The f32 outputs are compared with F.interpolate in f32."""
+    the same map on absolute values.  The f32 outputs are compared with F.interpolate in f32, and element by element
+    with the float64 taps of the coordinate the kernel itself takes in f32."""
     from flairhip import ops
     from insitu import Checker
     g = torch.Generator().manual_seed(hi * wo)
@@ -353,6 +354,13 @@ def test_bilinear(cuda, dtype, hi, wi, ho, wo):
         # to 2.9 x REL * a where the taps nearly cancel, so the float64 bound is for the bf16 outputs
         assert (from_nhwc(y, C) - ref.detach()).abs().max().item() <= 2e-6
         assert (from_nhwc(dx, C) - xq.grad).abs().max().item() <= 2e-5
+        # and element by element against the operation the kernel defines: float64 taps from the coordinate as the
+        # kernel rounds it (insitu.source_coordinate_f32), within REL * a -- at these ratios too
+        ck = Checker("full", chunk=1)
+        ck.bilinear({"op": "bilinear_fwd"}, xd, y, False)
+        ck.bilinear({"op": "bilinear_bwd"}, dyd, dx, True)
+        print("\n" + "\n".join(r.line() for r in ck.results))
+        assert len(ck.results) == 2 and all(r.ok for r in ck.results), [r.line() for r in ck.results if not r.ok]
     else:
         ck = Checker("full", chunk=1)
         ck.bilinear({"op": "bilinear_fwd"}, xd, y, False)
