@@ -26,6 +26,7 @@
 //   halo      [k-step plane][halo pixel][32 B], halves swapped when bit 3 of the pixel's x is set; plane stride
 //             = 64 mod 128 bytes -> conflict-free ds_read_b128 for 32 pixels of a row and conflict-free ds_write_b128
 #include "ffa_gfx950.h"
+#include "conv_call.h"
 
 #include <stdlib.h>
 
@@ -943,39 +944,6 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
 // ------------------------------------------------------------------------------------------------
 // host side
 
-struct RingPlan {
-  int cfg;     // 0: none
-  int th, tw;  // pixel tile
-  int bco;     // output channels per block
-};
-
-// Tile configuration of a layer.  cfg 1: 64 co x 8x32 px, 4 waves, two blocks per CU; cfg 2: 64 co x 16x16 px,
-// 4 waves; cfg 4: 128 co x 8x32 px, 8 waves.  (cfg 3 / 5 of round 2 -- 64 co x 128 px per wave -- measured slower and
-// are gone; their numbers map to 4 / 1.)
-static RingPlan ring_plan(int B, int H, int W, int co_rows) {
-  RingPlan p;
-  p.cfg = 0;
-  p.th = p.tw = p.bco = 0;
-  const char* force = getenv("FFA_RING_CFG");
-  int cfg = force ? atoi(force) : -1;
-  if (cfg < 0) {
-    if (W < 32) cfg = 2;
-    else cfg = 1;
-  }
-  if (cfg == 3) cfg = 4;
-  if (cfg == 5) cfg = 1;
-  if (cfg == 4 && (co_rows % 128 != 0 || W < 32)) cfg = (W < 32) ? 2 : 1;
-  if (cfg == 1 && W < 32) cfg = 2;
-  p.cfg = cfg;
-  switch (cfg) {
-    case 1: p.th = 8; p.tw = 32; p.bco = 64; break;
-    case 2: p.th = 16; p.tw = 16; p.bco = 64; break;
-    case 4: p.th = 8; p.tw = 32; p.bco = 128; break;
-    default: p.cfg = 0; break;
-  }
-  return p;
-}
-
 template <int WCO, int WPX, int NT, int TH, int TW, int OCC>
 static int ring16_launch(const Ring3Args& a, int grid, hipStream_t stream) {
   if (!a.pro_sc)  // measurement session open (bench.py): the kernel's own duration from launch-attached events
@@ -998,71 +966,79 @@ static int ring_launch(const Ring3Args& a, int grid, hipStream_t stream) {
   return ffa_check_launch("conv3x3_ring");
 }
 
-// rows of the per-tile statistics a ring launch writes (its pixel tiles), 0 when the ring kernel does not apply
-extern "C" long long ffa_ring_stat_rows(int B, int H, int W, int co_rows) {
-  const RingPlan p = ring_plan(B, H, W, co_rows);
-  if (!p.cfg) return 0;
-  return (long long)B * ffa_cdiv(W, p.tw) * ffa_cdiv(H, p.th);
-}
-
-// in: [B][H][W][Ci], out / residual: [B][H][W][Co]; w_ring: operand packed by the ring layout of
-// ffa_pack_conv_weight for co_rows rows.  pro_scale / pro_shift (both or neither): the convolution reads
-// relu(in * pro_scale[c] + pro_shift[c]) instead of in (training-mode BatchNorm + ReLU of the producing layer,
-// evaluated while the halo is staged; zero padding applies to the normalised tensor).
-extern "C" int ffa_ring_conv3x3(int dtype, const void* in, const void* w_ring, const float* bias, const void* residual, void* out,
-                     float* stat_partials, const float* pro_scale, const float* pro_shift, int B, int H, int W, int Ci,
-                     int Co, int co_rows, int relu, hipStream_t stream) {
-  FFA_REQUIRE(dtype == FFA_BF16 || dtype == FFA_F32, "ring conv: bad dtype %d", dtype);
-  FFA_REQUIRE(in && w_ring && out, "ring conv: null pointer");
-  FFA_REQUIRE((pro_scale == nullptr) == (pro_shift == nullptr), "ring conv: prologue needs scale and shift");
-  const int eb = (dtype == FFA_BF16) ? 2 : 4;
-  FFA_REQUIRE(B > 0 && H > 0 && W > 0 && (Ci * eb) % 64 == 0 && Co % 8 == 0 && co_rows % 64 == 0,
-              "ring conv: bad dims (Ci %d, Co %d, rows %d)", Ci, Co, co_rows);
-  FFA_REQUIRE((long long)B * H * W * Ci * eb < (1LL << 31), "ring conv: input tensor must be smaller than 2 GiB");
-  const RingPlan p = ring_plan(B, H, W, co_rows);
-  if (!p.cfg) {
-    ffa_set_error("ring conv: no configuration for %dx%d, %d rows", H, W, co_rows);
-    return FFA_ERR_UNSUPPORTED;
+// Ring layout: the plain form of a 3x3 stride-1 pad-1 convolution, with statistics and / or the prologue.
+// Tile configuration (r->variant).  cfg 1: 64 co x 8x32 px, 4 waves, two blocks per CU; cfg 2: 64 co x 16x16 px,
+// 4 waves; cfg 4: 128 co x 8x32 px, 8 waves.  (cfg 3 / 5 of round 2 -- 64 co x 128 px per wave -- measured slower and
+// are gone; their numbers map to 4 / 1.)
+int ffa_ring_route(const ffa_conv_call_t& c, ffa_conv_route_t* r) {
+  FFA_REQUIRE(c.kh == 3 && c.kw == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 && c.Hi == c.Ho && c.Wi == c.Wo &&
+                  c.bnx == nullptr,
+              "conv: a ring-layout operand serves plain 3x3 stride-1 pad-1 convolutions only");
+  FFA_REQUIRE((c.Ci * ffa_conv_elem_bytes(c.dtype)) % 64 == 0 && c.co_rows > 0 && c.co_rows % 64 == 0,
+              "ring conv: bad dims (Ci %d, Co %d, rows %d)", c.Ci, c.Co, c.co_rows);
+  const int W = c.Wo;
+  const char* force = getenv("FFA_RING_CFG");
+  int cfg = force ? atoi(force) : -1;
+  if (cfg < 0) cfg = (W < 32) ? 2 : 1;
+  if (cfg == 3) cfg = 4;
+  if (cfg == 5) cfg = 1;
+  if (cfg == 4 && (c.co_rows % 128 != 0 || W < 32)) cfg = (W < 32) ? 2 : 1;
+  if (cfg == 1 && W < 32) cfg = 2;
+  int bco = 64;
+  switch (cfg) {
+    case 1: r->th = 8; r->tw = 32; break;
+    case 2: r->th = 16; r->tw = 16; break;
+    case 4: r->th = 8; r->tw = 32; bco = 128; break;
+    default:
+      ffa_set_error("ring conv: no configuration for %dx%d, %d rows", c.Ho, c.Wo, c.co_rows);
+      return FFA_ERR_UNSUPPORTED;
   }
-  Ring3Args a;
-  a.in = in;
-  a.w = w_ring;
-  a.out = out;
-  a.bias = bias;
-  a.stats = stat_partials;
-  a.res = residual;
-  a.pro_sc = pro_scale;
-  a.pro_sh = pro_shift;
-  a.B = B; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co;
-  a.relu = relu;
-  a.nchunks = Ci * eb / 64;
-  a.tiles_x = ffa_cdiv(W, p.tw);
-  a.tiles_y = ffa_cdiv(H, p.th);
-  a.npt = B * a.tiles_x * a.tiles_y;
-  a.ncb = co_rows / p.bco;
-  a.cb64_stride = (long long)a.nchunks * 3 * (3 * 2 * 64 * 32);
-  const int total = ffa_cdiv(a.npt, 8) * 8 * a.ncb;
+  r->variant = cfg;
+  r->kernel = (c.dtype == FFA_BF16) ? FFA_CONV_KERNEL_RING16 : FFA_CONV_KERNEL_RING;
+  r->tiles_x = ffa_cdiv(W, r->tw);
+  r->tiles_y = ffa_cdiv(c.Ho, r->th);
+  r->ntiles = c.B * r->tiles_x * r->tiles_y;
+  r->ncb = c.co_rows / bco;
+  const int total = ffa_cdiv(r->ntiles, 8) * 8 * r->ncb;
   const char* pg = getenv("FFA_RING_GRID");
   // two 4-wave blocks per CU (cfg 1; cfg 2 on the bf16 kernel), one 8-wave block (cfg 4)
-  int cap = pg ? atoi(pg) : ((p.cfg == 1 || (p.cfg == 2 && dtype == FFA_BF16)) ? 512 : 256);
+  int cap = pg ? atoi(pg) : ((cfg == 1 || (cfg == 2 && c.dtype == FFA_BF16)) ? 512 : 256);
   cap = cap < 8 ? 8 : (cap / 8) * 8;
-  const int grid = total < cap ? total : cap;
-  if (dtype == FFA_BF16) {  // v_mfma_f32_16x16x32_bf16 kernel (NT counts 16-pixel fragments there)
-    switch (p.cfg) {
-      case 1: return ring16_launch<1, 4, 4, 8, 32, 2>(a, grid, stream);
-      case 2: return ring16_launch<1, 4, 4, 16, 16, 2>(a, grid, stream);
-      case 4: return ring16_launch<2, 4, 4, 8, 32, 2>(a, grid, stream);
+  r->grid = total < cap ? total : cap;
+  return 0;
+}
+
+int ffa_ring_launch(const ffa_conv_call_t& c, const ffa_conv_route_t& r, hipStream_t stream) {
+  Ring3Args a;
+  a.in = c.in;
+  a.w = c.w;
+  a.out = c.out;
+  a.bias = c.bias;
+  a.stats = c.stats;
+  a.res = c.residual;
+  a.pro_sc = c.pro_scale;
+  a.pro_sh = c.pro_shift;
+  a.B = c.B; a.H = c.Ho; a.W = c.Wo; a.Ci = c.Ci; a.Co = c.Co;
+  a.relu = c.relu;
+  a.nchunks = c.Ci * ffa_conv_elem_bytes(c.dtype) / 64;
+  a.tiles_x = r.tiles_x;
+  a.tiles_y = r.tiles_y;
+  a.npt = r.ntiles;
+  a.ncb = r.ncb;
+  a.cb64_stride = (long long)a.nchunks * 3 * (3 * 2 * 64 * 32);
+  if (c.dtype == FFA_BF16) {  // v_mfma_f32_16x16x32_bf16 kernel (NT counts 16-pixel fragments there)
+    switch (r.variant) {
+      case 1: return ring16_launch<1, 4, 4, 8, 32, 2>(a, r.grid, stream);
+      case 2: return ring16_launch<1, 4, 4, 16, 16, 2>(a, r.grid, stream);
+      case 4: return ring16_launch<2, 4, 4, 8, 32, 2>(a, r.grid, stream);
     }
     return FFA_ERR_UNSUPPORTED;
   }
-#define FFA_RING_DISPATCH(T_)                                                        \
-  switch (p.cfg) {                                                                   \
-    case 1: return ring_launch<T_, 1, 4, 2, 8, 32, 2>(a, grid, stream);              \
-    case 2: return ring_launch<T_, 1, 4, 2, 16, 16, 1>(a, grid, stream);             \
-    case 4: return ring_launch<T_, 2, 4, 2, 8, 32, 2>(a, grid, stream);              \
+  switch (r.variant) {
+    case 1: return ring_launch<float, 1, 4, 2, 8, 32, 2>(a, r.grid, stream);
+    case 2: return ring_launch<float, 1, 4, 2, 16, 16, 1>(a, r.grid, stream);
+    case 4: return ring_launch<float, 2, 4, 2, 8, 32, 2>(a, r.grid, stream);
   }
-  FFA_RING_DISPATCH(float)
-#undef FFA_RING_DISPATCH
   return FFA_ERR_UNSUPPORTED;
 }
 

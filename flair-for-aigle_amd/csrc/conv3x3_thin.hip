@@ -24,6 +24,7 @@
 // puts output channel 8*kg + 4*mt + i (two tiles) or 4*kg + i (one tile) into tile row 4*kg + i, so a lane stores 16
 // (or 8) contiguous bytes per pixel.
 #include "ffa_gfx950.h"
+#include "conv_call.h"
 
 #include <stdlib.h>
 
@@ -385,12 +386,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_thin_kernel(ThinArgs a) {
 // host side
 
 template <int CI, int MT>
-static int thin_launch(const ThinArgs& a, int up, int pool, hipStream_t stream) {
-  // two blocks per CU; FFA_THIN_GRID caps the grid (the tests force several tiles per persistent block on small tensors)
-  const char* pg = getenv("FFA_THIN_GRID");
-  int cap = pg ? atoi(pg) : 512;
-  if (cap < 1) cap = 1;
-  const int grid = a.ntiles < cap ? a.ntiles : cap;
+static int thin_launch(const ThinArgs& a, int up, int pool, int grid, hipStream_t stream) {
   const bool st = a.stats != nullptr, pro = a.pro_sc != nullptr;
 #define FFA_THIN_GO(UP_, POOL_, ST_, PRO_)                                                                         \
   hipLaunchKernelGGL((conv3x3_thin_kernel<CI, MT, UP_, POOL_, ST_, PRO_>), dim3(grid), dim3(256), 0, stream, a); \
@@ -413,48 +409,58 @@ static int thin_launch(const ThinArgs& a, int up, int pool, hipStream_t stream) 
 #undef FFA_THIN_GO
 }
 
-// 1 when a layer qualifies for the thin kernel: bf16, 3x3 stride 1, at most 32 stored input channels and 32 rows
-extern "C" int ffa_thin_eligible(int dtype, int kh, int kw, int stride, int rows_real, int ci_pitch) {
+// true when a layer qualifies for the thin kernel: bf16, 3x3 stride 1, at most 32 stored input channels and 32 rows
+bool ffa_thin_takes_layer(int dtype, int kh, int kw, int stride, int rows_real, int ci_pitch) {
   return dtype == FFA_BF16 && kh == 3 && kw == 3 && stride == 1 && (ci_pitch == 16 || ci_pitch == 32) &&
          rows_real > 0 && rows_real <= 32;
 }
 
-extern "C" long long ffa_thin_stat_rows(int B, int H, int W, int ci_pitch) {
-  const int th = (ci_pitch == 32) ? 8 : 16;
-  return (long long)B * ffa_cdiv(W, 32) * ffa_cdiv(H, th);
+// Thin layout: bf16 3x3 stride-1 pad-1 convolutions in the plain form (statistics, prologue), the skip-less two-source
+// form (the input is nearest_x2 of `in`; statistics, prologue) and the skip-less pooled form (the output is 2x2
+// sum-pooled).
+int ffa_thin_route(const ffa_conv_call_t& c, ffa_conv_route_t* r) {
+  if (c.form == FFA_CONV_UPCAT && (c.c1 != c.Ci || c.dtype != FFA_BF16)) {
+    ffa_set_error("conv_upcat: a thin-layout operand takes the skip-less form only");
+    return FFA_ERR_UNSUPPORTED;
+  }
+  FFA_REQUIRE(c.dtype == FFA_BF16 && c.kh == 3 && c.kw == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 && c.Hi == c.Ho &&
+                  c.Wi == c.Wo && c.bnx == nullptr,
+              "conv: a thin-layout operand serves bf16 3x3 stride-1 pad-1 convolutions only");
+  if (c.form == FFA_CONV_POOLED && c.c1 != c.Co) {
+    ffa_set_error("dgrad_upcat: a thin-layout operand takes the skip-less form only");
+    return FFA_ERR_UNSUPPORTED;
+  }
+  FFA_REQUIRE((c.Ci == 16 || c.Ci == 32) && (c.co_rows == 16 || c.co_rows == 32),
+              "thin conv: bad dims (Ci %d, Co %d, rows %d)", c.Ci, c.Co, c.co_rows);
+  FFA_REQUIRE((long long)c.B * c.Hi * c.Wi * c.Ci * 2 < (1LL << 40), "thin conv: input too large");
+  r->kernel = FFA_CONV_KERNEL_THIN;
+  r->variant = 0;
+  r->tw = 32;
+  r->th = (c.Ci == 32) ? 8 : 16;
+  r->tiles_x = ffa_cdiv(c.Wo, r->tw);
+  r->tiles_y = ffa_cdiv(c.Ho, r->th);
+  r->ntiles = c.B * r->tiles_x * r->tiles_y;
+  r->ncb = 1;
+  // two blocks per CU; FFA_THIN_GRID caps the grid (the tests force several tiles per persistent block on small tensors)
+  const char* pg = getenv("FFA_THIN_GRID");
+  int cap = pg ? atoi(pg) : 512;
+  if (cap < 1) cap = 1;
+  r->grid = r->ntiles < cap ? r->ntiles : cap;
+  return 0;
 }
 
-// in: [B][H][W][Ci] (up: [B][H/2][W/2][Ci]); out / residual: [B][H][W][Co] (pool: out [B][H/2][W/2][Co]).
-// co_rows = 16 or 32 (the packed operand's rows).  up: the input is nearest_x2 of `in`; pool: the output is 2x2
-// sum-pooled (no bias / residual / relu / statistics then).
-// pro_scale / pro_shift (both or neither, [Ci] f32): the convolution reads relu(in * scale[c] + shift[c]).
-extern "C" int ffa_thin_conv3x3(const void* in, const void* w_thin, const float* bias, const void* residual, void* out,
-                                float* stat_partials, int B, int H, int W, int Ci, int Co, int co_rows, int relu, int up,
-                                int pool, hipStream_t stream) {
-  return ffa_thin_conv3x3_pro(in, w_thin, bias, residual, out, stat_partials, nullptr, nullptr, B, H, W, Ci, Co, co_rows,
-                              relu, up, pool, stream);
-}
-extern "C" int ffa_thin_conv3x3_pro(const void* in, const void* w_thin, const float* bias, const void* residual,
-                                    void* out, float* stat_partials, const float* pro_scale, const float* pro_shift, int B,
-                                    int H, int W, int Ci, int Co, int co_rows, int relu, int up, int pool,
-                                    hipStream_t stream) {
-  FFA_REQUIRE((pro_scale == nullptr) == (pro_shift == nullptr) && !(pool && pro_scale),
-              "thin conv: prologue needs scale and shift (and is not part of the pooled form)");
-  FFA_REQUIRE(in && w_thin && out, "thin conv: null pointer");
-  FFA_REQUIRE(B > 0 && H > 0 && W > 0 && (Ci == 16 || Ci == 32) && (co_rows == 16 || co_rows == 32) && Co % 8 == 0,
-              "thin conv: bad dims (Ci %d, Co %d, rows %d)", Ci, Co, co_rows);
-  FFA_REQUIRE(!(up || pool) || (H % 2 == 0 && W % 2 == 0), "thin conv: the x2 forms need even sizes");
-  FFA_REQUIRE(!pool || (!bias && !residual && !relu && !stat_partials), "thin conv: the pooled form has a plain epilogue");
-  FFA_REQUIRE(!up || !residual, "thin conv: no residual input in the upsampled form");
-  FFA_REQUIRE((long long)B * H * W * Ci * 2 < (1LL << 40), "thin conv: input too large");
+// in: [B][H][W][Ci] (two-source form: [B][H/2][W/2][Ci]); out / residual: [B][H][W][Co] (pooled form: out
+// [B][H/2][W/2][Co]).  co_rows = 16 or 32 (the packed operand's rows).
+int ffa_thin_launch(const ffa_conv_call_t& c, const ffa_conv_route_t& r, hipStream_t stream) {
+  const int up = c.form == FFA_CONV_UPCAT, pool = c.form == FFA_CONV_POOLED;
   ThinArgs a;
-  a.in = in; a.w = w_thin; a.out = out; a.bias = bias; a.res = residual; a.stats = stat_partials;
-  a.pro_sc = pro_scale; a.pro_sh = pro_shift;
-  a.B = B; a.H = H; a.W = W; a.Co = Co; a.relu = relu;
-  const int th = (Ci == 32) ? 8 : 16;
-  a.tiles_x = ffa_cdiv(W, 32);
-  a.tiles_y = ffa_cdiv(H, th);
-  a.ntiles = B * a.tiles_x * a.tiles_y;
-  if (Ci == 32) return (co_rows == 32) ? thin_launch<32, 2>(a, up, pool, stream) : thin_launch<32, 1>(a, up, pool, stream);
-  return (co_rows == 32) ? thin_launch<16, 2>(a, up, pool, stream) : thin_launch<16, 1>(a, up, pool, stream);
+  a.in = c.in; a.w = c.w; a.out = c.out; a.bias = c.bias; a.res = c.residual; a.stats = c.stats;
+  a.pro_sc = c.pro_scale; a.pro_sh = c.pro_shift;
+  a.B = c.B; a.H = c.Ho; a.W = c.Wo; a.Co = c.Co; a.relu = c.relu;
+  a.tiles_x = r.tiles_x;
+  a.tiles_y = r.tiles_y;
+  a.ntiles = r.ntiles;
+  if (c.Ci == 32)
+    return (c.co_rows == 32) ? thin_launch<32, 2>(a, up, pool, r.grid, stream) : thin_launch<32, 1>(a, up, pool, r.grid, stream);
+  return (c.co_rows == 32) ? thin_launch<16, 2>(a, up, pool, r.grid, stream) : thin_launch<16, 1>(a, up, pool, r.grid, stream);
 }

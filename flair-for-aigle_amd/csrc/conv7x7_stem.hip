@@ -19,6 +19,7 @@
 #include "ffa_gfx950.h"
 
 #include "conv7x7_stem.h"
+#include "conv_call.h"
 
 struct StemArgs {
   const void* in;   // [B][Hi][Wi][16] bf16
@@ -239,35 +240,44 @@ __global__ void __launch_bounds__(512) conv7x7_stem_kernel(StemArgs a) {
   ffa_wait_vm<0>();  // nothing of this block may still be writing its LDS
 }
 
-extern "C" int ffa_stem_eligible(int dtype, int kh, int kw, int stride, int cout, int ci_pitch) {
+bool ffa_stem_takes_layer(int dtype, int kh, int kw, int stride, int cout, int ci_pitch) {
   return dtype == FFA_BF16 && kh == 7 && kw == 7 && stride == 2 && cout == 64 && ci_pitch == 16;
 }
 
-extern "C" long long ffa_stem_stat_rows(int B, int Ho, int Wo) {
-  return (long long)B * ffa_cdiv(Wo, StemGeom::TW) * ffa_cdiv(Ho, StemGeom::TH);
-}
-
-// in [B][Hi][Wi][16] bf16 (channels >= 8 are never read; pad channels must be zero), out [B][Ho][Wo][Co] with
-// Ho = (Hi - 1) / 2 + 1, Wo likewise and Co = 64; stat_partials [ffa_stem_stat_rows][2][Co] or null
-extern "C" int ffa_stem_conv7x7(const void* in, const void* w_stem, const float* bias, void* out, float* stat_partials, int B,
-                                int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int relu, hipStream_t stream) {
-  FFA_REQUIRE(in && w_stem && out, "stem conv: null pointer");
-  FFA_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ci == 16 && Co == 64, "stem conv: input pitch 16, output pitch 64 (got %d / %d)", Ci, Co);
-  FFA_REQUIRE(Ho == (Hi - 1) / 2 + 1 && Wo == (Wi - 1) / 2 + 1, "stem conv: output size of a 7x7 stride-2 pad-3 convolution");
-  FFA_REQUIRE((long long)B * Hi * Wi * 32 < (1LL << 31) && (long long)StemGeom::IH * Wi * 32 < (1LL << 31),
-              "stem conv: input tensor must be smaller than 2 GiB");
-  StemArgs a;
-  a.in = in; a.w = w_stem; a.out = out; a.bias = bias; a.stats = stat_partials;
-  a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.relu = relu;
-  a.tiles_x = ffa_cdiv(Wo, StemGeom::TW);
-  a.tiles_y = ffa_cdiv(Ho, StemGeom::TH);
-  a.npt = B * a.tiles_x * a.tiles_y;
+// Stem layout: the plain form of the bf16 7x7 stride-2 pad-3 convolution, with statistics; no residual input.
+int ffa_stem_route(const ffa_conv_call_t& c, ffa_conv_route_t* r) {
+  FFA_REQUIRE(c.dtype == FFA_BF16 && c.kh == 7 && c.kw == 7 && c.stride == 2 && c.pad == 3 && c.dil == 1 &&
+                  c.bnx == nullptr && c.residual == nullptr,
+              "conv: a stem-layout operand serves the bf16 7x7 stride-2 pad-3 convolution only (no residual input)");
+  FFA_REQUIRE(c.Ci == 16 && c.Co == 64, "stem conv: input pitch 16, output pitch 64 (got %d / %d)", c.Ci, c.Co);
+  FFA_REQUIRE(c.Ho == (c.Hi - 1) / 2 + 1 && c.Wo == (c.Wi - 1) / 2 + 1,
+              "stem conv: output size of a 7x7 stride-2 pad-3 convolution");
+  FFA_REQUIRE((long long)StemGeom::IH * c.Wi * 32 < (1LL << 31), "stem conv: input tensor must be smaller than 2 GiB");
+  r->kernel = FFA_CONV_KERNEL_STEM;
+  r->variant = 0;
+  r->th = StemGeom::TH;
+  r->tw = StemGeom::TW;
+  r->tiles_x = ffa_cdiv(c.Wo, r->tw);
+  r->tiles_y = ffa_cdiv(c.Ho, r->th);
+  r->ntiles = c.B * r->tiles_x * r->tiles_y;
+  r->ncb = 1;
   int cap = 256;
   if (const char* e = getenv("FFA_STEM_GRID")) {
     const int v = atoi(e);
     if (v > 0) cap = v;
   }
-  const int grid = a.npt < cap ? a.npt : cap;
-  hipLaunchKernelGGL(conv7x7_stem_kernel, dim3(grid), dim3(StemGeom::NTHR), 0, stream, a);
+  r->grid = r->ntiles < cap ? r->ntiles : cap;
+  return 0;
+}
+
+// in [B][Hi][Wi][16] bf16 (channels >= 8 are never read; pad channels must be zero), out [B][Ho][Wo][64]
+int ffa_stem_launch(const ffa_conv_call_t& c, const ffa_conv_route_t& r, hipStream_t stream) {
+  StemArgs a;
+  a.in = c.in; a.w = c.w; a.out = c.out; a.bias = c.bias; a.stats = c.stats;
+  a.B = c.B; a.Hi = c.Hi; a.Wi = c.Wi; a.Ho = c.Ho; a.Wo = c.Wo; a.Co = c.Co; a.relu = c.relu;
+  a.tiles_x = r.tiles_x;
+  a.tiles_y = r.tiles_y;
+  a.npt = r.ntiles;
+  hipLaunchKernelGGL(conv7x7_stem_kernel, dim3(r.grid), dim3(StemGeom::NTHR), 0, stream, a);
   return ffa_check_launch("conv7x7_stem");
 }

@@ -19,6 +19,7 @@
 //                     for 16 consecutive pixels, 3 is coprime with the 16 slots of a bank row)
 //              weight [BCO rows][TAPS*32 B + 16 B pad] (odd number of 16-B slots per row)
 #include "ffa_gfx950.h"
+#include "conv_call.h"
 
 #include <stdlib.h>
 
@@ -1063,16 +1064,10 @@ __global__ void __launch_bounds__(256, 2) conv3x3_persist_kernel(ConvArgs a) {
 // ------------------------------------------------------------------------------------------------
 // host side: configuration choice + launch
 
-struct ConvPlan {
-  int bco;     // output channels per block (= row count of one packed weight slab)
-  int rg;      // kernel rows per chunk
-  int th, tw;  // output pixel tile
-};
-
 static int conv_rg(int kh) { return kh == 7 ? 1 : kh; }
 
 // Preferred block height in output channels for a layer with `cout` real output channels.  The
-// caller packs the weights with this value and hands the same value back to ffa_conv2d.
+// caller packs the weights with this value and hands the same value back in ffa_conv_call_t.
 static int conv_pref_bco(int kh, int kw, int stride, int cout) {
   // 64 rows + deep (full 128-byte line) halo staging beats 128 rows + 32-byte staging, see ConvGeom
   if (kh == 3 && kw == 3 && stride == 1) return cout > 32 ? 64 : 32;
@@ -1104,65 +1099,63 @@ static int conv_persist_grid(int dil, int c1_out, const void* bnx, int grid) {
   return pgrid < grid ? pgrid : grid;
 }
 
+// The route (ffa_igemm_route) has chosen kernel, halo depth, tile and grid; the launch chain only turns them into
+// template arguments.
 template <typename T, int KH, int KW, int STRIDE, int RG, int BCO, int WCO, int WPX, int TH, int TW, int HK,
           bool UP = false>
-static int launch_hk(const ConvArgs& a, hipStream_t stream) {
-  const int grid = ffa_cdiv(a.npt, 8) * 8 * a.ncb;
-  if constexpr (KH == 3 && KW == 3 && STRIDE == 1 && HK >= 2 && !UP && WCO == 1 && WPX == 4) {
-    const int pgrid = conv_persist_grid(a.dil, a.c1_out, a.bnx, grid);
-    if (pgrid > 0) {
-      hipLaunchKernelGGL((conv3x3_persist_kernel<T, BCO, TH, TW, HK>), dim3(pgrid), dim3(256), 0, stream, a);
+static int launch_hk(const ConvArgs& a, const ffa_conv_route_t& r, hipStream_t stream) {
+  if (r.kernel == FFA_CONV_KERNEL_PERSIST) {
+    if constexpr (KH == 3 && KW == 3 && STRIDE == 1 && HK >= 2 && !UP && WCO == 1 && WPX == 4) {
+      hipLaunchKernelGGL((conv3x3_persist_kernel<T, BCO, TH, TW, HK>), dim3(r.grid), dim3(256), 0, stream, a);
       return ffa_check_launch("conv3x3_persist");
     }
+    ffa_set_error("conv: routed to a persistent kernel that is not instantiated");
+    return FFA_ERR_UNSUPPORTED;
   }
-  hipLaunchKernelGGL((conv_igemm_kernel<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, HK, UP>), dim3(grid),
+  hipLaunchKernelGGL((conv_igemm_kernel<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, HK, UP>), dim3(r.grid),
                      dim3(64 * WCO * WPX), 0, stream, a);
   return ffa_check_launch("conv_igemm");
 }
 
-// two-source (nearest x2 + concat) launch: 3x3 stride 1 only; the caller checked that C1 is a whole number of
-// HK-chunk groups
-template <typename T, int BCO, int TH, int TW>
-static int launch_up(const ConvArgs& a, hipStream_t stream) {
-  if (a.nchunks % 4 == 0) return launch_hk<T, 3, 3, 1, 3, BCO, 1, 4, TH, TW, 4, true>(a, stream);
-  return launch_hk<T, 3, 3, 1, 3, BCO, 1, 4, TH, TW, 2, true>(a, stream);
-}
-
 template <typename T, int KH, int KW, int STRIDE, int RG, int BCO, int WCO, int WPX, int TH, int TW>
-static int launch_cfg(const ConvArgs& a, hipStream_t stream) {
+static int launch_cfg(const ConvArgs& a, const ffa_conv_call_t& c, const ffa_conv_route_t& r, hipStream_t stream) {
   // deep halo staging for the 3x3 stride-1 workhorse when whole 64- / 128-byte runs of channels exist
   // (a 128-row block was measured equal at best: its weight slab leaves no LDS for the deep halo at two blocks
   // per CU, so 64 rows is the largest block instantiated)
   if constexpr (KH == 3 && STRIDE == 1) {
-    if (a.nchunks % 4 == 0) return launch_hk<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, 4>(a, stream);
-    if (a.nchunks % 2 == 0) return launch_hk<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, 2>(a, stream);
+    if (c.form == FFA_CONV_UPCAT) {  // two-source (nearest x2 + concat) loader: the route checked that C1 is whole groups
+      if (r.variant == 4) return launch_hk<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, 4, true>(a, r, stream);
+      return launch_hk<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, 2, true>(a, r, stream);
+    }
+    if (r.variant == 4) return launch_hk<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, 4>(a, r, stream);
+    if (r.variant == 2) return launch_hk<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, 2>(a, r, stream);
   }
-  return launch_hk<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, 1>(a, stream);
+  return launch_hk<T, KH, KW, STRIDE, RG, BCO, WCO, WPX, TH, TW, 1>(a, r, stream);
 }
 
 template <typename T, int KH, int KW, int STRIDE, int RG>
-static int launch_shape(const ConvArgs& a, const ConvPlan& p, hipStream_t stream) {
-  const bool wide = (p.tw == 32);
+static int launch_shape(const ConvArgs& a, const ffa_conv_call_t& c, const ffa_conv_route_t& r, hipStream_t stream) {
+  const bool wide = (r.tw == 32);
 #define FFA_CONV_CASE(BCO_, WCO_, WPX_)                                                      \
-  if (p.bco == BCO_) {                                                                       \
-    return wide ? launch_cfg<T, KH, KW, STRIDE, RG, BCO_, WCO_, WPX_, 8, 32>(a, stream)      \
-                : launch_cfg<T, KH, KW, STRIDE, RG, BCO_, WCO_, WPX_, 16, 16>(a, stream);    \
+  if (c.bco == BCO_) {                                                                       \
+    return wide ? launch_cfg<T, KH, KW, STRIDE, RG, BCO_, WCO_, WPX_, 8, 32>(a, c, r, stream)   \
+                : launch_cfg<T, KH, KW, STRIDE, RG, BCO_, WCO_, WPX_, 16, 16>(a, c, r, stream); \
   }
   FFA_CONV_CASE(64, 1, 4)
   FFA_CONV_CASE(32, 1, 4)
 #undef FFA_CONV_CASE
-  ffa_set_error("conv: no kernel for bco=%d", p.bco);
+  ffa_set_error("conv: no kernel for bco=%d", c.bco);
   return FFA_ERR_UNSUPPORTED;
 }
 
 template <typename T>
-static int launch_dtype(const ConvArgs& a, int kh, int kw, int stride, const ConvPlan& p, hipStream_t stream) {
-  if (kh == 3 && kw == 3 && stride == 1) return launch_shape<T, 3, 3, 1, 3>(a, p, stream);
-  if (kh == 3 && kw == 3 && stride == 2) return launch_shape<T, 3, 3, 2, 3>(a, p, stream);
-  if (kh == 1 && kw == 1 && stride == 1) return launch_shape<T, 1, 1, 1, 1>(a, p, stream);
-  if (kh == 1 && kw == 1 && stride == 2) return launch_shape<T, 1, 1, 2, 1>(a, p, stream);
-  if (kh == 7 && kw == 7 && stride == 2) return launch_shape<T, 7, 7, 2, 1>(a, p, stream);
-  ffa_set_error("conv: unsupported kernel %dx%d stride %d", kh, kw, stride);
+static int launch_dtype(const ConvArgs& a, const ffa_conv_call_t& c, const ffa_conv_route_t& r, hipStream_t stream) {
+  if (c.kh == 3 && c.kw == 3 && c.stride == 1) return launch_shape<T, 3, 3, 1, 3>(a, c, r, stream);
+  if (c.kh == 3 && c.kw == 3 && c.stride == 2) return launch_shape<T, 3, 3, 2, 3>(a, c, r, stream);
+  if (c.kh == 1 && c.kw == 1 && c.stride == 1) return launch_shape<T, 1, 1, 1, 1>(a, c, r, stream);
+  if (c.kh == 1 && c.kw == 1 && c.stride == 2) return launch_shape<T, 1, 1, 2, 1>(a, c, r, stream);
+  if (c.kh == 7 && c.kw == 7 && c.stride == 2) return launch_shape<T, 7, 7, 2, 1>(a, c, r, stream);
+  ffa_set_error("conv: unsupported kernel %dx%d stride %d", c.kh, c.kw, c.stride);
   return FFA_ERR_UNSUPPORTED;
 }
 
@@ -1171,30 +1164,28 @@ extern "C" int ffa_conv_block_co(int kh, int kw, int stride, int cout) {
   return conv_supported(kh, kw, stride, bco) ? bco : FFA_ERR_UNSUPPORTED;
 }
 
-// Operand layout + block height for a layer: the value to hand to ffa_pack_conv_weight / ffa_conv2d as `bco`.
+// Operand layout + block height for a layer: the value to hand to ffa_pack_conv_weight / ffa_conv_call_t as `bco`.
 // Bits 0..11 = rows per block (the padded row count is a multiple of it); FFA_BCO_RING set = the operand is packed
-// for the ring kernels of conv3x3_ring.hip (3x3 stride 1 pad 1, >= 64 rows, whole 64-byte groups of input channels;
-// plain ffa_conv2d / ffa_conv2d_stats calls only -- pass allow_ring = 0 for operands used by the two-source,
-// split-epilogue or zero-insertion (dil = 2) calls).
+// for the ring kernels of conv3x3_ring.hip (3x3 stride 1 pad 1, >= 64 rows, whole 64-byte groups of input channels).
+// Which forms of call a layout serves is the router's table (conv_call.cpp); the caller clears the bit otherwise.
 //   bf16: conv3x3_ring16_kernel (v_mfma_f32_16x16x32_bf16, LDS-DMA weights AND halo) is the default since round 3 --
 //         36 / 32.5 / 34.7 us on the 128 / 256 / 512-channel layers against 40 / 37.3 / 38 for conv3x3_persist_kernel
 //         (same box); FFA_RING=0 restores the conv_igemm operands;
 //   f32:  conv3x3_ring_kernel only with FFA_RING=1 (it equals the persist kernel).
 // allow_ring bit 1 (value 2): the caller can also take FFA_BCO_THIN -- conv3x3_thin_kernel for bf16 layers with at most
-// 32 stored input channels and 32 rows (plain, statistics, two-source with C2 = 0 and pooled-split with C2 = 0 calls;
-// not the zero-insertion or the BatchNorm-backward-partials forms); rows per block 16 or 32.  FFA_THIN=0 disables.
+// 32 stored input channels and 32 rows; rows per block 16 or 32.  FFA_THIN=0 disables.
 extern "C" int ffa_conv_plan(int dtype, int kh, int kw, int stride, int cout, int ci_pitch, int allow_ring) {
   const int bco = ffa_conv_block_co(kh, kw, stride, cout);
   if (bco < 0) return bco;
   {
     // the ResNet stem (bit 2 of `allow`; FFA_STEM=0 keeps conv_igemm_kernel<7, 7, 2>)
     const char* t = getenv("FFA_STEM");
-    if ((allow_ring & 4) && !(t && t[0] == '0') && ffa_stem_eligible(dtype, kh, kw, stride, cout, ci_pitch))
+    if ((allow_ring & 4) && !(t && t[0] == '0') && ffa_stem_takes_layer(dtype, kh, kw, stride, cout, ci_pitch))
       return 64 | FFA_BCO_STEM;
   }
   {
     const char* t = getenv("FFA_THIN");
-    if ((allow_ring & 2) && !(t && t[0] == '0') && ffa_thin_eligible(dtype, kh, kw, stride, cout, ci_pitch))
+    if ((allow_ring & 2) && !(t && t[0] == '0') && ffa_thin_takes_layer(dtype, kh, kw, stride, cout, ci_pitch))
       return (cout <= 16 ? 16 : 32) | FFA_BCO_THIN | (ci_pitch == 32 ? FFA_BCO_THIN32 : 0);
   }
   allow_ring &= 1;
@@ -1208,246 +1199,92 @@ extern "C" int ffa_conv_plan(int dtype, int kh, int kw, int stride, int cout, in
 
 extern "C" int ffa_conv_row_group(int kh) { return conv_rg(kh); }
 
-static int conv2d_impl(int dtype, const void* in, const void* w_packed, const float* bias, const void* residual,
-                       void* out, float* stat_partials, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co,
-                       int co_rows, int bco, int kh, int kw, int stride, int pad, int dil, int relu,
-                       hipStream_t stream, void* out2 = nullptr, int c1_out = 0, const void* bnx = nullptr,
-                       const float* bn_sc = nullptr, const float* bn_sh = nullptr) {
-  FFA_REQUIRE(dtype == FFA_BF16 || dtype == FFA_F32, "conv: bad dtype %d", dtype);
-  FFA_REQUIRE(in && w_packed && out, "conv: null pointer");
-  FFA_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "conv: bad dims");
-  FFA_REQUIRE(Ci % 16 == 0 && Co % 8 == 0, "conv: channel pitch must be a multiple of 16 (in) / 8 (out), got %d/%d", Ci, Co);
-  FFA_REQUIRE(dil == 1 || dil == 2, "conv: dil must be 1 or 2");
-  FFA_REQUIRE(dil == 1 || stride == 1, "conv: zero-insertion input needs stride 1");
-  FFA_REQUIRE((long long)B * Hi * Wi * Ci * (dtype == FFA_BF16 ? 2 : 4) < (1LL << 31),
-              "conv: input tensor must be smaller than 2 GiB (32-bit piece offsets)");
-  if (bco & FFA_BCO_STEM) {
-    FFA_REQUIRE(dtype == FFA_BF16 && kh == 7 && kw == 7 && stride == 2 && pad == 3 && dil == 1 && c1_out == 0 && bnx == nullptr &&
-                    residual == nullptr,
-                "conv: a stem-layout operand serves the bf16 7x7 stride-2 pad-3 convolution only (no residual input)");
-    return ffa_stem_conv7x7(in, w_packed, bias, out, stat_partials, B, Hi, Wi, Ci, Ho, Wo, Co, relu, stream);
-  }
-  if (bco & FFA_BCO_THIN) {
-    FFA_REQUIRE(dtype == FFA_BF16 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && Hi == Ho && Wi == Wo &&
-                    bnx == nullptr,
-                "conv: a thin-layout operand serves bf16 3x3 stride-1 pad-1 convolutions only");
-    if (c1_out > 0) {  // pooled split epilogue: only the all-low-resolution form (no skip part)
-      FFA_REQUIRE(c1_out == Co && out2 == nullptr && !stat_partials, "conv: thin pooled form takes C2 = 0 only");
-      return ffa_thin_conv3x3(in, w_packed, nullptr, nullptr, out, nullptr, B, Hi, Wi, Ci, Co, co_rows, 0, 0, 1, stream);
-    }
-    return ffa_thin_conv3x3(in, w_packed, bias, residual, out, stat_partials, B, Hi, Wi, Ci, Co, co_rows, relu, 0, 0,
-                            stream);
-  }
-  if (bco & FFA_BCO_RING) {
-    FFA_REQUIRE(kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && Hi == Ho && Wi == Wo && c1_out == 0 &&
-                    bnx == nullptr,
-                "conv: a ring-layout operand serves plain 3x3 stride-1 pad-1 convolutions only");
-    return ffa_ring_conv3x3(dtype, in, w_packed, bias, residual, out, stat_partials, nullptr, nullptr, B, Hi, Wi, Ci, Co,
-                            co_rows, relu, stream);
-  }
-  if (!conv_supported(kh, kw, stride, bco)) {
-    ffa_set_error("conv: unsupported kernel %dx%d stride %d block %d", kh, kw, stride, bco);
+// 32-byte channel groups staged per halo fill (HK of ConvGeom) for a convolution over Ci stored input channels
+static int igemm_halo_groups(int dtype, int kh, int stride, int Ci) {
+  const int nchunks = Ci * ffa_conv_elem_bytes(dtype) / 32;
+  if (!(kh == 3 && stride == 1)) return 1;
+  return nchunks % 4 == 0 ? 4 : (nchunks % 2 == 0 ? 2 : 1);
+}
+
+// The two-source loader fetches whole halo channel groups from one source: C1 must cover a whole number of them
+bool ffa_igemm_upcat_split_ok(int dtype, int c1, int c2) {
+  const int hk = igemm_halo_groups(dtype, 3, 1, c1 + c2);
+  return hk > 1 && (c1 * ffa_conv_elem_bytes(dtype)) % (hk * 32) == 0;
+}
+
+// conv_igemm layout: every supported kernel shape in the plain form (dil 1 / 2, statistics, BatchNorm-backward
+// partials), the two-source form when C1 covers whole channel groups, the pooled / split form when C1 is whole blocks.
+int ffa_igemm_route(const ffa_conv_call_t& c, ffa_conv_route_t* r) {
+  if (!conv_supported(c.kh, c.kw, c.stride, c.bco)) {
+    ffa_set_error("conv: unsupported kernel %dx%d stride %d block %d", c.kh, c.kw, c.stride, c.bco);
     return FFA_ERR_UNSUPPORTED;
   }
-  ConvPlan p;
-  p.bco = bco;
-  p.rg = conv_rg(kh);
-  p.tw = (Wo >= 32) ? 32 : 16;
-  p.th = (Wo >= 32) ? 8 : 16;
-  FFA_REQUIRE(co_rows % p.bco == 0, "conv: packed weight rows %d not a multiple of block %d", co_rows, p.bco);
-  ConvArgs a;
-  a.in = in;
-  a.w = w_packed;
-  a.out = out;
-  a.bias = bias;
-  a.stats = stat_partials;
-  a.in2 = nullptr;
-  a.c1_bytes = 0;
-  a.out2 = out2;
-  a.c1_out = c1_out;
-  a.bnx = bnx;
-  a.bn_sc = bn_sc;
-  a.bn_sh = bn_sh;
-  a.res = residual;
-  a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ci = Ci;
-  a.Ho = Ho; a.Wo = Wo; a.Co = Co;
-  a.pad = pad; a.dil = dil; a.relu = relu;
-  const int eb = (dtype == FFA_BF16) ? 2 : 4;
-  a.nchunks = Ci * eb / 32;
-  a.tiles_x = ffa_cdiv(Wo, p.tw);
-  a.tiles_y = ffa_cdiv(Ho, p.th);
-  a.npt = B * a.tiles_x * a.tiles_y;
-  a.ncb = co_rows / p.bco;
-  if (dtype == FFA_BF16) return launch_dtype<ffa_bf16>(a, kh, kw, stride, p, stream);
-  return launch_dtype<float>(a, kh, kw, stride, p, stream);
-}
-
-extern "C" int ffa_conv2d(int dtype, const void* in, const void* w_packed, const float* bias, const void* residual,
-                          void* out, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int co_rows, int bco,
-                          int kh, int kw, int stride, int pad, int dil, int relu, hipStream_t stream) {
-  return conv2d_impl(dtype, in, w_packed, bias, residual, out, nullptr, B, Hi, Wi, Ci, Ho, Wo, Co, co_rows, bco, kh, kw,
-                     stride, pad, dil, relu, stream);
-}
-
-// 3x3 stride-1 pad-1 convolution of relu(in * pro_scale[c] + pro_shift[c]) -- the training-mode BatchNorm + ReLU of the
-// PRODUCING layer evaluated while this layer stages its input ("normalise on load": the normalised tensor is never
-// written; smp Conv2dReLU / torchvision BasicBlock chains conv -> BN -> ReLU -> conv).  bf16 operands in the ring16 or
-// thin layout (ffa_conv_plan); `in` is the PRE-normalisation tensor [B][H][W][Ci] -- or, up != 0, the low-resolution
-// map [B][H/2][W/2][Ci] of the skip-less nearest-x2 form (thin layout only).  Zero padding applies to the normalised
-// tensor.  stat_partials may be null.  Bit-identical to ffa_bn_apply followed by ffa_conv2d / ffa_conv2d_stats.
-// FFA_ERR_UNSUPPORTED for operands in the conv_igemm layout.
-extern "C" int ffa_conv2d_pro(int dtype, const void* in, const void* w_packed, const float* bias, const void* residual,
-                              void* out, float* stat_partials, const float* pro_scale, const float* pro_shift, int B,
-                              int H, int W, int Ci, int Co, int co_rows, int bco, int relu, int up, hipStream_t stream) {
-  FFA_REQUIRE(dtype == FFA_BF16 && in && w_packed && out && pro_scale && pro_shift, "conv_pro: bad arguments");
-  if (bco & FFA_BCO_THIN)
-    return ffa_thin_conv3x3_pro(in, w_packed, bias, residual, out, stat_partials, pro_scale, pro_shift, B, H, W, Ci, Co,
-                                co_rows, relu, up, 0, stream);
-  if ((bco & FFA_BCO_RING) && !up)
-    return ffa_ring_conv3x3(dtype, in, w_packed, bias, residual, out, stat_partials, pro_scale, pro_shift, B, H, W, Ci, Co,
-                            co_rows, relu, stream);
-  ffa_set_error("conv_pro: no prologue kernel for this operand layout (bco 0x%x, up %d)", bco, up);
-  return FFA_ERR_UNSUPPORTED;
-}
-
-// ffa_conv2d whose output is the gradient dy of y = relu(bn(x)) (a dgrad convolution feeding a BatchNorm
-// backward): besides writing dy it leaves, per pixel tile, sum(g) and sum(g * x) with g = dy where
-// x * bn_scale + bn_shift > 0 else 0, in stat_partials[rows][2][Co] -- the reduction pass of the BatchNorm backward
-// comes out of the conv epilogue (ffa_bn_bwd_partials finishes the job).  bnx has the shape / pitch of out.
-extern "C" int ffa_conv2d_bnbwd(int dtype, const void* in, const void* w_packed, const void* residual, void* out,
-                                float* stat_partials, const void* bnx, const float* bn_scale, const float* bn_shift,
-                                int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int co_rows, int bco, int kh,
-                                int kw, int stride, int pad, int dil, hipStream_t stream) {
-  FFA_REQUIRE(stat_partials && bnx && bn_scale && bn_shift, "conv_bnbwd: null pointer");
-  return conv2d_impl(dtype, in, w_packed, nullptr, residual, out, stat_partials, B, Hi, Wi, Ci, Ho, Wo, Co, co_rows,
-                     bco, kh, kw, stride, pad, dil, 0, stream, nullptr, 0, bnx, bn_scale, bn_shift);
-}
-
-// Number of partial-statistics rows ffa_conv2d_stats writes for an output of B x Ho x Wo pixels (= pixel tiles).
-static long long conv_stat_rows_igemm(int B, int Ho, int Wo) {
-  const int tw = (Wo >= 32) ? 32 : 16, th = (Wo >= 32) ? 8 : 16;
-  return (long long)B * ffa_cdiv(Wo, tw) * ffa_cdiv(Ho, th);
-}
-// co_rows / bco: the operand the convolution will run with (ffa_conv_plan); the row count is the number of pixel
-// tiles of the kernel that serves it
-extern "C" long long ffa_conv_stat_rows(int B, int Ho, int Wo, int co_rows, int bco) {
-  if (bco & FFA_BCO_STEM) return ffa_stem_stat_rows(B, Ho, Wo);
-  if (bco & FFA_BCO_THIN) return ffa_thin_stat_rows(B, Ho, Wo, (bco & FFA_BCO_THIN32) ? 32 : 16);
-  if (bco & FFA_BCO_RING) return ffa_ring_stat_rows(B, Ho, Wo, co_rows);
-  return conv_stat_rows_igemm(B, Ho, Wo);
-}
-
-// 1 when ffa_conv2d / ffa_conv2d_stats run this convolution on the persistent kernel (conv3x3_persist_kernel: its
-// own symbol in a profile), 0 for conv_igemm_kernel.  Ci = input channel pitch, co_rows / bco as for ffa_conv2d.
-extern "C" int ffa_conv_is_persistent(int dtype, int B, int Ho, int Wo, int Ci, int co_rows, int bco, int kh, int kw,
-                                      int stride, int dil) {
-  if (!(kh == 3 && kw == 3 && stride == 1) || bco <= 0 || co_rows % bco != 0) return 0;
-  const int nchunks = Ci * (dtype == FFA_BF16 ? 2 : 4) / 32;
-  if (nchunks % 2 != 0) return 0;  // HK = 1 instantiations have no pipelined path
-  if (bco & (FFA_BCO_RING | FFA_BCO_THIN | FFA_BCO_STEM)) return 0;
-  const int npt = (int)conv_stat_rows_igemm(B, Ho, Wo);
-  return conv_persist_grid(dil, 0, nullptr, ffa_cdiv(npt, 8) * 8 * (co_rows / bco)) > 0 ? 1 : 0;
-}
-
-// ffa_conv2d that also leaves per-tile channel sums / sums of squares of the tensor it writes in
-// stat_partials[rows][2][Co] (rows = ffa_conv_stat_rows): the BatchNorm batch statistics come out of the conv
-// epilogue's registers instead of a second pass over the output (ffa_bn_finalize turns them into scale / shift).
-extern "C" int ffa_conv2d_stats(int dtype, const void* in, const void* w_packed, const float* bias,
-                                const void* residual, void* out, float* stat_partials, int B, int Hi, int Wi, int Ci,
-                                int Ho, int Wo, int Co, int co_rows, int bco, int kh, int kw, int stride, int pad,
-                                int dil, int relu, hipStream_t stream) {
-  FFA_REQUIRE(stat_partials, "conv_stats: null statistics buffer");
-  return conv2d_impl(dtype, in, w_packed, bias, residual, out, stat_partials, B, Hi, Wi, Ci, Ho, Wo, Co, co_rows, bco,
-                     kh, kw, stride, pad, dil, relu, stream);
-}
-
-// 3x3 stride-1 pad-1 convolution over the VIRTUAL input cat(nearest_x2(lo), skip) of a U-Net decoder block
-// (smp DecoderBlock.forward: F.interpolate(scale_factor=2, mode="nearest"), torch.cat, conv1): lo is
-// [B][Hl][Wl][C1], skip [B][2Hl][2Wl][C2] (null when C2 == 0), the packed weight has C1 + C2 input channels in that
-// order.  Returns FFA_ERR_UNSUPPORTED when C1 does not cover whole channel groups of the kernel's halo staging
-// (the caller then materialises the concat with ffa_upsample_nearest2x_concat_fwd).  bias (eval-mode folded
-// BatchNorm shift) and stat_partials may be null; relu applies in the epilogue.
-extern "C" int ffa_conv2d_upcat(int dtype, const void* lo, const void* skip, const void* w_packed, const float* bias,
-                                void* out, float* stat_partials, int B, int Hl, int Wl, int C1, int C2, int Co,
-                                int co_rows, int bco, int relu, hipStream_t stream) {
-  FFA_REQUIRE(dtype == FFA_BF16 || dtype == FFA_F32, "conv_upcat: bad dtype %d", dtype);
-  FFA_REQUIRE(lo && w_packed && out && (skip || C2 == 0), "conv_upcat: null pointer");
-  FFA_REQUIRE(B > 0 && Hl > 0 && Wl > 0 && C1 > 0 && C2 >= 0 && C1 % 16 == 0 && C2 % 16 == 0 && Co % 8 == 0,
-              "conv_upcat: bad dims");
-  const int eb = (dtype == FFA_BF16) ? 2 : 4;
-  const int Hi = 2 * Hl, Wi = 2 * Wl, Ci = C1 + C2;
-  if (bco & FFA_BCO_THIN) {
-    if (C2 != 0 || dtype != FFA_BF16) {
-      ffa_set_error("conv_upcat: a thin-layout operand takes the skip-less form only");
+  if (c.co_rows % c.bco != 0) {  // (an argument error in the plain form, as it always was)
+    ffa_set_error("conv: packed weight rows %d not a multiple of block %d", c.co_rows, c.bco);
+    return c.form == FFA_CONV_UPCAT ? FFA_ERR_UNSUPPORTED : FFA_ERR_ARG;
+  }
+  const int eb = ffa_conv_elem_bytes(c.dtype);
+  r->variant = igemm_halo_groups(c.dtype, c.kh, c.stride, c.Ci);
+  if (c.form == FFA_CONV_UPCAT) {
+    const int c2 = c.Ci - c.c1;
+    FFA_REQUIRE((long long)c.B * c.Hi * c.Wi * (c.c1 > c2 ? c.c1 : c2) * eb < (1LL << 31),
+                "conv_upcat: source tensors must be smaller than 2 GiB (32-bit piece offsets)");
+    if (!ffa_igemm_upcat_split_ok(c.dtype, c.c1, c2)) {
+      ffa_set_error("conv_upcat: C1 = %d does not cover whole %d-byte channel groups", c.c1, r->variant * 32);
       return FFA_ERR_UNSUPPORTED;
     }
-    return ffa_thin_conv3x3(lo, w_packed, bias, nullptr, out, stat_partials, B, Hi, Wi, C1, Co, co_rows, relu, 1, 0, stream);
   }
-  FFA_REQUIRE((long long)B * Hi * Wi * (C1 > C2 ? C1 : C2) * eb < (1LL << 31),
-              "conv_upcat: source tensors must be smaller than 2 GiB (32-bit piece offsets)");
-  if (!conv_supported(3, 3, 1, bco) || co_rows % bco != 0) {
-    ffa_set_error("conv_upcat: unsupported block %d / rows %d", bco, co_rows);
+  if (c.form == FFA_CONV_POOLED && c.c1 % c.bco != 0) {
+    ffa_set_error("dgrad_upcat: C1 = %d is not a multiple of the %d-row block", c.c1, c.bco);
     return FFA_ERR_UNSUPPORTED;
   }
-  const int nchunks = Ci * eb / 32;
-  const int hk = (nchunks % 4 == 0) ? 4 : (nchunks % 2 == 0 ? 2 : 1);
-  if (hk == 1 || (C1 * eb) % (hk * 32) != 0) {
-    ffa_set_error("conv_upcat: C1 = %d does not cover whole %d-byte channel groups", C1, hk * 32);
-    return FFA_ERR_UNSUPPORTED;
+  r->tw = (c.Wo >= 32) ? 32 : 16;
+  r->th = (c.Wo >= 32) ? 8 : 16;
+  r->tiles_x = ffa_cdiv(c.Wo, r->tw);
+  r->tiles_y = ffa_cdiv(c.Ho, r->th);
+  const long long ntiles = (long long)c.B * r->tiles_x * r->tiles_y;
+  r->ncb = c.co_rows / c.bco;
+  FFA_REQUIRE((ntiles + 7) / 8 * 8 * r->ncb < (1LL << 31), "conv: bad dims");
+  r->ntiles = (int)ntiles;
+  r->kernel = FFA_CONV_KERNEL_IGEMM;
+  r->grid = ffa_cdiv(r->ntiles, 8) * 8 * r->ncb;
+  // the persistent kernel exists for the pipelined (deep-halo) one-source 3x3 stride-1 instantiations
+  if (c.kh == 3 && c.kw == 3 && c.stride == 1 && r->variant >= 2 && c.form != FFA_CONV_UPCAT) {
+    const int pgrid = conv_persist_grid(c.dil, c.form == FFA_CONV_POOLED ? c.c1 : 0, c.bnx, r->grid);
+    if (pgrid > 0) {
+      r->kernel = FFA_CONV_KERNEL_PERSIST;
+      r->grid = pgrid;
+    }
   }
-  ConvArgs a;
-  a.in = lo;
-  a.in2 = skip;
-  a.c1_bytes = C1 * eb;
-  a.out2 = nullptr;
-  a.c1_out = 0;
-  a.bnx = nullptr;
-  a.bn_sc = a.bn_sh = nullptr;
-  a.w = w_packed;
-  a.out = out;
-  a.bias = bias;
-  a.stats = stat_partials;
-  a.res = nullptr;
-  a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ci = Ci;
-  a.Ho = Hi; a.Wo = Wi; a.Co = Co;
-  a.pad = 1; a.dil = 1; a.relu = relu;
-  a.nchunks = nchunks;
-  const int tw = (Wi >= 32) ? 32 : 16, th = (Wi >= 32) ? 8 : 16;
-  a.tiles_x = ffa_cdiv(Wi, tw);
-  a.tiles_y = ffa_cdiv(Hi, th);
-  a.npt = B * a.tiles_x * a.tiles_y;
-  a.ncb = co_rows / bco;
-#define FFA_UP_CASE(T_)                                                         \
-  if (bco == 64) return (tw == 32) ? launch_up<T_, 64, 8, 32>(a, stream) : launch_up<T_, 64, 16, 16>(a, stream); \
-  return (tw == 32) ? launch_up<T_, 32, 8, 32>(a, stream) : launch_up<T_, 32, 16, 16>(a, stream);
-  if (dtype == FFA_BF16) { FFA_UP_CASE(ffa_bf16) }
-  FFA_UP_CASE(float)
-#undef FFA_UP_CASE
+  return 0;
 }
 
-// Input gradient of the convolution ffa_conv2d_upcat computes, delivered as the two gradients the decoder block
-// needs: dlo [B][Ho/2][Wo/2][C1] (2x2 sums = adjoint of nearest x2) and dskip [B][Ho][Wo][C2] (null when C2 == 0).
-// dy is [B][Ho][Wo][Cdy]; w_packed_t is the transposed (dgrad) operand with co_rows >= C1 + C2 rows.  The gradient
-// of the concatenated tensor is never written.  FFA_ERR_UNSUPPORTED unless C1 is a whole number of bco-row blocks.
-extern "C" int ffa_conv2d_dgrad_upcat(int dtype, const void* dy, const void* w_packed_t, void* dlo, void* dskip, int B,
-                                      int Ho, int Wo, int Cdy, int C1, int C2, int co_rows, int bco,
-                                      hipStream_t stream) {
-  FFA_REQUIRE(dy && w_packed_t && dlo && (dskip || C2 == 0), "dgrad_upcat: null pointer");
-  FFA_REQUIRE(Ho % 2 == 0 && Wo % 2 == 0 && C1 > 0 && C2 >= 0 && C1 % 8 == 0 && C2 % 8 == 0, "dgrad_upcat: bad dims");
-  if (bco & FFA_BCO_THIN) {
-    if (C2 != 0) {
-      ffa_set_error("dgrad_upcat: a thin-layout operand takes the skip-less form only");
-      return FFA_ERR_UNSUPPORTED;
-    }
-    return conv2d_impl(dtype, dy, w_packed_t, nullptr, nullptr, dlo, nullptr, B, Ho, Wo, Cdy, Ho, Wo, C1, co_rows, bco, 3,
-                       3, 1, 1, 1, 0, stream, nullptr, C1);
-  }
-  if (C1 % bco != 0) {
-    ffa_set_error("dgrad_upcat: C1 = %d is not a multiple of the %d-row block", C1, bco);
-    return FFA_ERR_UNSUPPORTED;
-  }
-  return conv2d_impl(dtype, dy, w_packed_t, nullptr, nullptr, dlo, nullptr, B, Ho, Wo, Cdy, Ho, Wo, C1 + C2, co_rows,
-                     bco, 3, 3, 1, 1, 1, 0, stream, dskip, C1);
+int ffa_igemm_launch(const ffa_conv_call_t& c, const ffa_conv_route_t& r, hipStream_t stream) {
+  const bool up = c.form == FFA_CONV_UPCAT, pooled = c.form == FFA_CONV_POOLED;
+  ConvArgs a;
+  a.in = c.in;
+  a.w = c.w;
+  a.out = c.out;
+  a.bias = c.bias;
+  a.stats = c.stats;
+  a.in2 = up ? c.in2 : nullptr;
+  a.c1_bytes = up ? c.c1 * ffa_conv_elem_bytes(c.dtype) : 0;
+  a.out2 = pooled ? c.out2 : nullptr;
+  a.c1_out = pooled ? c.c1 : 0;
+  a.bnx = c.bnx;
+  a.bn_sc = c.bn_scale;
+  a.bn_sh = c.bn_shift;
+  a.res = c.residual;
+  a.B = c.B; a.Hi = c.Hi; a.Wi = c.Wi; a.Ci = c.Ci;
+  a.Ho = c.Ho; a.Wo = c.Wo; a.Co = c.Co;
+  a.pad = c.pad; a.dil = c.dil; a.relu = c.relu;
+  a.nchunks = c.Ci * ffa_conv_elem_bytes(c.dtype) / 32;
+  a.tiles_x = r.tiles_x;
+  a.tiles_y = r.tiles_y;
+  a.npt = r.ntiles;
+  a.ncb = r.ncb;
+  if (c.dtype == FFA_BF16) return launch_dtype<ffa_bf16>(a, c, r, stream);
+  return launch_dtype<float>(a, c, r, stream);
 }
 
 #if FFA_CONV_TRACE

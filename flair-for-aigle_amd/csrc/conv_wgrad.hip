@@ -14,6 +14,7 @@
 // subset of the spatial tiles and writes its f32 partial slab; wgrad_reduce_kernel sums the
 // slabs in fixed order (deterministic, no float atomics) and writes the OIHW f32 gradient.
 #include "ffa_gfx950.h"
+#include "conv_call.h"
 
 #include <stdlib.h>
 
@@ -1812,6 +1813,15 @@ static int launch_wgrad(const WgradArgs& a, const WgradPlan& p, int kh, int kw, 
   return FFA_ERR_UNSUPPORTED;
 }
 
+// Two-source input: a block's input channels come from one source, so C1 is a whole number of blocks
+static bool wgrad_upcat_c1_ok(const WgradPlan& p, int C1) { return C1 % (32 * p.wci) == 0; }
+
+// the same rule for the general (not the thin) 3x3 stride-1 kernels, asked before there is a call
+bool ffa_wgrad_upcat_split_ok(int dtype, int c1, int c2) {
+  WgradPlan p;
+  return wgrad_plan(dtype, 3, 3, 1, 64, c1 + c2, 1, 32, 32, &p, false, false) && wgrad_upcat_c1_ok(p, c1);
+}
+
 // x: [B][Hi][Wi][Ci] (the conv input), dy: [B][Ho][Wo][Co]; Ci / Co are channel pitches, the
 // gradient is written for the first Co_real x Ci_real entries as OIHW f32 (accumulate != 0 adds to it).
 static int wgrad_impl(int dtype, const void* x, const void* x2, int C1, const void* dy, float* dw_oihw, int B, int Hi,
@@ -1834,7 +1844,7 @@ static int wgrad_impl(int dtype, const void* x, const void* x2, int C1, const vo
     return FFA_ERR_UNSUPPORTED;
   }
   if (C1 > 0 && !p.thin) {
-    if (C1 % (32 * p.wci) != 0) {
+    if (!wgrad_upcat_c1_ok(p, C1)) {
       ffa_set_error("conv_wgrad_upcat: C1 = %d is not a multiple of the block's %d input channels", C1, 32 * p.wci);
       return FFA_ERR_UNSUPPORTED;
     }
@@ -1912,7 +1922,7 @@ extern "C" int ffa_conv_wgrad_pro(int dtype, const void* x, const void* dy, floa
 }
 
 // Weight gradient of the 3x3 stride-1 pad-1 convolution whose input is the virtual cat(nearest_x2(lo), skip)
-// (see ffa_conv2d_upcat): lo [B][Hl][Wl][C1], skip [B][2Hl][2Wl][C2] or null; dw is OIHW [Co_real][C1 + C2][3][3].
+// (the FFA_CONV_UPCAT form of ffa_conv_call_t): lo [B][Hl][Wl][C1], skip [B][2Hl][2Wl][C2] or null; dw is OIHW [Co_real][C1 + C2][3][3].
 // Workspace: ffa_conv_wgrad_workspace_bytes(dtype, 3, 3, 1, Co, C1 + C2, B, 2Hl, 2Wl).
 extern "C" int ffa_conv_wgrad_upcat(int dtype, const void* lo, const void* skip, const void* dy, float* dw_oihw, int B,
                                     int Hl, int Wl, int C1, int C2, int Co, int Co_real, int accumulate,

@@ -16,14 +16,13 @@
 
 // The C ABI is declared once, in the public header: every definition in this directory is compiled against its
 // prototype there (a drifted parameter list is "conflicting types"), and the public macros come from there too.
-#include "../../include/flairhip.h"
+#include "ffa_common_host.h"
 static_assert(std::is_same<ffa_stream_t, hipStream_t>::value, "ffa_stream_t must be hipStream_t");
 
 #define FFA_CE_MAXK 32  // largest class count and logit pitch of the per-pixel softmax kernels (resample_loss.hip, tta.hip)
 
 #define FFA_BCO_THIN32 0x4000  // with FFA_BCO_THIN: the operand multiplies 32-channel pixels (8-row tiles; else 16 ch, 16-row tiles)
 
-void ffa_set_error(const char* fmt, ...);
 int ffa_check_launch(const char* what);
 // kernel timing session (ffa_runtime.hip): true + an event pair when this thread has one open
 bool ffa_ktime_next(int tag, hipEvent_t* start, hipEvent_t* stop);
@@ -38,14 +37,6 @@ static inline void ffa_launch_timed(int tag, K kernel, dim3 grid, dim3 block, hi
   if (ffa_ktime_next(tag, &ts, &te)) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ts, te, 0, a);
   else hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
 }
-
-#define FFA_REQUIRE(cond, ...)                 \
-  do {                                         \
-    if (!(cond)) {                             \
-      ffa_set_error(__VA_ARGS__);              \
-      return FFA_ERR_ARG;                      \
-    }                                          \
-  } while (0)
 
 typedef __attribute__((ext_vector_type(8))) __bf16 ffa_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float ffa_f32x4;

@@ -564,7 +564,7 @@ partials_fold_kernel(const float* __restrict__ ws, long long nparts, int C, int 
   }
 }
 
-// Training-mode BatchNorm parameters from partial sums somebody else produced (ffa_conv2d_stats): same outputs and
+// Training-mode BatchNorm parameters from partial sums somebody else produced (ffa_conv_run with stats): same outputs and
 // running-statistics update as ffa_bn_stats, without the pass over the tensor.
 extern "C" int ffa_bn_finalize(const float* partials, long long nparts, long long npix, int C, const float* gamma,
                                const float* beta, float* running_mean, float* running_var, float momentum, float eps,
@@ -1054,7 +1054,7 @@ extern "C" int ffa_bn_bwd_fused(int dtype, const void* x, const void* dy, const 
 }
 
 // ffa_bn_bwd for y = relu(bn_train(x)) when the two reductions were already taken by the producer of dy
-// (ffa_conv2d_bnbwd): partials[nparts][2][C] = per-tile (sum g, sum g*x).  Finalize + apply only.
+// (ffa_conv_run with bnx): partials[nparts][2][C] = per-tile (sum g, sum g*x).  Finalize + apply only.
 extern "C" int ffa_bn_bwd_partials(int dtype, const void* x, const void* dy, const float* partials, long long nparts,
                                    const float* gamma, const float* beta, const float* mean, const float* rstd,
                                    void* dx, float* dgamma, float* dbeta, long long npix, int C, void* workspace,

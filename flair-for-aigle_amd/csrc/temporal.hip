@@ -1,7 +1,7 @@
 // Kernels of the U-TAE Sentinel time-series branch, NHWC, bf16 or f32 storage, f32 math.
 //
 // Replaces the torch ops the reference's UTAE reaches in flair_hub/models/multitemp_model.py:
-//   reflect padding of nn.Conv2d(padding_mode="reflect") :473-482        -> ffa_reflect_pad1 (+ ffa_conv2d, pad 0)
+//   reflect padding of nn.Conv2d(padding_mode="reflect") :473-482        -> ffa_reflect_pad1 (+ ffa_conv_run, pad 0)
 //   nn.GroupNorm(4) of ConvLayer :464-468, nn.GroupNorm(16) of LTAE2d :224-231,256,276 -> ffa_group_norm
 //   PositionalEncoder :287-313                                           -> ffa_positional_encoding
 //   "out + positional_encoder(bp)" :270                                  -> ffa_add_rowvec

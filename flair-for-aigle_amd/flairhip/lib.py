@@ -45,6 +45,26 @@ class Crs(C.Structure):
                 ("false_easting", C.c_double), ("false_northing", C.c_double)]
 
 
+class ConvCall(C.Structure):
+    """ffa_conv_call_t: one forward / input-gradient convolution call (forms CONV_PLAIN / CONV_UPCAT / CONV_POOLED)"""
+    _fields_ = [("dtype", C.c_int), ("form", C.c_int), ("in", C.c_void_p), ("in2", C.c_void_p), ("w", C.c_void_p),
+                ("bias", C.c_void_p), ("residual", C.c_void_p), ("out", C.c_void_p), ("out2", C.c_void_p),
+                ("stats", C.c_void_p), ("pro_scale", C.c_void_p), ("pro_shift", C.c_void_p), ("bnx", C.c_void_p),
+                ("bn_scale", C.c_void_p), ("bn_shift", C.c_void_p), ("co_rows", C.c_int), ("bco", C.c_int),
+                ("B", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Ci", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int),
+                ("Co", C.c_int), ("kh", C.c_int), ("kw", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
+                ("dil", C.c_int), ("relu", C.c_int), ("c1", C.c_int)]
+
+
+class ConvRoute(C.Structure):
+    """ffa_conv_route_t: what a ConvCall runs (kernel family, pixel tile, tile count = statistics rows, grid)"""
+    _fields_ = [("kernel", C.c_int), ("variant", C.c_int), ("th", C.c_int), ("tw", C.c_int), ("tiles_x", C.c_int),
+                ("tiles_y", C.c_int), ("ntiles", C.c_int), ("ncb", C.c_int), ("grid", C.c_int)]
+
+
+CONV_PLAIN, CONV_UPCAT, CONV_POOLED = 0, 1, 2  # FFA_CONV_*
+CONV_KERNEL_PERSIST = 1  # FFA_CONV_KERNEL_PERSIST
+
 CRS_GEOGRAPHIC, CRS_LCC2SP, CRS_TMERC = 0, 1, 2  # FFA_CRS_*
 
 _i, _ll, _p, _f, _d = C.c_int, C.c_longlong, C.c_void_p, C.c_float, C.c_double
@@ -61,29 +81,16 @@ SIGNATURES = {
     "ffa_pack_desc_bytes": (_i, []),
     "ffa_pack_desc_fill": (_i, [_p, _p, _p, _p] + [_i] * 12),
     "ffa_pack_conv_weights_batched": (_i, [_i, _i, _p, _i, _p]),
-    "ffa_conv2d": (_i, [_i, _p, _p, _p, _p, _p] + [_i] * 15 + [_p]),
-    "ffa_conv_stat_rows": (_ll, [_i, _i, _i, _i, _i]),
     "ffa_conv_plan": (_i, [_i] * 7),
-    "ffa_ring_conv3x3": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 7 + [_p]),
-    "ffa_ring_stat_rows": (_ll, [_i, _i, _i, _i]),
-    "ffa_conv2d_pro": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 9 + [_p]),
+    "ffa_conv_route": (_i, [C.POINTER(ConvCall), C.POINTER(ConvRoute)]),
+    "ffa_conv_run": (_i, [C.POINTER(ConvCall), _p]),
+    "ffa_conv_struct_bytes": (_i, [_i]),
+    "ffa_conv_upcat_supported": (_i, [_i, _i, _i]),
     "ffa_conv_wgrad_pro": (_i, [_i, _p, _p, _p, _p, _p] + [_i] * 11 + [_p, _ll, _p]),
-    "ffa_thin_eligible": (_i, [_i] * 6),
-    "ffa_stem_eligible": (_i, [_i] * 6),
-    "ffa_stem_stat_rows": (_ll, [_i, _i, _i]),
-    "ffa_stem_conv7x7": (_i, [_p, _p, _p, _p, _p] + [_i] * 8 + [_p]),
-    "ffa_thin_stat_rows": (_ll, [_i, _i, _i, _i]),
-    "ffa_thin_conv3x3": (_i, [_p, _p, _p, _p, _p, _p] + [_i] * 9 + [_p]),
-    "ffa_thin_conv3x3_pro": (_i, [_p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 9 + [_p]),
-    "ffa_conv2d_stats": (_i, [_i, _p, _p, _p, _p, _p, _p] + [_i] * 15 + [_p]),
-    "ffa_conv2d_bnbwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 14 + [_p]),
     "ffa_bn_bwd_partials": (_i, [_i, _p, _p, _p, _ll, _p, _p, _p, _p, _p, _p, _p, _ll, _i, _p, _ll, _p]),
-    "ffa_conv2d_dgrad_upcat": (_i, [_i, _p, _p, _p, _p] + [_i] * 8 + [_p]),
-    "ffa_conv2d_upcat": (_i, [_i, _p, _p, _p, _p, _p, _p] + [_i] * 9 + [_p]),
     "ffa_conv_wgrad_workspace_bytes": (_ll, [_i] * 9),
     "ffa_conv_wgrad": (_i, [_i, _p, _p, _p] + [_i] * 14 + [_p, _ll, _p]),
     "ffa_conv_wgrad_upcat": (_i, [_i, _p, _p, _p, _p] + [_i] * 8 + [_p, _ll, _p]),
-    "ffa_conv_is_persistent": (_i, [_i] * 11),
     "ffa_reflect_pad1": (_i, [_i, _p, _p, _i, _i, _i, _i, _p]),
     "ffa_group_norm": (_i, [_i, _p, _p, _p, _p, _p, _ll, _i, _ll, _ll, _i, _ll, _i, _i, _f, _i, _p]),
     "ffa_positional_encoding": (_i, [_p, _p, _i, _i, _i, _f, _p]),
@@ -211,6 +218,9 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args
+    for which, struct in enumerate((ConvCall, ConvRoute)):  # a mis-laid-out descriptor hands kernels wrong pointers
+        if lib.ffa_conv_struct_bytes(which) != C.sizeof(struct):
+            raise FlairHipError(f"{LIB_PATH}: sizeof {struct.__name__} differs between the library and this binding")
     _lib = lib
     return lib
 

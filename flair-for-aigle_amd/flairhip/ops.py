@@ -90,12 +90,10 @@ class PackedWeight:
 def pack_conv_weight(w_oihw: torch.Tensor, dtype: torch.dtype, stride: int, ci_pitch: int,
                      transpose: bool = False, scale: Optional[torch.Tensor] = None,
                      allow_ring: bool = True, allow_thin: bool = True, allow_stem: bool = True) -> PackedWeight:
-    """OIHW f32 master weight -> MFMA operand for ffa_conv2d (forward, or dgrad when transpose=True).
-    allow_ring=False keeps the operand in the conv_igemm layout (needed by the two-source / split-epilogue /
-    zero-insertion calls); otherwise ffa_conv_plan picks the LDS-DMA ring layout where it applies.  allow_thin:
-    bf16 layers with at most 32 stored input channels and 32 rows may get the register-resident layout of
-    conv3x3_thin_kernel (plain, statistics, skip-less two-source and skip-less pooled-split calls).  allow_stem: the bf16
-    forward operand of a 7x7 stride-2 PAD-3 convolution over <= 8 real input channels gets conv7x7_stem_kernel's layout."""
+    """OIHW f32 master weight -> MFMA operand for ffa_conv_run (forward, or dgrad when transpose=True).
+    allow_ring / allow_thin / allow_stem admit the layouts ffa_conv_plan may pick besides conv_igemm's; which forms of
+    call each layout serves is the table at ffa_conv_call_t (include/flairhip.h).  The caller vouches for the padding:
+    the ring and thin kernels are pad-1 kernels, the stem kernel a pad-3 one."""
     lib = _l.load()
     if w_oihw.dtype != torch.float32 or not w_oihw.is_contiguous():
         raise ValueError("pack_conv_weight: master weight must be contiguous f32 OIHW")
@@ -161,11 +159,59 @@ def conv_out_size(h: int, k: int, stride: int, pad: int) -> int:
     return (h + 2 * pad - k) // stride + 1
 
 
+def _conv_call(form: int, dtype_id: int, w: PackedWeight, geom, pad: int, dil: int = 1, relu: bool = False, c1: int = 0,
+               x=None, x2=None, bias=None, residual=None, out=None, out2=None, stats=None, pro=(None, None),
+               bn=(None, None, None)) -> "_l.ConvCall":
+    """The descriptor of one convolution call (ffa_conv_call_t) in one constructor call.  geom = (B, Hi, Wi, Ho, Wo, Co);
+    in the CONV_UPCAT form Hi, Wi and the operand's pitch describe the virtual input, in the CONV_POOLED form Ho, Wo, Co
+    the virtual output; c1 is the channel split of those two forms."""
+    B, Hi, Wi, Ho, Wo, Co = geom
+    return _l.ConvCall(dtype_id, form, _ptr(x), _ptr(x2), w.data.data_ptr(), _ptr(bias), _ptr(residual), _ptr(out),
+                       _ptr(out2), _ptr(stats), _ptr(pro[0]), _ptr(pro[1]), _ptr(bn[0]), _ptr(bn[1]), _ptr(bn[2]),
+                       w.rows, w.bco, B, Hi, Wi, w.ci_pitch, Ho, Wo, Co, w.kh, w.kw, w.stride, pad, dil,
+                       1 if relu else 0, c1)
+
+
+def _conv_run(call: "_l.ConvCall", what: str, stats: Optional[torch.Tensor] = None, may_refuse: bool = False) -> bool:
+    """Launch; False when may_refuse and the library has no kernel for this form of call on this operand.  ``stats``
+    is held to the tiles of the very call that writes it (a refused call is reported by the launch)."""
+    if stats is not None:
+        route = _conv_route(call)
+        if stats.dtype != torch.float32 or (route is not None and stats.numel() < route.ntiles * 2 * call.Co):
+            raise ValueError(f"{what}: statistics buffer too small or not f32")
+    rc = _l.load().ffa_conv_run(C.byref(call), _stream())
+    if may_refuse and rc == _l.ERR_UNSUPPORTED:
+        return False
+    _l.check(rc, what)
+    return True
+
+
+def _conv_route(call: "_l.ConvCall", what: Optional[str] = None) -> Optional["_l.ConvRoute"]:
+    """What the library would run for this call (kernel family, tile, statistics rows, grid).  A refused call gives
+    None, or raises when ``what`` names the caller.  Needs no device: the router reads no tensor."""
+    route = _l.ConvRoute()
+    rc = _l.load().ffa_conv_route(C.byref(call), C.byref(route))
+    if rc != 0 and what is not None:
+        _l.check(rc, what)
+    return route if rc == 0 else None
+
+
+def _operand_call(dtype_id: int, w: PackedWeight, B: int, Ho: int, Wo: int, dil: int = 1, form: int = _l.CONV_PLAIN,
+                  c1: int = 0, pro: bool = False, stats: bool = False, in_hw=None) -> "_l.ConvCall":
+    """The call of this form that operand ``w`` was packed for, at this output size, without tensors: what the queries
+    route.  in_hw: the stored input size where the output size does not fix it (stride 2)."""
+    Hi, Wi = in_hw or (Ho * w.stride // dil, Wo * w.stride // dil)
+    call = _conv_call(form, dtype_id, w, (B, Hi, Wi, Ho, Wo, w.rows), (w.kh - 1) // 2, dil, c1=c1)
+    call.pro_scale = call.pro_shift = 1 if pro else None  # the router reads only whether an optional pointer is null
+    call.stats = 1 if stats else None
+    return call
+
+
 def conv_is_persistent(x_dtype, B: int, Ho: int, Wo: int, w: "PackedWeight", dil: int = 1) -> bool:
     """True when conv2d runs this operand on conv3x3_persist_kernel (its own symbol in rocprofv3) rather than
     conv_igemm_kernel; used by bench.py to group launches the way a profile does."""
-    return bool(_l.load().ffa_conv_is_persistent(_dtype_id(x_dtype), B, Ho, Wo,
-                                                 w.ci_pitch, w.rows, w.bco, w.kh, w.kw, w.stride, dil))
+    route = _conv_route(_operand_call(_dtype_id(x_dtype), w, B, Ho, Wo, dil))
+    return route is not None and route.kernel == _l.CONV_KERNEL_PERSIST
 
 
 def conv2d(x: torch.Tensor, w: PackedWeight, pad: int, out_channels: int, bias: Optional[torch.Tensor] = None,
@@ -175,7 +221,6 @@ def conv2d(x: torch.Tensor, w: PackedWeight, pad: int, out_channels: int, bias: 
     """out[B,Ho,Wo,out_channels] = relu?(conv(x, w) + bias + residual).  out_channels is the stored pitch.
     ``stats`` (f32, >= conv_stat_rows * 2 * out_channels elements) receives per-tile channel sums / sums of squares
     of the stored output for a following training-mode BatchNorm (see bn_finalize)."""
-    lib = _l.load()
     _chk_nhwc(x, "conv input")
     B, Hi, Wi, Ci = x.shape
     if Ci != w.ci_pitch:
@@ -190,17 +235,9 @@ def conv2d(x: torch.Tensor, w: PackedWeight, pad: int, out_channels: int, bias: 
         raise ValueError("conv2d: residual shape mismatch")
     if bias is not None and bias.numel() < out_channels:
         raise ValueError("conv2d: bias shorter than the output pitch")
-    if stats is not None:
-        if stats.dtype != torch.float32 or stats.numel() < conv_stat_rows(B, Ho, Wo, w) * 2 * out_channels:
-            raise ValueError("conv2d: statistics buffer too small or not f32")
-        _l.check(lib.ffa_conv2d_stats(_dt(x), x.data_ptr(), w.data.data_ptr(), _ptr(bias), _ptr(residual),
-                                      out.data_ptr(), stats.data_ptr(), B, Hi, Wi, Ci, Ho, Wo, out_channels, w.rows,
-                                      w.bco, w.kh, w.kw, w.stride, pad, dil, 1 if relu else 0, _stream()),
-                 "conv2d_stats")
-        return out
-    _l.check(lib.ffa_conv2d(_dt(x), x.data_ptr(), w.data.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-                            B, Hi, Wi, Ci, Ho, Wo, out_channels, w.rows, w.bco, w.kh, w.kw, w.stride, pad, dil,
-                            1 if relu else 0, _stream()), "conv2d")
+    call = _conv_call(_l.CONV_PLAIN, _dt(x), w, (B, Hi, Wi, Ho, Wo, out_channels), pad, dil, relu, x=x, bias=bias,
+                      residual=residual, out=out, stats=stats)
+    _conv_run(call, "conv2d", stats)
     return out
 
 
@@ -211,7 +248,6 @@ def conv3x3_ring(x: torch.Tensor, w: PackedWeight, out_channels: int, bias: Opti
     """The ring kernel called directly (w must be a ring-layout operand): conv3x3 pad 1 of x, or -- with pro_scale /
     pro_shift -- of relu(x * pro_scale[c] + pro_shift[c]) evaluated while the input is staged (the BatchNorm + ReLU
     of the producing layer folded into this convolution, no normalised tensor in memory)."""
-    lib = _l.load()
     _chk_nhwc(x, "conv input")
     if not (w.bco & _l.BCO_RING):
         raise ValueError("conv3x3_ring: operand is not in the ring layout")
@@ -220,17 +256,14 @@ def conv3x3_ring(x: torch.Tensor, w: PackedWeight, out_channels: int, bias: Opti
         raise ValueError(f"conv3x3_ring: input pitch {Ci} != packed pitch {w.ci_pitch}")
     if out is None:
         out = torch.empty((B, H, W, out_channels), dtype=x.dtype, device=x.device)
-    if stats is not None and (stats.dtype != torch.float32 or
-                              stats.numel() < conv_stat_rows(B, H, W, w) * 2 * out_channels):
-        raise ValueError("conv3x3_ring: statistics buffer too small or not f32")
     if (pro_scale is None) != (pro_shift is None):
         raise ValueError("conv3x3_ring: prologue needs scale and shift")
     if pro_scale is not None and (pro_scale.numel() < Ci or pro_shift.numel() < Ci or
                                   pro_scale.dtype != torch.float32 or pro_shift.dtype != torch.float32):
         raise ValueError("conv3x3_ring: prologue vectors must be f32 with one entry per stored input channel")
-    _l.check(lib.ffa_ring_conv3x3(_dt(x), x.data_ptr(), w.data.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-                                  _ptr(stats), _ptr(pro_scale), _ptr(pro_shift), B, H, W, Ci, out_channels, w.rows,
-                                  1 if relu else 0, _stream()), "ring_conv3x3")
+    call = _conv_call(_l.CONV_PLAIN, _dt(x), w, (B, H, W, H, W, out_channels), 1, relu=relu, x=x, bias=bias,
+                      residual=residual, out=out, stats=stats, pro=(pro_scale, pro_shift))
+    _conv_run(call, "conv3x3_ring", stats)
     return out
 
 
@@ -239,7 +272,6 @@ def conv2d_upcat(lo: torch.Tensor, skip: Optional[torch.Tensor], w: PackedWeight
                  ) -> Optional[torch.Tensor]:
     """3x3 pad-1 conv over cat(nearest_x2(lo), skip) without materialising it.  Returns None when the library has no
     two-source kernel for this channel split (the caller then concatenates explicitly)."""
-    lib = _l.load()
     _chk_nhwc(lo, "upcat lo")
     B, Hl, Wl, C1 = lo.shape
     C2 = 0
@@ -250,18 +282,16 @@ def conv2d_upcat(lo: torch.Tensor, skip: Optional[torch.Tensor], w: PackedWeight
         C2 = skip.shape[3]
     if w.kh != 3 or w.kw != 3 or w.stride != 1 or w.ci_pitch != C1 + C2:
         raise ValueError("conv2d_upcat: needs a 3x3 stride-1 operand packed for C1 + C2 input channels")
-    out = torch.empty((B, 2 * Hl, 2 * Wl, out_channels), dtype=lo.dtype, device=lo.device)
+    H, W = 2 * Hl, 2 * Wl
+    out = torch.empty((B, H, W, out_channels), dtype=lo.dtype, device=lo.device)
     if bias is not None and bias.numel() < out_channels:
         raise ValueError("conv2d_upcat: bias shorter than the output pitch")
-    rc = lib.ffa_conv2d_upcat(_dt(lo), lo.data_ptr(), _ptr(skip), w.data.data_ptr(), _ptr(bias), out.data_ptr(),
-                              _ptr(stats), B, Hl, Wl, C1, C2, out_channels, w.rows, w.bco, 1 if relu else 0, _stream())
-    if rc == _l.ERR_UNSUPPORTED:
-        return None
-    _l.check(rc, "conv2d_upcat")
-    return out
+    call = _conv_call(_l.CONV_UPCAT, _dt(lo), w, (B, H, W, H, W, out_channels), 1, relu=relu, c1=C1, x=lo, x2=skip,
+                      bias=bias, out=out, stats=stats)
+    return out if _conv_run(call, "conv2d_upcat", stats, may_refuse=True) else None
 
 
-# BatchNorm-backward reductions from the dgrad epilogue (ffa_conv2d_bnbwd).  Measured on MI355X, same session: 16.31 vs
+# BatchNorm-backward reductions from the dgrad epilogue (conv2d_bnbwd).  Measured on MI355X, same session: 16.31 vs
 # 16.24 ms/step without -- the epilogue's per-lane 16-byte reads of x (one cache line per lane) cost what the saved
 # reduction pass gained -- so it stays OFF by default; FFA_FUSED_BN_BWD=1 turns it on (covered by the kernel tests).
 FUSED_BN_BWD = os.environ.get("FFA_FUSED_BN_BWD", "0") == "1"
@@ -272,7 +302,6 @@ def conv2d_bnbwd(x: torch.Tensor, w: PackedWeight, pad: int, out_channels: int, 
                  out_hw: Optional[Tuple[int, int]] = None):
     """A (dgrad) convolution whose output dy is the gradient of relu(bn(bnx)): -> (dy, partials, rows) with the
     BatchNorm-backward reductions sum(g), sum(g*bnx) taken in the conv epilogue (see bn_bwd_partials)."""
-    lib = _l.load()
     _chk_nhwc(x, "conv input")
     B, Hi, Wi, Ci = x.shape
     if out_hw is None:
@@ -282,12 +311,13 @@ def conv2d_bnbwd(x: torch.Tensor, w: PackedWeight, pad: int, out_channels: int, 
     if tuple(bnx.shape) != (B, Ho, Wo, out_channels) or bnx.dtype != x.dtype or not bnx.is_contiguous():
         raise ValueError("conv2d_bnbwd: bnx must have the shape, pitch and dtype of the output")
     out = torch.empty((B, Ho, Wo, out_channels), dtype=x.dtype, device=x.device)
-    rows = conv_stat_rows(B, Ho, Wo)
+    call = _conv_call(_l.CONV_PLAIN, _dt(x), w, (B, Hi, Wi, Ho, Wo, out_channels), pad, dil, x=x, residual=residual,
+                      out=out, bn=(bnx, bn_scale, bn_shift))
+    call.stats = 1  # routed before the buffer exists: the router reads only whether the pointer is null
+    rows = _conv_route(call, "conv2d_bnbwd").ntiles
     part = workspace(rows * 2 * out_channels * 4, x.device, "bnpart").view(torch.float32)
-    _l.check(lib.ffa_conv2d_bnbwd(_dt(x), x.data_ptr(), w.data.data_ptr(), _ptr(residual), out.data_ptr(),
-                                  part.data_ptr(), bnx.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), B, Hi, Wi,
-                                  Ci, Ho, Wo, out_channels, w.rows, w.bco, w.kh, w.kw, w.stride, pad, dil, _stream()),
-             "conv2d_bnbwd")
+    call.stats = part.data_ptr()
+    _conv_run(call, "conv2d_bnbwd")
     return out, part, rows
 
 
@@ -310,29 +340,28 @@ def conv2d_dgrad_upcat(dy: torch.Tensor, wt: PackedWeight, c1: int, c2: int):
     split is not supported (the caller then runs the plain dgrad + upsample2x_concat_bwd)."""
     if not FUSED_UPCAT_BWD:
         return None
-    lib = _l.load()
     _chk_nhwc(dy, "dgrad_upcat dy")
     B, H, W, Cdy = dy.shape
     if Cdy != wt.ci_pitch or wt.kh != 3 or wt.stride != 1 or H % 2 or W % 2:
         raise ValueError("conv2d_dgrad_upcat: operand / gradient mismatch")
     dlo = torch.empty((B, H // 2, W // 2, c1), dtype=dy.dtype, device=dy.device)
     dskip = torch.empty((B, H, W, c2), dtype=dy.dtype, device=dy.device) if c2 else None
-    rc = lib.ffa_conv2d_dgrad_upcat(_dt(dy), dy.data_ptr(), wt.data.data_ptr(), dlo.data_ptr(), _ptr(dskip), B, H, W, Cdy,
-                                    c1, c2, wt.rows, wt.bco, _stream())
-    if rc == _l.ERR_UNSUPPORTED:
-        return None
-    _l.check(rc, "conv2d_dgrad_upcat")
-    return dlo, dskip
+    call = _conv_call(_l.CONV_POOLED, _dt(dy), wt, (B, H, W, H, W, c1 + c2), 1, c1=c1, x=dy, out=dlo, out2=dskip)
+    return (dlo, dskip) if _conv_run(call, "conv2d_dgrad_upcat", may_refuse=True) else None
 
 
 FUSED_BN_STATS = os.environ.get("FFA_FUSED_BN_STATS", "1") != "0"
 
 
 def conv_stat_rows(B: int, Ho: int, Wo: int, w: Optional[PackedWeight] = None) -> int:
-    """rows of per-tile statistics the convolution with operand ``w`` writes (w=None: the conv_igemm tiling)"""
-    if w is None:
-        return int(_l.load().ffa_conv_stat_rows(B, Ho, Wo, 64, 64))
-    return int(_l.load().ffa_conv_stat_rows(B, Ho, Wo, w.rows, w.bco))
+    """rows of per-tile statistics the plain convolution with operand ``w`` writes (w=None: the conv_igemm tiling).
+    The functions here that take ``stats`` size and check it from the route of their own call, whatever its form."""
+    w = w or _IGEMM_OPERAND
+    return _conv_route(_operand_call(_dt(w.data), w, B, Ho, Wo, stats=True), "conv_stat_rows").ntiles
+
+
+# any conv_igemm operand: the pixel tile of that layout depends on the output size alone
+_IGEMM_OPERAND = PackedWeight(torch.empty(0, dtype=torch.bfloat16), 64, 64, 16, 64, 3, 3, 1)
 
 
 def _bn_finalize(part: torch.Tensor, rows: int, npix: int, channels: int, gamma, beta, running_mean, running_var,
@@ -357,7 +386,7 @@ def conv2d_bn_stats(x: torch.Tensor, w: PackedWeight, pad: int, out_channels: in
         return (y0,) + tuple(bn_stats(y0, gamma, beta, running_mean, running_var, momentum, eps))
     B, Hi, Wi, _ = x.shape
     Ho, Wo = conv_out_size(Hi, w.kh, w.stride, pad), conv_out_size(Wi, w.kw, w.stride, pad)
-    rows = conv_stat_rows(B, Ho, Wo, w)
+    rows = _conv_route(_operand_call(_dt(x), w, B, Ho, Wo, stats=True, in_hw=(Hi, Wi)), "conv2d_bn_stats").ntiles
     part = workspace(rows * 2 * out_channels * 4, x.device, "bnpart").view(torch.float32)
     y0 = conv2d(x, w, pad, out_channels, stats=part)
     return (y0,) + _bn_finalize(part, rows, B * Ho * Wo, out_channels, gamma, beta, running_mean, running_var,
@@ -377,40 +406,43 @@ NORM_ON_LOAD = os.environ.get("FFA_NORM_ON_LOAD", "0") == "1"
 
 
 def pro_supported(w: "PackedWeight", dtype: torch.dtype, up: bool = False) -> bool:
-    """True when conv2d_pro / conv_wgrad_pro exist for this operand: bf16, ring16 layout (>= 64 channels) or thin layout"""
-    if dtype != torch.bfloat16 or w.kh != 3 or w.stride != 1:
+    """True when conv2d_pro / conv_wgrad_pro exist for this operand: bf16, ring16 layout (>= 64 channels) or thin layout.
+    The library's answer for a prologue call on the operand (ffa_conv_plan gives no ring operand fewer than 64 real
+    rows); the weight-gradient kernel behind a ring operand adds whole 64-channel groups of real input channels, which
+    the library does not see."""
+    if dtype != torch.bfloat16 or not (w.bco & _l.BCO_THIN or (w.ch_real >= 64 and w.ci_pitch % 64 == 0)):
         return False
-    if w.bco & _l.BCO_THIN:
-        return True
-    return bool(w.bco & _l.BCO_RING) and not up and w.rows_real >= 64 and w.ch_real >= 64 and w.ci_pitch % 64 == 0
+    form, c1 = (_l.CONV_UPCAT, w.ci_pitch) if up else (_l.CONV_PLAIN, 0)
+    return _conv_route(_operand_call(_dtype_id(dtype), w, 1, 32, 32, form=form, c1=c1, pro=True)) is not None
 
 
 def conv2d_pro(x: torch.Tensor, w: PackedWeight, out_channels: int, pro_scale: torch.Tensor, pro_shift: torch.Tensor,
                bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, relu: bool = False,
                stats: Optional[torch.Tensor] = None, up: bool = False) -> torch.Tensor:
-    """3x3 pad-1 conv of relu(x * pro_scale + pro_shift) without the normalised tensor (ffa_conv2d_pro); up: x is the
-    low-resolution map of the skip-less nearest-x2 form (thin layout)."""
-    lib = _l.load()
+    """3x3 pad-1 conv of relu(x * pro_scale + pro_shift) without the normalised tensor; up: x is the low-resolution map
+    of the skip-less nearest-x2 form (thin layout)."""
     _chk_nhwc(x, "conv input")
     B, Hs, Ws, Ci = x.shape
     H, W = (2 * Hs, 2 * Ws) if up else (Hs, Ws)
     if Ci != w.ci_pitch or pro_scale.numel() < Ci or pro_shift.numel() < Ci:
         raise ValueError("conv2d_pro: operand / prologue vector mismatch")
+    if x.dtype != torch.bfloat16:
+        raise _l.FlairHipError("conv2d_pro: bf16 only")
     out = torch.empty((B, H, W, out_channels), dtype=x.dtype, device=x.device)
-    if stats is not None and (stats.dtype != torch.float32 or stats.numel() < conv_stat_rows(B, H, W, w) * 2 * out_channels):
-        raise ValueError("conv2d_pro: statistics buffer too small or not f32")
-    _l.check(lib.ffa_conv2d_pro(_dt(x), x.data_ptr(), w.data.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-                                _ptr(stats), pro_scale.data_ptr(), pro_shift.data_ptr(), B, H, W, Ci, out_channels, w.rows,
-                                w.bco, 1 if relu else 0, 1 if up else 0, _stream()), "conv2d_pro")
+    call = _conv_call(_l.CONV_UPCAT if up else _l.CONV_PLAIN, _dt(x), w, (B, H, W, H, W, out_channels), 1, relu=relu,
+                      c1=Ci if up else 0, x=x, bias=bias, residual=residual, out=out, stats=stats,
+                      pro=(pro_scale, pro_shift))
+    _conv_run(call, "conv2d_pro", stats)
     return out
 
 
 def conv2d_pro_bn_stats(x: torch.Tensor, w: PackedWeight, out_channels: int, pro_scale, pro_shift, gamma, beta,
                         running_mean, running_var, momentum: float, eps: float, up: bool = False):
     """conv2d_pro + batch statistics of its output -> (y0, scale, shift, mean, rstd)"""
-    B, Hs, Ws, _ = x.shape
+    B, Hs, Ws, Ci = x.shape
     H, W = (2 * Hs, 2 * Ws) if up else (Hs, Ws)
-    rows = conv_stat_rows(B, H, W, w)
+    form, c1 = (_l.CONV_UPCAT, Ci) if up else (_l.CONV_PLAIN, 0)
+    rows = _conv_route(_operand_call(_dt(x), w, B, H, W, form=form, c1=c1, pro=True, stats=True), "conv2d_pro").ntiles
     part = workspace(rows * 2 * out_channels * 4, x.device, "bnpart").view(torch.float32)
     y0 = conv2d_pro(x, w, out_channels, pro_scale, pro_shift, stats=part, up=up)
     return (y0,) + _bn_finalize(part, rows, B * H * W, out_channels, gamma, beta, running_mean, running_var, momentum, eps)
@@ -438,16 +470,9 @@ def conv_wgrad_pro(x: torch.Tensor, dy: torch.Tensor, co_real: int, ci_real: int
 
 
 def upcat_supported(c1: int, c2: int, dtype: torch.dtype) -> bool:
-    """Channel splits the two-source kernels take (ffa_conv2d_upcat: C1 covers whole halo channel groups;
-    ffa_conv_wgrad_upcat: C1 is a multiple of a block's input channels)."""
-    if not FUSED_UPCAT:
-        return False
-    eb = 2 if dtype == torch.bfloat16 else 4
-    ci = c1 + c2
-    nchunks = ci * eb // 32
-    hk = 4 if nchunks % 4 == 0 else (2 if nchunks % 2 == 0 else 1)
-    wci = 2 if (ci > 32 and eb == 2) else 1
-    return c1 > 0 and c1 % 16 == 0 and c2 % 16 == 0 and hk > 1 and (c1 * eb) % (hk * 32) == 0 and c1 % (32 * wci) == 0
+    """Channel splits the two-source kernels take (forward: C1 covers whole halo channel groups; weight gradient: C1 is
+    a multiple of a block's input channels)."""
+    return FUSED_UPCAT and bool(_l.load().ffa_conv_upcat_supported(_dtype_id(dtype), c1, c2))
 
 
 FUSED_UPCAT_BWD = os.environ.get("FFA_FUSED_UPCAT_BWD", "1") != "0"  # A/B: plain dgrad + up2_concat_bwd
@@ -457,9 +482,10 @@ FUSED_UPCAT = os.environ.get("FFA_FUSED_UPCAT", "1") != "0"  # A/B switch: mater
 def conv2d_upcat_bn_stats(lo: torch.Tensor, skip: Optional[torch.Tensor], w: PackedWeight, out_channels: int, gamma,
                           beta, running_mean, running_var, momentum: float, eps: float):
     """conv2d_upcat + batch statistics of its output -> (y0, scale, shift, mean, rstd)"""
-    B, Hl, Wl, _ = lo.shape
+    B, Hl, Wl, C1 = lo.shape
     Ho, Wo = 2 * Hl, 2 * Wl
-    rows = conv_stat_rows(B, Ho, Wo, w)
+    rows = _conv_route(_operand_call(_dt(lo), w, B, Ho, Wo, form=_l.CONV_UPCAT, c1=C1, stats=True),
+                       "conv2d_upcat (check upcat_supported first)").ntiles
     part = workspace(rows * 2 * out_channels * 4, lo.device, "bnpart").view(torch.float32)
     y0 = conv2d_upcat(lo, skip, w, out_channels, stats=part)
     if y0 is None:

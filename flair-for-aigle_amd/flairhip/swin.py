@@ -14,7 +14,7 @@ Arithmetic (all NHWC, a token = a pixel of the stage's map):
                     reverse by index arithmetic) -> proj GEMM with the residual add in its epilogue -> ffa_layer_norm ->
                     fc1 GEMM with GELU in its epilogue -> fc2 GEMM with the residual add in its epilogue
   PatchMerging      ffa_patch_merge_norm (2x2 gather + LayerNorm(4C)) -> reduction GEMM
-  PSP / FPN         ffa_adaptive_avg_pool, 1x1 / 3x3 convolutions with evaluation-mode BatchNorm folded (ffa_conv2d),
+  PSP / FPN         ffa_adaptive_avg_pool, 1x1 / 3x3 convolutions with evaluation-mode BatchNorm folded (ffa_conv_run),
                     ffa_bilinear_slice writing straight into the channel slice of the concat buffers (+ lateral addend)
   head              1x1 convolution + bias, x4 bilinear with align_corners=True (nn.UpsamplingBilinear2d)
 bf16 mode uses the hand-written token GEMM (csrc/gemm.hip); the f32 parity mode runs the same layers through the f32

@@ -3,7 +3,7 @@
 Counterpart of the reference's flair_hub/models/multitemp_model.py (UTAE :13-166, LTAE2d :169-284,
 MultiHeadAttention :316-373, ConvLayer / ConvBlock / DownConvBlock / UpConvBlock :452-599, Temporal_Aggregator
 :603-662) with the SAME parameter names, so a reference state dict loads unchanged.  Arithmetic: NHWC tensors with
-image index n = b * T + t; reflect-padded 3x3 convolutions = ffa_reflect_pad1 + ffa_conv2d(pad 0) with the bias in
+image index n = b * T + t; reflect-padded 3x3 convolutions = ffa_reflect_pad1 + ffa_conv_run (pad 0) with the bias in
 the conv epilogue; GroupNorm / attention / aggregation are the kernels of csrc/temporal.hip; evaluation-mode
 BatchNorm is folded into the packed conv operand (scale) and its bias (shift), as everywhere else in the product.
 

@@ -46,47 +46,21 @@ const char* ffa_target_arch(void);
 /* preferred block height (output channels per workgroup) for a layer; weights are packed for it */
 int ffa_conv_block_co(int kh, int kw, int stride, int cout);
 /* Operand layout + block height of a layer: the `bco` value for ffa_pack_conv_weight_bytes / ffa_pack_conv_weight /
- * ffa_pack_desc_fill / ffa_pack_conv_weights_batched / ffa_conv2d / ffa_conv2d_stats / ffa_conv_stat_rows.
- * Bits 0..11 = rows per block (pad the row count to a multiple of it); FFA_BCO_RING set = the operand is packed for the LDS-DMA ring kernels (bf16: conv3x3_ring16_kernel, the default
- * for 3x3 stride 1 pad 1 layers with >= 64 output channels and whole 64-byte groups of input channels -- FFA_RING=0 in the
- * environment restores the conv_igemm kernels; f32: conv3x3_ring_kernel, FFA_RING=1); bit 13 (0x2000) = the
- * register-resident operand of the thin layers (ffa_thin_*; FFA_THIN=0 disables).  `allow`: bit 0 admits the ring
- * layout, bit 1 the thin one, bit 2 the stem one (0x8000); pass 0 for operands that feed ffa_conv2d_bnbwd or a dil = 2 call. */
+ * ffa_pack_desc_fill / ffa_pack_conv_weights_batched and for the `bco` field of ffa_conv_call_t.
+ * Bits 0..11 = rows per block (pad the row count to a multiple of it).  FFA_BCO_RING = the operand is packed for the
+ * LDS-DMA ring kernels (csrc/conv3x3_ring.hip; bf16: conv3x3_ring16_kernel, the default for 3x3 stride 1 pad 1 layers
+ * with >= 64 output channels and whole 64-byte groups of input channels -- FFA_RING=0 in the environment restores the
+ * conv_igemm kernels; f32: conv3x3_ring_kernel, FFA_RING=1).  FFA_BCO_THIN = the register-resident operand of the thin
+ * layers (csrc/conv3x3_thin.hip: bf16, <= 32 real output rows, input pitch 16 or 32 -- the decoder's last two blocks
+ * and the segmentation head; FFA_THIN=0 disables).  FFA_BCO_STEM = the operand of the ResNet stem kernel
+ * (csrc/conv7x7_stem.hip: bf16 7x7 stride-2 pad-3 convolution of a <= 8-channel tile stored at pitch 16 into 64
+ * channels, torchvision's conv1 as smp's ResNetEncoder keeps it; FFA_STEM=0 disables).  `allow`: bit 0 admits the ring
+ * layout, bit 1 the thin one, bit 2 the stem one; which forms of call each layout serves is the table at
+ * ffa_conv_call_t. */
 #define FFA_BCO_RING 0x1000
 #define FFA_BCO_THIN 0x2000
-int ffa_conv_plan(int dtype, int kh, int kw, int stride, int cout, int ci_pitch, int allow);
-/* The ring kernel called directly: out = relu?(conv3x3(in', w) + bias + residual) with in' = in, or -- when
- * pro_scale / pro_shift are given -- in' = relu(in * pro_scale[c] + pro_shift[c]) evaluated while the input tile is
- * staged (the training-mode BatchNorm + ReLU of the producing layer folded into this convolution's loader: replaces
- * the F.batch_norm + relu pass between two convolutions of smp's Conv2dReLU / torchvision's BasicBlock; zero padding
- * applies to the normalised tensor).  stat_partials as for ffa_conv2d_stats (rows = ffa_conv_stat_rows) or null. */
-int ffa_ring_conv3x3(int dtype, const void* in, const void* w_ring, const float* bias, const void* residual, void* out,
-                     float* stat_partials, const float* pro_scale, const float* pro_shift, int B, int H, int W, int Ci,
-                     int Co, int co_rows, int relu, ffa_stream_t stream);
-long long ffa_ring_stat_rows(int B, int H, int W, int co_rows);
-/* Thin 3x3 stride-1 pad-1 layers (bf16, <= 32 real output rows, input pitch 16 or 32: the decoder's last two blocks and the
- * segmentation head; csrc/conv3x3_thin.hip): the whole weight operand lives in registers, the input halo arrives by
- * LDS-DMA three tiles deep.  Replaces the same F.conv2d as ffa_conv2d for those shapes; `up` reads nearest_x2(in)
- * (F.interpolate(scale_factor=2) in front of smp's DecoderBlock.conv1), `pool` stores the 2x2 sums of the output (its
- * adjoint, for the transposed operand), `_pro` evaluates relu(in * scale + shift) on the staged halo.  ffa_conv2d /
- * ffa_conv2d_upcat / ffa_conv2d_dgrad_upcat dispatch here when the operand was packed for it (ffa_conv_plan bit 13). */
-int ffa_thin_eligible(int dtype, int kh, int kw, int stride, int rows_real, int ci_pitch);
-long long ffa_thin_stat_rows(int B, int H, int W, int ci_pitch);
-int ffa_thin_conv3x3(const void* in, const void* w_thin, const float* bias, const void* residual, void* out,
-                     float* stat_partials, int B, int H, int W, int Ci, int Co, int co_rows, int relu, int up, int pool,
-                     ffa_stream_t stream);
-int ffa_thin_conv3x3_pro(const void* in, const void* w_thin, const float* bias, const void* residual, void* out,
-                         float* stat_partials, const float* pro_scale, const float* pro_shift, int B, int H, int W, int Ci,
-                         int Co, int co_rows, int relu, int up, int pool, ffa_stream_t stream);
-/* The ResNet stem (bf16 7x7 stride-2 pad-3 convolution of a <= 8-channel tile stored at pitch 16 into 64 channels;
- * csrc/conv7x7_stem.hip; torchvision's conv1 as smp's ResNetEncoder keeps it): four adjacent taps x 8 channels per
- * K = 32 MFMA step, only the first 16 bytes of every input pixel are staged.  ffa_conv2d / ffa_conv2d_stats dispatch here
- * when the operand was packed for it (ffa_conv_plan with bit 2 of `allow`; bit 15 of the returned code). */
 #define FFA_BCO_STEM 0x8000
-int ffa_stem_eligible(int dtype, int kh, int kw, int stride, int cout, int ci_pitch);
-long long ffa_stem_stat_rows(int B, int Ho, int Wo);
-int ffa_stem_conv7x7(const void* in, const void* w_stem, const float* bias, void* out, float* stat_partials, int B, int Hi,
-                     int Wi, int Ci, int Ho, int Wo, int Co, int relu, ffa_stream_t stream);
+int ffa_conv_plan(int dtype, int kh, int kw, int stride, int cout, int ci_pitch, int allow);
 int ffa_conv_row_group(int kh);
 /* Weight packing (csrc/conv_pack.hip): OIHW f32 master weight -> the operand of the layout in `bco` (ffa_conv_plan),
  * whose size in bytes the first call returns.  transpose=1 builds the dgrad operand (rows = input channels, taps
@@ -103,81 +77,128 @@ int ffa_pack_desc_bytes(void);
 int ffa_pack_desc_fill(void* host_desc, const float* w_oihw, const float* scale, void* dst, int O, int I_total, int col0,
                        int ncols, int kh, int kw, int transpose, int co_rows, int ci_pitch, int bco, int rg, int dtype);
 int ffa_pack_conv_weights_batched(int dtype, int bco, const void* descs_device, int n, ffa_stream_t stream);
-/* out = relu?( conv(in, w) + bias + residual ).  dil=2 reads `in` through a virtual zero insertion
- * (dgrad of a stride-2 layer, stride must then be 1). */
-int ffa_conv2d(int dtype, const void* in, const void* w_packed, const float* bias, const void* residual, void* out,
-               int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int co_rows, int bco, int kh, int kw, int stride,
-               int pad, int dil, int relu, ffa_stream_t stream);
 
-/* ffa_conv2d that also writes, per pixel tile, the channel sums and sums of squares of the output it stores:
- * stat_partials[rows][2][Co] f32, rows = ffa_conv_stat_rows(B, Ho, Wo, co_rows, bco).  With ffa_bn_finalize this replaces the
- * separate statistics pass of a training-mode BatchNorm that follows the convolution (torch.nn.functional.batch_norm
- * as called by smp's Conv2dReLU / torchvision's BasicBlock). */
-long long ffa_conv_stat_rows(int B, int Ho, int Wo, int co_rows, int bco);
-/* 1 when ffa_conv2d / ffa_conv2d_stats run this 3x3 stride-1 convolution on the persistent kernel
- * (conv3x3_persist_kernel, blocks that walk several pixel tiles; FFA_CONV_PERSIST=0 disables), else 0.
- * Profiling aid: the two kernels are separate symbols. */
-int ffa_conv_is_persistent(int dtype, int B, int Ho, int Wo, int Ci, int co_rows, int bco, int kh, int kw, int stride,
-                           int dil);
-int ffa_conv2d_stats(int dtype, const void* in, const void* w_packed, const float* bias, const void* residual,
-                     void* out, float* stat_partials, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co,
-                     int co_rows, int bco, int kh, int kw, int stride, int pad, int dil, int relu,
-                     ffa_stream_t stream);
+/* One forward / input-gradient convolution call.  Replaces F.conv2d and what surrounds it at the call sites below.
+ *
+ * form
+ *   FFA_CONV_PLAIN   out = relu?(conv(in', w) + bias + residual).  dil = 2 reads `in` through a virtual zero insertion
+ *                    (the input gradient of a stride-2 layer; stride must then be 1).  smp's Conv2dReLU / torchvision's
+ *                    BasicBlock and Bottleneck convolutions and their input gradients.
+ *   FFA_CONV_UPCAT   3x3 stride-1 pad-1 convolution over the virtual tensor cat(nearest_x2(in), in2) -- what smp's
+ *                    DecoderBlock builds with F.interpolate(scale_factor=2, mode="nearest") + torch.cat before its
+ *                    first conv (reached from flair_model.py:417-419) -- without writing it: in [B][Hi/2][Wi/2][c1],
+ *                    in2 [B][Hi][Wi][Ci - c1], or null with c1 = Ci (the skip-less form).  Hi, Wi, Ci describe the
+ *                    virtual tensor.  No residual.
+ *   FFA_CONV_POOLED  the input gradient of the FFA_CONV_UPCAT convolution as the two tensors the decoder block needs
+ *                    (replaces the dgrad convolution + ffa_upsample_nearest2x_concat_bwd): output channels below c1 are
+ *                    2x2-sum-pooled (the adjoint of nearest x2) into out [B][Ho/2][Wo/2][c1], the rest go to out2
+ *                    [B][Ho][Wo][Co - c1], or nowhere with c1 = Co.  Ho, Wo, Co describe the gradient of the virtual
+ *                    tensor; w is the transposed operand.  Plain epilogue: no bias, residual, relu or statistics.
+ * Epilogues and the prologue are switched on by their pointers:
+ *   stats      per pixel tile, the channel sums and sums of squares of the output stored:
+ *              stats[route.ntiles][2][Co] f32.  With ffa_bn_finalize this replaces the statistics pass of the
+ *              training-mode BatchNorm that follows (F.batch_norm as called by Conv2dReLU / BasicBlock).
+ *   pro_scale, pro_shift  (both or neither) in' = relu(in * pro_scale[c] + pro_shift[c]) evaluated while the input is
+ *              staged: the BatchNorm + ReLU of the PRODUCING layer (Conv2dReLU -> Conv2dReLU, BasicBlock conv1 -> bn1 ->
+ *              relu -> conv2: flair_hub/models/monotemp_model.py:68-92); the normalised tensor is never written and
+ *              zero padding applies to it.  Bit-identical to ffa_bn_apply followed by the same call without prologue.
+ *   bnx, bn_scale, bn_shift  (with stats) the output is the gradient dy of y = relu(bnx * bn_scale + bn_shift): stats
+ *              receives per tile sum(g), sum(g * bnx), g = dy where y > 0 else 0, so that ffa_bn_bwd_partials can skip
+ *              the reduction pass of ffa_bn_bwd.  bnx has the shape and pitch of out.
+ *
+ * Which operand layout (ffa_conv_plan) serves which form:
+ *                 conv_igemm                        ring                thin                        stem
+ *   PLAIN         any supported kernel; dil 1 / 2;  3x3 s1 p1 dil 1;    bf16 3x3 s1 p1 dil 1;       bf16 7x7 s2 p3;
+ *                 stats, bnx                        stats, prologue     stats, prologue             stats; no residual
+ *   UPCAT         c1 covers whole halo channel      --                  in2 = null only; stats,     --
+ *                 groups (else UNSUPPORTED); stats                      prologue
+ *   POOLED        c1 a multiple of the block's      --                  c1 = Co only                --
+ *                 rows (else UNSUPPORTED)
+ * A form the layout does not serve is FFA_ERR_UNSUPPORTED (the caller falls back to materialising the tensor), a call
+ * that breaks the geometry its layout was packed for is FFA_ERR_ARG. */
+#define FFA_CONV_PLAIN 0
+#define FFA_CONV_UPCAT 1
+#define FFA_CONV_POOLED 2
+typedef struct {
+  int dtype;
+  int form;
+  const void* in;
+  const void* in2;
+  const void* w;       /* packed operand (ffa_pack_conv_weight) of co_rows rows in the layout `bco` */
+  const float* bias;   /* [>= Co] or null */
+  const void* residual; /* shape and pitch of out, or null */
+  void* out;
+  void* out2;
+  float* stats;
+  const float* pro_scale;
+  const float* pro_shift;
+  const void* bnx;
+  const float* bn_scale;
+  const float* bn_shift;
+  int co_rows, bco;
+  int B, Hi, Wi, Ci;   /* channel pitches: a multiple of 16 (Ci) / 8 (Co) */
+  int Ho, Wo, Co;
+  int kh, kw, stride, pad, dil;
+  int relu;
+  int c1;              /* channel split of the UPCAT / POOLED forms, else 0 */
+} ffa_conv_call_t;
 
-/* ffa_conv2d whose output is the gradient dy of y = relu(bn_train(x)) -- a dgrad convolution feeding a BatchNorm
- * backward: also leaves per tile sum(g), sum(g*x), g = dy masked by x*bn_scale + bn_shift > 0, in
- * stat_partials[rows][2][Co], so that ffa_bn_bwd_partials can skip the reduction pass of ffa_bn_bwd. */
-int ffa_conv2d_bnbwd(int dtype, const void* in, const void* w_packed, const void* residual, void* out,
-                     float* stat_partials, const void* bnx, const float* bn_scale, const float* bn_shift, int B, int Hi,
-                     int Wi, int Ci, int Ho, int Wo, int Co, int co_rows, int bco, int kh, int kw, int stride, int pad,
-                     int dil, ffa_stream_t stream);
+/* What a call runs: kernel family, output pixel tile, pixel tiles (ntiles = rows of the statistics partials) and grid.
+ * conv3x3_persist_kernel and conv_igemm_kernel serve the same operands and are separate symbols in a profile
+ * (FFA_CONV_PERSIST=0 keeps every call on the latter). */
+#define FFA_CONV_KERNEL_IGEMM 0
+#define FFA_CONV_KERNEL_PERSIST 1
+#define FFA_CONV_KERNEL_RING 2
+#define FFA_CONV_KERNEL_RING16 3
+#define FFA_CONV_KERNEL_THIN 4
+#define FFA_CONV_KERNEL_STEM 5
+typedef struct {
+  int kernel;
+  int variant;  /* instantiation within the family (conv_igemm: 32-byte channel groups per halo fill; ring: tile configuration) */
+  int th, tw;
+  int tiles_x, tiles_y;
+  int ntiles;
+  int ncb;      /* blocks of output rows */
+  int grid;
+} ffa_conv_route_t;
 
-/* 3x3 stride-1 pad-1 convolution over the virtual tensor cat(nearest_x2(lo), skip) -- what smp's DecoderBlock builds
- * with F.interpolate(scale_factor=2, mode="nearest") + torch.cat before its first conv (reached from
- * flair_model.py:417-419) -- without writing it: lo [B][Hl][Wl][C1], skip [B][2Hl][2Wl][C2] or null.
- * FFA_ERR_UNSUPPORTED when C1 is not a whole number of the kernel's channel groups.  bias (per output channel, e.g.
- * an eval-mode BatchNorm shift) and stat_partials may be null; relu != 0 clamps in the epilogue. */
-int ffa_conv2d_upcat(int dtype, const void* lo, const void* skip, const void* w_packed, const float* bias, void* out,
-                     float* stat_partials, int B, int Hl, int Wl, int C1, int C2, int Co, int co_rows, int bco,
-                     int relu, ffa_stream_t stream);
-
-/* Input gradient of that convolution as the two tensors the decoder block needs -- dlo [B][Ho/2][Wo/2][C1] (2x2 sums,
- * the adjoint of nearest x2) and dskip [B][Ho][Wo][C2] -- without materialising the gradient of the concatenation
- * (replaces ffa_conv2d(dgrad) + ffa_upsample_nearest2x_concat_bwd).  w_packed_t: the transposed operand. */
-int ffa_conv2d_dgrad_upcat(int dtype, const void* dy, const void* w_packed_t, void* dlo, void* dskip, int B, int Ho,
-                           int Wo, int Cdy, int C1, int C2, int co_rows, int bco, ffa_stream_t stream);
+/* Validates geometry and form x layout and fills *route.  Launches nothing, reads no tensor (only whether the optional
+ * pointers are null) and makes no HIP call: it answers on a machine without a GPU. */
+int ffa_conv_route(const ffa_conv_call_t* call, ffa_conv_route_t* route);
+/* Checks the pointers, routes the same way and launches. */
+int ffa_conv_run(const ffa_conv_call_t* call, ffa_stream_t stream);
+/* sizeof(ffa_conv_call_t) (which = 0) / sizeof(ffa_conv_route_t) (1): a binding checks its own layout against it */
+int ffa_conv_struct_bytes(int which);
+/* 1 when the channel split (c1 from the low-resolution map, c2 from the skip tensor) of a 3x3 decoder convolution is
+ * served by both the FFA_CONV_UPCAT form (conv_igemm layout) and ffa_conv_wgrad_upcat, else 0 */
+int ffa_conv_upcat_supported(int dtype, int c1, int c2);
 long long ffa_conv_wgrad_workspace_bytes(int dtype, int kh, int kw, int stride, int Co, int Ci, int B, int Ho, int Wo);
 int ffa_conv_wgrad(int dtype, const void* x, const void* dy, float* dw_oihw, int B, int Hi, int Wi, int Ci, int Ho,
                    int Wo, int Co, int Co_real, int Ci_real, int kh, int kw, int stride, int pad, int accumulate,
                    void* workspace, long long workspace_bytes, ffa_stream_t stream);
 
-/* Weight gradient of the convolution ffa_conv2d_upcat computes: the input is the virtual cat(nearest_x2(lo), skip),
+/* Weight gradient of the FFA_CONV_UPCAT convolution: the input is the virtual cat(nearest_x2(lo), skip),
  * dw is OIHW [Co_real][C1 + C2][3][3] f32.  Workspace: ffa_conv_wgrad_workspace_bytes(dtype, 3, 3, 1, Co, C1 + C2, B,
  * 2*Hl, 2*Wl).  FFA_ERR_UNSUPPORTED when C1 is not a multiple of the kernel's input-channel block. */
 int ffa_conv_wgrad_upcat(int dtype, const void* lo, const void* skip, const void* dy, float* dw_oihw, int B, int Hl,
                          int Wl, int C1, int C2, int Co, int Co_real, int accumulate, void* workspace,
                          long long workspace_bytes, ffa_stream_t stream);
 
-/* "Normalise on load" (round 3): a convolution / weight gradient whose input is relu(x * pro_scale[c] + pro_shift[c]),
- * the training-mode BatchNorm + ReLU of the PRODUCING layer (smp Conv2dReLU -> Conv2dReLU, torchvision BasicBlock conv1 ->
- * bn1 -> relu -> conv2: flair_hub/models/monotemp_model.py:68-92), evaluated while the consumer stages x -- the
- * normalised tensor is never written (replaces ffa_bn_apply + ffa_conv2d[_stats] / ffa_conv_wgrad; bit-identical to that
- * sequence, zero padding applied after the normalisation).  bf16, 3x3 stride 1 pad 1; operands in the ring16 / thin
- * layouts of ffa_conv_plan.  up != 0: x is the low-resolution map of the skip-less nearest-x2 form.
- * FFA_ERR_UNSUPPORTED where no prologue kernel exists (the caller then materialises the tensor). */
-int ffa_conv2d_pro(int dtype, const void* in, const void* w_packed, const float* bias, const void* residual, void* out,
-                   float* stat_partials, const float* pro_scale, const float* pro_shift, int B, int H, int W, int Ci,
-                   int Co, int co_rows, int bco, int relu, int up, ffa_stream_t stream);
+/* "Normalise on load" for the weight gradient: ffa_conv_wgrad / ffa_conv_wgrad_upcat (skip-less) of a layer whose
+ * input was relu(x * pro_scale[c] + pro_shift[c]) -- the prologue of ffa_conv_call_t on the weight-gradient side; the
+ * normalised tensor is never written (replaces ffa_bn_apply + ffa_conv_wgrad; bit-identical to that sequence, zero
+ * padding applied after the normalisation).  bf16, 3x3 stride 1 pad 1.  up != 0: x is the low-resolution map of the
+ * skip-less nearest-x2 form.  FFA_ERR_UNSUPPORTED where no prologue kernel exists. */
 int ffa_conv_wgrad_pro(int dtype, const void* x, const void* dy, float* dw_oihw, const float* pro_scale,
                        const float* pro_shift, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int Co_real,
                        int Ci_real, int up, int accumulate, void* workspace, long long workspace_bytes,
                        ffa_stream_t stream);
 
 /* ---- U-TAE Sentinel time-series branch (flair_hub/models/multitemp_model.py) ------------------
- * Small NHWC kernels around ffa_conv2d for the temporally shared encoder, the L-TAE and the attention-weighted skip
+ * Small NHWC kernels around ffa_conv_run for the temporally shared encoder, the L-TAE and the attention-weighted skip
  * aggregation; evaluation-mode forward. */
 /* out[n][y][x] = in[n][refl(y-1)][refl(x-1)]: the padding of nn.Conv2d(padding=1, padding_mode="reflect")
- * (multitemp_model.py:473-482); the convolution itself is ffa_conv2d with pad 0 on the padded tensor */
+ * (multitemp_model.py:473-482); the convolution itself is ffa_conv_run with pad 0 on the padded tensor */
 int ffa_reflect_pad1(int dtype, const void* in, void* out, int N, int H, int W, int C, ffa_stream_t stream);
 /* y = [residual +] relu?(GroupNorm(x)): nn.GroupNorm of ConvLayer (:464-468, 4 groups over an image) and of LTAE2d
  * (:224-231, 16 groups over the dates of one pixel).  Sample s starts at element (s / Q) * stride_hi +
@@ -234,7 +255,7 @@ int ffa_mul(int dtype, const void* x, const void* m, void* y, long long n, ffa_s
 int ffa_mean_stack(int dtype, const void* const* xs, int n, float divisor, void* y, long long numel, ffa_stream_t stream);
 
 /* ---- measurement only: kernel timing session.  Between ffa_ktime_begin(max_launches) and ffa_ktime_end() the 3x3 MFMA
- *      launches of the process (ffa_conv2d on the ring operand, ffa_conv_wgrad on 64-channel blocks) carry their
+ *      launches of the process (ffa_conv_run on the ring operand, ffa_conv_wgrad on 64-channel blocks) carry their
  *      own start / stop events (hipExtLaunchKernelGGL): ffa_ktime_end waits for them and returns, in launch order, the
  *      kernels' durations in milliseconds and a tag (1: ring16 8x32 tiles, 2: ring16 16x16, 4: ring16 128-co blocks,
  *      16: wgrad64); its return value is the number of timed launches.  Not for use under stream capture. */
@@ -343,7 +364,7 @@ long long ffa_bn_workspace_bytes(int C);
 int ffa_bn_stats(int dtype, const void* x, long long npix, int C, const float* gamma, const float* beta,
                  float* running_mean, float* running_var, float momentum, float eps, float* scale, float* shift,
                  float* mean_out, float* rstd_out, void* workspace, long long workspace_bytes, ffa_stream_t stream);
-/* ffa_bn_stats without the pass over the tensor: partials[nparts][2][C] come from ffa_conv2d_stats */
+/* ffa_bn_stats without the pass over the tensor: partials[nparts][2][C] come from ffa_conv_run with stats */
 int ffa_bn_finalize(const float* partials, long long nparts, long long npix, int C, const float* gamma,
                     const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                     float* scale, float* shift, float* mean_out, float* rstd_out, void* workspace,
@@ -372,7 +393,7 @@ int ffa_bn_bwd_fused(int dtype, const void* x, const void* dy, const void* y, co
                      const float* mean, const float* rstd, void* dx, void* dres, float* dgamma, float* dbeta,
                      long long npix, int C, int relu, void* workspace, long long workspace_bytes, unsigned* sync,
                      ffa_stream_t stream);
-/* ffa_bn_bwd (ReLU mask recomputed from x) when sum(g) / sum(g*x) per tile already exist (ffa_conv2d_bnbwd) */
+/* ffa_bn_bwd (ReLU mask recomputed from x) when sum(g) / sum(g*x) per tile already exist (ffa_conv_run with bnx) */
 int ffa_bn_bwd_partials(int dtype, const void* x, const void* dy, const float* partials, long long nparts,
                         const float* gamma, const float* beta, const float* mean, const float* rstd, void* dx,
                         float* dgamma, float* dbeta, long long npix, int C, void* workspace, long long workspace_bytes,

@@ -532,7 +532,7 @@ def test_loss_backward_reuses_forward_gradient(cuda, scale):
     (16, 32, 3, 1, 300, 48),    # > 1024 pixel tiles: two-level fold of the partials
 ])
 def test_conv_epilogue_statistics_match_separate_pass(cuda, dtype, cin, cout, k, stride, H, W):
-    """ffa_conv2d_stats + ffa_bn_finalize == ffa_conv2d followed by ffa_bn_stats (scale, shift, mean, rstd and the
+    """conv2d with statistics + ffa_bn_finalize == conv2d followed by ffa_bn_stats (scale, shift, mean, rstd and the
     running buffers), on the values as stored"""
     from flairhip import ops
     g = torch.Generator().manual_seed(cin * 7 + cout)
@@ -567,7 +567,7 @@ def test_conv_epilogue_statistics_match_separate_pass(cuda, dtype, cin, cout, k,
     (256, 128, 128, 6, 6),    # 16x16 tiles (width < 32)
 ])
 def test_conv_over_virtual_upsample_concat(cuda, dtype, c1, c2, cout, Hl, Wl):
-    """ffa_conv2d_upcat(lo, skip) == ffa_conv2d(ffa_upsample_nearest2x_concat(lo, skip)), bit for bit (same
+    """conv2d_upcat(lo, skip) == conv2d(ffa_upsample_nearest2x_concat(lo, skip)), bit for bit (same
     reduction order), including the statistics epilogue"""
     from flairhip import ops
     g = torch.Generator().manual_seed(c1 + c2)
@@ -633,7 +633,7 @@ def test_wgrad_over_virtual_upsample_concat(cuda, dtype, c1, c2, cout, Hl, Wl):
     (256, 128, 128, 6, 6),    # 16x16 tiles
 ])
 def test_dgrad_with_fused_upsample_concat_backward(cuda, dtype, c1, c2, cout, Hl, Wl):
-    """ffa_conv2d_dgrad_upcat == dgrad conv + ffa_upsample_nearest2x_concat_bwd.  The pooled half sums four f32
+    """conv2d_dgrad_upcat == dgrad conv + ffa_upsample_nearest2x_concat_bwd.  The pooled half sums four f32
     accumulators before rounding once, the reference rounds dcat to storage precision first."""
     from flairhip import ops
     g = torch.Generator().manual_seed(c1 + 5 * c2)
@@ -658,7 +658,7 @@ def test_dgrad_with_fused_upsample_concat_backward(cuda, dtype, c1, c2, cout, Hl
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("cin,cout,H,W", [(64, 64, 40, 72), (128, 32, 24, 40), (16, 16, 300, 48), (256, 128, 6, 6)])
 def test_bn_backward_reductions_from_dgrad_epilogue(cuda, dtype, cin, cout, H, W):
-    """ffa_conv2d_bnbwd + ffa_bn_bwd_partials == ffa_conv2d + ffa_bn_bwd (mask recomputed from x)"""
+    """conv2d_bnbwd + ffa_bn_bwd_partials == conv2d + ffa_bn_bwd (mask recomputed from x)"""
     from flairhip import ops
     g = torch.Generator().manual_seed(cin + 3 * cout)
     B = 9 if H * W > 10000 else 3

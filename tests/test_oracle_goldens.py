@@ -284,7 +284,10 @@ def test_library_exports_every_declared_symbol(lib):
 
 def test_argument_errors_are_reported_not_thrown(lib):
     from flairhip import lib as L
-    rc = lib.ffa_conv2d(0, None, None, None, None, None, 1, 8, 8, 16, 8, 8, 16, 32, 32, 3, 3, 1, 1, 1, 0, None)
+    import ctypes as C
+    call = L.ConvCall(dtype=0, form=L.CONV_PLAIN, B=1, Hi=8, Wi=8, Ci=16, Ho=8, Wo=8, Co=16, co_rows=32, bco=32, kh=3, kw=3,
+                      stride=1, pad=1, dil=1, relu=0)  # the tensor pointers stay null
+    rc = lib.ffa_conv_run(C.byref(call), None)
     assert rc == -1 and b"null" in lib.ffa_last_error()
     assert lib.ffa_slice_grid(0.0, 0.0, 10.0, 10.0, 0.0, 0.0, 64, 32, 0.2, None, 0) == -1
     with pytest.raises(L.FlairHipError):

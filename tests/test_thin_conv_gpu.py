@@ -208,7 +208,7 @@ def test_thin_wgrad_of_the_upsampled_input(cuda):
 @pytest.mark.parametrize("cin,cout,H,W,up", [(16, 16, 32, 64, False), (32, 32, 24, 40, False), (16, 19, 40, 40, False),
                                               (32, 16, 20, 24, True), (64, 64, 24, 40, False), (128, 64, 16, 32, False)])
 def test_normalise_on_load_equals_the_materialised_tensor(cuda, monkeypatch, cin, cout, H, W, up):
-    """ffa_conv2d_pro / ffa_conv_wgrad_pro: conv and weight gradient of relu(x * sc + sh) with the normalisation done on
+    """ops.conv2d_pro / ffa_conv_wgrad_pro: conv and weight gradient of relu(x * sc + sh) with the normalisation done on
     the staged input (thin kernels: LDS fix-up of the DMA'd halo; ring16: the same; conv_wgrad_kernel: at the LDS store)
     == the same kernels run on the tensor ffa_bn_apply writes, bit for bit (zero padding applied after the
     normalisation: positive shifts would show otherwise)."""
