@@ -363,6 +363,23 @@ class Checker:
             raise KeyError("operand not produced by HipConv2d.packed or _fusion_slice during the recording")
         return info
 
+    def register_operand(self, pw, weight: torch.Tensor, transpose: bool = False, stride: int = 1, padding: int = 0,
+                         name: str = "?"):
+        """make a hand-packed operand known (ops.pack_conv_weight called directly, as the kernel tests do): pw the
+        PackedWeight, weight the f32 OIHW master it was packed from, transpose / stride / padding those of the layer.
+        The entry is what HipConv2d.packed leaves under the recording; the master is copied, and the operand is held
+        so that its id cannot pass to another object while the checker lives.  -> pw"""
+        if weight.dtype != torch.float32 or weight.dim() != 4:
+            raise ValueError(f"master weight must be f32 OIHW, got {weight.dtype} {tuple(weight.shape)}")
+        O, I, kh, kw = weight.shape
+        want = (I if transpose else O, kh, kw, 1 if transpose else int(stride))
+        if (pw.rows_real, pw.kh, pw.kw, pw.stride) != want:
+            raise ValueError(f"operand (rows, kh, kw, stride) = {(pw.rows_real, pw.kh, pw.kw, pw.stride)} was not packed "
+                             f"from this weight as stated: {want}")
+        self.weights[id(pw)] = {"name": name, "transpose": bool(transpose), "weight": weight.detach().clone(),
+                                "stride": int(stride), "padding": int(padding), "operand": pw}
+        return pw
+
     def _chunks(self, B: int):
         c = max(1, self.chunk)
         return [(b, min(B, b + c)) for b in range(0, B, c)]

@@ -1009,3 +1009,154 @@ def test_too_many_open_values_is_a_failed_check():
     ck = Checker("full", chunk=1)  # the label is decided all the same: the lowest index
     ck.predict_u8({"op": "predict_u8"}, z, 2, "argmax", None, torch.zeros(1, 8, 8, dtype=torch.uint8))
     assert [r.ok for r in ck.results] == [True] and ck.ties["predict_u8"] == 64
+
+
+# --------------------------------------------------------------------------------------------------
+# the shapes of tests/test_conv_edges_gpu.py: what its checks catch and the per-tensor bound did not
+
+def _bf16_conv(x, w, stride=1, pad=1):
+    """an honest bf16 kernel: the f32 convolution of the bf16 operands, rounded once"""
+    return F.conv2d(x, w, stride=stride, padding=pad)
+
+
+def _edge_layer(seed, cin, cout, k, hw, batch=2):
+    g = torch.Generator().manual_seed(seed)
+    x = _bf(torch.randn(batch, cin, *hw, generator=g))
+    w = _bf(torch.randn(cout, cin, k, k, generator=g) * (cin * k * k) ** -0.5)
+    return g, x, w
+
+
+def _verdicts(run, y, ref_nchw, real=None):
+    """(failed checks of the checker, whether max|ref| * 2^-7 -- the bound of tests/test_kernels_gpu.py and its
+    siblings for bf16 -- passes the same tensor) for the stored NHWC result y against the f32 reference"""
+    ck = Checker("full", chunk=1)
+    run(ck, y)
+    got = _nchw(y[..., :real].float()) if real else _nchw(y.float())
+    err, old = (got - ref_nchw).abs().max().item(), ref_nchw.abs().max().item() * 2.0 ** -7
+    return [r for r in ck.results if not r.ok], err <= old, ck, (err, old)
+
+
+def test_register_operand_makes_a_hand_packed_operand_known_to_the_adapters():
+    """Checker.register_operand: the entry HipConv2d.packed leaves under a recording, for an operand packed by hand.
+    The adapters of the Recorder then take the call: an honest result passes, a nonzero pad channel is flagged."""
+    from flairhip import ops
+    g, x, w = _edge_layer(81, 30, 19, 3, (3, 5))
+    pw = ops.PackedWeight(torch.empty(0, dtype=torch.bfloat16), 32, 19, 32, 32 | insitu.BCO_THIN, 3, 3, 1, 30)
+    rec = insitu.Recorder(mode="full", chunk=1)
+    rec._ops = ops
+    with pytest.raises(KeyError):
+        rec._weight(pw)
+    assert rec.register_operand(pw, w, transpose=False, stride=1, padding=1, name="head") is pw
+    info = rec._weight(pw)
+    assert (info["name"], info["transpose"], info["stride"], info["padding"]) == ("head", False, 1, 1)
+    assert torch.equal(info["weight"], w) and info["weight"] is not w and info["operand"] is pw
+    for bad in (dict(transpose=True), dict(stride=2)):  # rows / stride of the operand contradict the statement
+        with pytest.raises(ValueError, match="not packed"):
+            rec.register_operand(pw, w, **{"transpose": False, "stride": 1, "padding": 1, **bad})
+    with pytest.raises(ValueError, match="f32 OIHW"):
+        rec.register_operand(pw, w.double(), stride=1, padding=1)
+    pwt = ops.PackedWeight(torch.empty(0, dtype=torch.bfloat16), 32, 30, 32, 32 | insitu.BCO_THIN, 3, 3, 1, 19)
+    rec.register_operand(pwt, w, transpose=True, stride=1, padding=1)  # rows = input channels, stride 1
+
+    xs = _store(x, 32)
+    y = _store(_bf16_conv(x, w), 32)
+    args = dict(x=xs, w=pw, pad=1, dil=1, residual=None, bias=None, relu=False, stats=None)
+    rec._op_conv2d({"op": "conv2d", "call": 0}, args, args, y)
+    assert rec.results and all(r.ok for r in rec.results), [r.line() for r in rec.failures()]
+    assert {r["what"] for r in rec.results} == {"out", "out pad channels"}
+    y[1, 2, 4, 25] = 2.0 ** -20  # 19 classes in a pitch of 32: channel 25 feeds the next layer's k loop
+    rec._op_conv2d({"op": "conv2d", "call": 1}, args, args, y)
+    assert [r["what"] for r in rec.failures()] == ["out pad channels"] and rec.failures()[0]["where"] == (1, 2, 4, 6)
+    ref = _bf16_conv(x, w)
+    assert (_nchw(y[..., :19].float()) - ref).abs().max() <= ref.abs().max() * 2.0 ** -7  # the old bound never looked there
+
+
+EDGE_HONEST = [  # cin, cout, k, stride, pad, input size
+    (192, 64, 3, 1, 1, (9, 33)), (64, 128, 3, 2, 1, (17, 35)), (64, 128, 3, 2, 1, (18, 34)), (64, 128, 1, 2, 0, (17, 35)),
+    (64, 64, 3, 1, 1, (3, 5)), (64, 64, 3, 1, 1, (1, 1)), (5, 64, 7, 2, 3, (19, 35)),
+]
+
+
+@pytest.mark.parametrize("cin,cout,k,stride,pad,hw", EDGE_HONEST)
+def test_honest_bf16_results_pass_at_the_shapes_of_the_edge_grid(cin, cout, k, stride, pad, hw):
+    """forward, input gradient (the dil = 2 call where stride = 2, asked for the odd and the even input size) and weight
+    gradient: worst error / bound stays below 1, and near the half ulp of the one rounding for the stored tensors"""
+    g, x, w = _edge_layer(83 + cin + hw[1], cin, cout, k, hw)
+    ck = Checker("full", chunk=1)
+    y = _bf16_conv(x, w, stride, pad)
+    ck.conv_forward({"op": "conv2d"}, _store(x), _f64(w), stride, pad, _store(y))
+    dy = _bf(torch.randn(y.shape, generator=g))
+    dx = conv2d_input(x.shape, w, dy, stride=stride, padding=pad)
+    ck.conv_dgrad({"op": "conv2d"}, _store(dy), _f64(w), stride, pad, _store(dx))
+    dw = conv2d_weight(x, w.shape, dy, stride=stride, padding=pad)
+    ck.conv_wgrad({"op": "conv_wgrad"}, _store(x), _store(dy), k, k, stride, pad, dw)
+    assert [r["what"] for r in ck.results] == ["out", "dx", "dW"]
+    assert all(r.ok for r in ck.results), [r.line() for r in ck.results if not r.ok]
+    assert all(r["worst"] <= 0.75 for r in ck.results), [r.line() for r in ck.results]
+
+
+def _fault_partial_sums():
+    """192 -> 64 at 9 x 33: the partial sum of each half of the input channels rounded to bf16 before they are added"""
+    _, x, w = _edge_layer(85, 192, 64, 3, (9, 33))
+    y = _bf(_bf16_conv(x[:, :96], w[:, :96])) + _bf(_bf16_conv(x[:, 96:], w[:, 96:]))
+    return (lambda ck, o: ck.conv_forward({"op": "conv2d"}, _store(x), _f64(w), 1, 1, o)), _store(y), _bf16_conv(x, w)
+
+
+def _fault_residual_after_rounding():
+    """64 -> 64 at 17 x 31 with a residual: the convolution is rounded to bf16, then the residual is added"""
+    g, x, w = _edge_layer(87, 64, 64, 3, (17, 31))
+    res = _bf(torch.randn(2, 64, 17, 31, generator=g))
+    y = _bf(_bf16_conv(x, w)) + res
+    return (lambda ck, o: ck.conv_forward({"op": "conv2d"}, _store(x), _f64(w), 1, 1, o, residual=_store(res))), \
+        _store(y), _bf16_conv(x, w) + res
+
+
+def _fault_dil2_last_row(hw):
+    """the dil = 2 input gradient of 64 -> 128 (3 x 3 stride 2) for an input of size hw: the contribution of the last row
+    of dy never arrives (at an odd height it feeds the last two input rows, at an even one the last three)"""
+    g, x, w = _edge_layer(89 + hw[0], 64, 128, 3, hw)
+    ho, wo = (hw[0] - 1) // 2 + 1, (hw[1] - 1) // 2 + 1
+    dy = _bf(torch.randn(2, 128, ho, wo, generator=g))
+    cut = dy.clone()
+    cut[:, :, -1] = 0
+    dx = conv2d_input(x.shape, w, cut, stride=2, padding=1)
+    return (lambda ck, o: ck.conv_dgrad({"op": "conv2d"}, _store(dy), _f64(w), 2, 1, o)), _store(dx), \
+        conv2d_input(x.shape, w, dy, stride=2, padding=1)
+
+
+def _fault_ragged_column_group():
+    """192 -> 64 at 9 x 33: in the ragged last column of tiles (output column 32) input channels 64..95 are read from
+    the column before"""
+    _, x, w = _edge_layer(91, 192, 64, 3, (9, 33))
+    xs = x.clone()
+    xs[:, 64:96] = torch.roll(x[:, 64:96], 1, dims=3)
+    y = _bf16_conv(x, w)
+    y[..., 32] = _bf16_conv(xs, w)[..., 32]
+    return (lambda ck, o: ck.conv_forward({"op": "conv2d"}, _store(x), _f64(w), 1, 1, o)), _store(y), _bf16_conv(x, w)
+
+
+# fault -> (builder, does max|ref| * 2^-7 pass the faulty tensor?)
+EDGE_FAULTS = {
+    "bf16 partial sums of two channel halves": (_fault_partial_sums, True),
+    "residual added after the rounding": (_fault_residual_after_rounding, True),
+    "dil = 2 dgrad drops the last row of dy, odd out_hw": (lambda: _fault_dil2_last_row((17, 35)), False),
+    "dil = 2 dgrad drops the last row of dy, even out_hw": (lambda: _fault_dil2_last_row((18, 34)), False),
+    "one channel group of the ragged column read one column off": (_fault_ragged_column_group, False),
+}
+
+
+@pytest.mark.parametrize("fault", sorted(EDGE_FAULTS))
+def test_planted_fault_at_an_edge_shape_is_flagged_and_what_the_per_tensor_bound_said(fault):
+    """every fault is flagged by the elementwise float64 bound; the second column of EDGE_FAULTS keeps on file which of
+    them the bound of the stand-alone kernel tests (one number per tensor) let through: the precision detours -- the
+    reason tests/test_conv_edges_gpu.py compares through tests/insitu.py"""
+    build, old_passes = EDGE_FAULTS[fault]
+    run, y, ref = build()
+    honest_fails, honest_old, ck, _ = _verdicts(run, _store(ref), ref)
+    assert not honest_fails and honest_old and ck.results[0]["worst"] <= 0.75, "the honest result must pass both bounds"
+    fails, old, ck, (err, bound) = _verdicts(run, y, ref)
+    print(f"\n{fault}: {fails[0]['fail'] if fails else 0} of {ck.results[0]['n']} elements flagged, worst error / bound "
+          f"{ck.results[0]['worst']:.3g}; max error {err:.4g} against max|ref| * 2^-7 = {bound:.4g}: "
+          f"{'passes' if old else 'fails'} the per-tensor bound")
+    assert fails and fails[0]["what"] in ("out", "dx"), "the elementwise bound must flag the fault"
+    assert old == old_passes

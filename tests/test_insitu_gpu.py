@@ -130,6 +130,16 @@ def test_every_kernel_of_the_bf16_step_at_2x512_with_low_grid_caps_matches_float
     _report_and_assert(task, rec, t0)
 
 
+def test_every_kernel_of_the_bf16_step_at_3x96x160_matches_float64(cuda):
+    """non-square, odd batch: the maps are 48 x 80, 24 x 40, 12 x 20, 6 x 10 and 3 x 5, so every ring16, thin, stem and
+    weight-gradient launch has ragged tiles and the deepest levels are smaller than one tile (the fp32 step has this
+    case in tests/test_insitu_fp32_gpu.py; at 512 x 512 every map is a power of two and every tile is full)"""
+    t0 = time.perf_counter()
+    _assert_default_switches()
+    task, rec, _ = _checked_step(3, "full", seed=43, chunk=1, hw=(96, 160))
+    _report_and_assert(task, rec, t0)
+
+
 def test_every_kernel_of_the_bf16_step_at_32x512_matches_float64_projected(cuda):
     t0 = time.perf_counter()
     _assert_default_switches()
