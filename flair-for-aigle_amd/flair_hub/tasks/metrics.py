@@ -1,7 +1,8 @@
 """Small device-side stand-ins for the two torchmetrics classes the reference's SegmentationTask
 uses (flair_hub/tasks/tasks_module.py:63-93): MulticlassJaccardIndex and MeanMetric.  Metric plumbing is
 outside the measured hot path; these exist so the task module keeps its logging behaviour without
-torchmetrics (not installed here).  State is a K x K confusion matrix kept on the device."""
+torchmetrics (not installed here).  State is a K x K confusion matrix kept on the device.  ClassMeanLoss is the epoch
+state of the per-class validation loss the reference logs per batch (:280-300)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -42,6 +43,35 @@ class MulticlassJaccardIndex(nn.Module):
 
     def reset(self) -> None:
         self.confmat.zero_()
+
+
+class ClassMeanLoss(nn.Module):
+    """The epoch value of a per-class loss that the reference logs per batch with on_epoch=True
+    (flair_hub/tasks/tasks_module.py:280-300): the mean over the batches, weighted by batch size, of the batch's mean
+    loss over the pixels of a class -- 0 where the batch has no pixel of the class.  State: ``total`` [K] float64 =
+    sum of B * class mean, ``count`` = sum of B; both sum over ranks like MeanMetric's."""
+
+    def __init__(self, num_classes: int):
+        super().__init__()
+        self.num_classes = num_classes
+        self.register_buffer("total", torch.zeros(num_classes, dtype=torch.float64), persistent=False)
+        self.register_buffer("count", torch.zeros((), dtype=torch.float64), persistent=False)
+
+    @torch.no_grad()
+    def update(self, class_nll: torch.Tensor, class_count: torch.Tensor, batch_size: int) -> None:
+        """class_nll [K] float64 = per-class sums of the batch's pixel losses, class_count [K] int64 = pixels per class
+        (ops.eval_stats); no host synchronisation"""
+        mean = torch.where(class_count > 0, class_nll / class_count.clamp(min=1).to(torch.float64),
+                           torch.zeros_like(class_nll))
+        self.total += batch_size * mean
+        self.count += batch_size
+
+    def compute(self) -> torch.Tensor:
+        return self.total / self.count.clamp(min=1)
+
+    def reset(self) -> None:
+        self.total.zero_()
+        self.count.zero_()
 
 
 class MeanMetric(nn.Module):

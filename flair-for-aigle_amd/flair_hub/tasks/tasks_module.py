@@ -12,6 +12,9 @@ What changes on the hot path (same results, fewer passes over B x K x H x W):
     targets are accepted directly
   * the NaN/Inf check of :156/:204 costs a host sync per step in the reference; here the flag stays on the
     device and is inspected at epoch end unless hyperparams.check_loss_every_step is set.
+  * the per-class validation loss (reference :280-300: a second forward per task and K host reads per batch) and the
+    per-class validation IoU state come from one more pass over the logits the step already produced
+    (ops.eval_stats), accumulated on the device and read once per task at epoch end.
 """
 from __future__ import annotations
 
@@ -22,8 +25,8 @@ import torch
 import torch.nn as nn
 
 from flairhip import ops
-from flairhip.nn import HipCrossEntropyLoss
-from flair_hub.tasks.metrics import MeanMetric, MulticlassJaccardIndex
+from flairhip.nn import LOGIT_PITCH, HipCrossEntropyLoss, to_nhwc
+from flair_hub.tasks.metrics import ClassMeanLoss, MeanMetric, MulticlassJaccardIndex
 
 logger = logging.getLogger(__name__)
 
@@ -57,6 +60,8 @@ class SegmentationTask(nn.Module):
                                   for t in labels})
 
         self.train_metrics, self.val_metrics, self.val_iou = jaccard("weighted"), jaccard("weighted"), jaccard(None)
+        self.val_class_loss = nn.ModuleDict({t.replace(".", "_"): ClassMeanLoss(len(lcfg[t]["value_name"]))
+                                             for t in labels})
         self.train_loss, self.val_loss = MeanMetric(), MeanMetric()
         self.register_buffer("_invalid_loss_flag", torch.zeros((), dtype=torch.int32), persistent=False)
 
@@ -77,7 +82,8 @@ class SegmentationTask(nn.Module):
     def forward(self, batch, apply_mod_dropout: bool = False):
         return self.model(batch, apply_mod_dropout)
 
-    def step(self, batch, training: bool = False):
+    def step(self, batch, training: bool = False, logits_out=None):
+        """-> (loss, {task: predictions}, {task: targets}); ``logits_out``: a dict that receives {task: logits}"""
         apply_mod_dropout = self.mod_dropout if training else False
         dict_logits_task, dict_logits_aux = self.forward(batch, apply_mod_dropout)
 
@@ -102,6 +108,8 @@ class SegmentationTask(nn.Module):
             loss_sum = loss_sum + task_weight * (main_loss + aux_loss)
             all_preds[task] = main_preds
             all_targets[task] = targets
+            if logits_out is not None:
+                logits_out[task] = logits
         return loss_sum, all_preds, all_targets
 
     @staticmethod
@@ -160,34 +168,69 @@ class SegmentationTask(nn.Module):
 
     def validation_step(self, batch, batch_idx):
         batch = self._without_aug(batch)  # validation never augments
-        loss, all_preds, all_targets = self.step(batch, training=False)
+        logits = {}
+        loss, all_preds, all_targets = self.step(batch, training=False, logits_out=logits)
         self.val_loss.update(loss)
         for task in all_preds:
             key = task.replace(".", "_")
             self.val_metrics[key].update(all_preds[task], all_targets[task])
-            self.val_iou[key].update(all_preds[task], all_targets[task])
+            self._update_class_stats(key, logits[task], all_preds[task], all_targets[task])
         return loss
+
+    @torch.no_grad()
+    def _update_class_stats(self, key, logits, preds, targets):
+        """The per-class state of a validation batch from one pass over the step's own logits (no second forward): the
+        confusion counts behind val_iou_* go straight into self.val_iou[key].confmat -- the integers its own update()
+        would add, the kernel's labels being the loss kernel's byte for byte -- and the batch's class means of
+        -log softmax[target] into self.val_class_loss[key].  Everything stays on the device."""
+        metric = self.val_iou[key]
+        nhwc = getattr(logits, "_ffa_nhwc", None)
+        if nhwc is None:  # a model outside flairhip.nn: NCHW f32 logits, laid out as HipCrossEntropyLoss.forward does
+            nhwc = to_nhwc(logits.detach().float().contiguous(), torch.float32, LOGIT_PITCH)
+        _, class_nll, class_count = ops.eval_stats(nhwc, targets, metric.num_classes, confmat=metric.confmat,
+                                                   want_pred=False)
+        self.val_class_loss[key].update(class_nll, class_count, int(targets.shape[0]))
 
     def on_validation_epoch_end(self):
         self._report_invalid_loss()
-        self._sync_metrics(list(self.val_metrics.values()) + list(self.val_iou.values()) + [self.val_loss])
+        self._sync_metrics(list(self.val_metrics.values()) + list(self.val_iou.values()) +
+                           list(self.val_class_loss.values()) + [self.val_loss])
         self.log("val_loss", self.val_loss.compute())
         mious = []
         for task in self.val_metrics:
             miou = self.val_metrics[task].compute()
             mious.append(float(miou))
             self.log(f"val_miou_{task.split('-')[-1]}", miou)
+            self._log_per_class(task)
             self.val_metrics[task].reset()
             self.val_iou[task].reset()
+            self.val_class_loss[task].reset()
         self.log("val_miou", sum(mious) / max(len(mious), 1))
         val_loss = self._logged.get("val_loss")
         self.val_loss.reset()
         if self._scheduler_type == "cycle_then_plateau" and self._using_plateau and val_loss is not None:
             self._plateau_scheduler.step(val_loss)
 
+    def _log_per_class(self, key):
+        """val_loss_class_<task>_<i>_<name> (reference :280-300: the mean over the batches, weighted by batch size, of
+        the batch's mean loss over the pixels of class i, 0 where the batch has none) and val_iou_<task>_<i>_<name>
+        (:318-335, NaN -> 0): one device-to-host copy of 2 K numbers per task, names and values assembled on the
+        host."""
+        task = next(t for t in self.config["labels"] if t.replace(".", "_") == key)
+        names = self.config["labels_configs"][task]["value_name"]
+        iou = torch.nan_to_num(self.val_iou[key].compute(), nan=0.0)  # float32, as logged by the reference
+        state = torch.cat([self.val_class_loss[key].compute(), iou.to(torch.float64)]).cpu().tolist()
+        k = len(state) // 2
+        short = key.split("-")[-1]
+        for i in range(k):
+            name = names.get(i, f"class_{i}") if hasattr(names, "get") else names[i]
+            self.log(f"val_loss_class_{short}_{i}_{name}", state[i])
+            self.log(f"val_iou_{short}_{i}_{name}", state[k + i])
+
     def predict_step(self, batch, batch_idx=0, dataloader_idx=0):
         """{'preds_<task>': argmax(softmax(logits))} -- uint8 class maps straight from the logits kernel."""
         dict_logits_task, _ = self.forward(self._without_aug(batch), apply_mod_dropout=False)  # nor does prediction
+        self._last_logits = dict_logits_task  # flair_hub.writer.PredictionWriter reads them: no second forward
         out = {}
         for task, logits in dict_logits_task.items():
             nhwc = getattr(logits, "_ffa_nhwc", None)

@@ -113,7 +113,8 @@ class HipTrainer:
 
     def __init__(self, accelerator: str = "gpu", devices: int = 1, strategy: str = "auto", num_nodes: int = 1,
                  max_epochs: int = 1, default_root_dir: Optional[str] = None, monitor: str = "val_miou",
-                 monitor_mode: str = "max", max_steps: Optional[int] = None, hip_graph: bool = False, **unused):
+                 monitor_mode: str = "max", max_steps: Optional[int] = None, hip_graph: bool = False,
+                 callbacks: Optional[Iterable] = None, **unused):
         if accelerator not in ("gpu", "cuda", "auto"):
             raise RuntimeError("HipTrainer drives the MI355X path only (accelerator='gpu'); the CPU restatement "
                                "lives in oracle/ and is test infrastructure")
@@ -124,6 +125,9 @@ class HipTrainer:
         self.hip_graph = bool(hip_graph)
         self.default_root_dir = default_root_dir
         self.monitor, self.monitor_mode = monitor, monitor_mode
+        # prediction writers (flair_hub.writer.PredictionWriter): predict() calls their write_on_batch_end after every
+        # predict_step and their on_predict_epoch_end at the end, as Lightning does for a BasePredictionWriter
+        self.callbacks = list(callbacks or [])
         local = int(os.environ.get("LOCAL_RANK", "0"))
         # FFA_DIST_BACKEND=gloo rehearses several ranks on a one-GPU box: they then share cuda:0
         ndev = max(torch.cuda.device_count(), 1)
@@ -276,11 +280,18 @@ class HipTrainer:
             dataloaders = datamodule.predict_dataloader()
         dataloaders = self._shard(dataloaders, shuffle=False, drop_last=False)  # every rank predicts its own share
         model.eval()
+        writers = [c for c in self.callbacks if hasattr(c, "write_on_batch_end")]
         outs = []
         for i, batch in enumerate(dataloaders):
-            out = model.predict_step(_to_device(batch, self.device), i)
+            dev_batch = _to_device(batch, self.device)
+            out = model.predict_step(dev_batch, i)
+            for w in writers:
+                w.write_on_batch_end(self, model, out, None, dev_batch, i, 0)
             if return_predictions:
                 outs.append(out)
+        for c in self.callbacks:
+            if hasattr(c, "on_predict_epoch_end"):
+                c.on_predict_epoch_end(self, model)
         return outs
 
 
@@ -301,7 +312,18 @@ def train(config: Dict[str, Any], data_module, seg_module, out_dir: str) -> HipT
 
 
 def predict(config: Dict[str, Any], data_module, seg_module, out_dir: str):
+    """Same role as the reference's predict() (:111-136): a PredictionWriter writes PRED_<label file> rasters
+    (tasks.write_files), accumulates the confusion matrix against the label files and leaves metrics.json and
+    confmat_predict.npy under out_dir.  ``tasks.metrics_only`` without ``tasks.predict`` scores the rasters of an
+    earlier run instead of predicting.  -> the writer (its accumulated_confmats hold the matrices)"""
+    from flair_hub.writer.prediction_writer import PredictionWriter
+    writer = PredictionWriter(config, output_dir=os.path.join(out_dir), write_interval="batch")
+    tasks = config.get("tasks", {})
+    if tasks.get("metrics_only", False) and not tasks.get("predict", True):
+        writer.load_predictions_and_compute_metrics()
+        return writer
     hw = config.get("hardware", {})
     trainer = HipTrainer(accelerator=hw.get("accelerator", "gpu"), devices=hw.get("gpus_per_node", 1),
-                         strategy=hw.get("strategy", "auto"), num_nodes=hw.get("num_nodes", 1))
-    return trainer.predict(seg_module, datamodule=data_module, return_predictions=True)
+                         strategy=hw.get("strategy", "auto"), num_nodes=hw.get("num_nodes", 1), callbacks=[writer])
+    trainer.predict(seg_module, datamodule=data_module, return_predictions=False)
+    return writer

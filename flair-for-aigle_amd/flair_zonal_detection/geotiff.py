@@ -529,7 +529,8 @@ class GeoTiffWriter(ArrayRaster):
 
     def __init__(self, path: str, width: int, height: int, count: int, left: float, top: float, res,
                  crs: Optional[str] = None, dtype=np.uint8, compress: Optional[str] = "lzw", geokeys: Sequence[int] = (),
-                 geoascii: str = "", geodoubles: Sequence[float] = (), nodata=None, scratch_above: int = 2 << 30):
+                 geoascii: str = "", geodoubles: Sequence[float] = (), nodata=None, scratch_above: int = 2 << 30,
+                 georeferenced: bool = True):
         nbytes = int(count) * int(height) * int(width) * np.dtype(dtype).itemsize
         self._scratch = None
         if nbytes > scratch_above:  # keep very large class-probability rasters out of RAM
@@ -547,6 +548,7 @@ class GeoTiffWriter(ArrayRaster):
         self.compress = (compress or "none").lower()
         self.geokeys = tuple(int(v) for v in geokeys)
         self.geoascii, self.geodoubles, self.nodata = geoascii, tuple(geodoubles), nodata
+        self.georeferenced = bool(georeferenced)  # False: a plain TIFF, no GeoTIFF tag at all
         if not self.geokeys and crs and str(crs).upper().startswith("EPSG:"):
             self.geokeys = _geokeys_for_epsg(int(str(crs).split(":")[1]))
 
@@ -588,9 +590,10 @@ class GeoTiffWriter(ArrayRaster):
             offs, cnts, pos = _write_tiles(f, f.tell(), self.data, B, self.compress)
             _check_classic_size(big, pos)
             # ---- the IFD, after the pixel data ----
-            entries = _image_entries(self.data, B, self.compress, offs, cnts, big) + \
-                _geo_entries(self._res, self._yres, self.left, self.top, self.geokeys, self.geodoubles, self.geoascii,
-                             self.nodata)
+            entries = _image_entries(self.data, B, self.compress, offs, cnts, big)
+            if self.georeferenced:
+                entries += _geo_entries(self._res, self._yres, self.left, self.top, self.geokeys, self.geodoubles,
+                                        self.geoascii, self.nodata)
             f.write(_pack_ifd(entries, pos, big))
             f.seek(8 if big else 4)
             f.write(struct.pack("<Q" if big else "<I", pos))

@@ -197,6 +197,12 @@ SIGNATURES = {
     "ffa_probe_mfma": (_i, [_p, _p, _p, _i, _p]),
 }
 
+# the prototypes of include/flairhip_eval.h (the evaluation stage), which include/flairhip.h brings along
+EVAL_SIGNATURES = {
+    "ffa_eval_stats_workspace_bytes": (_ll, []),
+    "ffa_eval_stats": (_i, [_i, _p, _p, _ll, _i, _i, _p, _p, _p, _p, _p, _ll, _p]),
+}
+
 _lib = None
 
 
@@ -214,7 +220,7 @@ def load() -> C.CDLL:
     # every launch fails with "no ROCm-capable device is detected"
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args

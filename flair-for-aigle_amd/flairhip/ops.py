@@ -1061,6 +1061,43 @@ def confusion_matrix_update(counts: torch.Tensor, pred: torch.Tensor, target: to
                                       counts.data_ptr(), _stream()), "confusion_matrix")
 
 
+def eval_stats(logits_nhwc: torch.Tensor, targets_u8: torch.Tensor, num_classes: int,
+               confmat: Optional[torch.Tensor] = None, want_pred: bool = True, want_class_nll: bool = True):
+    """One pass over NHWC logits [B,H,W,Cp] and uint8 targets [B,H,W] for everything an evaluation needs.
+
+    -> (pred uint8 like the targets or None, class_nll [K] float64 or None, class_count [K] int64 or None):
+    pred = the first maximum over the K classes (softmax_ce's pred, byte for byte); class_count[k] = pixels with target
+    k; class_nll[k] = the sum over those pixels of -log softmax[k], unweighted, in a fixed order (equal inputs give equal
+    bytes).  ``confmat`` (int64 [K, K] on the logits' device) is updated in place: confmat[target, pred] += 1.  A target
+    >= K contributes to nothing.  No host synchronisation.
+    """
+    lib = _l.load()
+    _chk_nhwc(logits_nhwc, "logits")
+    if targets_u8.dtype != torch.uint8 or not targets_u8.is_contiguous():
+        raise ValueError("eval_stats: targets must be contiguous uint8 class indices")
+    cp = logits_nhwc.shape[-1]
+    npix = logits_nhwc.numel() // cp
+    if targets_u8.numel() != npix:
+        raise ValueError("eval_stats: target / logit pixel count mismatch")
+    dev = logits_nhwc.device
+    if targets_u8.device != dev:
+        raise ValueError(f"eval_stats: targets on {targets_u8.device}, logits on {dev}")
+    k = int(num_classes)
+    if confmat is not None and not (confmat.dtype == torch.int64 and tuple(confmat.shape) == (k, k)
+                                    and confmat.is_contiguous() and confmat.device == dev):
+        raise ValueError(f"eval_stats: confmat must be a contiguous int64 [{k}, {k}] tensor on {dev}")
+    pred = torch.empty(targets_u8.shape, dtype=torch.uint8, device=dev) if want_pred else None
+    nll = cnt = ws = None
+    if want_class_nll:
+        nll = torch.empty(k, dtype=torch.float64, device=dev)
+        cnt = torch.empty(k, dtype=torch.int64, device=dev)
+        ws = workspace(lib.ffa_eval_stats_workspace_bytes(), dev, "eval_stats")
+    _l.check(lib.ffa_eval_stats(_dt(logits_nhwc), logits_nhwc.data_ptr(), targets_u8.data_ptr(), npix, k, cp, _ptr(pred),
+                                _ptr(confmat), _ptr(nll), _ptr(cnt), _ptr(ws), 0 if ws is None else ws.numel(),
+                                _stream()), "eval_stats")
+    return pred, nll, cnt
+
+
 # --------------------------------------------------------------------------------------------------
 # host-side tile bookkeeping (no GPU involved)
 

@@ -505,6 +505,9 @@ int ffa_onehot_to_index(const float* onehot, uint8_t* idx, int B, int K, int H, 
 /* counts[target][pred] += 1 (int64, accumulating): the IoU-metric state of tasks_module.py:210-212 */
 int ffa_confusion_matrix(const uint8_t* pred, const uint8_t* target, long long n, int K, long long* counts,
                          ffa_stream_t stream);
+/* The evaluation entry points (labels, confusion counts and per-class loss sums from one pass over the logits) are
+ * declared in flairhip_eval.h, which this header brings along. */
+#include "flairhip_eval.h"
 
 /* ---- host-side tile bookkeeping, bit-exact with the reference's float64 arithmetic
  *      (flair_zonal_detection/slicing.py:51-112, flair_zonal_detection/inference.py:318-335) -------- */
