@@ -232,6 +232,15 @@ class FLAIR_HUB_Model(nn.Module):
         ``aug`` (batch['AUG'], uint8 [B] on the device): the training augmentation's per-sample flip / rotation codes
         (flairhip.augment), applied by the same pass."""
         enc = self.encoders[mod].seg_model
+        if mod == "DEM_ELEV" and x.ndim == 4 and x.shape[1] == 2 and enc.in_channels == 1 and norm is not None and \
+                self.config["modalities"].get("pre_processings", {}).get("calc_elevation", False):
+            # the raw 2-band patch (surface model, terrain model): calc_elevation happens in the layout pass -- the
+            # batch read as a store of B samples with index = arange(B) (csrc/sample_gather.hip)
+            self._check_input_plane(x)
+            norm = norm.to(x.device, torch.float32)
+            return ops.gather_layout(x.contiguous(), self._arange(x.shape[0], x.device), self.compute_dtype, aug,
+                                     norm[0].contiguous(), norm[1].contiguous(),
+                                     getattr(enc, "input_pitch", ops.pad_channels(1)), ops.ELEV_DIFF)
         if x.ndim != 4 or x.shape[1] != enc.in_channels:
             raise ValueError(f"batch['{mod}'] must be [B,{enc.in_channels},H,W], got {tuple(x.shape)}")
         if x.shape[-1] % 32 or x.shape[-2] % 32:
@@ -255,6 +264,40 @@ class FLAIR_HUB_Model(nn.Module):
             return ops.d4_layout(x.contiguous(), self.compute_dtype, aug,
                                  cp=getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
         return hnn.to_nhwc(x, self.compute_dtype, getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
+
+    @staticmethod
+    def _check_input_plane(x: torch.Tensor) -> None:
+        if x.shape[-1] % 32 or x.shape[-2] % 32:
+            raise RuntimeError(f"input height and width must be divisible by 32, got {tuple(x.shape[-2:])}")
+        if not x.is_cuda:
+            raise RuntimeError("FLAIR_HUB_Model (libflairhip) runs on an MI355X only: move the batch to cuda")
+
+    def _arange(self, n: int, device) -> torch.Tensor:
+        """int32 [n] = 0..n-1 on the device: the index vector of a streamed batch read as a store of its own samples"""
+        key = (int(n), str(device))
+        cache = self.__dict__.setdefault("_arange_cache", {})
+        if key not in cache:
+            cache[key] = torch.arange(n, dtype=torch.int32, device=device)
+        return cache[key]
+
+    def attach_store(self, store) -> None:
+        """a flairhip.sample_store.SampleStore: batches that carry 'INDEX' (int32 [B]) instead of image tensors are
+        gathered from it.  The store is held here, not in the batch: a captured step clones what is in the batch."""
+        self.__dict__["_store"] = store
+
+    @property
+    def store(self):
+        return self.__dict__.get("_store")
+
+    def _store_nhwc(self, mod: str, index: torch.Tensor, aug) -> torch.Tensor:
+        store, enc = self.store, self.encoders[mod].seg_model
+        if mod not in store.inputs:
+            raise KeyError(f"batch['INDEX']: the attached sample store holds no {mod}")
+        if store.channels(mod) != enc.in_channels:
+            raise ValueError(f"the store's {mod} gives {store.channels(mod)} channels, the encoder takes {enc.in_channels}")
+        self._check_input_plane(store.inputs[mod])
+        return store.input_nhwc(mod, index, self.compute_dtype, aug,
+                                getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
 
     def modality_dropout(self, feature_maps: Dict[str, list], modalities_dropout_dict: Dict[str, float]):
         """Reference :328-352: with probability ``modalities_dropout_dict[mod]`` the modality's feature maps are
@@ -292,8 +335,18 @@ class FLAIR_HUB_Model(nn.Module):
         # zero label for that purpose -- fall back to the input size when no label rides along
         # (the reference passes the int shape[-1], i.e. assumes square tiles; both dims are kept here, which is
         # the same thing for the square tiles it is used with)
+        # a batch of the resident path names its samples by index into the attached store and carries no image
+        index = batch.get("INDEX")
+        store = self.store if index is not None else None
+        if index is not None:
+            if store is None:
+                raise RuntimeError("batch['INDEX'] needs a sample store: call attach_store(store) first")
+            index = index.to(store.device, torch.int32)
         if labels and labels[0] in batch:
             img_size = tuple(batch[labels[0]].shape[-2:])
+        elif store is not None:
+            ref = store.labels[labels[0]] if labels and labels[0] in store.labels else store.inputs[first_mod]
+            img_size = tuple(ref.shape[-2:])
         else:
             img_size = tuple(batch[first_mod].shape[-2:])
 
@@ -301,7 +354,7 @@ class FLAIR_HUB_Model(nn.Module):
         # task applies the same codes to the labels); without the key nothing changes
         aug = batch.get("AUG")
         if aug is not None:
-            aug = aug.to(batch[first_mod].device, torch.uint8)
+            aug = aug.to(store.device if store is not None else batch[first_mod].device, torch.uint8)
 
         logits_tasks: Dict[str, torch.Tensor] = {}
         logits_aux: Dict[str, torch.Tensor] = {}
@@ -323,7 +376,9 @@ class FLAIR_HUB_Model(nn.Module):
         scores: Dict[str, torch.Tensor] = {}  # class scores of the time-series branches (NHWC)
         for mod, encoder in self.encoders.items():
             if mod in self.mono_keys:
-                fmaps[mod] = encoder.seg_model(self._input_nhwc(batch[mod], mod, batch.get(mod + "_NORM"), aug))
+                x = self._store_nhwc(mod, index, aug) if store is not None and mod not in batch else \
+                    self._input_nhwc(batch[mod], mod, batch.get(mod + "_NORM"), aug)
+                fmaps[mod] = encoder.seg_model(x)
                 if self.aux_losses.get(mod):
                     for task in labels:
                         logits_aux[f"aux_{mod}_{task}"] = decode(self.aux_decoders[f"{mod}__{task}"], fmaps[mod], task)

@@ -32,7 +32,27 @@ def get_input_img_sizes(config: Dict[str, Any], dm: Any, stage: str = "fit") -> 
     dm.setup(stage)
     loader = dm.train_dataloader() if stage == "fit" else dm.predict_dataloader()
     first = next(iter(loader))
+    if "INDEX" in first:  # the resident path: the batch names its samples, the store knows their size
+        sizes = dm.input_img_sizes()
+        return {m: sizes[m] for m, on in config["modalities"]["inputs"].items() if on and m in sizes}
     return {m: first[m][0].shape[-1] for m, on in config["modalities"]["inputs"].items() if on and m in first}
+
+
+def build_data_module(config: Dict[str, Any], dict_train: Optional[dict] = None, dict_val: Optional[dict] = None,
+                      dict_test: Optional[dict] = None):
+    """The data module of a run (reference :12-44).  ``hardware.sample_cache: device`` keeps the decoded train and
+    validation patches resident on the card (``hardware.sample_cache_bytes`` bounds them; default 60 % of the free
+    device memory); both keys are optional and default to the streamed loaders."""
+    from flair_hub.data.datamodule import FlairDataModule
+    assert isinstance(config, dict), "config must be a dictionary"
+    assert isinstance(config["modalities"]["pre_processings"]["use_augmentation"], bool), \
+        "use_augmentation must be a boolean"
+    hw = config.get("hardware", {})
+    return FlairDataModule(config=config, dict_train=dict_train, dict_val=dict_val, dict_test=dict_test,
+                           batch_size=config["hyperparams"]["batch_size"], num_workers=hw.get("num_workers", 0),
+                           drop_last=True, use_augmentations=config["modalities"]["pre_processings"]["use_augmentation"],
+                           cache=str(hw.get("sample_cache", "none") or "none"),
+                           cache_bytes=hw.get("sample_cache_bytes"))
 
 
 class FLAIRLosses:

@@ -82,6 +82,14 @@ class SegmentationTask(nn.Module):
     def forward(self, batch, apply_mod_dropout: bool = False):
         return self.model(batch, apply_mod_dropout)
 
+    def attach_store(self, store) -> None:
+        """hand a flairhip.sample_store.SampleStore to the model: 'INDEX' batches are then gathered from it"""
+        self.model.attach_store(store)
+
+    @property
+    def store(self):
+        return getattr(self.model, "store", None)
+
     def step(self, batch, training: bool = False, logits_out=None):
         """-> (loss, {task: predictions}, {task: targets}); ``logits_out``: a dict that receives {task: logits}"""
         apply_mod_dropout = self.mod_dropout if training else False
@@ -95,8 +103,19 @@ class SegmentationTask(nn.Module):
 
         loss_sum = 0
         all_preds, all_targets = {}, {}
+        index, store = batch.get("INDEX"), self.store
         for task, logits in dict_logits_task.items():
-            targets = HipCrossEntropyLoss.prepare_targets(batch[task].to(self.device), aug)
+            if task not in batch and index is not None and store is not None:
+                # the resident path: labels gathered from the store, with the reference's label rule on the way
+                targets = store.targets(task, index.to(store.device, torch.int32), aug)
+            elif "RAW_LABELS" in batch:
+                # raw label channels of a streamed device_prepare batch (the data module marks it with this key, a
+                # tensor so that it survives into a captured step): the same kernel, reading the batch itself
+                t = batch[task].to(self.device)
+                targets = ops.gather_labels(t.contiguous(), self.model._arange(t.shape[0], t.device),
+                                            len(self.config["labels_configs"][task]["value_name"]), aug)
+            else:
+                targets = HipCrossEntropyLoss.prepare_targets(batch[task].to(self.device), aug)
             crit = self.criterion[task]
             main_loss = crit(logits, targets)
             self._check_for_invalid_loss(main_loss, task)

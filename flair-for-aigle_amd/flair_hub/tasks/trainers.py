@@ -87,8 +87,9 @@ class AugmentedLoader:
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
-        if isinstance(self.loader, ShardedLoader):
-            self.loader.set_epoch(epoch)  # a new shared permutation per epoch, as Lightning does
+        if isinstance(self.loader, ShardedLoader) or getattr(self.loader, "rank_sharded", False):
+            self.loader.set_epoch(epoch)  # a new permutation per epoch (shared by the ranks, as Lightning draws it, or
+            # of the rank's own fixed share for the loaders of flair_hub.data.datamodule)
 
     def rng(self):
         from flairhip.augment import rank_epoch_rng
@@ -99,7 +100,9 @@ class AugmentedLoader:
         rng = self.rng()
         for batch in self.loader:
             if "AUG" not in batch:
-                key = next((k for k in self.keys if k in batch and torch.is_tensor(batch[k])), None)
+                # a batch of the resident path carries the sample indices instead of images and labels
+                key = "INDEX" if torch.is_tensor(batch.get("INDEX")) else \
+                    next((k for k in self.keys if k in batch and torch.is_tensor(batch[k])), None)
                 if key is None:
                     raise KeyError("use_augmentation: the batch holds none of the configured labels / inputs")
                 codes = torch.from_numpy(draw_codes(int(batch[key].shape[0]), rng=rng))
@@ -153,7 +156,16 @@ class HipTrainer:
         """the rank's share of a loader (what Lightning's DistributedSampler injection does under DDP)"""
         if loader is None or self.world_size == 1 or isinstance(loader, ShardedLoader):
             return loader
+        if getattr(loader, "rank_sharded", False):  # flair_hub.data.datamodule: already the rank's fixed share
+            return loader
         return ShardedLoader(loader, self.rank, self.world_size, shuffle=shuffle, seed=self.seed, drop_last=drop_last)
+
+    @staticmethod
+    def _attach_store(model, datamodule) -> None:
+        """a data module with a device-resident sample store yields 'INDEX' batches: the model gathers them from it"""
+        store = getattr(datamodule, "store", None)
+        if store is not None and hasattr(model, "attach_store"):
+            model.attach_store(store)
 
     def fit(self, model, datamodule=None, train_dataloaders: Optional[Iterable] = None,
             val_dataloaders: Optional[Iterable] = None) -> None:
@@ -162,6 +174,7 @@ class HipTrainer:
         model.trainer = self
         if datamodule is not None:
             datamodule.setup("fit")
+            self._attach_store(model, datamodule)
             train_dataloaders = datamodule.train_dataloader()
             val_dataloaders = datamodule.val_dataloader() if hasattr(datamodule, "val_dataloader") else None
         train_dataloaders = self._shard(train_dataloaders, drop_last=True)
@@ -197,7 +210,8 @@ class HipTrainer:
         graphed, graph_sig, loss = None, None, None
         for epoch in range(self.max_epochs):
             model.train()
-            if isinstance(train_dataloaders, (ShardedLoader, AugmentedLoader)):
+            if isinstance(train_dataloaders, (ShardedLoader, AugmentedLoader)) or \
+                    getattr(train_dataloaders, "rank_sharded", False):
                 train_dataloaders.set_epoch(epoch)  # a new shared permutation per epoch, as Lightning does
             for i, batch in enumerate(DevicePrefetcher(train_dataloaders, self.device)):
                 if use_graph and graphed is None and model.global_step >= 2:
@@ -262,6 +276,7 @@ class HipTrainer:
         model.trainer = self
         if datamodule is not None:
             datamodule.setup("validate")
+            self._attach_store(model, datamodule)
             dataloaders = datamodule.val_dataloader()
         dataloaders = self._shard(dataloaders, shuffle=False, drop_last=False)
         model.eval()

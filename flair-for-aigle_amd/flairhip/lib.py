@@ -203,6 +203,12 @@ EVAL_SIGNATURES = {
     "ffa_eval_stats": (_i, [_i, _p, _p, _ll, _i, _i, _p, _p, _p, _p, _p, _ll, _p]),
 }
 
+# the prototypes of include/flairhip_gather.h (the device-resident sample store), which include/flairhip.h brings along
+GATHER_SIGNATURES = {
+    "ffa_gather_layout": (_i, [_i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p]),
+    "ffa_gather_labels_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+}
+
 _lib = None
 
 
@@ -220,7 +226,7 @@ def load() -> C.CDLL:
     # every launch fails with "no ROCm-capable device is detected"
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES, **GATHER_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args

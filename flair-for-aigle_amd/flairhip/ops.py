@@ -805,6 +805,95 @@ def d4_onehot_to_index(onehot: torch.Tensor, codes: torch.Tensor) -> torch.Tenso
     return out
 
 
+ELEV_NONE, ELEV_DIFF, ELEV_STACK = 0, 1, 2  # FFA_ELEV_*
+ELEV_CHANNELS = {ELEV_NONE: None, ELEV_DIFF: 1, ELEV_STACK: 2}
+
+
+def _gather_index(index: torch.Tensor, n: int, dev, what: str) -> torch.Tensor:
+    """the index vector of a gather: int32 [B] on the device.  A host tensor is validated against [0, n) here and
+    copied over; the values of a device tensor stay on the device (a captured step replays with new ones: the kernels
+    clamp, the caller answers for the range)."""
+    if not torch.is_tensor(index) or index.dtype != torch.int32 or index.ndim != 1 or index.numel() < 1:
+        raise ValueError(f"{what}: index must be a non-empty int32 vector")
+    if not index.is_cuda:
+        lo, hi = int(index.min()), int(index.max())
+        if lo < 0 or hi >= n:
+            raise ValueError(f"{what}: index values {lo}..{hi} outside the store's [0, {n})")
+        return index.to(dev, non_blocking=True)
+    if index.device != dev:
+        raise ValueError(f"{what}: index lives on {index.device}, the store on {dev}")
+    return index.contiguous()
+
+
+def gather_layout(store: torch.Tensor, index: torch.Tensor, dtype: torch.dtype, codes: Optional[torch.Tensor] = None,
+                  mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, cp: Optional[int] = None,
+                  elevation: int = ELEV_NONE, group: int = 1) -> torch.Tensor:
+    """A batch from a device-resident sample store: image b of the NHWC result is image ``index[b]`` of the raw
+    contiguous store [N,C,H,W] (uint8 / uint16 / int16 with mean and std, float32 with or without), read through the
+    gather of ``codes[b // group]`` and normalised, in one pass.  ``codes=None`` is the identity and allows H != W.
+    ``elevation``: 0 channels as stored; 1 the one channel z0 - z1 of a 2-band DEM (the reference's calc_elevation);
+    2 the two channels (z0, z0 - z1) (calc_elevation_stack_dsm); mean / std then have one entry per OUTPUT channel.
+    With ``elevation=0`` the result equals ``d4_layout(store[index], ...)`` bit for bit."""
+    lib = _l.load()
+    if not torch.is_tensor(store) or store.dtype not in RAW_SAMPLE_KINDS or store.ndim != 4 or not store.is_cuda or \
+            not store.is_contiguous() or store.numel() == 0:
+        raise ValueError("gather_layout: contiguous device store [N,C,H,W] of uint8 / uint16 / int16 / float32 expected")
+    N, C_, H, W = store.shape
+    if elevation not in ELEV_CHANNELS:
+        raise ValueError(f"gather_layout: unknown elevation mode {elevation}")
+    if elevation != ELEV_NONE and C_ != 2:
+        raise ValueError(f"gather_layout: the elevation modes need the 2 bands of a DEM, got {C_}")
+    c_out = ELEV_CHANNELS[elevation] or C_
+    if codes is not None and H != W:
+        raise ValueError(f"gather_layout: rotations need square planes, got {H} x {W}")
+    index = _gather_index(index, N, store.device, "gather_layout")
+    B = index.numel()
+    if group < 1 or B % group:
+        raise ValueError(f"gather_layout: {B} images do not split into groups of {group}")
+    if (mean is None) != (std is None) or (mean is None and store.dtype != torch.float32):
+        raise ValueError("gather_layout: mean and std come together, and integer samples need them")
+    if mean is not None and (mean.numel() < c_out or std.numel() < c_out or mean.dtype != torch.float32 or
+                             std.dtype != torch.float32 or mean.device != store.device or
+                             std.device != store.device or not mean.is_contiguous() or not std.is_contiguous()):
+        raise ValueError("gather_layout: mean / std must be contiguous f32 device vectors with one entry per output "
+                         "channel")
+    if codes is not None:
+        codes = _d4_codes(codes, B // group, store.device, "gather_layout")
+    cp = pad_channels(c_out) if cp is None else cp
+    if cp % 8 or cp < c_out:
+        raise ValueError(f"gather_layout: channel pitch {cp} must be a multiple of 8 and hold {c_out} channels")
+    out = torch.empty((B, H, W, cp), dtype=dtype, device=store.device)
+    _l.check(lib.ffa_gather_layout(_dtype_id(dtype), RAW_SAMPLE_KINDS[store.dtype], store.data_ptr(), index.data_ptr(),
+                                   out.data_ptr(), N, B, C_, H, W, cp, _ptr(mean), _ptr(std), _ptr(codes), group,
+                                   elevation, _stream()), "gather_layout")
+    return out
+
+
+def gather_labels(store: torch.Tensor, index: torch.Tensor, num_classes: int,
+                  codes: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 label store [N,H,W] (the raw label channel of every patch) -> uint8 class indices [B,H,W] of the samples
+    ``index``, flipped / rotated by ``codes`` like the inputs.  The label rule is the reference's
+    ``argmax(reshape_label_ohe(label, K))``: a value v < K stays v, and a value v >= K becomes **0** -- its one-hot
+    is all false, and the argmax of an all-false vector is 0.  Such pixels train as class 0; they are not ignored."""
+    lib = _l.load()
+    if not torch.is_tensor(store) or store.dtype != torch.uint8 or store.ndim != 3 or not store.is_cuda or \
+            not store.is_contiguous() or store.numel() == 0:
+        raise ValueError("gather_labels: contiguous uint8 device store [N,H,W] expected")
+    N, H, W = store.shape
+    if not 1 <= int(num_classes) <= 256:
+        raise ValueError(f"gather_labels: {num_classes} classes do not fit a byte")
+    if codes is not None and H != W:
+        raise ValueError(f"gather_labels: rotations need square planes, got {H} x {W}")
+    index = _gather_index(index, N, store.device, "gather_labels")
+    B = index.numel()
+    if codes is not None:
+        codes = _d4_codes(codes, B, store.device, "gather_labels")
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=store.device)
+    _l.check(lib.ffa_gather_labels_u8(store.data_ptr(), index.data_ptr(), out.data_ptr(), N, B, H, W, int(num_classes),
+                                      _ptr(codes), _stream()), "gather_labels")
+    return out
+
+
 def nhwc_to_nchw(x: torch.Tensor, channels: int) -> torch.Tensor:
     lib = _l.load()
     _chk_nhwc(x, "nhwc_to_nchw input")

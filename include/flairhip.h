@@ -508,6 +508,9 @@ int ffa_confusion_matrix(const uint8_t* pred, const uint8_t* target, long long n
 /* The evaluation entry points (labels, confusion counts and per-class loss sums from one pass over the logits) are
  * declared in flairhip_eval.h, which this header brings along. */
 #include "flairhip_eval.h"
+/* The sample-store entry points (a batch gathered by index from raw samples resident on the device, with the layout
+ * pass, the elevation pre-processing and the label rule on the way) are declared in flairhip_gather.h, likewise. */
+#include "flairhip_gather.h"
 
 /* ---- host-side tile bookkeeping, bit-exact with the reference's float64 arithmetic
  *      (flair_zonal_detection/slicing.py:51-112, flair_zonal_detection/inference.py:318-335) -------- */

@@ -165,6 +165,39 @@ def bench_layout(args):
         print(f"{'d4_labels ' + label:24s} {us:9.1f} {'':>7s} {2 * tgt.numel() / us / 1e6:7.2f}")
 
 
+def bench_gather(args):
+    """ops.gather_layout / ops.gather_labels (a batch gathered from a device-resident sample store, csrc/sample_gather.hip)
+    against ops.d4_layout / ops.d4_labels at the same shape in the same process: a store of 4 * B patches of 5 x 512 x 512
+    uint8, a batch of B random indices -> bf16 pitch 16; then a 2-band float32 DEM with the elevation difference"""
+    dev = torch.device("cuda:0")
+    dt = torch.bfloat16
+    N = 4 * B
+    store = torch.randint(0, 255, (N, 5, 512, 512), device=dev, dtype=torch.uint8)
+    index = torch.randperm(N, device=dev)[:B].to(torch.int32)
+    x = store[index.long()].contiguous()
+    mu, sd = torch.full((5,), 110.0, device=dev), torch.full((5,), 50.0, device=dev)
+    nbytes = x.numel() + B * 512 * 512 * 16 * 2
+    print(f"{'kernel':32s} {'us':>9s} {'ratio':>7s} {'TB/s':>7s}")
+    for label, codes in (("code 0", torch.zeros(B, dtype=torch.uint8, device=dev)),
+                         ("mixed codes", torch.arange(B, device=dev).to(torch.uint8) % 16)):
+        base = timeit(lambda: ops.d4_layout(x, dt, codes, mu, sd, 16), iters=args.iters)
+        us = timeit(lambda: ops.gather_layout(store, index, dt, codes, mu, sd, 16), iters=args.iters)
+        print(f"{'d4_layout ' + label:32s} {base:9.1f} {1.0:7.2f} {nbytes / base / 1e6:7.2f}")
+        print(f"{'gather_layout ' + label:32s} {us:9.1f} {us / base:7.2f} {nbytes / us / 1e6:7.2f}")
+    lstore = torch.randint(0, 24, (N, 512, 512), device=dev, dtype=torch.uint8)
+    t = lstore[index.long()].contiguous()
+    codes = torch.arange(B, device=dev).to(torch.uint8) % 16
+    base = timeit(lambda: ops.d4_labels(t, codes), iters=args.iters)
+    us = timeit(lambda: ops.gather_labels(lstore, index, 19, codes), iters=args.iters)
+    print(f"{'d4_labels mixed codes':32s} {base:9.1f} {1.0:7.2f} {2 * t.numel() / base / 1e6:7.2f}")
+    print(f"{'gather_labels mixed codes':32s} {us:9.1f} {us / base:7.2f} {2 * t.numel() / us / 1e6:7.2f}")
+    dem = torch.randn(N, 2, 512, 512, device=dev)
+    m1, s1 = torch.full((1,), 9.5, device=dev), torch.full((1,), 7.25, device=dev)
+    db = B * 2 * 512 * 512 * 4 + B * 512 * 512 * 16 * 2
+    us = timeit(lambda: ops.gather_layout(dem, index, dt, codes, m1, s1, 16, elevation=ops.ELEV_DIFF), iters=args.iters)
+    print(f"{'gather_layout DEM z0 - z1':32s} {us:9.1f} {'':>7s} {db / us / 1e6:7.2f}")
+
+
 def bench_blas(args):
     """The equal-FLOP GEMM of every MFMA-bound conv shape (M = B*Ho*Wo pixels, N = Cout, K = Cin*k*k) through torch's
     matmul = hipBLASLt on this image, same box, random bf16 operands: what a tuned vendor GEMM reaches on these M/N/K,
@@ -195,7 +228,9 @@ def main():
     ap.add_argument("--kinds", default="fwd,dgrad,wgrad")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--bn", action="store_true", help="BatchNorm kernels instead of the convolutions")
-    ap.add_argument("--layout", action="store_true", help="the input layout pass with and without the augmentation gather")
+    ap.add_argument("--layout", nargs="?", const="d4", choices=("d4", "gather"), default=None,
+                    help="the input layout pass with and without the augmentation gather; 'gather': the sample-store "
+                         "gather kernels against d4_layout / d4_labels at the same shape")
     ap.add_argument("--data", default="randn", choices=["randn", "relu", "zeros"],
                     help="activation values: randn (worst case for power), relu (post-ReLU: half zeros, no "
                          "negative values -- what the network's 3x3 convs actually read), zeros")
@@ -203,7 +238,7 @@ def main():
     if args.bn:
         return bench_bn(args)
     if args.layout:
-        return bench_layout(args)
+        return bench_gather(args) if args.layout == "gather" else bench_layout(args)
     if args.blas:
         return bench_blas(args)
     dev = torch.device("cuda:0")

@@ -5,6 +5,10 @@ the product also accepts (uint8 imagery + '<MOD>_NORM' + uint8 class indices, 1.
 has its inputs resident in HBM; this is the number next to it.
 
   python tools/bench_trainer_pcie.py [--batch 32] [--steps 30] [--schemas compact,reference] [--repeat 1] [--augment]
+  python tools/bench_trainer_pcie.py --dataset DIR --cache none|device [--batch 32] [--steps 30] [--repeat 1]
+
+--dataset DIR (written by tools/make_patch_dataset.py): the same step fed by FlairDataModule from GeoTIFF patches on
+disk, gathered from the device-resident sample store (--cache device) or decoded and streamed per batch (--cache none).
 
 --augment: the same run with modalities.pre_processings.use_augmentation on (per-sample flips / rotations drawn by the
 trainer, applied inside the layout and label kernels).  --schemas picks the schemas to run and --repeat N runs each N
@@ -78,14 +82,62 @@ def run(schema: str, B: int, steps: int, warm: int = 10, augment: bool = False):
             "tiles_per_s": round(B * steps / dt, 1), "h2d_GBps_needed": round(mb / 1024 / (dt / steps), 1)}
 
 
+def run_dataset(root: str, cache: str, B: int, steps: int, warm: int = 10):
+    """the training step fed by FlairDataModule from the on-disk dataset tools/make_patch_dataset.py wrote under
+    ``root``: cache='device' gathers every batch from the device-resident sample store, cache='none' decodes the
+    GeoTIFF patches per batch and streams the raw samples.  Aerial only, augmentation on, hipGraph step."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from make_patch_dataset import make_config
+    from flair_hub.data.datamodule import FlairDataModule
+    from flair_hub.data.utils_data.paths import get_datasets
+    from flair_hub.tasks.module_setup import build_segmentation_module, get_input_img_sizes
+    from flair_hub.tasks.trainers import HipTrainer
+    csvs = {k: os.path.join(root, f"{k}.csv") for k in ("train", "val", "test")}
+    cfg = make_config(root, csvs, cache, B, 1, "bf16", dem=False)
+    cfg["tasks"]["predict"] = False
+    tr_paths, va_paths, _ = get_datasets(cfg)
+    dm = FlairDataModule(cfg, tr_paths, va_paths, None, num_workers=16, batch_size=B, drop_last=True,
+                         use_augmentations=True, cache=cache, device_prepare=True)
+    t0 = time.perf_counter()
+    sizes = get_input_img_sizes(cfg, dm, "fit")
+    fill_s = time.perf_counter() - t0
+    torch.manual_seed(2025)
+    task = build_segmentation_module(cfg, sizes, "train")
+    marks = {}
+    orig = task.on_train_batch_end
+
+    def hook(loss, batch, i):
+        if task.global_step in (warm, warm + steps):
+            torch.cuda.synchronize()
+            marks[task.global_step] = time.perf_counter()
+        return orig(loss, batch, i)
+
+    task.on_train_batch_end = hook
+    if dm.store is not None:
+        task.attach_store(dm.store)  # fit() is handed the loader, not the data module
+    per_epoch = max(len(dm.train_dataloader()), 1)
+    tr = HipTrainer(max_epochs=-(-(warm + steps) // per_epoch), max_steps=warm + steps, hip_graph=True)
+    tr.fit(task, train_dataloaders=dm.train_dataloader())
+    dt = marks[warm + steps] - marks[warm]
+    return {"dataset": root, "cache": cache, "resident": dm.store is not None,
+            "store_MB": round(dm.store.bytes / 2 ** 20, 1) if dm.store is not None else 0, "setup_s": round(fill_s, 2),
+            "ms_per_step": round(dt / steps * 1e3, 3), "tiles_per_s": round(B * steps / dt, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dataset", default=None, help="a directory written by tools/make_patch_dataset.py: train from it")
+    ap.add_argument("--cache", choices=("none", "device"), default="device", help="with --dataset: the sample cache")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--schemas", default="compact,reference")
     ap.add_argument("--augment", action="store_true", help="use_augmentation on")
     ap.add_argument("--repeat", type=int, default=1, help="runs per schema (the spread of the number)")
     args = ap.parse_args()
+    if args.dataset:
+        for _ in range(args.repeat):
+            print(json.dumps(run_dataset(os.path.abspath(args.dataset), args.cache, args.batch, args.steps)), flush=True)
+        return
     for schema in args.schemas.split(","):
         for _ in range(args.repeat):
             print(json.dumps(run(schema, args.batch, args.steps, augment=args.augment)), flush=True)
