@@ -1,5 +1,6 @@
 // What the D4 passes share (augment.hip: the layout / label kernels of a batch tensor; sample_gather.hip: the same
-// passes reading a device-resident sample store through an index vector): the code -> source-rectangle map, the tile
+// passes reading a device-resident sample store through an index vector; series_gather.hip: the layout pass reading a
+// ragged store of time series): the code -> source-rectangle map, the tile
 // sizes, the normalisation expression and the layout pass of one tile itself (d4_layout_image).  One definition, so that
 // the two families agree bit for bit by construction.
 //

@@ -540,50 +540,64 @@ __global__ void __launch_bounds__(128) ltae_attention_bwd_kernel(
     const float* __restrict__ drop, const float* __restrict__ prob, const T* __restrict__ dout,
     const float* __restrict__ dattn_ext, T* __restrict__ dk, T* __restrict__ dv, float* __restrict__ dq_partial, int B,
     int Tn, int P, int NH, int DK, int DV) {
-  extern __shared__ float sdq[];  // [NH * DK]
+  // dQ is summed in a fixed order -- each thread stages its row, then column c adds the rows of its head in thread
+  // order -- so the gradient is the same bits in every run (an LDS atomic would add in the order the waves arrive)
+  extern __shared__ float sdq[];  // [NH * DK] sums, then [blockDim.x][8] staged rows
+  float* stage = sdq + NH * DK;
   for (int i = threadIdx.x; i < NH * DK; i += blockDim.x) sdq[i] = 0.f;
-  __syncthreads();
   const long long total = (long long)B * P * NH;
   const float inv_temp = 1.0f / sqrtf((float)DK);
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int h = (int)(i % NH);
-    const long long bp = i / NH;
-    const int p = (int)(bp % P);
-    const int b = (int)(bp / P);
-    float go[32];
-    const T* dd = dout + (((long long)b * P + p) * NH + h) * DV;
-    for (int j = 0; j < DV; ++j) go[j] = ffa_load_elem<T>(dd + j);
-    float dot = 0.f;  // sum_t prob[t] dp[t]
-    for (int t = 0; t < Tn; ++t) {
-      const long long ai = (((long long)h * B + b) * Tn + t) * P + p;
-      const T* vv = v + (((long long)(b * Tn + t) * P + p) * NH + h) * DV;
-      float da = dattn_ext ? dattn_ext[ai] : 0.f;
-      for (int j = 0; j < DV; ++j) da += go[j] * ffa_load_elem<T>(vv + j);
-      const float dr = drop ? drop[ai] : 1.f;
-      dot += prob[ai] * da * dr;
-    }
+  for (long long base = blockIdx.x * (long long)blockDim.x; base < total; base += (long long)gridDim.x * blockDim.x) {
+    const long long i = base + threadIdx.x;
     float dqh[8];
-    for (int j = 0; j < DK; ++j) dqh[j] = 0.f;
-    for (int t = 0; t < Tn; ++t) {
-      const long long ai = (((long long)h * B + b) * Tn + t) * P + p;
-      const long long row = ((long long)(b * Tn + t) * P + p) * NH + h;
-      const T* vv = v + row * DV;
-      const float dr = drop ? drop[ai] : 1.f;
-      const float pr = prob[ai];
-      float da = dattn_ext ? dattn_ext[ai] : 0.f;
-      for (int j = 0; j < DV; ++j) da += go[j] * ffa_load_elem<T>(vv + j);
-      const float a = pr * dr;
-      for (int j = 0; j < DV; ++j) ffa_store_elem<T>(dv + row * DV + j, a * go[j]);
-      float ds = pr * (da * dr - dot);
-      if (pad[b * Tn + t]) ds = 0.f;
-      ds *= inv_temp;
-      const T* kk = k + row * DK;
-      for (int j = 0; j < DK; ++j) {
-        ffa_store_elem<T>(dk + row * DK + j, ds * Q[h * DK + j]);
-        dqh[j] += ds * ffa_load_elem<T>(kk + j);
+    for (int j = 0; j < 8; ++j) dqh[j] = 0.f;
+    if (i < total) {
+      const int h = (int)(i % NH);
+      const long long bp = i / NH;
+      const int p = (int)(bp % P);
+      const int b = (int)(bp / P);
+      float go[32];
+      const T* dd = dout + (((long long)b * P + p) * NH + h) * DV;
+      for (int j = 0; j < DV; ++j) go[j] = ffa_load_elem<T>(dd + j);
+      float dot = 0.f;  // sum_t prob[t] dp[t]
+      for (int t = 0; t < Tn; ++t) {
+        const long long ai = (((long long)h * B + b) * Tn + t) * P + p;
+        const T* vv = v + (((long long)(b * Tn + t) * P + p) * NH + h) * DV;
+        float da = dattn_ext ? dattn_ext[ai] : 0.f;
+        for (int j = 0; j < DV; ++j) da += go[j] * ffa_load_elem<T>(vv + j);
+        const float dr = drop ? drop[ai] : 1.f;
+        dot += prob[ai] * da * dr;
+      }
+      for (int t = 0; t < Tn; ++t) {
+        const long long ai = (((long long)h * B + b) * Tn + t) * P + p;
+        const long long row = ((long long)(b * Tn + t) * P + p) * NH + h;
+        const T* vv = v + row * DV;
+        const float dr = drop ? drop[ai] : 1.f;
+        const float pr = prob[ai];
+        float da = dattn_ext ? dattn_ext[ai] : 0.f;
+        for (int j = 0; j < DV; ++j) da += go[j] * ffa_load_elem<T>(vv + j);
+        const float a = pr * dr;
+        for (int j = 0; j < DV; ++j) ffa_store_elem<T>(dv + row * DV + j, a * go[j]);
+        float ds = pr * (da * dr - dot);
+        if (pad[b * Tn + t]) ds = 0.f;
+        ds *= inv_temp;
+        const T* kk = k + row * DK;
+        for (int j = 0; j < DK; ++j) {
+          ffa_store_elem<T>(dk + row * DK + j, ds * Q[h * DK + j]);
+          dqh[j] += ds * ffa_load_elem<T>(kk + j);
+        }
       }
     }
-    for (int j = 0; j < DK; ++j) unsafeAtomicAdd(&sdq[h * DK + j], dqh[j]);  // ds_add_f32
+    for (int j = 0; j < 8; ++j) stage[threadIdx.x * 8 + j] = dqh[j];
+    __syncthreads();
+    for (int c = threadIdx.x; c < NH * DK; c += blockDim.x) {
+      const int hh = c / DK, j = c % DK;
+      float sum = sdq[c];
+      for (int tt = 0; tt < (int)blockDim.x && base + tt < total; ++tt)
+        if ((int)((base + tt) % NH) == hh) sum += stage[tt * 8 + j];
+      sdq[c] = sum;
+    }
+    __syncthreads();
   }
   __syncthreads();
   const int pitch = (NH * DK + 7) & ~7;  // rows padded with zeros to the 8 columns ffa_column_sums works in
@@ -604,7 +618,7 @@ extern "C" int ffa_ltae_attention_bwd(int dtype, const void* k, const void* v, c
   FFA_REQUIRE(B > 0 && T > 0 && P > 0 && n_head > 0 && d_k > 0 && d_k <= 8 && d_v > 0 && d_v <= 32,
               "ltae_attention_bwd: bad geometry");
   const int grid = ffa_ltae_attention_bwd_blocks(B, P, n_head);
-  const size_t lds = (size_t)n_head * d_k * sizeof(float);
+  const size_t lds = ((size_t)n_head * d_k + 128 * 8) * sizeof(float);
   if (dtype == FFA_BF16)
     hipLaunchKernelGGL(ltae_attention_bwd_kernel<ffa_bf16>, dim3(grid), dim3(128), lds, stream, (const ffa_bf16*)k,
                        (const ffa_bf16*)v, Q, pad, drop, prob, (const ffa_bf16*)dout, dattn_ext, (ffa_bf16*)dk,

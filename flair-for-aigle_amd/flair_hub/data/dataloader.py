@@ -10,8 +10,9 @@ host augmentation applied to the arrays.
 file's sample type (uint8 aerial, the 2-band float32 DEM), the raw label channel as uint8 [H, W] and ``ID_<task>``.
 Normalisation, the elevation difference, the label rule and the augmentation then happen in the kernels of
 csrc/sample_gather.hip on the device; the ``<MOD>_NORM`` vectors those kernels need are supplied once by the data
-module (``norm_vectors``), not per sample.  Time series keep the host schema: they are of variable length and never
-enter the device-resident store."""
+module (``norm_vectors``), not per sample.  Time series keep the host schema (filtered / averaged on the host, float32)
+on the streamed path; while the data module fills a store that takes them (``keep_series_raw``) they are handed out as
+the numpy arrays they are before that cast, so that the store can keep the decoded sample type."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -45,6 +46,7 @@ class flair_dataset(Dataset):
         self.config = config
         self.device_prepare = bool(device_prepare)
         self.keep_dem_bands = False  # set by the data module while it fills a device-resident store
+        self.keep_series_raw = False  # likewise: '<SENSOR>_TS' / '<SENSOR>_DATES' stay numpy arrays, uncast
         self.use_augmentations = apply_numpy_augmentations if use_augmentations is True else use_augmentations
         mods = config["modalities"]
         enabled = mods["inputs"]
@@ -173,6 +175,8 @@ class flair_dataset(Dataset):
             for k, v in batch.items():
                 if k in MONO_KEYS or k in self.tasks:
                     out[k] = torch.from_numpy(v)  # the sample type as decoded
+                elif self.keep_series_raw and k.endswith(("_TS", "_DATES")):
+                    out[k] = np.asarray(v)
                 elif isinstance(v, (np.ndarray, list)) and "ID_" not in k:
                     out[k] = torch.tensor(v, dtype=torch.float32)
                 else:

@@ -9,7 +9,11 @@ Three batch schemas leave this module ('Training from a dataset on di
   uint8 label channels and the ``RAW_LABELS`` marker; the device normalises, takes the elevation difference and applies
   the label rule;
 * resident (``cache="device"``): on the first setup every patch of the train and validation splits is decoded once into
-  a flairhip.sample_store.SampleStore, and a batch is ``{"INDEX": int32 [B] (pinned), "ID_<task>": [...]}``.
+  a flairhip.sample_store.SampleStore, and a batch is ``{"INDEX": int32 [B] (pinned), "ID_<task>": [...]}``.  With
+  ``series_cache=True`` the Sentinel time series go into the store as well (ragged, one SeriesStore per modality),
+  and the batch also carries ``"<SENSOR>_DATES"``: float32 [B, T], the samples' date offsets zero-padded to the longest
+  series of the batch -- the reference's own key, and what tells the model and the captured step the batch's T.
+  Without it (the default) an enabled ``*_TS`` input keeps the whole dataset on the streamed path.
 
 Sharding of the two device schemas: rank r owns the fixed share ``r::world_size`` of a split (it stores nothing else)
 and draws a seeded permutation of that share per epoch; the rank is the process group's, or RANK / WORLD_SIZE of the
@@ -101,6 +105,10 @@ class RankShareLoader:
             yield batch
 
 
+class _StoreFallback(Exception):
+    """a sample the store cannot take: the split stays streamed (the message names the patch)"""
+
+
 def default_cache_bytes(device) -> int:
     free, _total = torch.cuda.mem_get_info(device)
     return int(free * CACHE_SHARE)
@@ -110,7 +118,8 @@ class FlairDataModule:
     def __init__(self, config, dict_train: Optional[Dict] = None, dict_val: Optional[Dict] = None,
                  dict_test: Optional[Dict] = None, num_workers: int = 1, batch_size: int = 2, drop_last: bool = True,
                  use_augmentations: bool = True, cache: str = "none", cache_bytes: Optional[int] = None,
-                 device_prepare: Optional[bool] = None, seed: Optional[int] = None, device=None):
+                 device_prepare: Optional[bool] = None, seed: Optional[int] = None, device=None,
+                 series_cache: bool = False):
         if cache not in ("none", "device"):
             raise ValueError(f"cache must be 'none' or 'device', got {cache!r}")
         self.config = config
@@ -118,6 +127,7 @@ class FlairDataModule:
         self.batch_size, self.num_workers, self.drop_last = batch_size, num_workers, drop_last
         self.use_augmentations = use_augmentations
         self.cache, self.cache_bytes = cache, cache_bytes
+        self.series_cache = bool(series_cache)  # cache="device" only: time series enter the store too
         # raw samples + device-side preparation: what the resident path needs, and optional for the streamed one
         self.device_prepare = (cache == "device") if device_prepare is None else bool(device_prepare)
         self.seed = int(config.get("hyperparams", {}).get("seed", 0) if seed is None else seed)
@@ -181,18 +191,22 @@ class FlairDataModule:
         labels = {t: tuple(sample[t].shape) for t in self.config["labels"]}
         return inputs, labels
 
+    _TOO_LARGE = ("sample cache: %d patches need %.1f MB, the budget is %.1f MB: falling back to the streamed loaders "
+                  "(a split is never stored in part)")
+
     def _build_store(self) -> None:
         from flairhip import ops
-        from flairhip.sample_store import SampleStore, store_bytes
+        from flairhip.sample_store import SampleStore, SeriesStore, store_bytes
         inputs_on = [m for m, on in self.config["modalities"]["inputs"].items() if on]
         series = [m for m in inputs_on if m.endswith("_TS")]
-        if series:
+        if series and not self.series_cache:
             logger.info("sample cache: %s are time series of variable length and stay streamed: no store", series)
             return
         rank, world = self._rank, self._world = _rank_world()
         splits = {"train": self.train_dataset, "val": self.val_dataset}
         for ds in splits.values():
             ds.keep_dem_bands = True  # the store keeps both DEM bands; its kernel takes the difference
+            ds.keep_series_raw = bool(series)  # ... and the series in their decoded sample type
         try:
             self._shares = {k: rank_share(len(ds), rank, world) for k, ds in splits.items()}
             n = sum(len(s) for s in self._shares.values())
@@ -205,9 +219,8 @@ class FlairDataModule:
             need = store_bytes(n, inputs, labels)
             device = torch.device(self.device) if self.device is not None else _rank_device()
             budget = self.cache_bytes if self.cache_bytes is not None else default_cache_bytes(device)
-            if need > budget:
-                logger.info("sample cache: %d patches need %.1f MB, the budget is %.1f MB: falling back to the "
-                            "streamed loaders (a split is never stored in part)", n, need / 1e6, budget / 1e6)
+            if need > budget:  # without the series, whose size is known only once they are decoded
+                logger.info(self._TOO_LARGE, n, need / 1e6, budget / 1e6)
                 return
             mode = elevation_mode(self.config)
             ids = {t: [] for t in self.config["labels"]}
@@ -215,26 +228,73 @@ class FlairDataModule:
                                 {t: len(self.config["labels_configs"][t]["value_name"]) for t in self.config["labels"]},
                                 self._norm_vectors(sample),
                                 {m: (mode if m == "DEM_ELEV" else ops.ELEV_NONE) for m in inputs}, device, ids)
-            at = 0
-            for k, ds in splits.items():
-                self._offsets[k] = at
-                at = self._fill(store, ds, self._shares[k], at)
+            # the series are small: the one decoding pass keeps them on the host, and their sum of lengths sizes the
+            # ragged stores afterwards
+            held = {m: [] for m in series}
+            at, offsets = 0, {}
+            try:
+                for k, ds in splits.items():
+                    offsets[k] = at
+                    at = self._fill(store, ds, self._shares[k], at, held)
+            except _StoreFallback as why:
+                logger.info("sample cache: %s: falling back to the streamed loaders (a split is never stored in part)",
+                            why)
+                return
+            if series:
+                spec = {m: (sum(len(a) for a, _ in held[m]), tuple(held[m][0][0].shape[1:]), held[m][0][0].dtype)
+                        for m in series}
+                need = store_bytes(n, inputs, labels, spec)
+                if need > budget:
+                    logger.info(self._TOO_LARGE, n, need / 1e6, budget / 1e6)
+                    return
+                pad_value = self.config["models"]["multitemp_model"].get("pad_value", 0)
+                for m, (total, shape, dt) in spec.items():
+                    st = SeriesStore(n, total, shape, dt, pad_value, device)
+                    for c0 in range(0, n, FILL_CHUNK):
+                        part = held[m][c0:c0 + FILL_CHUNK]
+                        st.fill(c0, np.concatenate([a for a, _ in part]), np.concatenate([d for _, d in part]),
+                                [len(a) for a, _ in part])
+                    store.attach_series(m, st)
             if store.device.type == "cuda":
                 torch.cuda.synchronize(store.device)
+            self._offsets = offsets
             self.store = store
             logger.info("sample cache: %d patches (%.1f MB) resident on %s", n, store.bytes / 1e6, store.device)
         finally:
             for ds in splits.values():
                 ds.keep_dem_bands = False
+                ds.keep_series_raw = False
 
-    def _fill(self, store, ds: flair_dataset, share: np.ndarray, at: int) -> int:
-        """decode the rank's share of one split once, in chunks through pinned buffers; -> the next free slot"""
+    def _series_of(self, sample: dict, mod: str, first) -> tuple:
+        """(series in its stored sample type, float32 diff_dates) of one decoded sample, or _StoreFallback"""
+        from flairhip.sample_store import series_dtype
+        patch = next((sample[f"ID_{t}"] for t in self.config["labels"] if f"ID_{t}" in sample), "?")
+        arr = sample.get(mod)
+        if arr is None:
+            raise _StoreFallback(f"{patch} has no {mod}")
+        arr = np.asarray(arr)
+        if arr.shape[0] == 0:
+            raise _StoreFallback(f"the {mod} series of {patch} is empty after filtering")
+        pp = self.config["modalities"].get("pre_processings", {})
+        averaged = bool(pp.get("temporal_average_sentinel2" if mod == "SENTINEL2_TS" else "temporal_average_sentinel1"))
+        arr = np.ascontiguousarray(arr.astype(series_dtype(arr.dtype, averaged), copy=False))
+        if first is not None and (arr.shape[1:] != first.shape[1:] or arr.dtype != first.dtype):
+            raise _StoreFallback(f"the {mod} planes of {patch} are {arr.shape[1:]} {arr.dtype}, those before it "
+                                 f"{first.shape[1:]} {first.dtype}")
+        return arr, np.asarray(sample[mod.replace("_TS", "_DATES")]).astype(np.float32)
+
+    def _fill(self, store, ds: flair_dataset, share: np.ndarray, at: int, held: Optional[Dict[str, list]] = None) -> int:
+        """decode the rank's share of one split once, in chunks through pinned buffers; -> the next free slot.
+        ``held``: {time-series modality: [(series, diff_dates) per sample]}, kept on the host"""
         workers = max(1, min(MAX_DECODE_THREADS, int(self.num_workers) or 1))
         keys = list(store.inputs) + list(store.labels)
         pin = torch.cuda.is_available() and store.device.type == "cuda"
         with ThreadPoolExecutor(max_workers=workers) as pool:
             for c0 in range(0, len(share), FILL_CHUNK):
                 samples = list(pool.map(lambda i: ds[int(i)], share[c0:c0 + FILL_CHUNK]))
+                for mod, rows in (held or {}).items():
+                    for s in samples:
+                        rows.append(self._series_of(s, mod, rows[0][0] if rows else None))
                 chunk = {}
                 for key in keys:
                     host = torch.stack([s[key] for s in samples])
@@ -259,6 +319,8 @@ class FlairDataModule:
             batch = {"INDEX": idx.pin_memory() if pin else idx}
             for t in self.config["labels"]:
                 batch[f"ID_{t}"] = store.ids_of(t, idx)
+            for mod, st in store.series.items():  # [B, T], T the longest series of the batch
+                batch[mod.replace("_TS", "_DATES")] = st.dates_of(idx)
             return batch
 
         return RankShareLoader(len(self._shares[split]), self.batch_size, fetch, shuffle, drop_last, self.seed, rank)

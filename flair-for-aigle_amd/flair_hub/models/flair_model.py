@@ -299,6 +299,24 @@ class FLAIR_HUB_Model(nn.Module):
         return store.input_nhwc(mod, index, self.compute_dtype, aug,
                                 getattr(enc, "input_pitch", ops.pad_channels(enc.in_channels)))
 
+    def _store_series(self, mod: str, index: torch.Tensor, dates: torch.Tensor, aug):
+        """(nhwc, pad, B, T) of a time-series modality for HipUTAE.forward_nhwc(prepared=...): T is the width of the
+        batch's date matrix, the padded dates hold the 0 pad_collate_flair pads with"""
+        store, enc = self.store, self.encoders[mod]
+        series = getattr(store, "series", {})
+        if mod not in series:
+            raise KeyError(f"batch['INDEX']: the attached sample store holds no {mod}")
+        st = series[mod]
+        if st.shape[0] != enc.input_dim:
+            raise ValueError(f"the store's {mod} gives {st.shape[0]} channels, the encoder takes {enc.input_dim}")
+        if dates.ndim != 2 or dates.shape[0] != index.numel() or dates.shape[1] < 1:
+            raise ValueError(f"batch['{mod.replace('TS', 'DATES')}'] must be [B = {index.numel()}, T >= 1], got "
+                             f"{tuple(dates.shape)}")
+        T = int(dates.shape[1])
+        nhwc, pad = ops.gather_series(st, index, T, self.compute_dtype, aug, ops.pad_channels(enc.input_dim), 0.0,
+                                      enc.pad_value)
+        return nhwc, pad, index.numel(), T
+
     def modality_dropout(self, feature_maps: Dict[str, list], modalities_dropout_dict: Dict[str, float]):
         """Reference :328-352: with probability ``modalities_dropout_dict[mod]`` the modality's feature maps are
         replaced by fresh Xavier-uniform noise (created per call, never trained).  Same host RNG draws
@@ -387,7 +405,11 @@ class FLAIR_HUB_Model(nn.Module):
                 dates = batch.get(mod.replace("TS", "DATES"))
                 if dates is None:
                     raise KeyError(f"batch['{mod.replace('TS', 'DATES')}'] (acquisition dates, [B, T]) is required")
-                s_nhwc, maps, _ = encoder.forward_nhwc(batch[mod], dates, aug=aug)
+                if store is not None and mod not in batch:
+                    # the resident path: the padded batch and its pad flags come from the ragged series store
+                    s_nhwc, maps, _ = encoder.forward_nhwc(None, dates, prepared=self._store_series(mod, index, dates, aug))
+                else:
+                    s_nhwc, maps, _ = encoder.forward_nhwc(batch[mod], dates, aug=aug)
                 scores[mod] = self.interpolate_map(s_nhwc, img_size)
                 fmaps[mod] = maps
                 if self.aux_losses.get(mod):

@@ -42,7 +42,9 @@ def build_data_module(config: Dict[str, Any], dict_train: Optional[dict] = None,
                       dict_test: Optional[dict] = None):
     """The data module of a run (reference :12-44).  ``hardware.sample_cache: device`` keeps the decoded train and
     validation patches resident on the card (``hardware.sample_cache_bytes`` bounds them; default 60 % of the free
-    device memory); both keys are optional and default to the streamed loaders."""
+    device memory); both keys are optional and default to the streamed loaders.  ``hardware.sample_cache_series: true``
+    (default false) lets the Sentinel time series into that store; without it an enabled ``*_TS`` input keeps the
+    whole dataset streamed."""
     from flair_hub.data.datamodule import FlairDataModule
     assert isinstance(config, dict), "config must be a dictionary"
     assert isinstance(config["modalities"]["pre_processings"]["use_augmentation"], bool), \
@@ -52,7 +54,8 @@ def build_data_module(config: Dict[str, Any], dict_train: Optional[dict] = None,
                            batch_size=config["hyperparams"]["batch_size"], num_workers=hw.get("num_workers", 0),
                            drop_last=True, use_augmentations=config["modalities"]["pre_processings"]["use_augmentation"],
                            cache=str(hw.get("sample_cache", "none") or "none"),
-                           cache_bytes=hw.get("sample_cache_bytes"))
+                           cache_bytes=hw.get("sample_cache_bytes"),
+                           series_cache=bool(hw.get("sample_cache_series", False)))
 
 
 class FLAIRLosses:

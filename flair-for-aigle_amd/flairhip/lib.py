@@ -209,6 +209,11 @@ GATHER_SIGNATURES = {
     "ffa_gather_labels_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
 }
 
+# the prototype of include/flairhip_series.h (the ragged time-series store), which include/flairhip.h brings along
+SERIES_SIGNATURES = {
+    "ffa_gather_series": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _p]),
+}
+
 _lib = None
 
 
@@ -226,7 +231,7 @@ def load() -> C.CDLL:
     # every launch fails with "no ROCm-capable device is detected"
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES, **GATHER_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES, **GATHER_SIGNATURES, **SERIES_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args

@@ -894,6 +894,59 @@ def gather_labels(store: torch.Tensor, index: torch.Tensor, num_classes: int,
     return out
 
 
+def gather_series(store, index: torch.Tensor, T: int, dtype: torch.dtype, codes: Optional[torch.Tensor] = None,
+                  cp: Optional[int] = None, fill: float = 0.0, pad_value: float = 0.0):
+    """The padded batch of a U-TAE branch from a ragged flairhip.sample_store.SeriesStore: -> (nhwc [B*T,H,W,cp] of
+    ``dtype``, pad uint8 [B*T]).  Image b*T + t is date t of sample ``index[b]`` read through the gather of
+    ``codes[b]`` (``None``: the identity, H != W allowed), widened to f32 and converted, not normalised; the dates past
+    the sample's length hold ``fill`` (what pad_collate_flair pads with).  ``pad`` is the store's flag of a stored date
+    and ``fill == pad_value`` of a padded one.  Both equal, bit for bit, ``d4_layout(x, dtype, codes, cp=cp, group=T)``
+    and ``detect_pad_images(x, pad_value)`` on the padded f32 batch x.  A host ``index`` is checked against the
+    store's host offsets (range, longest series <= T); the values of a device ``index`` stay on the device."""
+    data = getattr(store, "data", None)
+    if not torch.is_tensor(data) or data.dtype not in RAW_SAMPLE_KINDS or data.ndim != 4 or \
+            not data.is_contiguous() or data.numel() == 0:
+        raise ValueError("gather_series: a SeriesStore with contiguous data [D,C,h,w] of uint8 / uint16 / int16 / float32 "
+                         "expected")
+    D, C_, H, W = data.shape
+    N, T = int(store.n), int(T)
+    if T < 1:
+        raise ValueError(f"gather_series: T = {T} dates")
+    if codes is not None and H != W:
+        raise ValueError(f"gather_series: rotations need square planes, got {H} x {W}")
+    if not torch.is_tensor(index) or index.dtype != torch.int32 or index.ndim != 1 or index.numel() < 1:
+        raise ValueError("gather_series: index must be a non-empty int32 vector")
+    if not index.is_cuda:
+        lo, hi = int(index.min()), int(index.max())
+        if lo < 0 or hi >= N:
+            raise ValueError(f"gather_series: index values {lo}..{hi} outside the store's [0, {N})")
+        longest = int(store.lengths[index.numpy()].max())
+        if longest > T:
+            raise ValueError(f"gather_series: the longest indexed series has {longest} dates, T = {T}")
+    cp = pad_channels(C_) if cp is None else int(cp)
+    if cp % 8 or cp < C_:
+        raise ValueError(f"gather_series: channel pitch {cp} must be a multiple of 8 and hold {C_} channels")
+    if not data.is_cuda:
+        raise ValueError("gather_series: the store lives on the host; the gather runs on the device")
+    lib = _l.load()
+    index = _gather_index(index, N, data.device, "gather_series")
+    B = index.numel()
+    if codes is not None:
+        codes = _d4_codes(codes, B, data.device, "gather_series")
+    offsets, is_pad = store.offsets, store.is_pad
+    if offsets.dtype != torch.int32 or offsets.numel() != N + 1 or offsets.device != data.device or \
+            is_pad.dtype != torch.uint8 or is_pad.numel() != D or is_pad.device != data.device or \
+            not offsets.is_contiguous() or not is_pad.is_contiguous():
+        raise ValueError("gather_series: offsets int32 [N + 1] and is_pad uint8 [D] must live next to the data")
+    out = torch.empty((B * T, H, W, cp), dtype=dtype, device=data.device)
+    pad = torch.empty(B * T, dtype=torch.uint8, device=data.device)
+    _l.check(lib.ffa_gather_series(_dtype_id(dtype), RAW_SAMPLE_KINDS[data.dtype], data.data_ptr(), offsets.data_ptr(),
+                                   is_pad.data_ptr(), index.data_ptr(), out.data_ptr(), pad.data_ptr(), N, B, T, C_, H,
+                                   W, cp, float(fill), int(float(fill) == float(pad_value)), _ptr(codes), _stream()),
+             "gather_series")
+    return out, pad
+
+
 def nhwc_to_nchw(x: torch.Tensor, channels: int) -> torch.Tensor:
     lib = _l.load()
     _chk_nhwc(x, "nhwc_to_nchw input")

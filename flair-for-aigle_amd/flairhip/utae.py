@@ -423,27 +423,35 @@ class HipUTAE(nn.Module):
 
     # ---- forward -------------------------------------------------------------------------------------
 
-    def forward_nhwc(self, x: torch.Tensor, batch_positions: torch.Tensor, aug: Optional[torch.Tensor] = None):
+    def forward_nhwc(self, x: Optional[torch.Tensor], batch_positions: torch.Tensor,
+                     aug: Optional[torch.Tensor] = None, prepared=None):
         """x f32 [B,T,C,H,W], batch_positions [B,T] -> (logits NHWC [B,H,W,pitch], maps NHWC (coarse to fine),
         attn f32 [n_head,B,T,H,W]).  ``aug`` (uint8 [B] on the device): per-sample flip / rotation codes of the training
-        augmentation (flairhip.augment), applied to all T dates of a sample by the layout pass."""
+        augmentation (flairhip.augment), applied to all T dates of a sample by the layout pass.
+        ``prepared`` = (nhwc, pad, B, T): the input as ops.gather_series leaves it (the NHWC compute tensor
+        [B*T,H,W,pitch], already flipped / rotated, and its u8 pad flags [B*T]); ``x`` and ``aug`` are then not looked
+        at, and everything after the layout pass is the same code."""
         if self.training and torch.is_grad_enabled():
-            return self._forward_train(x, batch_positions, aug)
+            return self._forward_train(x, batch_positions, aug, prepared)
         if self.training:
             raise NotImplementedError("HipUTAE in training mode runs under autograd only (BatchNorm batch statistics "
                                       "and dropout belong to the training step); call .eval() for inference")
-        if not x.is_cuda:
-            raise RuntimeError("HipUTAE runs on the MI355X only (no CPU path in the product)")
-        B, T, C, H, W = x.shape
-        if C != self.input_dim or H < 2 or W < 2:
-            raise ValueError(f"expected [B,T,{self.input_dim},H>=2,W>=2], got {tuple(x.shape)}")
-        N = B * T
-        flat = x.reshape(N, C, H, W).float().contiguous()
-        pad = ops.detect_pad_images(flat, self.pad_value)            # u8 [N], n = b * T + t
+        if prepared is not None:
+            cur, pad, B, T, H, W = self._prepared(prepared)
+            dev = cur.device
+        else:
+            if not x.is_cuda:
+                raise RuntimeError("HipUTAE runs on the MI355X only (no CPU path in the product)")
+            B, T, C, H, W = x.shape
+            if C != self.input_dim or H < 2 or W < 2:
+                raise ValueError(f"expected [B,T,{self.input_dim},H>=2,W>=2], got {tuple(x.shape)}")
+            dev = x.device
+            flat = x.reshape(B * T, C, H, W).float().contiguous()
+            pad = ops.detect_pad_images(flat, self.pad_value)            # u8 [N], n = b * T + t
+            cur = self._layout(flat, C, T, aug)
         # Temporal_Aggregator branches on pad_mask.any() (:609) only to skip a multiplication by (~pad_mask): applying the
         # mask always is the same arithmetic and needs no device -> host synchronisation (the step stays graph-capturable)
         any_pad = True
-        cur = self._layout(flat, C, T, aug)
 
         def shared(t):  # TemporallySharedBlock.smart_forward: padded dates come out as pad_value
             return ops.mask_images_(t, pad, self.pad_value)
@@ -463,7 +471,7 @@ class HipUTAE(nn.Module):
                                self.n_head)
         pw, bias = self._packed("inconv", te.inconv, z.shape[-1])
         z = ops.conv2d(z, pw, 0, self.d_model, bias=bias)
-        pe = ops.positional_encoding(batch_positions.to(x.device), self.d_model // self.n_head, self.n_head)
+        pe = ops.positional_encoding(batch_positions.to(dev), self.d_model // self.n_head, self.n_head)
         ops.add_rowvec_(z, pe)
         pw, bias = self._packed("fc1_k", te.attention_heads.fc1_k, self.d_model)
         keys = ops.conv2d(z, pw, 0, self.n_head * self.d_k, bias=bias)
@@ -508,18 +516,38 @@ class HipUTAE(nn.Module):
             return ops.nchw_to_nhwc(flat, self.dtype, ops.pad_channels(C))
         return ops.d4_layout(flat, self.dtype, aug, cp=ops.pad_channels(C), group=T)
 
-    def _forward_train(self, x: torch.Tensor, batch_positions: torch.Tensor, aug: Optional[torch.Tensor] = None):
+    def _prepared(self, prepared):
+        """(nhwc, pad, B, T) of forward_nhwc's ``prepared`` argument, checked -> (nhwc, pad, B, T, H, W)"""
+        cur, pad, B, T = prepared
+        B, T = int(B), int(T)
+        pitch = ops.pad_channels(self.input_dim)
+        if not (torch.is_tensor(cur) and cur.is_cuda and cur.is_contiguous() and cur.ndim == 4 and
+                cur.dtype == self.dtype and cur.shape[0] == B * T and cur.shape[3] == pitch and
+                cur.shape[1] >= 2 and cur.shape[2] >= 2):
+            raise ValueError(f"prepared input: contiguous {self.dtype} device tensor [{B * T},H>=2,W>=2,{pitch}] expected, "
+                             f"got {tuple(cur.shape) if torch.is_tensor(cur) else type(cur)}")
+        if not (torch.is_tensor(pad) and pad.dtype == torch.uint8 and pad.device == cur.device and
+                pad.is_contiguous() and tuple(pad.shape) == (B * T,)):
+            raise ValueError(f"prepared input: pad must be a uint8 device vector [{B * T}]")
+        return cur, pad, B, T, int(cur.shape[1]), int(cur.shape[2])
+
+    def _forward_train(self, x: Optional[torch.Tensor], batch_positions: torch.Tensor,
+                       aug: Optional[torch.Tensor] = None, prepared=None):
         """training-mode forward_nhwc through autograd nodes (same return convention)"""
-        if not x.is_cuda:
-            raise RuntimeError("HipUTAE runs on the MI355X only (no CPU path in the product)")
-        B, T, C, H, W = x.shape
-        if C != self.input_dim or H < 2 or W < 2:
-            raise ValueError(f"expected [B,T,{self.input_dim},H>=2,W>=2], got {tuple(x.shape)}")
-        N = B * T
-        flat = x.reshape(N, C, H, W).float().contiguous()
-        pad = ops.detect_pad_images(flat, self.pad_value)
+        if prepared is not None:
+            cur, pad, B, T, H, W = self._prepared(prepared)
+            dev = cur.device
+        else:
+            if not x.is_cuda:
+                raise RuntimeError("HipUTAE runs on the MI355X only (no CPU path in the product)")
+            B, T, C, H, W = x.shape
+            if C != self.input_dim or H < 2 or W < 2:
+                raise ValueError(f"expected [B,T,{self.input_dim},H>=2,W>=2], got {tuple(x.shape)}")
+            dev = x.device
+            flat = x.reshape(B * T, C, H, W).float().contiguous()
+            pad = ops.detect_pad_images(flat, self.pad_value)
+            cur = self._layout(flat, C, T, aug)
         any_pad = True  # see forward_nhwc: the mask is applied unconditionally (no host synchronisation)
-        cur = self._layout(flat, C, T, aug)
 
         def gn(t, seq, idx, tag, residual=None):
             conv, nrm = seq[idx], seq[idx + 1]
@@ -544,14 +572,14 @@ class HipUTAE(nn.Module):
         te = self.temporal_encoder
         z = _GNSeq.apply(fmaps[-1], te.in_norm.weight, te.in_norm.bias, B, T, self.n_head)
         z = _Conv1x1.apply(z, te.inconv.weight, te.inconv.bias, self, "inconv", te.inconv)
-        pe = ops.positional_encoding(batch_positions.to(x.device), self.d_model // self.n_head, self.n_head)
+        pe = ops.positional_encoding(batch_positions.to(dev), self.d_model // self.n_head, self.n_head)
         z = _AddRows.apply(z, pe)
         fk = te.attention_heads.fc1_k
         keys = _Conv1x1.apply(z, fk.weight, fk.bias, self, "fc1_k", fk)
         drop = None
         if self.attn_dropout > 0:
             keep = 1.0 - self.attn_dropout
-            drop = torch.empty((self.n_head, B, T, H * W), dtype=torch.float32, device=x.device).bernoulli_(keep).div_(keep)
+            drop = torch.empty((self.n_head, B, T, H * W), dtype=torch.float32, device=dev).bernoulli_(keep).div_(keep)
         o, attn = _LtaeAttention.apply(keys, z, te.attention_heads.Q, pad, B, T, drop)
         o = bnc(o, te.mlp[0], te.mlp[1], "mlp", reflect=False)
         if self.mlp_dropout > 0:

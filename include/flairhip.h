@@ -511,6 +511,9 @@ int ffa_confusion_matrix(const uint8_t* pred, const uint8_t* target, long long n
 /* The sample-store entry points (a batch gathered by index from raw samples resident on the device, with the layout
  * pass, the elevation pre-processing and the label rule on the way) are declared in flairhip_gather.h, likewise. */
 #include "flairhip_gather.h"
+/* The ragged time-series store (the padded U-TAE batch and its pad flags gathered by index from series of variable
+ * length resident on the device) is declared in flairhip_series.h, likewise. */
+#include "flairhip_series.h"
 
 /* ---- host-side tile bookkeeping, bit-exact with the reference's float64 arithmetic
  *      (flair_zonal_detection/slicing.py:51-112, flair_zonal_detection/inference.py:318-335) -------- */

@@ -198,6 +198,43 @@ def bench_gather(args):
     print(f"{'gather_layout DEM z0 - z1':32s} {us:9.1f} {'':>7s} {db / us / 1e6:7.2f}")
 
 
+def bench_series(args):
+    """ops.gather_series (the padded U-TAE batch and its pad flags from a ragged series store, csrc/series_gather.hip)
+    against the pair it replaces on the streamed path, ops.d4_layout(group=T) + ops.detect_pad_images on the same
+    padded f32 batch, in the same process: B samples of 10 bands x 10 x 10 uint16 -> bf16 pitch 16, every series T
+    dates long (T = 12: monthly averages) and of ragged lengths up to T = 40.  Three medians each: the spread."""
+    import numpy as np
+    from flairhip.sample_store import SeriesStore
+    dev = torch.device("cuda:0")
+    dt = torch.bfloat16
+    r = np.random.RandomState(0)
+    print(f"{'kernel':44s} {'us (3 medians)':>24s} {'ratio':>7s}")
+    for T, lengths in ((12, [12] * (4 * B)), (40, list(r.randint(20, 41, 4 * B - 1)) + [40])):
+        N, D = len(lengths), int(sum(lengths))
+        st = SeriesStore(N, D, (10, 10, 10), np.uint16, device=dev)
+        st.fill(0, r.randint(1, 10000, (D, 10, 10, 10)).astype(np.uint16), np.zeros(D), lengths)
+        index = torch.from_numpy(np.concatenate([[N - 1], r.permutation(N - 1)[:B - 1]]).astype(np.int32)).to(dev)
+        codes = torch.arange(B, device=dev).to(torch.uint8) % 16
+        nhwc, _ = ops.gather_series(st, index, T, torch.float32, None, 16)
+        x = nhwc[..., :10].permute(0, 3, 1, 2).contiguous()  # the padded f32 batch [B*T, 10, 10, 10]
+        want = ops.d4_layout(x, dt, codes, cp=16, group=T)
+        got, pad = ops.gather_series(st, index, T, dt, codes, 16)
+        assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+        assert torch.equal(pad, ops.detect_pad_images(x, 0.0))
+
+        def pair():
+            ops.d4_layout(x, dt, codes, cp=16, group=T)
+            ops.detect_pad_images(x, 0.0)
+
+        rows = {"d4_layout(group=T)": lambda: ops.d4_layout(x, dt, codes, cp=16, group=T),
+                "detect_pad_images": lambda: ops.detect_pad_images(x, 0.0), "the pair": pair,
+                "gather_series": lambda: ops.gather_series(st, index, T, dt, codes, 16)}
+        us = {k: sorted(timeit(fn, iters=args.iters) for _ in range(3)) for k, fn in rows.items()}
+        for k, v in us.items():
+            text = " ".join(f"{t:7.1f}" for t in v)
+            print(f"{k + f' B={B} T={T} ({B * T} images)':44s} {text:>24s} {v[1] / us['the pair'][1]:7.2f}")
+
+
 def bench_blas(args):
     """The equal-FLOP GEMM of every MFMA-bound conv shape (M = B*Ho*Wo pixels, N = Cout, K = Cin*k*k) through torch's
     matmul = hipBLASLt on this image, same box, random bf16 operands: what a tuned vendor GEMM reaches on these M/N/K,
@@ -228,9 +265,10 @@ def main():
     ap.add_argument("--kinds", default="fwd,dgrad,wgrad")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--bn", action="store_true", help="BatchNorm kernels instead of the convolutions")
-    ap.add_argument("--layout", nargs="?", const="d4", choices=("d4", "gather"), default=None,
+    ap.add_argument("--layout", nargs="?", const="d4", choices=("d4", "gather", "series"), default=None,
                     help="the input layout pass with and without the augmentation gather; 'gather': the sample-store "
-                         "gather kernels against d4_layout / d4_labels at the same shape")
+                         "gather kernels against d4_layout / d4_labels at the same shape; 'series': gather_series "
+                         "against d4_layout(group=T) + detect_pad_images on the same padded batch")
     ap.add_argument("--data", default="randn", choices=["randn", "relu", "zeros"],
                     help="activation values: randn (worst case for power), relu (post-ReLU: half zeros, no "
                          "negative values -- what the network's 3x3 convs actually read), zeros")
@@ -238,7 +276,7 @@ def main():
     if args.bn:
         return bench_bn(args)
     if args.layout:
-        return bench_gather(args) if args.layout == "gather" else bench_layout(args)
+        return {"gather": bench_gather, "series": bench_series}.get(args.layout, bench_layout)(args)
     if args.blas:
         return bench_blas(args)
     dev = torch.device("cuda:0")

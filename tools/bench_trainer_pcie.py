@@ -9,6 +9,8 @@ has its inputs resident in HBM; this is the number next to it (DESIGN.md section
 
 --dataset DIR (written by tools/make_patch_dataset.py): the same step fed by FlairDataModule from GeoTIFF patches on
 disk, gathered from the device-resident sample store (--cache device) or decoded and streamed per batch (--cache none).
+A dataset written with --sentinel2 adds the U-TAE branch; DIR/config says whether its series are averaged per period
+(one T: the captured step replays) and whether hardware.sample_cache_series lets them into the store.
 
 --augment: the same run with modalities.pre_processings.use_augmentation on (per-sample flips / rotations drawn by the
 trainer, applied inside the layout and label kernels).  --schemas picks the schemas to run and --repeat N runs each N
@@ -85,7 +87,10 @@ def run(schema: str, B: int, steps: int, warm: int = 10, augment: bool = False):
 def run_dataset(root: str, cache: str, B: int, steps: int, warm: int = 10):
     """the training step fed by FlairDataModule from the on-disk dataset tools/make_patch_dataset.py wrote under
     ``root``: cache='device' gathers every batch from the device-resident sample store, cache='none' decodes the
-    GeoTIFF patches per batch and streams the raw samples.  Aerial only, augmentation on, hipGraph step."""
+    GeoTIFF patches per batch and streams the raw samples.  Aerial, plus the Sentinel-2 branch when the dataset was
+    written with one (``--sentinel2``; DIR/config then says whether the series are averaged per period and whether
+    hardware.sample_cache_series lets them into the store); augmentation on, hipGraph step where the batches share
+    one T."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from make_patch_dataset import make_config
     from flair_hub.data.datamodule import FlairDataModule
@@ -93,11 +98,19 @@ def run_dataset(root: str, cache: str, B: int, steps: int, warm: int = 10):
     from flair_hub.tasks.module_setup import build_segmentation_module, get_input_img_sizes
     from flair_hub.tasks.trainers import HipTrainer
     csvs = {k: os.path.join(root, f"{k}.csv") for k in ("train", "val", "test")}
-    cfg = make_config(root, csvs, cache, B, 1, "bf16", dem=False)
+    written = {}
+    if os.path.isdir(os.path.join(root, "config")):
+        from flair_hub.utils.config_io import read_config
+        written = read_config(os.path.join(root, "config"))
+    s2 = bool(written.get("modalities", {}).get("inputs", {}).get("SENTINEL2_TS", False))
+    average = written.get("modalities", {}).get("pre_processings", {}).get("temporal_average_sentinel2") or None
+    series_cache = bool(written.get("hardware", {}).get("sample_cache_series", False))
+    cfg = make_config(root, csvs, cache, B, 1, "bf16", dem=False, sentinel2=s2, s2_average=average,
+                      cache_series=series_cache)
     cfg["tasks"]["predict"] = False
     tr_paths, va_paths, _ = get_datasets(cfg)
     dm = FlairDataModule(cfg, tr_paths, va_paths, None, num_workers=16, batch_size=B, drop_last=True,
-                         use_augmentations=True, cache=cache, device_prepare=True)
+                         use_augmentations=True, cache=cache, device_prepare=True, series_cache=series_cache)
     t0 = time.perf_counter()
     sizes = get_input_img_sizes(cfg, dm, "fit")
     fill_s = time.perf_counter() - t0
@@ -119,7 +132,8 @@ def run_dataset(root: str, cache: str, B: int, steps: int, warm: int = 10):
     tr = HipTrainer(max_epochs=-(-(warm + steps) // per_epoch), max_steps=warm + steps, hip_graph=True)
     tr.fit(task, train_dataloaders=dm.train_dataloader())
     dt = marks[warm + steps] - marks[warm]
-    return {"dataset": root, "cache": cache, "resident": dm.store is not None,
+    return {"dataset": root, "cache": cache, "resident": dm.store is not None, "sentinel2": s2,
+            "s2_average": average, "series_resident": dm.store is not None and bool(dm.store.series),
             "store_MB": round(dm.store.bytes / 2 ** 20, 1) if dm.store is not None else 0, "setup_s": round(fill_s, 2),
             "ms_per_step": round(dt / steps * 1e3, 3), "tiles_per_s": round(B * steps / dt, 1)}
 
