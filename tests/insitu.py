@@ -37,6 +37,7 @@ import torch.nn.functional as F
 REL = 2.0 ** -16          # f32 summation term, relative to the magnitude bound a
 AMBIG_REL = 2.0 ** -20    # |pre-activation| below this * (|x*s| + |t|): the ReLU mask may go either way
 AMBIG_MAX_FRACTION = 1e-4
+ADAM_K = 8                # roundings per quantity of the AdamW update, in units of 2^-24 (Checker.adamw counts them)
 F64 = torch.float64
 
 BCO_RING, BCO_THIN, BCO_STEM = 0x1000, 0x2000, 0x8000
@@ -562,7 +563,10 @@ class Checker:
             parts.append(_shift(_compare(o[b0:b1], r, ulp_stored(r, o.dtype) + REL * a, "y"), b0, o.shape))
         return self._add(call, _merge(parts, "y"))
 
-    def bn_bwd(self, call, x, dy, y, gamma, beta, mean, rstd, relu, dx, dres, dgamma, dbeta):
+    def bn_bwd(self, call, x, dy, y, gamma, beta, mean, rstd, relu, dx, dres, dgamma, dbeta, raw_x=False):
+        """raw_x: the sums came as (sum g, sum g*x) and the finalize formed dgamma = rstd * (sum g*x - mean * sum g)
+        (ffa_bn_bwd_partials): the summation term of dgamma is then stated in what was summed,
+        REL * rstd * (sum |g*x| + |mean| * sum |g|), which does not shrink where the two sums cancel."""
         C = x.shape[-1]
         mode = 0 if not relu else (1 if y is not None else 2)
         n = x.numel() // C
@@ -594,7 +598,7 @@ class Checker:
             sb += gm.reshape(-1, C).sum(0)
             sg += (gm * xh).reshape(-1, C).sum(0)
             ab += gm.abs().reshape(-1, C).sum(0)
-            ag += (gm * xh).abs().reshape(-1, C).sum(0)
+            ag += ((gm * xc).abs() if raw_x else (gm * xh).abs()).reshape(-1, C).sum(0)
             if amb is not None:
                 namb += int(amb.sum().item())
                 xb += torch.where(amb, dc.abs(), torch.zeros_like(dc)).reshape(-1, C).sum(0)
@@ -605,6 +609,8 @@ class Checker:
             if namb > AMBIG_MAX_FRACTION * x.numel():
                 self._add(call, {"what": "ambiguous ReLU masks", "shape": tuple(x.shape), "n": x.numel(), "fail": namb,
                                  "worst": float("inf"), "error": f"{namb} ambiguous of {x.numel()}"})
+        if raw_x:
+            ag = rs * (ag + mu.abs() * ab)
         t_b = REL * ab + xb + ulp_f32(sb)
         t_g = REL * ag + xg + ulp_f32(sg)
         self._add(call, dict(_compare(dbeta, sb, t_b, "dbeta"), ambiguous=namb))
@@ -630,6 +636,66 @@ class Checker:
         v = x.to(F64).reshape(-1, C)
         self._add(call, _compare(s, v.sum(0), REL * v.abs().sum(0), "sum"))
         self._add(call, _compare(q, (v * v).sum(0), REL * (v * v).sum(0), "sum of squares"))
+
+    # ---- optimizer -------------------------------------------------------------------------------
+
+    def adamw(self, call, p0, g, m0, v0, step, lr, p1, m1, v1, betas, eps, weight_decay, decoupled=True,
+              maximize=False):
+        """One tensor of ffa_adamw_multi (csrc/optim.hip): the update restated in float64 from the f32 p0, g, m0, v0, lr
+        and step the kernel received (eps and weight_decay as the f32 values its arguments hold; the betas are doubles
+        there), against the p1, m1, v1 it left, per element.
+
+        Bounds, u = 2^-24, ADAM_K = 8 roundings at most per quantity (the kernel forbids contraction, so every f32
+        operation rounds once; counted from the kernel, HIP's documented 1 ulp for sqrtf and the f32 divide as 2 u each):
+          g' = g + wd p  (Adam's L2 branch only)   wd p, the sum: 2        t_g = K u (|g| + wd |p|)
+          m  = m + b1w (g' - m)      b1w = f32(1 - beta1), the difference, the product, the sum: 4
+                                     t_m = ulp + K u (|m| + (1 - beta1)(|g'| + |m|)) + (1 - beta1) t_g
+          v  = b2 v + b2w g' g'      b2 and its product: 2 on b2 v; b2w and two products: 3 on b2w g'^2; the sum 1: 4 at most
+                                     t_v = ulp + K u v + (1 - beta2)(2 |g'| t_g + t_g^2)
+          den = sqrtf(v) / f32(sqrt(bc2)) + eps    sqrtf 2, the constant 1, the divide 2, the sum 1: 6
+                                     t_den = (sqrt(v + t_v) - sqrt(v)) / sqrt(bc2) + K u den
+          p  = p - lr wd p (AdamW) - f32(lr / bc1) m / den    lr wd, its product with p, the difference: 3 on a_p = |p| +
+               lr wd |p|;  the step size 1, its product with m 1, the divide 2, the difference 1: 5 on q = ss |m| / den
+                                     t_p = ulp + K u (a_p + q) + ss t_m / den + ss (|m| + t_m) t_den / (den den_lo)
+        The error of m, v and den is carried into p: |m'/den' - m/den| <= t_m / den + |m'| |den - den'| / (den den') with
+        |m'| <= |m| + t_m and den' >= den_lo = max(den - t_den, eps): the bound holds where g + wd p nearly cancels and den
+        comes down to eps, where the quotient magnifies the error of that sum."""
+        u, K = 2.0 ** -24, ADAM_K
+        b1, b2 = float(betas[0]), float(betas[1])
+        lr64 = float(torch.as_tensor(lr).to(torch.float32).reshape(()).item())
+        s = float(torch.as_tensor(step).reshape(()).item())
+        wd = float(torch.tensor(float(weight_decay), dtype=torch.float32).item())
+        ep = float(torch.tensor(float(eps), dtype=torch.float32).item())
+        p, gg, m, v = (t.detach().to(F64) for t in (p0, g, m0, v0))
+        if maximize:
+            gg = -gg
+        ap = p.abs()
+        t_g = torch.zeros_like(p)
+        if decoupled:
+            pd, a_p, ag = p - lr64 * wd * p, ap + lr64 * wd * ap, gg.abs()
+        else:
+            pd, a_p, ag = p, ap, gg.abs()
+            if wd != 0.0:
+                ag = ag + wd * ap
+                gg = gg + wd * p
+                t_g = K * u * ag
+        rm = m + (1 - b1) * (gg - m)
+        a_m = m.abs() + (1 - b1) * (ag + m.abs())
+        rv = b2 * v + (1 - b2) * gg * gg
+        bc1, bc2 = 1.0 - b1 ** s, 1.0 - b2 ** s
+        den = rv.sqrt() / bc2 ** 0.5 + ep
+        ss = lr64 / bc1
+        rp = pd - ss * rm / den
+        t_m = ulp_f32(rm) + K * u * a_m + (1 - b1) * t_g
+        t_v = ulp_f32(rv) + K * u * rv + (1 - b2) * (2 * gg.abs() * t_g + t_g * t_g)
+        t_den = ((rv + t_v).sqrt() - rv.sqrt()) / bc2 ** 0.5 + K * u * den
+        q = ss * rm.abs() / den
+        den_lo = torch.clamp(den - t_den, min=ep * (1 - K * u))  # the kernel's denominator is never below f32(eps)
+        t_p = ulp_f32(rp) + K * u * (a_p + q) + ss * t_m / den + ss * (rm.abs() + t_m) / (den * den_lo) * t_den
+        out = [self._add(call, _compare(p1.detach(), rp, t_p, "p")),
+               self._add(call, _compare(m1.detach(), rm, t_m, "exp_avg")),
+               self._add(call, _compare(v1.detach(), rv, t_v, "exp_avg_sq"))]
+        return out
 
     # ---- pooling, loss, layout -------------------------------------------------------------------
 

@@ -17,6 +17,10 @@ BatchNorm scale folded along the wrong axis or in another precision than the pac
 added after the ReLU, a zeroed row of a ragged tile, the higher label at an exact tie, a band off by one, a crop origin
 off by one, a quarter-turn view taken back with the forward code, a first view added where it should overwrite, a view
 count off by one.
+
+Last, the optimizer (Checker.adamw): an f32 emulation of ffa_adamw_multi must sit inside the bound at steps 1 .. 1e5 and
+gradient scales 1e-9 .. 10, and seven mutants must fail it: no bias correction of v or of m, beta1 as the lerp weight,
+decoupled and L2 decay exchanged, eps inside the square root, maximize ignored, another tensor's step count.
 """
 import pytest
 import torch
@@ -1160,3 +1164,109 @@ def test_planted_fault_at_an_edge_shape_is_flagged_and_what_the_per_tensor_bound
           f"{'passes' if old else 'fails'} the per-tensor bound")
     assert fails and fails[0]["what"] in ("out", "dx"), "the elementwise bound must flag the fault"
     assert old == old_passes
+
+
+# ---- AdamW / Adam (csrc/optim.hip) against Checker.adamw ---------------------------------------------------------------
+# An f32 torch emulation that rounds where the kernel rounds (f32 constants, every operation on its own, step size and
+# sqrt(bc2) formed in double and rounded once) must stay inside the bound at every step count and gradient scale; each
+# mutant of it must be flagged.  Step counts of the mutants are 20 or below: by step 1000 both bias corrections are 1
+# to f32 precision and leaving them out is honestly invisible.
+
+ADAM_LR, ADAM_BETAS, ADAM_N = 3e-3, (0.9, 0.95), 20000
+# (decoupled, weight_decay, maximize, eps)
+ADAM_KINDS = {
+    "adamw": (True, 0.02, False, 1e-8),
+    "adamw_max_eps1e-3": (True, 0.02, True, 1e-3),
+    "adamw_wd0": (True, 0.0, False, 1e-8),
+    "adam_l2": (False, 0.02, False, 1e-8),
+    "adam_l2_max_eps1e-3": (False, 0.02, True, 1e-3),
+    "adam_wd0_max": (False, 0.0, True, 1e-8),
+}
+ADAM_MUTANTS = ("no_bc2", "no_bc1", "lerp_beta1", "swapped_decay", "eps_in_sqrt", "maximize_ignored", "other_step")
+
+
+def _f32(x):
+    return torch.tensor(float(x), dtype=torch.float32)
+
+
+def _adam_f32(p, g, m, v, lr, betas, eps, wd, step, decoupled, maximize, mutant=None):
+    """the kernel's update in f32 torch, operation by operation -> (p, m, v)"""
+    import math
+    b1, b2 = betas
+    s = step if mutant != "other_step" else step + 1  # the neighbouring tensor's count (it skipped no step)
+    bc1 = 1.0 if mutant == "no_bc1" else 1.0 - b1 ** s
+    bc2 = 1.0 if mutant == "no_bc2" else 1.0 - b2 ** s
+    lr32 = _f32(lr)
+    step_size, bc2_sqrt = _f32(float(lr32) / bc1), _f32(math.sqrt(bc2))
+    b1w = _f32(b1 if mutant == "lerp_beta1" else 1.0 - b1)
+    b2f, b2w, wdf, epsf = _f32(b2), _f32(1.0 - b2), _f32(wd), _f32(eps)
+    p, g, m, v = p.clone(), g.clone(), m.clone(), v.clone()
+    if maximize and mutant != "maximize_ignored":
+        g = -g
+    dec = (not decoupled) if mutant == "swapped_decay" else decoupled
+    if dec:
+        p = p - lr32 * wdf * p
+    elif wd != 0:
+        g = g + wdf * p
+    m = m + b1w * (g - m)
+    v = b2f * v + b2w * g * g
+    if mutant == "eps_in_sqrt":
+        den = torch.sqrt(v / (bc2_sqrt * bc2_sqrt) + epsf)
+    else:
+        den = torch.sqrt(v) / bc2_sqrt + epsf
+    p = p - step_size * m / den
+    return p, m, v
+
+
+def _adam_inputs(step, seed):
+    """parameters of order 1, gradients of scale 1e-9 .. 10 (so that eps matters for some and not for others), exact
+    zeros among them, moments of the gradient's scale (zero before the first step)"""
+    g = torch.Generator().manual_seed(seed)
+    n = ADAM_N
+    p = torch.randn(n, generator=g)
+    scale = 10.0 ** torch.randint(-9, 2, (n,), generator=g).float()
+    gr = torch.randn(n, generator=g) * scale
+    gr[:50] = 0
+    if step > 1:
+        m, v = torch.randn(n, generator=g) * scale * 0.3, (torch.randn(n, generator=g) * scale) ** 2 * 0.5
+    else:
+        m, v = torch.zeros(n), torch.zeros(n)
+    return p, gr, m, v
+
+
+def _adam_check(kind, step, mutant=None, seed=1):
+    decoupled, wd, maximize, eps = ADAM_KINDS[kind]
+    p, gr, m, v = _adam_inputs(step, seed + step)
+    p1, m1, v1 = _adam_f32(p, gr, m, v, ADAM_LR, ADAM_BETAS, eps, wd, step, decoupled, maximize, mutant)
+    ck = Checker("full")
+    ck.adamw({"op": "adamw", "call": 0}, p, gr, m, v, torch.tensor(float(step)), _f32(ADAM_LR), p1, m1, v1, ADAM_BETAS,
+             eps, wd, decoupled, maximize)
+    return ck
+
+
+@pytest.mark.parametrize("step", [1, 2, 7, 20, 1000, 100000])
+@pytest.mark.parametrize("kind", sorted(ADAM_KINDS))
+def test_honest_adamw_emulation_passes(kind, step):
+    ck = _adam_check(kind, step)
+    assert [r["what"] for r in ck.results] == ["p", "exp_avg", "exp_avg_sq"]
+    print("\n" + "\n".join(r.line() for r in ck.results))
+    assert all(r.ok for r in ck.results), [r.line() for r in ck.results if not r.ok]
+    assert max(r["worst"] for r in ck.results) <= 0.5, "an exact f32 emulation must sit well inside a bound of 8 roundings"
+
+
+def _adam_mutant_applies(mutant, kind):
+    decoupled, wd, maximize, _ = ADAM_KINDS[kind]
+    return not ((mutant == "maximize_ignored" and not maximize) or (mutant == "swapped_decay" and wd == 0))
+
+
+@pytest.mark.parametrize("step", [1, 2, 7, 20])
+@pytest.mark.parametrize("mutant,kind", [(m, k) for m in ADAM_MUTANTS for k in sorted(ADAM_KINDS)
+                                         if _adam_mutant_applies(m, k)])
+def test_planted_adamw_fault_is_flagged(mutant, kind, step):
+    ck = _adam_check(kind, step, mutant)
+    bad = [r for r in ck.results if not r.ok]
+    print(f"\n{mutant} {kind} step {step}: " + "; ".join(r.line() for r in ck.results))
+    assert bad, f"{mutant} passed the float64 bound: " + "; ".join(r.line() for r in ck.results)
+    # the moments do not depend on the bias corrections, eps or the step count: only p may be flagged for those
+    if mutant in ("no_bc2", "no_bc1", "eps_in_sqrt", "other_step"):
+        assert {r["what"] for r in bad} == {"p"}, [r.line() for r in bad]

@@ -4,7 +4,9 @@ The benchmarked program (bf16 U-Net at 512 x 512) runs on kernels the fp32 model
 tile walks and re-packed operands the per-kernel tests never see.  Here the real step runs under a Recorder: every
 flairhip.ops call is compared with a float64 evaluation of the same operation on the call's own inputs, so a wrong
 tile, channel block or dropped partial shows up where it happens instead of drowning in the bf16 avalanche of a
-whole-model comparison.
+whole-model comparison.  The optimizer step is no ops function and the recorder does not see it: the eager step that
+precedes the recorded one snapshots p, g, exp_avg, exp_avg_sq, step and lr around HipAdamW.step() and holds every tensor to
+the float64 update (Checker.adamw); those results join the table (family "adamw") and the assertions.
 """
 import os
 import time
@@ -13,7 +15,7 @@ import pytest
 import torch
 
 from helpers import MOD, TASK, make_pair
-from insitu import Recorder
+from insitu import Checker, Recorder
 
 pytestmark = pytest.mark.gpu
 
@@ -79,7 +81,7 @@ def _checked_step(B, mode, seed, chunk, precision="bf16", hw=(TILE, TILE)):
     loss = task.training_step(batch, 0)
     opt.zero_grad(set_to_none=True)
     loss.backward()
-    opt.step()
+    adam = _checked_optimizer_step(task, opt)
     del loss
     opt.zero_grad(set_to_none=True)
     torch.cuda.synchronize()
@@ -87,7 +89,33 @@ def _checked_step(B, mode, seed, chunk, precision="bf16", hw=(TILE, TILE)):
         loss = task.training_step(batch, 1)
         loss.backward()
         torch.cuda.synchronize()
+    rec.results.extend(adam.results)  # the optimizer is no ops function: its checks join the table and the assertions here
     return task, rec, loss
+
+
+def _checked_optimizer_step(task, opt):
+    """opt.step() of the product's HipAdamW on the step's own gradients, every tensor against float64 (Checker.adamw):
+    p, g, exp_avg, exp_avg_sq, step and lr snapshotted around the call -> the checker holding the results"""
+    names = {id(p): n for n, p in task.model.named_parameters()}
+    before = []
+    for gi, grp in enumerate(opt.param_groups):
+        for p in grp["params"]:
+            if p.grad is None:
+                continue
+            st = opt.state.get(p, {})
+            before.append((gi, p, p.detach().clone(), p.grad.detach().clone(),
+                           st["exp_avg"].clone() if st else torch.zeros_like(p),
+                           st["exp_avg_sq"].clone() if st else torch.zeros_like(p)))
+    opt.step()
+    torch.cuda.synchronize()
+    ck = Checker("full")
+    for i, (gi, p, p0, g0, m0, v0) in enumerate(before):
+        grp, st = opt.param_groups[gi], opt.state[p]
+        ck.adamw({"op": "adamw", "family": "adamw", "call": f"adamw:{i}", "module": names.get(id(p), "?")}, p0, g0, m0, v0,
+                 st["step"], grp["lr"], p, st["exp_avg"], st["exp_avg_sq"], grp["betas"], grp["eps"], grp["weight_decay"],
+                 opt.decoupled, grp["maximize"])
+    assert len(ck.results) == 3 * len(before) > 0
+    return ck
 
 
 def _report_and_assert(task, rec, t0, required=REQUIRED_FAMILIES):
