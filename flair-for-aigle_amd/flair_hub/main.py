@@ -13,7 +13,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 
 from flair_hub.data.utils_data.paths import get_datasets  # noqa: E402
 from flair_hub.tasks.module_setup import build_data_module  # noqa: E402
-from flair_hub.tasks.stages import predict_stage, training_stage  # noqa: E402
+from flair_hub.tasks.stages import calibrate_stage, predict_stage, training_stage  # noqa: E402
 from flair_hub.utils.config_io import setup_environment  # noqa: E402
 
 logger = logging.getLogger(__name__)
@@ -30,6 +30,8 @@ def main(argv=None) -> None:
     state = None
     if config["tasks"]["train"]:
         state = training_stage(config, dm, out_dir)
+    if config["tasks"].get("calibrate", False):  # per-class thresholds from the validation split: best_thresholds.yaml
+        calibrate_stage(config, dm, out_dir, state)
     if config["tasks"].get("predict") or config["tasks"].get("metrics_only"):
         out_dir_predict = Path(out_dir, "results_" + config["paths"]["out_model_name"])
         out_dir_predict.mkdir(parents=True, exist_ok=True)

@@ -115,10 +115,39 @@ def validate_cog_overview_resampling(config: dict) -> str:
     return method.strip().lower()
 
 
+def validate_threshold_fallback(config: dict) -> int:
+    """The optional key threshold_fallback (default 18, raster_to_polygons' default background_value, so that rejected
+    pixels never become polygons): the label of a pixel at which no class reaches its calibrated threshold.  An int in
+    0..255, else ValueError."""
+    fallback = config.get("threshold_fallback", 18)
+    if isinstance(fallback, bool) or not isinstance(fallback, int) or not 0 <= fallback <= 255:
+        raise ValueError(f"threshold_fallback must be an integer in 0..255, got {fallback!r}")
+    return fallback
+
+
+def threshold_file(config: dict):
+    """The calibrated class thresholds in effect: the path in config["model_threshold_filepath"] (what prep_config
+    stores; flair_hub's calibrate stage writes the file, flairhip.calibration reads it), or None.  A path that does not
+    exist is warned about and ignored, as the reference's prepare_local_model_folder does with a model folder without
+    best_thresholds.yaml; so is a file next to output_type: class_prob, where there is no label to threshold."""
+    path = config.get("model_threshold_filepath")
+    if not path:
+        return None
+    if not os.path.isfile(str(path)):
+        logger.warning("threshold file %s does not exist: running without calibrated thresholds", path)
+        return None
+    if config.get("output_type", "argmax") != "argmax":
+        logger.warning("threshold file %s is not applied: thresholds apply to label output (output_type: argmax), not "
+                       "to %s", path, config.get("output_type"))
+        return None
+    return str(path)
+
+
 def validate_config(config: dict) -> None:
     for key in REQUIRED_KEYS:
         if key not in config:
             raise ValueError(f"Missing required config key: {key}")
+    validate_threshold_fallback(config)
     validate_write_confidence(config)
     validate_tta(config)
     validate_skip_tiles_outside_zone(config)

@@ -50,7 +50,8 @@ from flairhip import ops
 from flairhip.augment import tta_views
 from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_cog_conversion,
                                           validate_cog_overview_resampling, validate_config, validate_geozone_crs,
-                                          validate_skip_tiles_outside_zone, validate_tta, validate_write_confidence)
+                                          threshold_file, validate_skip_tiles_outside_zone, validate_threshold_fallback,
+                                          validate_tta, validate_write_confidence)
 from flair_zonal_detection.dataset import MultiModalSlicedDataset, TileBatcher, pad_series_collate
 from flair_zonal_detection.model_utils import build_inference_model, compute_patch_sizes
 from flair_zonal_detection.postprocess import convert, convert_to_cog  # noqa: F401  (re-exported like the reference)
@@ -274,10 +275,30 @@ def inference_and_write(model: torch.nn.Module, dataloader: DataLoader, tiles_gd
     graphed = None  # hipGraph of forward + conversion for full batches (the eval forward is ~120 launches)
     use_graph = bool(config.get("hip_graph", True)) and str(device).startswith("cuda")
 
+    # calibrated class thresholds (config["model_threshold_filepath"], flairhip.calibration): read and uploaded once per
+    # task, at the first forward (the eager warm-up of a graphed run); the labels -- and the confidence plane -- then
+    # come from the thresholded entries, same shapes and dtypes.  Without a file the calls are the plain ones.
+    thr_path = threshold_file(config)
+    fallback = validate_threshold_fallback(config)
+    thr_dev: Dict[str, torch.Tensor] = {}
+
+    def thresholds(task_name, classes):
+        thr = thr_dev.get(task_name)
+        if thr is None:
+            from flairhip.calibration import read_thresholds
+            thr = thr_dev[task_name] = torch.from_numpy(read_thresholds(thr_path, classes, task=task_name)
+                                                        ["thresholds_u8"]).to(device)
+        return thr
+
     def forward_eager(inputs):
         logits_tasks, _ = model(inputs)
         preds = {}
         for task_name, logits in logits_tasks.items():
+            if thr_path is not None:
+                preds[task_name] = ops.predict_thresholded_u8(
+                    logits._ffa_nhwc, logits._ffa_classes, predict_mode, thresholds(task_name, logits._ffa_classes),
+                    fallback, crop=(margin, margin, keep, keep))
+                continue
             preds[task_name] = ops.predict_u8(logits._ffa_nhwc, logits._ffa_classes, predict_mode,
                                               crop=(margin, margin, keep, keep))
         return preds
@@ -304,6 +325,10 @@ def inference_and_write(model: torch.nn.Module, dataloader: DataLoader, tiles_gd
                     accs[task_name] = ops.tta_buffer(nhwc.shape[0], classes, keep, keep, nhwc.device, cp=nhwc.shape[3])
                 ops.tta_accumulate_(accs[task_name], nhwc, classes, code, crop=(margin, margin, keep, keep),
                                     first=v == 0)
+        if thr_path is not None:
+            return {task_name: ops.tta_predict_thresholded_u8(acc, predict_mode, len(views),
+                                                              thresholds(task_name, acc._ffa_classes), fallback)
+                    for task_name, acc in accs.items()}
         return {task_name: ops.tta_predict_u8(acc, predict_mode, len(views)) for task_name, acc in accs.items()}
 
     forward = forward_tta if len(views) > 1 else forward_eager

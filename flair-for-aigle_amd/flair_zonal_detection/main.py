@@ -121,6 +121,14 @@ def build_parser() -> argparse.ArgumentParser:
                              "geozone_crs, else the raster's CRS (no reprojection)")
     parser.add_argument("--target-crs", type=str, default=None, metavar="EPSG:NNNN",
                         help="with --polygons: write the polygons in this CRS (e.g. EPSG:4326) instead of the raster's")
+    parser.add_argument("--thresholds", type=str, default=None, metavar="FILE",
+                        help="calibrated class thresholds (best_thresholds.yaml, written by flair_hub's calibrate "
+                             "stage): a class takes a pixel only where its score reaches its threshold, the best "
+                             "passing class wins, and a pixel no class passes at gets the fallback label.  Default: the "
+                             "config key model_threshold_filepath, else none")
+    parser.add_argument("--threshold-fallback", type=int, default=None, metavar="N",
+                        help="the label (0..255) of a pixel at which no class reaches its threshold.  Default: the "
+                             "config key threshold_fallback, else 18")
     return parser
 
 
@@ -149,9 +157,15 @@ def main(argv=None) -> None:
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     config = args.config
-    if args.cog or args.tta is not None:  # the keys, for this run only
-        from flair_zonal_detection.config import load_config
+    if args.threshold_fallback is not None and not 0 <= args.threshold_fallback <= 255:
+        parser.error(f"--threshold-fallback expects an integer in 0..255, got {args.threshold_fallback}")
+    if args.cog or args.tta is not None or args.thresholds is not None or args.threshold_fallback is not None:
+        from flair_zonal_detection.config import load_config  # the keys, for this run only
         config = load_config(args.config)
+        if args.thresholds is not None:
+            config["model_threshold_filepath"] = args.thresholds
+        if args.threshold_fallback is not None:
+            config["threshold_fallback"] = args.threshold_fallback
         if args.cog:
             config["cog_conversion"] = True
         if args.tta is not None:

@@ -214,6 +214,13 @@ SERIES_SIGNATURES = {
     "ffa_gather_series": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _p]),
 }
 
+# the prototypes of include/flairhip_calib.h (calibrated class thresholds), which include/flairhip.h brings along
+CALIB_SIGNATURES = {
+    "ffa_calib_hist": (_i, [_i, _p, _p, _ll, _i, _i, _p, _p]),
+    "ffa_predict_thresholded_u8": (_i, [_i, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "ffa_tta_predict_thresholded_u8": (_i, [_i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+}
+
 _lib = None
 
 
@@ -231,7 +238,8 @@ def load() -> C.CDLL:
     # every launch fails with "no ROCm-capable device is detected"
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES, **GATHER_SIGNATURES, **SERIES_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES, **GATHER_SIGNATURES, **SERIES_SIGNATURES,
+                              **CALIB_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args

@@ -1241,6 +1241,84 @@ def eval_stats(logits_nhwc: torch.Tensor, targets_u8: torch.Tensor, num_classes:
 
 
 # --------------------------------------------------------------------------------------------------
+# calibrated class thresholds (csrc/calibration.hip; the host side is flairhip.calibration)
+
+def calib_hist(logits_nhwc: torch.Tensor, targets_u8: torch.Tensor, num_classes: int,
+               hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The score histograms of NHWC logits [..., Cp] against uint8 targets: int64 [K, 2, 256] on the logits' device,
+    hist[k, t == k, q_k] += 1 for every pixel with target t < K and every class k, q_k the byte predict_u8 'class_prob'
+    writes for class k at the pixel.  ``hist`` is updated in place when given, else a zeroed one is made.  Integer
+    counts: equal inputs give equal bytes.  No host synchronisation."""
+    lib = _l.load()
+    _chk_nhwc(logits_nhwc, "logits")
+    if targets_u8.dtype != torch.uint8 or not targets_u8.is_contiguous():
+        raise ValueError("calib_hist: targets must be contiguous uint8 class indices")
+    cp = logits_nhwc.shape[-1]
+    npix = logits_nhwc.numel() // cp
+    dev = logits_nhwc.device
+    if targets_u8.numel() != npix or targets_u8.device != dev:
+        raise ValueError("calib_hist: targets and logits must hold the same pixels on one device")
+    k = int(num_classes)
+    if hist is None:
+        hist = torch.zeros((k, 2, 256), dtype=torch.int64, device=dev)
+    elif not (hist.dtype == torch.int64 and tuple(hist.shape) == (k, 2, 256) and hist.is_contiguous()
+              and hist.device == dev):
+        raise ValueError(f"calib_hist: hist must be a contiguous int64 [{k}, 2, 256] tensor on {dev}")
+    _l.check(lib.ffa_calib_hist(_dt(logits_nhwc), logits_nhwc.data_ptr(), targets_u8.data_ptr(), npix, k, cp,
+                                hist.data_ptr(), _stream()), "calib_hist")
+    return hist
+
+
+_THRESHOLDED_MODES = {"argmax": 0, "argmax_conf": 2}
+
+
+def _chk_thresholds(thr: torch.Tensor, k: int, fallback: int, mode: str, device, op: str) -> int:
+    if mode not in _THRESHOLDED_MODES:
+        raise ValueError(f"{op}: thresholds apply to 'argmax' and 'argmax_conf' output, not to {mode!r}")
+    if not (torch.is_tensor(thr) and thr.dtype == torch.uint8 and thr.dim() == 1 and thr.is_contiguous()
+            and thr.device == device):
+        raise ValueError(f"{op}: the thresholds must be a contiguous uint8 vector on {device}")
+    if thr.numel() != k:
+        raise ValueError(f"{op}: {thr.numel()} thresholds for {k} classes")
+    if isinstance(fallback, bool) or not isinstance(fallback, int) or not 0 <= fallback <= 255:
+        raise ValueError(f"{op}: fallback must be an int in 0..255, got {fallback!r}")
+    return _THRESHOLDED_MODES[mode]
+
+
+def predict_thresholded_u8(logits: torch.Tensor, num_classes: int, mode: str, thr: torch.Tensor, fallback: int,
+                           crop: Optional[Tuple[int, int, int, int]] = None) -> torch.Tensor:
+    """predict_u8's 'argmax' / 'argmax_conf' outputs under per-class thresholds ``thr`` (uint8 [K] on the device): class
+    k passes where its 'class_prob' byte is >= thr[k]; the label is the passing class with the greatest logit (lowest
+    index on a tie), ``fallback`` where none passes; the confidence plane holds the chosen class's byte, 0 where
+    nothing passed.  All thresholds 0: predict_u8's outputs byte for byte."""
+    lib = _l.load()
+    _chk_nhwc(logits, "logits")
+    m = _chk_thresholds(thr, int(num_classes), fallback, mode, logits.device, "predict_thresholded_u8")
+    B, H, W, cp = logits.shape
+    y0, x0, h, w = crop if crop is not None else (0, 0, H, W)
+    out = torch.empty((B, h, w) if m == 0 else (B, 2, h, w), dtype=torch.uint8, device=logits.device)
+    _l.check(lib.ffa_predict_thresholded_u8(_dt(logits), m, logits.data_ptr(), thr.data_ptr(), fallback,
+                                            out.data_ptr(), B, H, W, int(num_classes), cp, y0, x0, h, w, _stream()),
+             "predict_thresholded_u8")
+    return out
+
+
+def tta_predict_thresholded_u8(acc: torch.Tensor, mode: str, views: int, thr: torch.Tensor, fallback: int,
+                               num_classes: Optional[int] = None) -> torch.Tensor:
+    """predict_thresholded_u8's outputs from an accumulator of ``views`` views: the rule on acc / views, with the
+    bytes of tta_predict_u8 'class_prob'.  With one identity view they equal predict_thresholded_u8's bit for bit."""
+    lib = _l.load()
+    _chk_tta_views(views, "tta_predict_thresholded_u8")
+    k = _chk_tta_acc(acc, num_classes, "tta_predict_thresholded_u8")
+    m = _chk_thresholds(thr, k, fallback, mode, acc.device, "tta_predict_thresholded_u8")
+    B, h, w, cp = acc.shape
+    out = torch.empty((B, h, w) if m == 0 else (B, 2, h, w), dtype=torch.uint8, device=acc.device)
+    _l.check(lib.ffa_tta_predict_thresholded_u8(m, acc.data_ptr(), thr.data_ptr(), fallback, out.data_ptr(), B, k, cp,
+                                                h, w, views, _stream()), "tta_predict_thresholded_u8")
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # host-side tile bookkeeping (no GPU involved)
 
 def slice_grid(min_x, min_y, max_x, max_y, ref_left, ref_bottom, patch_size: int, margin: int, resolution: float):

@@ -514,6 +514,10 @@ int ffa_confusion_matrix(const uint8_t* pred, const uint8_t* target, long long n
 /* The ragged time-series store (the padded U-TAE batch and its pad flags gathered by index from series of variable
  * length resident on the device) is declared in flairhip_series.h, likewise. */
 #include "flairhip_series.h"
+/* Calibrated class thresholds (per-class histograms of the score bytes over a validation split, and the label /
+ * confidence outputs of ffa_predict_u8 and ffa_tta_predict_u8 under per-class thresholds) are declared in
+ * flairhip_calib.h, likewise. */
+#include "flairhip_calib.h"
 
 /* ---- host-side tile bookkeeping, bit-exact with the reference's float64 arithmetic
  *      (flair_zonal_detection/slicing.py:51-112, flair_zonal_detection/inference.py:318-335) -------- */

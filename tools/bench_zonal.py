@@ -18,6 +18,8 @@ the tiles).
 --tta flips|d4: the tile loop with the config key tta (V forward passes per batch, probabilities averaged in the tile's
 frame), after the kernels of that path alone at the loop's shapes: ffa_tta_accumulate for an even-k and an odd-k view
 and ffa_tta_predict_u8 (hip events over queued calls, best of 3 after a warm-up), with the bytes each moves per second.
+--thresholds FILE: the tile loop with calibrated class thresholds in effect (the thresholded label kernels in place of
+ffa_predict_u8 / ffa_tta_predict_u8); 'flat:T' stands for a file of 19 thresholds T.
 """
 from __future__ import annotations
 
@@ -165,6 +167,9 @@ def main():
                     help="run the tile loop with write_confidence: true (argmax output only)")
     ap.add_argument("--tta", default=None, choices=["flips", "d4"],
                     help="run the tile loop with the config key tta, after timing the kernels of that path alone")
+    ap.add_argument("--thresholds", default=None, metavar="FILE",
+                    help="run the tile loop with calibrated class thresholds (config key model_threshold_filepath; "
+                         "'flat:T' writes a file of 19 thresholds T first)")
     ap.add_argument("--zone", action="store_true",
                     help="time the tile loop under a geozone with skip_tiles_outside_zone off and on")
     ap.add_argument("--cog", action="store_true",
@@ -214,6 +219,12 @@ def main():
                "monotemp_arch": args.arch})
     if args.write_confidence:
         zc["write_confidence"] = True
+    if args.thresholds:
+        path = args.thresholds
+        if path.startswith("flat:"):
+            from flairhip.calibration import write_thresholds
+            path = write_thresholds("/tmp/bench_zonal_thresholds.yaml", [int(path[5:])] * 19, task=TASK)
+        zc["model_threshold_filepath"] = path
     if args.tta:
         bench_tta_kernels(args.batch, args.precision,
                           "argmax_conf" if args.write_confidence else args.output_type)
@@ -256,6 +267,8 @@ def main():
     dt = time.time() - t0
     ntiles = ((H + 80 + 431) // 432) ** 2
     what = f"run_inference with tta {args.tta}" if args.tta else "run_inference"
+    if args.thresholds:
+        what += f" with thresholds {args.thresholds}"
     print(f"{what} on {H}x{W} px ({ntiles} tiles of 512, batch {args.batch}): {dt:.2f} s = {ntiles / dt:.1f} tiles/s, "
           f"{H * W / dt / 1e6:.1f} Mpx/s; output {out[TASK].data.shape}")
 
