@@ -7,9 +7,9 @@
 // batch (flair_hub/tasks/tasks_module.py:280-300); its test stage takes argmax and the confusion matrix on the host
 // (flair_hub/writer/prediction_writer.py).
 //
-// The per-pixel arithmetic is softmax_ce_kernel's (f32: maximum, __expf(z - m), sum in class order, __logf(se)) except
-// for the target's term, taken as z_t - m itself where that kernel takes __logf(__expf(z_t - m)): the two agree to an f32
-// rounding until the exponential underflows, 87 below the maximum, where the latter is -inf and this one still right.
+// The per-pixel arithmetic is softmax_ce_kernel's (f32: maximum, __expf(z - m), sum in class order, __logf(se), the
+// target's term as z_t - m itself, kept from before the exponentials: __logf(__expf(z_t - m)) would be -inf once the
+// exponential underflows, 87 below the maximum).
 // The thread <-> pixel assignment is that of softmax_ce_tiled_kernel, whose staging
 // of the logits through LDS in memory order is reused: a thread that owns a 64-byte pixel otherwise touches 32 cache
 // lines per wave instruction.
@@ -126,8 +126,8 @@ eval_stats_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ tgt,
               se += __expf(d);
             }
           }
-          // -log softmax[t] = log(se) - (z_t - m).  softmax_ce_kernel takes the second term as __logf(__expf(z_t - m)),
-          // which is -inf once z_t lies 87 below the maximum (an untrained model does that): the sum of a class would
+          // -log softmax[t] = log(se) - (z_t - m), as in softmax_ce_kernel.  Taken as __logf(__expf(z_t - m)) the second
+          // term is -inf once z_t lies 87 below the maximum (an untrained model does that): the sum of a class would
           // be inf where the loss of the pixel is a finite 87.  The difference itself is exact to an f32 rounding.
           acc[t * FFA_EVAL_THREADS + tid] += __logf(se) - dt;  // this thread's own cell
         }

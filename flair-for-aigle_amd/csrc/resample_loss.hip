@@ -366,23 +366,23 @@ softmax_ce_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ tgt,
         am = k;
       }
     }
-    float se = 0.f;
+    const int t = tgt[i];
+    const float wt = (t < K) ? w[t] : 0.f;
+    // -log softmax[t] = log(se) - (z_t - m).  d_t = z_t - m is kept from before the exponentials: taken back out of
+    // z[t] = exp(z_t - m) as a logarithm it is -inf once the target lies about 87 below the maximum, where the
+    // exponential underflows, and one confidently wrong pixel made the loss +inf (eval_stats_kernel does the same)
+    float se = 0.f, dt = 0.f;
 #pragma unroll
     for (int k = 0; k < FFA_CE_MAXK; ++k) {
       if (k < K) {
-        z[k] = __expf(z[k] - m);
+        const float d = z[k] - m;
+        if (k == t) dt = d;
+        z[k] = __expf(d);
         se += z[k];
       }
     }
-    const int t = tgt[i];
-    const float wt = (t < K) ? w[t] : 0.f;
     const float inv = 1.f / se;
-    // -log softmax[t] = log(se) - (z_t - m); z[k] now holds exp(z_k - m)
-    float zt = 1.f;
-#pragma unroll
-    for (int k = 0; k < FFA_CE_MAXK; ++k)
-      if (k == t) zt = z[k];
-    if (wt != 0.f) lsum += wt * (__logf(se) - __logf(zt));
+    if (wt != 0.f) lsum += wt * (__logf(se) - dt);  // z[k] now holds exp(z_k - m), for the gradient
     if (pred) pred[i] = (uint8_t)am;
     if (dlogits) {
       const float c = wt * gs;
@@ -503,22 +503,20 @@ softmax_ce_tiled_kernel(const T* __restrict__ logits, const uint8_t* __restrict_
           am = k;
         }
       }
-      float se = 0.f;
+      const int t = tgt[i];
+      const float wt = (t < K) ? w[t] : 0.f;
+      float se = 0.f, dt = 0.f;  // d_t = z_t - m, kept from before the exponentials (softmax_ce_kernel)
 #pragma unroll
       for (int k = 0; k < FFA_CE_MAXK; ++k) {
         if (k < K) {
-          z[k] = __expf(z[k] - m);
+          const float d = z[k] - m;
+          if (k == t) dt = d;
+          z[k] = __expf(d);
           se += z[k];
         }
       }
-      const int t = tgt[i];
-      const float wt = (t < K) ? w[t] : 0.f;
       const float inv = 1.f / se;
-      float zt = 1.f;
-#pragma unroll
-      for (int k = 0; k < FFA_CE_MAXK; ++k)
-        if (k == t) zt = z[k];
-      if (wt != 0.f) lsum += wt * (__logf(se) - __logf(zt));
+      if (wt != 0.f) lsum += wt * (__logf(se) - dt);
       if (pred) pred[i] = (uint8_t)am;
       if (dlogits) {
         const float c = wt * gs;

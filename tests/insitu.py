@@ -763,6 +763,16 @@ class Checker:
                 pk = pred[b0:b1].long()
                 ok = (pk < K) & (torch.gather(zb, -1, pk.clamp(max=K - 1).unsqueeze(-1)).squeeze(-1) == zb.max(-1).values)
                 parts_p.append(_shift(_exact_zero((~ok).to(torch.int8), "pred is a maximiser"), b0, pred.shape))
+        if tot_w == 0.0:
+            # no pixel counts: the weighted mean is 0 / 0, NaN in torch.nn.CrossEntropyLoss and here; the label and the
+            # gradient's pad channels are still defined, the gradient itself (0 * inf) is not
+            self._add(call, _exact_zero(wsum, "wsum without a counted pixel"))
+            self._add(call, _exact_zero((~loss.isnan()).to(torch.int8), "loss is NaN without a counted pixel"))
+            if parts_p:
+                self._add(call, _merge(parts_p, "pred"))
+            if dlogits is not None and Cp > K:
+                self._add(call, _exact_zero(dlogits[..., K:], "dlogits pad channels"))
+            return
         self._add(call, _compare(wsum, torch.tensor([tot_w], dtype=F64, device=wsum.device),
                                  torch.tensor([REL * tot_w], dtype=F64, device=wsum.device), "wsum"))
         self._add(call, _compare(loss, torch.tensor([tot_l / tot_w], dtype=F64, device=loss.device),
@@ -883,10 +893,23 @@ class Checker:
         return self._add(call, _compare(db, r, REL * abs_sums[:K] + ulp_f32(r), "bias gradient from the loss sums"))
 
     def confusion(self, call, before, after, pred, target):
+        """after = before + one count per pixel at [target, pred]; a pixel whose target or prediction is >= K (an
+        ignored label, a label of a wider class set) contributes nothing: the kernel's contract (csrc/resample_loss.hip)"""
         K = before.shape[0]
-        idx = target.reshape(-1).long() * K + pred.reshape(-1).long()
+        t, p = target.reshape(-1).long(), pred.reshape(-1).long()
+        if t.numel() != p.numel():
+            raise ValueError(f"{p.numel()} predictions for {t.numel()} targets")
+        valid = (t < K) & (p < K)
+        idx = t[valid] * K + p[valid]
         r = before + torch.bincount(idx, minlength=K * K).view(K, K).to(before.device)
         self._add(call, _exact_zero((after != r).to(torch.int8), "counts"))
+
+    def onehot_to_index(self, call, onehot, out):
+        """out [B,H,W] uint8 = the first maximum over the class axis of onehot [B,K,H,W]: no tolerance"""
+        z = onehot.to(F64).permute(0, 2, 3, 1)
+        if tuple(out.shape) != tuple(z.shape[:-1]):
+            raise ValueError(f"indices of shape {tuple(out.shape)} for a one-hot map {tuple(onehot.shape)}")
+        self._add(call, _exact_zero((out.long() != first_max(z)).to(torch.int8), "index"))
 
 
     # ---- the eval step: folded BatchNorm, uint8 outputs, test-time augmentation ------------------
@@ -1384,6 +1407,10 @@ class Recorder(Checker):
     def _op_confusion_matrix_update(self, call, a, live, out):
         call["family"] = "confusion_matrix"
         self.confusion(call, a["counts"], live["counts"], a["pred"], a["target"])
+
+    def _op_onehot_to_index(self, call, a, live, out):
+        call["family"] = "onehot_to_index"
+        self.onehot_to_index(call, a["onehot"], out)
 
     def _op_bn_eval_params(self, call, a, live, out):
         call["family"] = "bn_eval_params"

@@ -1270,3 +1270,142 @@ def test_planted_adamw_fault_is_flagged(mutant, kind, step):
     # the moments do not depend on the bias corrections, eps or the step count: only p may be flagged for those
     if mutant in ("no_bc2", "no_bc1", "eps_in_sqrt", "other_step"):
         assert {r["what"] for r in bad} == {"p"}, [r.line() for r in bad]
+
+
+# --------------------------------------------------------------------------------------------------
+# the loss, resampling and label kernels at their edges (tests/test_loss_edges_gpu.py runs the real ones): an f32
+# emulation of softmax_ce_kernel on the wide-logit table, pad channels, ignored labels, the 2 x 2 sum of the upsample
+# backward, a weight sum of zero, the one-hot index
+
+LK, LCP = 19, 32
+
+
+def _ce_f32(logits, t, cw, K, gs=1.0, target_term="difference", pad="zero"):
+    """csrc/resample_loss.hip's per-pixel arithmetic in f32 torch ops -> (loss, wsum, dlogits, pred, sums).
+    target_term: "difference" keeps z_t - m from before the exponentials; "log_of_exp" takes it back out of
+    exp(z_t - m) as a logarithm.  pad: "zero" writes zeros to the gradient's pad channels, "leak" 0 * the logit."""
+    Cp = logits.shape[-1]
+    z = logits[..., :K].float()
+    tl = t.long()
+    tc = tl.clamp(max=K - 1)
+    wp = cw.float()[tc] * (tl < K)
+    m = z.max(-1, keepdim=True).values
+    d = z - m
+    e = torch.exp(d)
+    se = e.sum(-1)
+    if target_term == "difference":
+        term = torch.log(se) - d.gather(-1, tc.unsqueeze(-1)).squeeze(-1)
+    else:
+        term = torch.log(se) - torch.log(e.gather(-1, tc.unsqueeze(-1)).squeeze(-1))
+    wsum = wp.sum()
+    loss = (wp * term)[wp != 0].sum() / wsum
+    dl = (gs * wp / wsum).unsqueeze(-1) * (e / se.unsqueeze(-1) - F.one_hot(tc, K))
+    padding = torch.zeros(*z.shape[:-1], Cp - K) if pad == "zero" else 0.0 * logits[..., K:].float()
+    dl = torch.cat([dl, padding], -1).to(logits.dtype)
+    pred = insitu.first_max(z.double()).to(torch.uint8)
+    return loss.reshape(1), wsum.reshape(1), dl, pred, dl.float().reshape(-1, Cp).sum(0)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("S", [176, 1000])
+def test_a_target_term_taken_as_the_log_of_an_underflowed_exponential_is_flagged(S, dt):
+    """the wide-logit input of tests/test_loss_edges_gpu.py: the target of some pixels lies S below the maximum, where
+    exp(z_t - m) is 0 in f32.  log(exp(z_t - m)) is then -inf and the loss +inf: flagged; z_t - m itself passes."""
+    from test_loss_edges_gpu import wide_case, wide_preconditions
+    z, t, cw, _, _ = wide_case(S, "target", LK, LCP, dt, 0.0, "cpu")
+    wide_preconditions(z, t, cw, LK, (1.0,))
+    for term, want_bad in (("difference", set()), ("log_of_exp", {"loss"})):
+        out = _ce_f32(z, t, cw, LK, target_term=term)
+        assert bool(out[0].isinf().all()) == bool(want_bad)
+        ck = Checker("full", chunk=1)
+        ck.softmax_ce({"op": "softmax_ce"}, z, t, cw, LK, None, out)
+        bad = {r["what"] for r in ck.results if not r.ok}
+        assert bad == want_bad, (term, [r.line() for r in ck.results if not r.ok])
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+def test_a_gradient_that_lets_a_nan_pad_channel_through_is_flagged(dt):
+    from test_loss_edges_gpu import GARBAGE, wide_case
+    z, t, cw, _, _ = wide_case(0, "other", LK, LCP, dt, 0.0, "cpu")
+    z = z.clone()
+    z[..., LK:] = torch.tensor(GARBAGE).to(dt)[torch.arange(z[..., LK:].numel()).reshape(z[..., LK:].shape) % len(GARBAGE)]
+    for pad, want_bad in (("zero", set()), ("leak", {"dlogits exact zeros", "per-class sums of the stored dlogits"})):
+        ck = Checker("full", chunk=1)
+        ck.softmax_ce({"op": "softmax_ce"}, z, t, cw, LK, None, _ce_f32(z, t, cw, LK, pad=pad))
+        bad = {r["what"] for r in ck.results if not r.ok}
+        assert ("dlogits exact zeros" in bad) == bool(want_bad) and bad <= want_bad, [r.line() for r in ck.results if not r.ok]
+
+
+def test_a_weight_sum_of_zero_is_a_nan_loss_and_nothing_about_the_gradient():
+    g = torch.Generator().manual_seed(5)
+    z = F.pad(torch.randn(1, 1, 257, LK, generator=g) * 3, (0, LCP - LK))
+    t = torch.full((1, 1, 257), 2, dtype=torch.uint8)
+    cw = torch.ones(LK)
+    cw[2] = 0.0
+    assert bool(F.cross_entropy(z[..., :LK].reshape(-1, LK).double(), t.reshape(-1).long(), weight=cw.double()).isnan())
+    loss, wsum, dl, pred, _ = _ce_f32(z, t, cw, LK)
+    assert bool(loss.isnan()) and wsum.item() == 0.0 and bool(dl[..., :LK].isnan().all())
+    cases = {"honest": (loss, wsum, dl, pred), "zero loss": (torch.zeros(1), wsum, dl, pred),
+             "counted": (loss, torch.ones(1), dl, pred), "label": (loss, wsum, dl, (pred + 1) % LK),
+             "pad": (loss, wsum, torch.full_like(dl, float("nan")), pred)}
+    for name, out in cases.items():
+        ck = Checker("full", chunk=1)
+        ck.softmax_ce({"op": "softmax_ce"}, z, t, cw, LK, None, out)
+        assert len(ck.results) == 4 and all(r.ok for r in ck.results) == (name == "honest"), \
+            (name, [r.line() for r in ck.results])
+
+
+def test_confusion_takes_labels_beyond_the_class_count_as_contributing_nothing():
+    g = torch.Generator().manual_seed(6)
+    K, n = 13, 4099
+    t = torch.randint(0, K, (n,), generator=g).to(torch.uint8)
+    p = torch.randint(0, K, (n,), generator=g).to(torch.uint8)
+    t[::31] = 255
+    t[5::97] = K
+    p[7::53] = K + 2
+    before = torch.randint(0, 9, (K, K), generator=g)
+    valid = (t < K) & (p < K)
+    honest = before + torch.bincount(t[valid].long() * K + p[valid].long(), minlength=K * K).view(K, K)
+    # the planted defect: an ignored target counted in the last row
+    tv = t.long().clamp(max=K - 1)[p < K]
+    counted = before + torch.bincount(tv * K + p[p < K].long(), minlength=K * K).view(K, K)
+    assert not torch.equal(honest, counted)
+    for after, ok in ((honest, True), (counted, False), (before, False)):
+        ck = Checker("full", chunk=1)
+        ck.confusion({"op": "confusion_matrix_update"}, before, after, p, t)
+        assert [r.ok for r in ck.results] == [ok], [r.line() for r in ck.results]
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+def test_upsample_backward_sum_through_bf16_is_flagged(dt):
+    """dlo = the sum of four children: held to ulp_stored(r) + REL * sum |child|.  A kernel that takes the sum through
+    bf16 -- each child of an f32 tensor rounded to bf16 first; for a bf16 tensor the running sum rounded after every
+    child -- is flagged."""
+    g = torch.Generator().manual_seed(7)
+    Bn, Hl, Wl, c1, c2 = 3, 9, 17, 24, 40
+    dcat = torch.randn(Bn, 2 * Hl, 2 * Wl, c1 + c2, generator=g).to(dt)
+    kids = dcat[..., :c1].float().reshape(Bn, Hl, 2, Wl, 2, c1).permute(2, 4, 0, 1, 3, 5).reshape(4, Bn, Hl, Wl, c1)
+    honest = (kids[0] + kids[1] + kids[2] + kids[3]).to(dt)
+    if dt == torch.float32:
+        through = _bf(kids[0]) + _bf(kids[1]) + _bf(kids[2]) + _bf(kids[3])
+    else:
+        through = _bf(_bf(_bf(kids[0] + kids[1]) + kids[2]) + kids[3]).to(dt)
+    rec = insitu.Recorder(None, "full", chunk=1)
+    for dlo, ok in ((honest, True), (through, False)):
+        n0 = len(rec.results)
+        rec._op_upsample2x_concat_bwd({"op": "upsample2x_concat_bwd"}, {"dcat": dcat, "c1": c1}, None,
+                                      (dlo, dcat[..., c1:]))
+        res = rec.results[n0:]
+        assert [r["what"] for r in res] == ["dlo", "dskip"] and res[1].ok and res[0].ok == ok, [r.line() for r in res]
+
+
+def test_onehot_to_index_is_held_to_the_first_maximum():
+    g = torch.Generator().manual_seed(8)
+    oh = torch.randint(-1, 3, (2, 7, 5, 9), generator=g).float()
+    first = insitu.first_max(oh.permute(0, 2, 3, 1).double()).to(torch.uint8)
+    last = (6 - insitu.first_max(oh.flip(1).permute(0, 2, 3, 1).double())).to(torch.uint8)
+    assert not torch.equal(first, last)
+    for out, ok in ((first, True), (last, False)):
+        ck = Checker("full", chunk=1)
+        ck.onehot_to_index({"op": "onehot_to_index"}, oh, out)
+        assert [r.ok for r in ck.results] == [ok]
