@@ -58,6 +58,28 @@ def compute_metrics(confmat: np.ndarray, config: Dict[str, Any], task: str) -> D
     }
 
 
+def compute_and_save_object_metrics(counts: np.ndarray, iou_sums: np.ndarray, config: Dict[str, Any], output_dir: str,
+                                    task: str, iou_threshold: float, min_pixels: int, classes=None) -> Dict[str, Any]:
+    """<output_dir>/metrics_<paths.out_model_name>/<task>/object_metrics.json, next to metrics.json: per class (by
+    value_name) tp / fp / fn, precision, recall, f1 and mean_matched_iou of the predicted objects against the reference
+    objects (flairhip/objects.py; ``counts`` int64 [K, 3], ``iou_sums`` float64 [K]), their micro average, the IoU
+    threshold, min_pixels and the class filter.  A value whose denominator is 0 is null."""
+    from flairhip import objects
+    names = config["labels_configs"][task]["value_name"]
+    names = [str(names[i]) for i in range(len(names))]
+    out = objects.scores_json(objects.object_scores(counts, iou_sums), names)
+    out.update(iou_threshold=float(iou_threshold), min_pixels=int(min_pixels),
+               class_filter=None if classes is None else [int(c) for c in classes])
+    folder = os.path.join(str(output_dir), f"metrics_{config['paths']['out_model_name']}", task)
+    os.makedirs(folder, exist_ok=True)
+    with open(os.path.join(folder, "object_metrics.json"), "w") as f:
+        json.dump(out, f, indent=2)
+    micro = out["micro"]
+    logger.info("Task: %s - objects at IoU >= %.2f: %d found, %d invented, %d missed", task, float(iou_threshold),
+                micro["tp"], micro["fp"], micro["fn"])
+    return out
+
+
 def compute_and_save_metrics(confmat: np.ndarray, config: Dict[str, Any], output_dir: str, task: str,
                              mode: str = "predict") -> None:
     """<output_dir>/metrics_<paths.out_model_name>/<task>/metrics.json and confmat_<mode>.npy (the full matrix), and the

@@ -23,7 +23,7 @@ import torch.distributed as dist
 from flairhip import ops
 from flairhip.distributed import all_reduce_sum_
 from flairhip.nn import LOGIT_PITCH, to_nhwc
-from flair_hub.writer.metrics_utils import compute_and_save_metrics
+from flair_hub.writer.metrics_utils import compute_and_save_metrics, compute_and_save_object_metrics
 from flair_zonal_detection.geotiff import GeoTiffRaster, GeoTiffWriter
 
 logger = logging.getLogger(__name__)
@@ -37,6 +37,29 @@ def read_label_band(path: str, channel: int) -> np.ndarray:
     if band.dtype == np.uint8:
         return band
     return np.where((band < 0) | (band > 255), 255, band).astype(np.uint8)
+
+
+def object_metrics_options(config: Dict[str, Any]):
+    """The key tasks.object_metrics: absent or false = off (None); else {iou_threshold: 0.5, min_pixels: 1,
+    classes: null} (true or an empty mapping: those defaults).  A bad value raises ValueError."""
+    opt = (config.get("tasks") or {}).get("object_metrics")
+    if opt is None or opt is False:
+        return None
+    if opt is True:
+        opt = {}
+    if not isinstance(opt, dict) or set(opt) - {"iou_threshold", "min_pixels", "classes"}:
+        raise ValueError(f"tasks.object_metrics must be false or a mapping of iou_threshold, min_pixels and classes, "
+                         f"got {opt!r}")
+    thr, minp, classes = opt.get("iou_threshold", 0.5), opt.get("min_pixels", 1), opt.get("classes")
+    if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not 0.0 < float(thr) <= 1.0:
+        raise ValueError(f"tasks.object_metrics.iou_threshold must be a number in (0, 1], got {thr!r}")
+    if isinstance(minp, bool) or not isinstance(minp, int) or minp < 1:
+        raise ValueError(f"tasks.object_metrics.min_pixels must be an integer >= 1, got {minp!r}")
+    if classes is not None:
+        classes = sorted({int(c) for c in classes})
+        if not all(0 <= c < 255 for c in classes):
+            raise ValueError(f"tasks.object_metrics.classes must be class ids below 255, got {classes}")
+    return {"iou_threshold": float(thr), "min_pixels": int(minp), "classes": classes}
 
 
 def _write_prediction(path: str, labels: np.ndarray, like: str, georeferenced: bool) -> None:
@@ -59,6 +82,10 @@ class PredictionWriter:
         self.output_dir = str(output_dir)
         self.write_interval = write_interval
         self.accumulated_confmats: Dict[str, Any] = {task: None for task in config["labels"]}
+        # object metrics (tasks.object_metrics, off by default): per task int64 [K, 3] TP / FP / FN, float64 [K] IoU sums
+        self.object_options = object_metrics_options(config)
+        self.object_counts: Dict[str, Any] = {}
+        self.object_iou_sums: Dict[str, Any] = {}
         self._io = None       # one thread: files of batch k are encoded while the device runs batch k + 1
         self._pending: List[Any] = []
 
@@ -76,6 +103,39 @@ class PredictionWriter:
         pending, self._pending = self._pending, []
         for job in pending:
             job.result()  # a failed write surfaces here
+
+    # ---- object metrics --------------------------------------------------------------------------------------------
+    def _object_state(self, task: str):
+        if task not in self.object_counts:
+            k = self._classes(task)
+            self.object_counts[task] = np.zeros((k, 3), np.int64)
+            self.object_iou_sums[task] = np.zeros(k, np.float64)
+        return self.object_counts[task], self.object_iou_sums[task]
+
+    def _count_objects(self, task: str, pred: torch.Tensor, target: torch.Tensor) -> None:
+        """Add the objects of device uint8 [B, H, W] predictions (A) against targets (B) to the task's counts.  On
+        copies: a target >= K becomes the background 255 -- with the optional class filter in the same
+        ffa_zone_clip_u8 pass -- and the prediction takes 255 where the target was >= K, so ignored ground truth
+        creates no false positive; with a class filter the prediction is filtered like the target."""
+        from flairhip import objects
+        opt, k = self.object_options, self._classes(task)
+        keep = [c for c in (range(k) if opt["classes"] is None else opt["classes"]) if c < k]
+        tgt = target.contiguous().clone()
+        prd = pred.contiguous().clone()
+        prd.masked_fill_(tgt >= k, 255)
+        ops.zone_clip_(tgt, None, keep_classes=keep, fill=255)
+        if opt["classes"] is not None:
+            ops.zone_clip_(prd, None, keep_classes=keep, fill=255)
+        counts, iou_sums = self._object_state(task)
+        for ov in ops.region_overlaps_batch(prd, tgt, 255, 255, opt["min_pixels"], opt["min_pixels"]):
+            c, s = objects.object_counts(ov, objects.match_objects(ov, opt["iou_threshold"], "same"), k)
+            counts += c
+            iou_sums += s
+
+    def _save_object_metrics(self, task: str, counts, iou_sums) -> None:
+        opt = self.object_options
+        compute_and_save_object_metrics(counts, iou_sums, self.config, self.output_dir, task, opt["iou_threshold"],
+                                        opt["min_pixels"], opt["classes"])
 
     # ---- hooks -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -115,6 +175,8 @@ class PredictionWriter:
             tgt = targets[spans[task]:spans[task] + B * H * W].view(B, H, W)
             labels, _, _ = ops.eval_stats(nhwc, tgt, k, confmat=self.accumulated_confmats[task], want_pred=True,
                                           want_class_nll=False)
+            if self.object_options is not None:
+                self._count_objects(task, labels.view(B, H, W), tgt)
             if not write:
                 continue
             out_dir = self._prediction_dir(task)
@@ -147,11 +209,19 @@ class PredictionWriter:
                 k = self._classes(task)
                 self.accumulated_confmats[task] = torch.zeros(k, k, dtype=torch.int64, device=device)
             mats.append(self.accumulated_confmats[task])
-        all_reduce_sum_(mats)
+        objs = []
+        if self.object_options is not None:  # one more tensor per task: float64 [K, 4] of TP, FP, FN, IoU sum
+            for task in self.config["labels"]:
+                counts, iou_sums = self._object_state(task)
+                objs.append(torch.from_numpy(np.concatenate([counts.astype(np.float64), iou_sums[:, None]], 1)).to(device))
+        all_reduce_sum_(mats + objs)
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         if rank == 0:
             for task, mat in zip(self.config["labels"], mats):
                 compute_and_save_metrics(mat.cpu().numpy(), self.config, self.output_dir, task, mode="predict")
+            for task, obj in zip(self.config["labels"], objs):
+                obj = obj.cpu().numpy()
+                self._save_object_metrics(task, np.rint(obj[:, :3]).astype(np.int64), obj[:, 3])
         if self._io is not None:
             self._io.shutdown(wait=True)
             self._io = None
@@ -169,6 +239,7 @@ class PredictionWriter:
             with open(self.config["paths"]["test_csv"], newline="") as f:
                 gt_paths = [row[task] for row in csv.DictReader(f)]
             confmat = torch.zeros(k, k, dtype=torch.int64, device=device)
+            self.object_counts.pop(task, None)  # this path counts from the files alone
             pred_dir = self._prediction_dir(task)
             missing, valid = [], 0
             for gt_path in gt_paths:
@@ -183,6 +254,8 @@ class PredictionWriter:
                     continue
                 both = torch.from_numpy(np.stack([pred, gt])).to(device)
                 ops.confusion_matrix_update(confmat, both[0], both[1])
+                if self.object_options is not None:
+                    self._count_objects(task, both[0:1], both[1:2])
                 valid += 1
             for p in missing:
                 logger.info("missing prediction: %s", p)
@@ -190,6 +263,8 @@ class PredictionWriter:
             if valid:
                 self.accumulated_confmats[task] = confmat
                 compute_and_save_metrics(confmat.cpu().numpy(), self.config, self.output_dir, task, mode="metrics_only")
+                if self.object_options is not None:
+                    self._save_object_metrics(task, *self._object_state(task))
                 found_any = True
         if not found_any:
             logger.info("[ERROR] no predictions found at all: metrics are not calculated")

@@ -88,6 +88,23 @@ def validate_sieve_area(config: dict) -> float:
     return value
 
 
+def validate_compare(config: dict):
+    """The optional keys of object matching against a reference (raster_to_polygons(compare=...)): compare_raster
+    (default none: off; a path to a class raster on the prediction's grid, or to a GeoJSON layer of known objects),
+    compare_iou (default 0.5, a number in (0, 1]) and compare_classes ("same", the default, or "any").  Returns the
+    three; a bad value raises ValueError."""
+    path = config.get("compare_raster")
+    if path is not None and not isinstance(path, (str, os.PathLike)):
+        raise ValueError(f"compare_raster must be a path, got {path!r}")
+    iou = config.get("compare_iou", 0.5)
+    if isinstance(iou, bool) or not isinstance(iou, (int, float)) or not 0.0 < float(iou) <= 1.0:
+        raise ValueError(f"compare_iou must be a number in (0, 1], got {iou!r}")
+    mode = config.get("compare_classes", "same")
+    if mode not in ("same", "any"):
+        raise ValueError(f"compare_classes must be 'same' or 'any', got {mode!r}")
+    return (None if path is None else os.fspath(path)), float(iou), mode
+
+
 COG_OVERVIEW_RESAMPLING = ("nearest", "mode", "average")
 
 
@@ -153,6 +170,7 @@ def validate_config(config: dict) -> None:
     validate_skip_tiles_outside_zone(config)
     validate_geozone_crs(config)
     validate_sieve_area(config)
+    validate_compare(config)
     validate_cog_conversion(config)
     validate_cog_overview_resampling(config)
     if not os.path.isfile(config["model_weights"]):

@@ -609,7 +609,8 @@ def _confidence_source(tiff_path, confidence):
 def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, top: float, xres: float, yres: float,
                    crs, bg: Optional[int], min_pixels: int, simplification: float, n_jobs: Optional[int],
                    zone=None, classes=None, zone_crs=None, target_crs=None, sieve_pixels: int = 0,
-                   workspace: str = "auto"):
+                   workspace: str = "auto", compare=None, compare_iou: float = 0.5, compare_classes: str = "same",
+                   compare_sink: Optional[dict] = None):
     """Shared tail of raster_to_polygons / rasters_to_polygons / vectorize_segmentation_parallel: on the device copy
     of the raster the
     sieve (ops.sieve_, only when ``sieve_pixels`` > 1), then zone clip and class filter (one ffa_zone_clip_u8 pass,
@@ -617,7 +618,10 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
     uint8 confidence plane), map coordinates, host simplification, reprojection of the kept vertices to
     ``target_crs`` (one ffa_crs_transform_f64 pass, only when asked for), frame.  ``data`` / ``conf`` are host arrays,
     or device tensors this call may change (the mosaic of rasters_to_polygons).  ``workspace``: "bound"
-    (ops.polygonize), "counted" (ops.polygonize_counted) or "auto" = bound where 4 * H * W < 2^31, else counted."""
+    (ops.polygonize), "counted" (ops.polygonize_counted) or "auto" = bound where 4 * H * W < 2^31, else counted.
+    ``compare``: None, or what _compare_source returned -- a reference class band (host array) or ("zone", geometry);
+    the four object-matching columns of _compare_columns then follow the others (``compare_sink``: a dict that
+    receives the reference's side of the matching, for compare.compare_objects)."""
     from flair_zonal_detection.polygons import FlatPolygons, PolygonFrame
     if workspace not in ("auto", "bound", "counted"):
         raise ValueError(f"raster_to_polygons: workspace must be 'auto', 'bound' or 'counted', got {workspace!r}")
@@ -651,6 +655,12 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
             mask = zone_mask(zone, left, top, xres, yres, data.shape[0], data.shape[1], zone_crs=zone_crs,
                              raster_crs=crs)
         ops.zone_clip_(cls_dev, mask, keep_classes=keep, fill=bg)
+    else:
+        mask = keep = None
+    compare_columns = None
+    if compare is not None:
+        compare_columns = _compare_columns(cls_dev, compare, bg, min_pixels, mask, keep, (left, top, xres, yres), crs,
+                                           zone_crs, compare_iou, compare_classes, compare_sink)
     res = [t.cpu().numpy() for t in polygonize(cls_dev, bg, min_pixels,
                                                **({} if values is None else {"values": values}))]
     pc, pix, pro, rvo, verts = res[:5]
@@ -677,6 +687,11 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
         pixels = pix.astype(np.int64)
         # exact integer sum / (255 * pixel count), one float64 division per polygon: a number in [0, 1]
         columns = {"confidence": res[5].astype(np.int64) / (255.0 * pixels), "pixels": pixels}
+    if compare_columns is not None:
+        if len(compare_columns["matched"]) != len(pc):
+            raise RuntimeError(f"raster_to_polygons: {len(compare_columns['matched'])} regions matched, {len(pc)} "
+                               "polygons emitted")
+        columns = {**columns, **compare_columns}
     try:
         import geopandas as gpd  # type: ignore
         from shapely.geometry import Polygon as ShapelyPolygon  # type: ignore
@@ -684,6 +699,93 @@ def _polygon_table(data: np.ndarray, conf: Optional[np.ndarray], left: float, to
         return PolygonFrame.from_flat(flat, crs, **({"columns": columns} if columns else {}))
     geoms = [ShapelyPolygon(r[0], r[1:]) for r in (flat.rings(q) for q in range(len(flat)))]
     return gpd.GeoDataFrame({"class_id": flat.class_id.astype(np.int64), **columns, "geometry": geoms}, crs=crs)
+
+
+def _compare_is_zone(compare) -> bool:
+    """whether raster_to_polygons' ``compare`` is a geometry (anything zone.zone_rings reads) and not a class raster"""
+    if hasattr(compare, "__geo_interface__"):
+        return True
+    if isinstance(compare, dict):
+        return "type" in compare  # GeoJSON; an outputs dict has task names for keys
+    if isinstance(compare, (str, os.PathLike)):
+        return str(os.fspath(compare)).lower().endswith((".geojson", ".json"))
+    return isinstance(compare, (list, tuple))
+
+
+def _compare_source(compare, shape, bounds, res, name: str):
+    """What _polygon_table takes as ``compare``: ("zone", geometry), or the one uint8 band of the reference class
+    raster ``compare`` (path, raster object, outputs dict or closed writer), which must have the prediction's
+    ``shape``, ``bounds`` (left, bottom, right, top; to within 1e-6 of a pixel) and ``res``, else ValueError starting
+    with ``name``."""
+    if _compare_is_zone(compare):
+        return ("zone", compare)
+    csrc = _polygon_source(compare)
+    if csrc.count != 1:
+        raise ValueError(f"{name}: the compare raster must have one band, got {csrc.count}")
+    ref = np.asarray(csrc.read(1))
+    if ref.dtype != np.uint8:
+        raise ValueError(f"{name}: uint8 compare raster expected, got {ref.dtype}")
+    if ref.shape != tuple(shape):
+        raise ValueError(f"{name}: compare raster is {ref.shape}, the class raster {tuple(shape)}")
+    cres, cbounds = tuple(float(v) for v in csrc.res), _bounds4(csrc)
+    tol = 1e-6 * max(float(v) for v in res)
+    if cres != tuple(float(v) for v in res) or any(abs(a - b) > tol for a, b in zip(cbounds, bounds)):
+        raise ValueError(f"{name}: the compare raster's bounds / resolution differ from the class raster's "
+                         f"({cbounds}, {cres} vs {tuple(bounds)}, {tuple(res)})")
+    return ref
+
+
+def _compare_regions(cls_dev, compare, bg, min_pixels, mask, keep, grid, crs, zone_crs, compare_classes):
+    """(ops.RegionOverlaps of the class plane against the reference, compare_classes in force).  The reference raster
+    gets the zone clip and class filter the class plane got; a geometry becomes one "known" class (1 inside, 0 =
+    background outside), clipped to the zone, and is compared with ``classes="any"``."""
+    dev = cls_dev.device
+    if isinstance(compare, tuple):
+        from flair_zonal_detection.zone import zone_mask
+        left, top, xres, yres = grid
+        ref = zone_mask(compare[1], left, top, xres, yres, cls_dev.shape[0], cls_dev.shape[1], zone_crs=zone_crs,
+                        raster_crs=crs).clone()
+        if mask is not None:
+            ref.mul_(mask)
+        return ops.region_overlaps(cls_dev, ref, bg, 0, min_pixels, min_pixels), "any"
+    ref = torch.from_numpy(np.ascontiguousarray(compare)).to(dev)
+    if mask is not None or keep is not None:
+        ops.zone_clip_(ref, mask, keep_classes=keep, fill=bg)
+    return ops.region_overlaps(cls_dev, ref, bg, bg, min_pixels, min_pixels), compare_classes
+
+
+def _class_order(cls: np.ndarray):
+    """(order, rank): the stable sort by class that puts a region table into polygon order, and its inverse"""
+    order = np.argsort(cls, kind="stable")
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.arange(len(order))
+    return order, rank
+
+
+def _compare_frames_data(ov, compare_iou, compare_classes):
+    """object matching of a RegionOverlaps with both sides in polygon order: (columns of the prediction's polygons,
+    columns of the reference's regions, the host matching)"""
+    from flairhip import objects
+    m = objects.match_objects(ov, float(compare_iou), compare_classes)
+    order_a, rank_a = _class_order(ov.a_class.cpu().numpy())
+    order_b, rank_b = _class_order(ov.b_class.cpu().numpy())
+    hit_a, hit_b = m.a_match >= 0, m.b_match >= 0
+    ref_id = np.where(hit_a, rank_b[np.where(hit_a, m.a_match, 0)] if len(rank_b) else -1, -1).astype(np.int64)
+    pred_id = np.where(hit_b, rank_a[np.where(hit_b, m.b_match, 0)] if len(rank_a) else -1, -1).astype(np.int64)
+    pred = {"match_iou": m.a_match_iou[order_a], "matched": hit_a[order_a].astype(np.int64), "ref_id": ref_id[order_a],
+            "ref_fraction": m.a_covered[order_a]}
+    ref = {"match_iou": m.b_match_iou[order_b], "matched": hit_b[order_b].astype(np.int64), "pred_id": pred_id[order_b]}
+    return pred, ref, m
+
+
+def _compare_columns(cls_dev, compare, bg, min_pixels, mask, keep, grid, crs, zone_crs, compare_iou, compare_classes,
+                     sink=None):
+    """the four columns raster_to_polygons(compare=...) adds, in polygon order"""
+    ov, mode = _compare_regions(cls_dev, compare, bg, min_pixels, mask, keep, grid, crs, zone_crs, compare_classes)
+    pred, ref, m = _compare_frames_data(ov, compare_iou, mode)
+    if sink is not None:
+        sink.update(ref=ref, overlaps=ov, matches=m, classes=mode)
+    return pred
 
 
 def _class_band(src, name: str, shape=None):
@@ -726,7 +828,8 @@ def _background(ignore_background: bool, background_value):
 def raster_to_polygons(tiff_path, ignore_background: bool = True, background_value: int = 18, min_area: float = 1.0,
                        simplification: float = 0.1, n_jobs: Optional[int] = None, confidence=None, zone=None,
                        classes=None, zone_crs=None, target_crs=None, sieve_area: float = 0.0,
-                       workspace: str = "auto"):
+                       workspace: str = "auto", compare=None, compare_iou: float = 0.5, compare_classes: str = "same",
+                       _compare_sink: Optional[dict] = None):
     """Vector polygons of a class raster -- the reference's raster_to_polygons (inference.py:377-413) with its
     signature and call form ``raster_to_polygons(output_files, n_jobs=4)``.
 
@@ -789,7 +892,24 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
     same polygons, byte for byte.  "auto" (the default) is "bound" wherever it can run, else "counted", so no call
     that worked before changes.  ``sieve_area`` > 0 on a raster beyond 4 * H * W < 2^31 still raises from ops.sieve_,
     whose limit is its own, as a ``zone`` does from the zone mask's.
+
+    ``compare``: None, or a reference to match the polygons against as objects (flairhip/objects.py).  A class raster
+    (path, raster object or closed writer; one band, uint8, the class raster's shape, bounds and resolution, else
+    ValueError): the ground truth, or last run's prediction.  It gets the same zone clip and class filter, the same
+    background and ``min_area``; its regions are numbered in (class, first pixel) order like the polygons.  Or a
+    geometry (anything zone.zone_rings reads, in ``zone_crs`` like the zone): a layer of known objects, rasterised
+    with zone.zone_mask into one "known" class -- each feature filled even-odd over its rings (ffa_zone_mask_u8) and
+    the features united, so overlapping and touching features merge into one region -- and ``compare_classes`` is
+    then "any".  The regions of both are overlapped on the GPU (ops.region_overlaps, after the sieve, the zone clip
+    and the class filter) and matched one to one, greedily by descending IoU, a pair counting when its IoU >=
+    ``compare_iou`` and, with ``compare_classes="same"`` (not "any"), its classes agree.  Four columns follow the
+    others: ``match_iou`` (float64, 0.0 without a match), ``matched`` (int64, 0 or 1), ``ref_id`` (int64, index of the
+    matched reference region, or -1) and ``ref_fraction`` (float64, the share of the polygon's pixels that reference
+    regions cover -- of the same class with "same").  Geometry, order, class_id, confidence and pixels do not depend
+    on ``compare``; None makes no new call.
     """
+    if compare_classes not in ("same", "any"):
+        raise ValueError(f"raster_to_polygons: compare_classes must be 'same' or 'any', got {compare_classes!r}")
     src = _polygon_source(tiff_path)
     data = _class_band(src, "raster_to_polygons")
     xres, yres = (float(v) for v in src.res)
@@ -799,9 +919,13 @@ def raster_to_polygons(tiff_path, ignore_background: bool = True, background_val
         conf = _confidence_band(_confidence_source(tiff_path, confidence), src, data, "raster_to_polygons")
     min_pixels = min_pixels_for_area(float(min_area), abs(xres * yres))
     bg = _background(ignore_background, background_value)
+    if compare is not None:
+        compare = _compare_source(compare, data.shape, _bounds4(src), (xres, yres), "raster_to_polygons")
     return _polygon_table(data, conf, left, top, xres, yres, getattr(src, "crs", None), bg, min_pixels, simplification,
                           n_jobs, zone=zone, classes=classes, zone_crs=zone_crs, target_crs=target_crs,
-                          sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)), workspace=workspace)
+                          sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)), workspace=workspace,
+                          compare=compare, compare_iou=compare_iou, compare_classes=compare_classes,
+                          compare_sink=_compare_sink)
 
 
 def mosaic_grid(bounds_list, res, names=None):
@@ -870,7 +994,7 @@ def _same_crs(a, b) -> bool:
 def rasters_to_polygons(sources, confidence=None, ignore_background: bool = True, background_value: int = 18,
                         min_area: float = 1.0, simplification: float = 0.1, n_jobs: Optional[int] = None, zone=None,
                         classes=None, zone_crs=None, target_crs=None, sieve_area: float = 0.0,
-                        workspace: str = "auto"):
+                        workspace: str = "auto", compare=None, compare_iou: float = 0.5, compare_classes: str = "same"):
     """``raster_to_polygons`` of several rasters of one grid as ONE raster: an object lying across two dalles comes
     out as one polygon with its whole pixel count and one confidence, where polygonising each raster on its own and
     concatenating the frames (the driver's loop) cuts it at the seam and lets ``min_area`` drop the halves.
@@ -885,7 +1009,10 @@ def rasters_to_polygons(sources, confidence=None, ignore_background: bool = True
 
     The mosaic is assembled on the device -- a uint8 plane filled with the background, each source uploaded once and
     copied into its window -- and goes through raster_to_polygons' own tail with the mosaic's origin: the result
-    equals raster_to_polygons of a single raster holding the same pixels."""
+    equals raster_to_polygons of a single raster holding the same pixels.  ``compare``: as for raster_to_polygons; a
+    reference raster must cover the mosaic's grid (its shape, bounds and resolution)."""
+    if compare_classes not in ("same", "any"):
+        raise ValueError(f"rasters_to_polygons: compare_classes must be 'same' or 'any', got {compare_classes!r}")
     sources = list(sources)
     if not sources:
         raise ValueError("rasters_to_polygons: no sources")
@@ -935,9 +1062,13 @@ def rasters_to_polygons(sources, confidence=None, ignore_background: bool = True
         conf = _confidence_band(_confidence_source(s, carg), src, data, f"rasters_to_polygons: {name}")
         cplane[r0:r0 + h, c0:c0 + w] = torch.from_numpy(np.ascontiguousarray(conf)).to(dev)
     min_pixels = min_pixels_for_area(float(min_area), abs(xres * yres))
+    if compare is not None:
+        compare = _compare_source(compare, (H, W), (left, top - H * yres, left + W * xres, top), (xres, yres),
+                                  "rasters_to_polygons")
     return _polygon_table(plane, cplane, left, top, xres, yres, getattr(rasters[0], "crs", None), bg, min_pixels,
                           simplification, n_jobs, zone=zone, classes=classes, zone_crs=zone_crs, target_crs=target_crs,
-                          sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)), workspace=workspace)
+                          sieve_pixels=sieve_pixels_for_area(sieve_area, abs(xres * yres)), workspace=workspace,
+                          compare=compare, compare_iou=compare_iou, compare_classes=compare_classes)
 
 
 def logits_to_labels_and_confidence(probs):

@@ -129,7 +129,31 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--threshold-fallback", type=int, default=None, metavar="N",
                         help="the label (0..255) of a pixel at which no class reaches its threshold.  Default: the "
                              "config key threshold_fallback, else 18")
+    parser.add_argument("--compare", type=str, default=None, metavar="PATH",
+                        help="with --polygons: match the polygons as objects against a reference -- a class raster on "
+                             "the prediction's grid (ground truth, or last run's output) or a GeoJSON layer of known "
+                             "objects.  The GeoPackage gains the columns match_iou, matched, ref_id and ref_fraction, "
+                             "and per-class object precision / recall / F1 go to <polygons stem>_objects.json.  "
+                             "Default: the config key compare_raster, else none")
+    parser.add_argument("--compare-iou", type=float, default=None, metavar="X",
+                        help="the IoU from which a polygon and a reference object match.  Default: the config key "
+                             "compare_iou, else 0.5")
+    parser.add_argument("--compare-classes", type=str, default=None, choices=("same", "any"),
+                        help="whether only objects of the same class may match.  Default: the config key "
+                             "compare_classes, else same")
     return parser
+
+
+def _write_object_summary(path: str, gdf, compare, compare_iou: float, sink: dict) -> str:
+    """<polygons stem>_objects.json: the object scores of the run against the reference (compare.summary_of)"""
+    import json
+    from flair_zonal_detection.compare import summary_of
+    summary = summary_of(sink, compare_iou)
+    summary.update(compare=str(compare), polygons=int(len(gdf)))
+    out = os.path.splitext(path)[0] + "_objects.json"
+    with open(out, "w") as f:
+        json.dump(summary, f, indent=2)
+    return out
 
 
 def main(argv=None) -> None:
@@ -141,6 +165,12 @@ def main(argv=None) -> None:
         parser.error("--target-crs needs --polygons")
     if args.sieve_area is not None and args.polygons is None:
         parser.error("--sieve-area needs --polygons")
+    for opt, value in (("--compare", args.compare), ("--compare-iou", args.compare_iou),
+                       ("--compare-classes", args.compare_classes)):
+        if value is not None and args.polygons is None:
+            parser.error(f"{opt} needs --polygons")
+    if args.compare_iou is not None and not 0.0 < args.compare_iou <= 1.0:
+        parser.error(f"--compare-iou expects a number in (0, 1], got {args.compare_iou}")
     if args.sieve_area is not None and not 0.0 <= args.sieve_area < float("inf"):
         parser.error(f"--sieve-area expects a number >= 0, got {args.sieve_area}")
     for opt, value in (("--zone-crs", args.zone_crs), ("--target-crs", args.target_crs)):
@@ -190,9 +220,20 @@ def main(argv=None) -> None:
             sieve_area = validate_sieve_area(load_config(args.config))
         extra = {k: v for k, v in (("zone", args.zone), ("classes", classes), ("zone_crs", zone_crs),
                                    ("target_crs", args.target_crs), ("sieve_area", sieve_area or None)) if v is not None}
+        from flair_zonal_detection.config import load_config, validate_compare
+        compare, compare_iou, compare_classes = validate_compare(load_config(args.config))
+        compare = args.compare if args.compare is not None else compare
+        compare_iou = args.compare_iou if args.compare_iou is not None else compare_iou
+        compare_classes = args.compare_classes if args.compare_classes is not None else compare_classes
+        sink = {}
+        if compare is not None:
+            extra.update(compare=compare, compare_iou=compare_iou, compare_classes=compare_classes, _compare_sink=sink)
         gdf = raster_to_polygons(outputs, **({"confidence": True} if with_conf else {}), **extra)
         gdf.to_file(args.polygons, driver="GPKG")
         logger.info("wrote %d polygons to %s", len(gdf), args.polygons)
+        if compare is not None:
+            out = _write_object_summary(args.polygons, gdf, compare, compare_iou, sink)
+            logger.info("wrote the object scores against %s to %s", compare, out)
 
 
 if __name__ == "__main__":

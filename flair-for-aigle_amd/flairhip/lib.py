@@ -221,6 +221,15 @@ CALIB_SIGNATURES = {
     "ffa_tta_predict_thresholded_u8": (_i, [_i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
+# the prototypes of include/flairhip_objects.h (region overlaps for object matching), which include/flairhip.h brings
+# along
+OBJECT_SIGNATURES = {
+    "ffa_region_overlap_bytes": (_ll, [_i, _i]),
+    "ffa_region_overlap_count": (_i, [_p, _p, _i, _i, _i, _i, _ll, _ll, _p, _ll, _p, _p]),
+    "ffa_region_overlap_table_bytes": (_ll, [_ll]),
+    "ffa_region_overlap_pairs": (_i, [_p, _ll, _i, _i, _ll, _ll, _ll, _p, _ll] + [_p] * 11),
+}
+
 _lib = None
 
 
@@ -239,7 +248,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES, **GATHER_SIGNATURES, **SERIES_SIGNATURES,
-                              **CALIB_SIGNATURES}.items():
+                              **CALIB_SIGNATURES, **OBJECT_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args

@@ -1552,6 +1552,112 @@ def sieve_(classes: torch.Tensor, min_pixels: int, background: Optional[int] = N
 
 
 # --------------------------------------------------------------------------------------------------
+# region overlaps of two class rasters (csrc/region_overlap.hip)
+
+@dataclass
+class RegionOverlaps:
+    """The region tables of two class maps and their overlap list (include/flairhip_objects.h), device tensors:
+    ``a_first`` int32 / ``a_class`` int32 / ``a_pixels`` int64 [Pa] and the same for b, in ascending label order;
+    ``pair_a`` int32 / ``pair_b`` int32 / ``pair_pixels`` int64 [n_pairs], sorted by (pair_a, pair_b).  ``pair_bound`` is
+    the head count Q that sized the pair table (n_pairs <= Q)."""
+    a_first: torch.Tensor
+    a_class: torch.Tensor
+    a_pixels: torch.Tensor
+    b_first: torch.Tensor
+    b_class: torch.Tensor
+    b_pixels: torch.Tensor
+    pair_a: torch.Tensor
+    pair_b: torch.Tensor
+    pair_pixels: torch.Tensor
+    pair_bound: int = 0
+
+
+def _chk_overlap_maps(a, b, dims: int, op: str) -> None:
+    shape = "[B, H, W]" if dims == 3 else "[H, W]"
+    for t in (a, b):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == dims):
+            raise ValueError(f"{op}: CUDA uint8 {shape} class maps expected")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"{op}: the two class maps must have one shape and one device, got {tuple(a.shape)} on "
+                         f"{a.device} and {tuple(b.shape)} on {b.device}")
+    if a.numel() == 0:
+        raise ValueError(f"{op}: empty class maps {tuple(a.shape)}")
+
+
+def _overlap_backgrounds(background_a, background_b, op: str):
+    for bg in (background_a, background_b):
+        if bg is not None and not 0 <= int(bg) <= 255:
+            raise ValueError(f"{op}: background {bg} is not a uint8 value")
+    return tuple(-1 if bg is None else int(bg) for bg in (background_a, background_b))
+
+
+def _region_overlaps(a: torch.Tensor, b: torch.Tensor, bgs, minps, op: str):
+    """[B, H, W] maps -> list of B RegionOverlaps: the count phases back to back, one read of all counts, the pair
+    phases back to back, one read of all pair counts"""
+    lib = _l.load()
+    B, H, W = a.shape
+    if H * W >= 1 << 30:
+        raise ValueError(f"{op}: a {H} x {W} raster exceeds the limit H * W < 2^30 (about 1074 Mpx per call)")
+    a, b = a.contiguous(), b.contiguous()
+    dev = a.device
+    nbytes = _polygonize_size(lib.ffa_region_overlap_bytes(H, W))
+    st = _stream()
+    counts = torch.empty((B, 4), dtype=torch.int64, device=dev)
+    wss = [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(B)]
+    for i in range(B):
+        _l.check(lib.ffa_region_overlap_count(a[i].data_ptr(), b[i].data_ptr(), H, W, bgs[0], bgs[1], minps[0], minps[1],
+                                              wss[i].data_ptr(), nbytes, counts[i].data_ptr(), st),
+                 "region_overlap_count")
+    sizes = counts.cpu().tolist()
+    outs = []
+    for i, (Pa, Pb, Q, _) in enumerate(sizes):
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)  # noqa: E731
+        i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)  # noqa: E731
+        out = [i32(Pa), i32(Pa), i64(Pa), i32(Pb), i32(Pb), i64(Pb), i32(Q), i32(Q), i64(Q)]
+        tbytes = _polygonize_size(lib.ffa_region_overlap_table_bytes(Q))
+        table = torch.empty(tbytes, dtype=torch.uint8, device=dev) if Pa and Pb and Q else None
+        # an empty tensor's pointer goes as NULL, which the entry point takes for "nothing to write"
+        _l.check(lib.ffa_region_overlap_pairs(wss[i].data_ptr(), nbytes, H, W, Pa, Pb, Q, _ptr(table), tbytes,
+                                              *(t.data_ptr() if t.numel() else None for t in out),
+                                              counts[i].data_ptr(), st), "region_overlap_pairs")
+        outs.append(out)
+    done = counts.cpu().tolist()
+    res = []
+    for (Pa, Pb, Q, _), (_, _, overflow, n_pairs), out in zip(sizes, done, outs):
+        if overflow or n_pairs > Q:
+            raise _l.FlairHipError(f"{op}: the pair table overflowed ({n_pairs} pairs, bound {Q}, flag {overflow})")
+        pa, pb, pn = (t[:n_pairs] for t in out[6:])
+        order = torch.sort(pa.to(torch.int64) * max(Pb, 1) + pb.to(torch.int64)).indices
+        res.append(RegionOverlaps(*out[:6], pa[order], pb[order], pn[order], int(Q)))
+    return res
+
+
+def region_overlaps(a: torch.Tensor, b: torch.Tensor, background_a: Optional[int] = None,
+                    background_b: Optional[int] = None, min_pixels_a: int = 1, min_pixels_b: int = 1) -> RegionOverlaps:
+    """The regions of two device uint8 class maps [H, W] on one grid and the pairs of them that share pixels.
+
+    A region is a 4-connected component of equal value (``background_*``: that value is no region; None: every value
+    is a class) with at least ``min_pixels_*`` pixels: the polygoniser's meaning, and the class-sorted region table is
+    ``polygonize``'s polygon order (include/flairhip_objects.h).  Returns ``RegionOverlaps``: both region tables and
+    the triples (index in a, index in b, shared pixels), sorted by (index in a, index in b) -- the C ABI leaves their
+    order open; after this sort equal inputs give equal bytes.  Two host synchronisations: the read of the counts
+    between the two phases and the read of the number of pairs."""
+    _chk_overlap_maps(a, b, 2, "region_overlaps")
+    bgs = _overlap_backgrounds(background_a, background_b, "region_overlaps")
+    return _region_overlaps(a[None], b[None], bgs, (int(min_pixels_a), int(min_pixels_b)), "region_overlaps")[0]
+
+
+def region_overlaps_batch(a: torch.Tensor, b: torch.Tensor, background_a: Optional[int] = None,
+                          background_b: Optional[int] = None, min_pixels_a: int = 1, min_pixels_b: int = 1):
+    """``region_overlaps`` over [B, H, W] maps: a list of B ``RegionOverlaps``, image by image (no region crosses an
+    image).  The B count phases are launched back to back, all counts read once, then the B pair phases and one more
+    read: two host synchronisations per batch, not per image."""
+    _chk_overlap_maps(a, b, 3, "region_overlaps_batch")
+    bgs = _overlap_backgrounds(background_a, background_b, "region_overlaps_batch")
+    return _region_overlaps(a, b, bgs, (int(min_pixels_a), int(min_pixels_b)), "region_overlaps_batch")
+
+
+# --------------------------------------------------------------------------------------------------
 # geozone clipping on the pixel grid (csrc/zone_mask.hip)
 
 ZONE_WORKSPACE_SLOT = "zone_mask"

@@ -518,6 +518,9 @@ int ffa_confusion_matrix(const uint8_t* pred, const uint8_t* target, long long n
  * confidence outputs of ffa_predict_u8 and ffa_tta_predict_u8 under per-class thresholds) are declared in
  * flairhip_calib.h, likewise. */
 #include "flairhip_calib.h"
+/* Object matching (the overlaps between the regions of two class rasters: region tables and the list of region pairs
+ * that share pixels, with the size of each intersection) is declared in flairhip_objects.h, likewise. */
+#include "flairhip_objects.h"
 
 /* ---- host-side tile bookkeeping, bit-exact with the reference's float64 arithmetic
  *      (flair_zonal_detection/slicing.py:51-112, flair_zonal_detection/inference.py:318-335) -------- */

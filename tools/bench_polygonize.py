@@ -1,7 +1,7 @@
 """Polygonisation timings on synthetic class maps (GPU required).
 
     python tools/bench_polygonize.py [--sizes 5000 16384] [--reps 3] [--confidence] [--zone] [--sieve-area 0.2]
-        [--target-crs EPSG:4326]
+        [--target-crs EPSG:4326] [--compare]
 
 Maps: 'voronoi' (blocky nearest-seed map of 19 classes with 2 % label noise), 'checker' (checkerboard: every pixel a
 component, four boundary edges per pixel -- the worst case for edges), 'uniform' (one class: a single component over
@@ -35,6 +35,13 @@ With --workspace counted (or both) the count-sized path is timed: one JSON line 
 per-repetition sum "label_ms" (the figure to hold against the bound-sized "label_ms"; "label_ms_all" lists every
 repetition, for the spread), "emit_ms", both workspaces' sizes and the edges per pixel.  Device stages only;
 `--sizes 25000 --maps voronoi --workspace counted` is a full 5 km BD ORTHO dalle, which the bound-sized path refuses.
+With --compare one JSON line per voronoi size: object matching of the map (the prediction) against a copy of it
+shifted by 3 rows and 5 columns (the reference).  "label_ms" is ffa_polygonize_label on the map, as in the plain run
+and in the same session; "overlap_count_ms" (ffa_region_overlap_count: both rasters labelled, regions numbered, the
+pair bound) and "overlap_pairs_ms" (region tables, hash insert, compaction) are hip-event times, best of --reps after
+a warm-up; "count_over_two_labels" = overlap_count_ms / (2 * label_ms), the count phase against its yardstick of
+two label phases; "match_host_ms" is flairhip.objects.match_objects + object_counts on the host (wall clock), and
+"ops_ms" the whole ops.region_overlaps call with its two synchronisations and the sort.
 Per-kernel times (count_kernel, the labelling kernels and zonal_sum_kernel of the same run side by side): run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_polygonize.py --confidence --device-only`.
 """
@@ -380,6 +387,72 @@ def run_sieve(cls: np.ndarray, reps: int, sieve_area: float, device_only: bool =
     return res
 
 
+def run_compare(cls: np.ndarray, reps: int) -> dict:
+    import torch
+    from flairhip import lib as L
+    from flairhip import objects, ops
+    lib = L.load()
+    H, W = cls.shape
+    dev = torch.device("cuda")
+    a = torch.from_numpy(cls).to(dev)
+    b = torch.from_numpy(np.roll(cls, (3, 5), (0, 1))).to(dev)
+    st = torch.cuda.current_stream().cuda_stream
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+
+    def timed(call):
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+        call()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    res = {"map": "voronoi+compare", "H": H, "W": W}
+    if 4 * H * W < 1 << 31:  # the label phase of the plain run, in this session
+        nbytes = int(lib.ffa_polygonize_workspace_bytes(H, W))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        t = [timed(lambda: L.check(lib.ffa_polygonize_label(a.data_ptr(), H, W, 18, 1, ws.data_ptr(), nbytes,
+                                                            counts.data_ptr(), st))) for _ in range(reps + 1)][1:]
+        res["label_ms"] = round(min(t), 3)
+        del ws
+    nbytes = int(lib.ffa_region_overlap_bytes(H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    t_count, t_pairs = [], []
+    for rep in range(reps + 1):
+        ms = timed(lambda: L.check(lib.ffa_region_overlap_count(a.data_ptr(), b.data_ptr(), H, W, 18, 18, 1, 1,
+                                                                ws.data_ptr(), nbytes, counts.data_ptr(), st)))
+        Pa, Pb, Q, _ = (int(v) for v in counts.cpu().tolist())
+        tbytes = int(lib.ffa_region_overlap_table_bytes(Q))
+        table = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+        out = [torch.empty(n, dtype=dt, device=dev) for n, dt in
+               ((Pa, torch.int32), (Pa, torch.int32), (Pa, torch.int64), (Pb, torch.int32), (Pb, torch.int32),
+                (Pb, torch.int64), (Q, torch.int32), (Q, torch.int32), (Q, torch.int64))]
+        ms2 = timed(lambda: L.check(lib.ffa_region_overlap_pairs(ws.data_ptr(), nbytes, H, W, Pa, Pb, Q, table.data_ptr(),
+                                                                 tbytes, *(o.data_ptr() for o in out),
+                                                                 counts.data_ptr(), st)))
+        if rep:
+            t_count.append(ms)
+            t_pairs.append(ms2)
+    overflow, n_pairs = (int(v) for v in counts[2:].cpu().tolist())
+    assert not overflow and n_pairs <= Q
+    del ws, table, out
+    t0 = time.perf_counter()
+    ov = ops.region_overlaps(a, b, 18, 18)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    m = objects.match_objects(ov, 0.5, "same")
+    c, _ = objects.object_counts(ov, m, 19)
+    t2 = time.perf_counter()
+    assert len(ov.pair_a) == n_pairs
+    res.update({"workspace_GB": round(nbytes / 1e9, 3), "table_MB": round(tbytes / 1e6, 1), "regions_a": Pa,
+                "regions_b": Pb, "pair_bound": Q, "pairs": n_pairs, "overlap_count_ms": round(min(t_count), 3),
+                "overlap_pairs_ms": round(min(t_pairs), 3), "ops_ms": round((t1 - t0) * 1e3, 1),
+                "match_host_ms": round((t2 - t1) * 1e3, 1), "matched": int(c[:, 0].sum())})
+    if "label_ms" in res:
+        res["count_over_two_labels"] = round(res["overlap_count_ms"] / (2 * res["label_ms"]), 3)
+    return res
+
+
 def run_reproject(n: int, target_crs: str, reps: int) -> dict:
     import torch
     from flairhip import ops
@@ -437,6 +510,9 @@ def main() -> None:
                     help="voronoi maps only: time the sieve round by round and the stages after it with and without")
     ap.add_argument("--target-crs", type=str, default=None, metavar="EPSG:NNNN",
                     help="time the reprojection of --vertices Lambert-93 vertices to this CRS instead of the maps")
+    ap.add_argument("--compare", action="store_true",
+                    help="voronoi maps only: time the region overlaps (count, pairs) and the host matching of the map "
+                         "against a shifted copy, next to the label phase")
     ap.add_argument("--vertices", type=int, nargs="+", default=[4_000_000, 43_000_000])
     ap.add_argument("--workspace", choices=["bound", "counted", "both"], default="bound",
                     help="bound: ffa_polygonize_label, sizes up to 23170; counted: ffa_polygonize_count / _trace, device "
@@ -449,6 +525,10 @@ def main() -> None:
     if args.target_crs:
         for n in args.vertices:
             print(json.dumps(run_reproject(n, args.target_crs, args.reps)), flush=True)
+        return
+    if args.compare:
+        for n in args.sizes:
+            print(json.dumps(run_compare(voronoi(n), args.reps)), flush=True)
         return
     if args.sieve_area is not None:
         for n in args.sizes:
