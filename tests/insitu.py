@@ -23,6 +23,14 @@ product's own scale vector -- which is itself checked, as the output of ``bn_eva
 uint8 outputs (``predict_u8``, ``tta_accumulate_``, ``tta_predict_u8``, ``tta_probabilities``) against the float64
 softmax of the call's own logits: labels exactly (first maximum), bands and confidence under the half-integer rule.
 
+The U-TAE time-series branch (flairhip/utae.py on csrc/temporal.hip) is covered the same way: ``HipUTAE._packed`` is
+hooked so that every operand it hands out is known with its master weight (Conv1d / Linear weights as 1x1 OIHW), the
+column slice, the transpose flag and, in eval mode, the product's own checked ``bn_eval_params`` scale; the temporal ops
+(GroupNorm over images and over the dates of a pixel, the L-TAE attention with its dropout mask, saved probabilities
+and ``dattn_ext`` as call inputs, the temporal aggregation, reflect padding, the date encoding, column sums) have
+float64 restatements of the reference's multitemp_model.py; a transposed operand is held to ``F.conv_transpose2d`` of
+the master weight, whatever the product uses it for; ``dattn_ext`` must be the sum of what the aggregators sent back.
+
 The references work on any device (CPU for tests/test_insitu_checker.py, the GPU in float64 for the step).
 """
 from __future__ import annotations
@@ -587,7 +595,8 @@ class Checker:
             else:
                 pre = xc * sc + sh
                 gm = torch.where(pre > 0, dc, torch.zeros_like(dc))
-                amb = pre.abs() <= AMBIG_REL * ((xc * sc).abs() + sh.abs())
+                # where dy is 0 the mask decides nothing (the zero pad channels of a class-score layer at the logits pitch)
+                amb = (pre.abs() <= AMBIG_REL * ((xc * sc).abs() + sh.abs())) & (dc != 0)
             return xc, dc, gm, amb
 
         sb, sg, ab, ag, xb, xg = (x.new_zeros(C, dtype=F64) for _ in range(6))
@@ -999,6 +1008,266 @@ class Checker:
             raise ValueError(f"probabilities of shape {tuple(out.shape)} for an accumulator {tuple(acc.shape)}")
         return self._add(call, _compare(out, r, 2 * ulp_f32(r), "mean probabilities"))
 
+    # ---- the U-TAE time-series branch (csrc/temporal.hip, flairhip/utae.py) -----------------------
+    # Every kernel there keeps f32 between its loads and its single store, so the bound is the stored rounding plus
+    # REL * a, with the first-order effect of a REL-relative error in each f32 intermediate (mean and rstd, the scores
+    # and the softmax denominator, the argument of the encoding) added where the op forms one.  No bf16 rounding point
+    # inside a kernel was found, so no 2^-8 term appears.
+
+    def conv_transposed(self, call, x, w64, pad, o, bias=None, relu=False, what="out"):
+        """o = relu?(F.conv_transpose2d(x, w, stride 1, padding=pad) + bias) for the weight w64 [in, out, k, k] of an
+        nn.ConvTranspose2d -- which is also the input gradient of the convolution with OIHW weight w64 (pad = that
+        convolution's padding; the output may be larger than the input).  Taken on the CPU: the tensors are small."""
+        ci, co = w64.shape[:2]
+        xc = x[..., :ci].to(F64).permute(0, 3, 1, 2).cpu()
+        wc = w64.cpu()
+        r = F.conv_transpose2d(xc, wc, padding=pad).permute(0, 2, 3, 1).to(x.device)
+        a = F.conv_transpose2d(xc.abs(), wc.abs(), padding=pad).permute(0, 2, 3, 1).to(x.device)
+        if tuple(r.shape[:3]) != tuple(o.shape[:3]):
+            raise ValueError(f"transposed conv: output {tuple(o.shape)} where the reference gives {tuple(r.shape)}")
+        if bias is not None:
+            bb = bias[:co].to(F64)
+            r, a = r + bb, a + bb.abs()
+        if relu:
+            r = r.clamp_min(0)
+        if o.shape[-1] > co:
+            self._add(call, _exact_zero(o[..., co:], what + " pad channels"))
+        return self._add(call, _compare(o[..., :co], r, ulp_stored(r, o.dtype) + REL * a, what))
+
+    def reflect_pad1(self, call, x, o):
+        r = F.pad(x.permute(0, 3, 1, 2).to(F64), (1, 1, 1, 1), mode="reflect").permute(0, 2, 3, 1)
+        if tuple(r.shape) != tuple(o.shape):
+            raise ValueError(f"reflect_pad1: output {tuple(o.shape)} for an input {tuple(x.shape)}")
+        return self._add(call, _compare(o, r, torch.zeros_like(r), "padded copy"))
+
+    def reflect_pad1_bwd(self, call, dpad, o):
+        """o[n, y, x] = the sum of dpad over the padded positions that read (y, x): the float64 adjoint of reflect_pad1"""
+        def adjoint(t):
+            t = t.clone()
+            t[:, 2] += t[:, 0]
+            t[:, -3] += t[:, -1]
+            t = t[:, 1:-1]
+            t[:, :, 2] += t[:, :, 0]
+            t[:, :, -3] += t[:, :, -1]
+            return t[:, :, 1:-1]
+        d = dpad.to(F64)
+        r, a = adjoint(d), adjoint(d.abs())
+        if tuple(r.shape) != tuple(o.shape):
+            raise ValueError(f"reflect_pad1_bwd: output {tuple(o.shape)} for a gradient {tuple(dpad.shape)}")
+        return self._add(call, _compare(o, r, ulp_stored(r, o.dtype) + REL * a, "dx"))
+
+    @staticmethod
+    def _gn_rows(t, groups, seq):
+        """[S, inner, G, C/G] view of an NHWC tensor whose GroupNorm statistics run over axes 1 and 3: one sample per
+        image (seq None, nn.GroupNorm on [N,C,H,W]) or per pixel of each series (seq = (B, T): images n = b * T + t,
+        nn.GroupNorm on [B*h*w, C, T] as LTAE2d builds it -- padded dates included)"""
+        C = t.shape[-1]
+        if seq is None:
+            return t.reshape(t.shape[0], -1, groups, C // groups)
+        B, T = seq
+        if t.shape[0] != B * T:
+            raise ValueError(f"group norm over sequences: {t.shape[0]} images for B * T = {B * T}")
+        return t.reshape(B, T, -1, groups, C // groups).permute(0, 2, 1, 3, 4).reshape(-1, T, groups, C // groups)
+
+    def _gn_stats(self, x, groups, seq, eps):
+        """float64 statistics of the kernel's two passes and what a REL-relative error of its f32 sums does to them:
+        mean (t_m), the centred squares (REL var, plus the f32 rounding of x - mean where |x| >> |x - mean|), rstd"""
+        xg = self._gn_rows(x.to(F64), groups, seq)
+        m = xg.mean((1, 3), keepdim=True)
+        d = xg - m
+        var = (d * d).mean((1, 3), keepdim=True)
+        rs = 1.0 / torch.sqrt(var + float(eps))
+        t_m = REL * xg.abs().mean((1, 3), keepdim=True) + ulp_f32(m)
+        t_v = REL * var + 2.0 ** -23 * (d.abs() * (xg.abs() + m.abs())).mean((1, 3), keepdim=True)
+        t_rs = 0.5 * rs ** 3 * t_v + ulp_f32(rs)
+        return xg, m, d, rs, t_m, t_rs
+
+    def group_norm(self, call, x, gamma, beta, groups, eps, relu, residual, o, seq=None):
+        """o = [residual +] relu?((x - mean) * rstd * gamma + beta), biased statistics per (sample, group)"""
+        xg, m, d, rs, t_m, t_rs = self._gn_stats(x, groups, seq, eps)
+        g, b = gamma.to(F64).reshape(groups, -1), beta.to(F64).reshape(groups, -1)
+        r = d * rs * g + b
+        a = (xg.abs() + m.abs()) * rs * g.abs() + b.abs()
+        if relu:
+            r = r.clamp_min(0)
+        if residual is not None:
+            rr = self._gn_rows(residual.to(F64), groups, seq)
+            r, a = r + rr, a + rr.abs()
+        tol = ulp_stored(r, o.dtype) + REL * a + g.abs() * (rs * t_m + d.abs() * t_rs)
+        return self._add(call, _compare(self._gn_rows(o, groups, seq), r, tol, "y"))
+
+    def group_norm_bwd(self, call, x, dy, gamma, beta, groups, eps, relu, dx, dgamma, dbeta, seq=None):
+        """g = dy * [pre > 0] * gamma, dx = rstd (g - mean(g) - xhat mean(g xhat)) per (sample, group);
+        dgamma = sum dy' xhat, dbeta = sum dy' over samples and positions.  The ReLU mask follows the AMBIG_REL rule of
+        bn_bwd: elements whose pre-activation is within AMBIG_REL of zero (and whose dy is not 0) may go either way."""
+        xg, m, d, rs, t_m, t_rs = self._gn_stats(x, groups, seq, eps)
+        dg = self._gn_rows(dy.to(F64), groups, seq)
+        g, b = gamma.to(F64).reshape(groups, -1), beta.to(F64).reshape(groups, -1)
+        n = xg.shape[1] * xg.shape[3]
+        xh = d * rs
+        t_xh = rs * t_m + d.abs() * t_rs
+        amb, namb = None, 0
+        gm = dg
+        if relu:
+            pre = xh * g + b
+            amb = (pre.abs() <= AMBIG_REL * ((xh * g).abs() + b.abs())) & (dg != 0)
+            gm = torch.where(pre > 0, dg, torch.zeros_like(dg))
+            namb = int(amb.sum().item())
+            self.ambiguous[0] += namb
+            self.ambiguous[1] += x.numel()
+            if namb > AMBIG_MAX_FRACTION * x.numel():
+                self._add(call, {"what": "ambiguous ReLU masks", "shape": tuple(x.shape), "n": x.numel(), "fail": namb,
+                                 "worst": float("inf"), "error": f"{namb} ambiguous of {x.numel()}"})
+        open_ = torch.zeros_like(dg) if amb is None else torch.where(amb, dg.abs(), torch.zeros_like(dg))
+        sb, sg = gm.sum((0, 1)).reshape(-1), (gm * xh).sum((0, 1)).reshape(-1)
+        t_b = REL * gm.abs().sum((0, 1)).reshape(-1) + open_.sum((0, 1)).reshape(-1) + ulp_f32(sb)
+        t_g = (REL * (gm * xh).abs().sum((0, 1)) + (gm.abs() * t_xh).sum((0, 1)) + (open_ * xh.abs()).sum((0, 1))
+               ).reshape(-1) + ulp_f32(sg)
+        self._add(call, dict(_compare(dbeta, sb, t_b, "dbeta"), ambiguous=namb))
+        self._add(call, _compare(dgamma, sg, t_g, "dgamma"))
+        self.grad_sources += [("dgamma", dgamma.detach().clone()), ("dbeta", dbeta.detach().clone())]
+        gg = gm * g
+        mean = lambda t: t.mean((1, 3), keepdim=True)
+        m1, m2 = mean(gg), mean(gg * xh)
+        r = rs * (gg - m1 - xh * m2)
+        big = gg.abs() + mean(gg.abs()) + xh.abs() * mean((gg * xh).abs())
+        e1, e2 = mean(open_ * g.abs()), mean(open_ * g.abs() * xh.abs())
+        tol = ulp_stored(r, dx.dtype) + REL * rs * big + t_rs * big \
+            + rs * (t_xh * m2.abs() + xh.abs() * mean(gg.abs() * t_xh)) + rs * (e1 + xh.abs() * e2)
+        return self._add(call, _compare(self._gn_rows(dx, groups, seq), r, tol, "dx", exclude=amb))
+
+    def positional_encoding(self, call, pos, d, repeat, period, o):
+        """o[n, r*d + j] = sin (j even) / cos (j odd) of pos[n] / period^(2 (j // 2) / d); the f32 argument errs by
+        REL of itself, which moves the value by as much (|sin'|, |cos'| <= 1)"""
+        p = pos.reshape(-1).to(F64)
+        j = torch.arange(d, dtype=F64, device=p.device)
+        arg = p[:, None] / torch.pow(torch.tensor(float(period), dtype=F64, device=p.device),
+                                     2.0 * torch.div(j, 2, rounding_mode="floor") / d)
+        r = torch.where((torch.arange(d, device=p.device) % 2 == 1)[None, :], torch.cos(arg), torch.sin(arg))
+        r, arg = r.repeat(1, repeat), arg.repeat(1, repeat)
+        if tuple(r.shape) != tuple(o.shape):
+            raise ValueError(f"positional_encoding: output {tuple(o.shape)}, expected {tuple(r.shape)}")
+        return self._add(call, _compare(o, r, REL * (1.0 + arg.abs()), "encoding"))
+
+    def add_rowvec(self, call, before, vec, after):
+        v = vec.to(F64)[:, None, None, :]
+        r = before.to(F64) + v
+        a = before.to(F64).abs() + v.abs()
+        return self._add(call, _compare(after, r, ulp_stored(r, after.dtype) + REL * a, "x + vec"))
+
+    def detect_pad_images(self, call, x, value, o):
+        r = (x.reshape(x.shape[0], -1) == float(value)).all(1)
+        return self._add(call, _exact_zero((o.bool() != r).to(torch.int8), "pad flags"))
+
+    def mask_images(self, call, before, pad, value, after):
+        fill = torch.tensor(float(value), dtype=before.dtype, device=before.device)
+        keep = (pad == 0).reshape((-1,) + (1,) * (before.dim() - 1))
+        r = torch.where(keep, before, fill).to(F64)
+        return self._add(call, _compare(after, r, torch.zeros_like(r), "masked copy"))
+
+    def mul(self, call, x, m, o):
+        r = x.to(F64) * m.to(F64)
+        return self._add(call, _compare(o, r, ulp_stored(r, o.dtype) + REL * r.abs(), "x * m"))
+
+    @staticmethod
+    def _ltae_views(k, v, Q, pad, drop, B, T):
+        NH, DK = Q.shape
+        k5 = k.to(F64).reshape(B, T, -1, NH, DK)
+        v5 = v.to(F64).reshape(B, T, k5.shape[2], NH, -1)
+        padm = (pad.reshape(B, T) != 0)[:, :, None, None]
+        dr = None if drop is None else drop.to(F64).permute(1, 2, 3, 0)
+        return k5, v5, Q.to(F64), padm, dr
+
+    def ltae_attention(self, call, k, v, Q, pad, drop, B, T, out, attn, prob=None):
+        """score[t] = <Q[h], k[t]> / sqrt(d_k), padded dates -1e3, prob = softmax over the dates, attn = prob * drop,
+        out = sum_t attn[t] v[t].  A score errs by REL of its magnitude sum (t_s); the softmax passes that on as
+        p_t (t_s[t] + sum_u p_u t_s[u]) and adds REL p for the exponential and the denominator."""
+        k5, v5, q, padm, dr = self._ltae_views(k, v, Q, pad, drop, B, T)
+        temp = float(q.shape[1]) ** 0.5
+        s = ((k5 * q).sum(-1) / temp).masked_fill(padm, -1e3)
+        t_s = (REL * (k5 * q).abs().sum(-1) / temp).masked_fill(padm, 0.0)
+        p = torch.softmax(s, dim=1)
+        t_p = REL * p + p * (t_s + (p * t_s).sum(1, keepdim=True))
+        at, t_a = (p, t_p) if dr is None else (p * dr, t_p * dr)
+        r = (at[..., None] * v5).sum(1)
+        a = (at[..., None] * v5.abs()).sum(1)
+        tol = ulp_stored(r, out.dtype) + REL * a + (t_a[..., None] * v5.abs()).sum(1)
+        self._add(call, _compare(out.reshape(r.shape), r, tol, "out"))
+        self._add(call, _compare(attn.permute(1, 2, 3, 0), at, t_a, "attn"))
+        if prob is not None:
+            self._add(call, _compare(prob.permute(1, 2, 3, 0), p, t_p, "prob"))
+
+    def ltae_attention_bwd(self, call, k, v, Q, pad, drop, prob, dout, dattn_ext, B, T, dk, dv, dq):
+        """from the saved clean prob: da = <dout, v> + dattn_ext, dp = da drop, ds = prob (dp - sum prob dp), 0 at a
+        padded date, over sqrt(d_k); dk = ds Q, dv = prob drop dout, dQ = sum over samples, dates and pixels of ds k"""
+        k5, v5, q, padm, dr = self._ltae_views(k, v, Q, pad, drop, B, T)
+        temp = float(q.shape[1]) ** 0.5
+        p = prob.to(F64).permute(1, 2, 3, 0)
+        dr = torch.ones_like(p) if dr is None else dr
+        go = dout.to(F64).reshape(B, 1, k5.shape[2], q.shape[0], -1)
+        da, a_da = (go * v5).sum(-1), (go * v5).abs().sum(-1)
+        if dattn_ext is not None:
+            ext = dattn_ext.to(F64).permute(1, 2, 3, 0)
+            da, a_da = da + ext, a_da + ext.abs()
+        t_da = REL * a_da
+        dp = da * dr
+        ds = p * (dp - (p * dp).sum(1, keepdim=True))
+        t_ds = p * (dr * t_da + (p * dr * t_da).sum(1, keepdim=True)) \
+            + REL * p * (dp.abs() + (p * dp.abs()).sum(1, keepdim=True))
+        ds, t_ds = ds.masked_fill(padm, 0.0) / temp, t_ds.masked_fill(padm, 0.0) / temp
+        r = ds[..., None] * q
+        self._add(call, _compare(dk.reshape(r.shape), r, ulp_stored(r, dk.dtype) + REL * r.abs() + t_ds[..., None] * q.abs(),
+                                 "dk"))
+        r = (p * dr)[..., None] * go
+        self._add(call, _compare(dv.reshape(r.shape), r, ulp_stored(r, dv.dtype) + REL * r.abs(), "dv"))
+        r = (ds[..., None] * k5).sum((0, 1, 2))
+        tol = REL * (ds.abs()[..., None] * k5.abs()).sum((0, 1, 2)) + (t_ds[..., None] * k5.abs()).sum((0, 1, 2)) + ulp_f32(r)
+        self._add(call, _compare(dq, r, tol, "dQ"))
+        self.grad_sources.append(("dQ", dq.detach().clone()))
+
+    @staticmethod
+    def _aggregate_views(x, attn, pad, B, T, use_pad):
+        NH = attn.shape[0]
+        x5 = x.to(F64).reshape(B, T, -1, NH, x.shape[-1] // NH)
+        a4 = attn.to(F64).permute(1, 2, 3, 0)
+        dead = (pad.reshape(B, T) != 0)[:, :, None, None] & bool(use_pad)
+        return x5, a4.masked_fill(dead, 0.0) if use_pad else a4, dead
+
+    def temporal_aggregate(self, call, x, attn, pad, B, T, use_pad, o):
+        """o[b, p, c] = sum_t attn[c // (C / n_head), b, t, p] x[b, t, p, c], padded dates left out when use_pad"""
+        x5, a4, _ = self._aggregate_views(x, attn, pad, B, T, use_pad)
+        r = (a4[..., None] * x5).sum(1)
+        a = (a4.abs()[..., None] * x5.abs()).sum(1)
+        return self._add(call, _compare(o.reshape(r.shape), r, ulp_stored(r, o.dtype) + REL * a, "out"))
+
+    def temporal_aggregate_bwd(self, call, x, attn, pad, dout, B, T, use_pad, dx, dattn):
+        x5, a4, dead = self._aggregate_views(x, attn, pad, B, T, use_pad)
+        go = dout.to(F64).reshape(B, 1, x5.shape[2], x5.shape[3], -1)
+        r = a4[..., None] * go
+        self._add(call, _compare(dx.reshape(r.shape), r, ulp_stored(r, dx.dtype) + REL * r.abs(), "dx"))
+        r = (x5 * go).sum(-1).masked_fill(dead, 0.0)
+        a = (x5 * go).abs().sum(-1).masked_fill(dead, 0.0)
+        self._add(call, _compare(dattn.permute(1, 2, 3, 0), r, REL * a, "dattn"))
+
+    def column_sums(self, call, x, o):
+        v = x.to(F64).reshape(-1, x.shape[-1])
+        return self._add(call, _compare(o, v.sum(0), REL * v.abs().sum(0), "column sums"))
+
+    def packed_bias(self, call, bias, holder_bias, n_out, scale=None, shift=None):
+        """the bias vector HipUTAE._packed hands out with an operand: the layer's bias, in eval mode
+        shift + scale * bias (one f32 multiply and add), zeros behind the real channels"""
+        r = bias.new_zeros(bias.shape, dtype=F64)
+        tol = torch.zeros_like(r)
+        if holder_bias is not None:
+            hb = holder_bias.to(F64)
+            if scale is None:
+                r[:n_out] = hb
+            else:
+                sc, sh = scale[:n_out].to(F64), shift[:n_out].to(F64)
+                r[:n_out] = sh + sc * hb
+                tol[:n_out] = 2 * ulp_f32(sh.abs() + (sc * hb).abs())
+        return self._add(call, _compare(bias, r, tol, "bias vector"))
+
 
 # --------------------------------------------------------------------------------------------------
 # the recorder: patches flairhip.ops and dispatches every outermost call to the Checker
@@ -1023,6 +1292,10 @@ class Recorder(Checker):
         self._chains = {}        # fusion conv name -> real channels of the links of its forward chain, in order
         self._scaled = {}        # address of a rescaled dlogits buffer -> what its consumer's bias gradient must be
         self.head_bias = {}      # module name of a head -> the entry of _scaled its dgrad call consumed
+        self.sum_inputs = {}     # id of a checked column_sums output -> (call index, (address, shape) of what it summed)
+        self.wgrad_operands = []  # (call index, (address, shape)) of the x and dy of every checked conv_wgrad call
+        self._dattn_parts = []   # dattn of the temporal_aggregate_bwd calls since the last ltae_attention_bwd
+        self._convT_grad = None  # (call index, (address, shape)) of the output gradient a ConvTranspose2d's backward read
 
     def adopt(self, model):
         """take the module names of `model` (a program that builds its model inside the recording hands it over here)"""
@@ -1099,6 +1372,46 @@ class Recorder(Checker):
 
         self._saved.append((hnn, "_eval_folded", orig_fold))
         hnn._eval_folded = eval_folded
+        from flairhip import utae as hutae
+        orig_utae = hutae.HipUTAE._packed
+
+        def utae_packed(net, tag, holder, ci_pitch, bn=None, transpose=False, cols=None, with_bias=True):
+            """an operand of the U-TAE: the master weight as 4-D OIHW (Conv1d / Linear weights are 1x1 convolutions), the
+            column slice and the transpose flag the product asked for, in eval mode the product's own bn_eval_params
+            scale (checked like any other call).  The bias vector that comes with the operand is checked here; a conv
+            call on the operand must pass that very vector.  Padding comes from the call."""
+            rec._fold_params = None
+            pw, bias = orig_utae(net, tag, holder, ci_pitch, bn=bn, transpose=transpose, cols=cols, with_bias=with_bias)
+            params, rec._fold_params = rec._fold_params, None
+            known = rec.weights.get(id(pw))
+            fresh = known is None or known.get("operand") is not pw
+            if bn is not None and params is None and fresh:
+                params = rec._ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
+                                                 bn.eps)
+            if not fresh and params is None:
+                return pw, bias
+            key = (id(holder), holder.weight._version, holder.weight.data_ptr(), hnn.state_epoch())
+            w = rec._wcache.get(key)
+            if w is None:
+                w = holder.weight.detach().float()
+                w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim())).clone()
+                rec._wcache[key] = w
+            c0, c1, _ = (cols if cols is not None else slice(None)).indices(w.shape[1])
+            name = rec.names.get(id(holder), "?")
+            info = {"name": name, "tag": tag, "utae": True, "transpose": bool(transpose), "weight": w, "cols": (c0, c1),
+                    "operand": pw, "stride": 1, "padding": None, "bias": bias, "with_bias": bool(with_bias)}
+            if params is not None:
+                info["scale"], info["shift"] = params[0].detach().clone(), params[1].detach().clone()
+            rec.weights[id(pw)] = info
+            n_out = w.shape[1] if transpose else w.shape[0]
+            with torch.no_grad():
+                rec.packed_bias({"op": "utae_packed", "family": "utae_packed_bias", "call": f"packed:{tag}", "module": name},
+                                bias, holder.bias.detach() if with_bias else None, n_out, info.get("scale"),
+                                info.get("shift"))
+            return pw, bias
+
+        self._saved.append((hutae.HipUTAE, "_packed", orig_utae))
+        hutae.HipUTAE._packed = utae_packed
         return self
 
     def __exit__(self, *exc):
@@ -1212,7 +1525,50 @@ class Recorder(Checker):
             info = self.weights.get(id(a["w"]))
             if info is not None and info["transpose"]:
                 self.head_bias[info["name"]] = hit
+        info = self.weights.get(id(a["w"]))
+        if info is not None and info.get("utae"):
+            return self._utae_conv(call, a, live, out, info)
         self._conv_call(call, a, out, a["w"], a["dil"], a["residual"], bias=a["bias"], relu=a["relu"])
+
+    def _utae_conv(self, call, a, live, out, info):
+        """conv2d on an operand of HipUTAE._packed.  Forward operands: the convolution of the call's padding with the
+        column slice of the master weight (the second link of a sliced pair comes through the residual input).
+        Transposed operands, whatever the product uses them for -- ConvTranspose2d(3, 1, 1) as a pad-1 conv, the input
+        gradient of a pad-0 conv as a pad-(k-1) conv with out_hw -- are held to F.conv_transpose2d of the master weight
+        [in, out, k, k] with padding k - 1 - pad: the transposed convolution and the adjoint are one map."""
+        pw = a["w"]
+        c0, c1 = info["cols"]
+        W = info["weight"][:, c0:c1]
+        transpose, tag = info["transpose"], info["tag"]
+        n_out = W.shape[1] if transpose else W.shape[0]
+        folded = "scale" in info
+        if folded:  # the packer's fold (csrc/conv_pack.hip): w * scale[row] in f32, then the storage rounding
+            sc = info["scale"].float()[:n_out]
+            W = W.float() * (sc[None, :, None, None] if transpose else sc[:, None, None, None])
+        w64 = bf16_round(W) if pw.data.dtype == torch.bfloat16 else W.to(F64)
+        bias, residual = a["bias"], a["residual"]
+        if bias is not None and not torch.equal(bias, info["bias"]):
+            raise ValueError("conv call with another bias vector than the one packed with its operand")
+        if bias is not None and not info["with_bias"] and bool((bias != 0).any()):
+            raise ValueError("conv call with the bias vector of an operand packed without one")
+        if folded and bias is None and residual is None:
+            raise ValueError("eval-mode operand called without the shift of its fold")
+        if a["dil"] != 1 or a["stats"] is not None:
+            raise ValueError("U-TAE conv call with a dilation or a statistics buffer")
+        call.update(module=info["name"], tag=tag, layout=layout_of(pw), transpose=transpose, kernel=f"{pw.kh}x{pw.kw}",
+                    stride=1, dil=1, residual=residual is not None, bias=bias is not None, relu=bool(a["relu"]),
+                    folded=folded, cols=(c0, c1), sliced=(c1 - c0) != info["weight"].shape[1],
+                    out_hw=a["out_hw"] is not None, dtype=str(a["x"].dtype).replace("torch.", ""), utae=True)
+        if not transpose:
+            call["family"] = "utae_fwd"
+            if tag.endswith(":D"):  # the input gradient of a ConvTranspose2d: a forward conv of the output gradient
+                self._convT_grad = (call["call"], (live["x"].data_ptr(), tuple(live["x"].shape)))
+            return self.conv_forward(call, a["x"], w64, 1, a["pad"], out, bias=bias, residual=residual, relu=a["relu"])
+        if residual is not None:
+            raise ValueError("transposed U-TAE operand called with a residual")
+        call["family"] = "utae_dgrad" if tag.endswith(":T") else "utae_conv_transpose"
+        return self.conv_transposed(call, a["x"], w64, pw.kh - 1 - a["pad"], out, bias=bias, relu=a["relu"],
+                                    what="dx" if tag.endswith(":T") else "out")
 
     def _op_conv2d_bn_stats(self, call, a, live, out):
         y0, scale, shift, mean, rstd = out
@@ -1288,6 +1644,15 @@ class Recorder(Checker):
                     dtype=str(a["x"].dtype).replace("torch.", ""))
         call.update(co=out.shape[0], ci=out.shape[1], hw=tuple(a["x"].shape[1:3]))
         before = a["out"] if a["accumulate"] else None
+        self.wgrad_operands += [(call["call"], (live[k].data_ptr(), tuple(live[k].shape))) for k in ("x", "dy")]
+        node, self._convT_grad = self._convT_grad, None
+        if node is not None and call["call"] == node[0] + 1:
+            # y = C^T x for the convolution C with OIHW weight w [in, out, k, k]: dW is the weight gradient of C with the
+            # output gradient as C's input and x as C's output gradient -- the roles exchanged
+            call["conv_transpose"] = True
+            ok = node[1] == (live["x"].data_ptr(), tuple(live["x"].shape))
+            self._add(call, {"what": "ConvTranspose2d weight gradient: x is the output gradient", "shape": tuple(out.shape),
+                             "n": 1, "fail": 0 if ok else 1, "worst": 0.0 if ok else float("inf")})
         self.conv_wgrad(call, a["x"], a["dy"], a["kh"], a["kw"], a["stride"], a["pad"], out, before=before)
         self.grad_sources.append(("dW", out.detach().clone()))
 
@@ -1331,6 +1696,8 @@ class Recorder(Checker):
         dx, dres, dg, db = out
         mode = 0 if not a["relu"] else (1 if a["y"] is not None else 2)
         call.update(family=f"bn_bwd_mode{mode}", dres=dres is not None)
+        # a rescaled dlogits buffer that a BatchNorm consumes (the U-TAE's class-score layer) feeds no head's bias gradient
+        self._scaled.pop(live["dy"].data_ptr(), None)
         self.bn_bwd(call, a["x"], a["dy"], a["y"], a["gamma"], a["beta"], a["mean"], a["rstd"], a["relu"], dx, dres, dg, db)
 
     def _op_bn_stats(self, call, a, live, out):
@@ -1440,6 +1807,82 @@ class Recorder(Checker):
         call.update(family="tta_probabilities", views=a["views"])
         self.tta_probabilities(call, a["acc"], a["views"], self._tta_classes(a, live), out)
 
+    # ---- the U-TAE branch ------------------------------------------------------------------------
+
+    def _op_reflect_pad1(self, call, a, live, out):
+        self.reflect_pad1(call, a["x"], out)
+
+    def _op_reflect_pad1_bwd(self, call, a, live, out):
+        self.reflect_pad1_bwd(call, a["dpad"], out)
+
+    def _op_group_norm(self, call, a, live, out):
+        call.update(relu=bool(a["relu"]), residual=a["residual"] is not None)
+        self.group_norm(call, a["x"], a["gamma"], a["beta"], a["groups"], a["eps"], a["relu"], a["residual"], out)
+
+    def _op_group_norm_seq(self, call, a, live, out):
+        call.update(T=a["T"])
+        self.group_norm(call, a["x"], a["gamma"], a["beta"], a["groups"], a["eps"], False, None, out, seq=(a["B"], a["T"]))
+
+    def _op_group_norm_bwd(self, call, a, live, out):
+        call.update(relu=bool(a["relu"]))
+        self.group_norm_bwd(call, a["x"], a["dy"], a["gamma"], a["beta"], a["groups"], a["eps"], a["relu"], *out)
+
+    def _op_group_norm_seq_bwd(self, call, a, live, out):
+        call.update(T=a["T"])
+        self.group_norm_bwd(call, a["x"], a["dy"], a["gamma"], a["beta"], a["groups"], a["eps"], False, *out,
+                            seq=(a["B"], a["T"]))
+
+    def _op_positional_encoding(self, call, a, live, out):
+        self.positional_encoding(call, a["pos"], a["d"], a["repeat"], a["period"], out)
+
+    def _op_add_rowvec_(self, call, a, live, out):
+        self.add_rowvec(call, a["x"], a["vec"], out)
+
+    def _op_detect_pad_images(self, call, a, live, out):
+        self.detect_pad_images(call, a["x"], a["value"], out)
+
+    def _op_mask_images_(self, call, a, live, out):
+        call.update(value=float(a["value"]))
+        self.mask_images(call, a["x"], a["pad"], a["value"], out)
+
+    def _op_mul(self, call, a, live, out):
+        self.mul(call, a["x"], a["m"], out)
+
+    def _op_ltae_attention(self, call, a, live, out):
+        call.update(T=a["T"])
+        self.ltae_attention(call, a["k"], a["v"], a["Q"], a["pad"], None, a["B"], a["T"], *out)
+
+    def _op_ltae_attention_train(self, call, a, live, out):
+        call.update(T=a["T"], drop=a["drop"] is not None)
+        self.ltae_attention(call, a["k"], a["v"], a["Q"], a["pad"], a["drop"], a["B"], a["T"], *out)
+
+    def _op_ltae_attention_bwd(self, call, a, live, out):
+        call.update(T=a["T"], drop=a["drop"] is not None, dattn_ext=a["dattn_ext"] is not None)
+        self.ltae_attention_bwd(call, a["k"], a["v"], a["Q"], a["pad"], a["drop"], a["prob"], a["dout"], a["dattn_ext"],
+                                a["B"], a["T"], *out)
+        # what the aggregators sent back to the returned masks: dattn_ext must be the sum of the dattn of every
+        # temporal_aggregate_bwd call of this backward pass (autograd adds them in f32, in some order)
+        parts, self._dattn_parts = self._dattn_parts, []
+        call["aggregators"] = len(parts)
+        if parts or a["dattn_ext"] is not None:
+            ext = a["dattn_ext"] if a["dattn_ext"] is not None else torch.zeros_like(a["prob"])
+            r = sum(p.to(F64) for p in parts) if parts else torch.zeros_like(ext, dtype=F64)
+            mag = sum(p.to(F64).abs() for p in parts) if parts else r
+            self._add(call, _compare(ext, r, len(parts) * ulp_f32(mag), "dattn_ext = sum of the aggregators' dattn"))
+
+    def _op_temporal_aggregate(self, call, a, live, out):
+        self.temporal_aggregate(call, a["x"], a["attn"], a["pad"], a["B"], a["T"], a["use_pad"], out)
+
+    def _op_temporal_aggregate_bwd(self, call, a, live, out):
+        self.temporal_aggregate_bwd(call, a["x"], a["attn"], a["pad"], a["dout"], a["B"], a["T"], a["use_pad"], *out)
+        self._dattn_parts.append(out[1].detach().clone())
+
+    def _op_column_sums(self, call, a, live, out):
+        self.column_sums(call, a["x"], out)
+        src = out.detach().clone()
+        self.sum_sources.append(src)
+        self.sum_inputs[id(src)] = (call["call"], (live["x"].data_ptr(), tuple(live["x"].shape)))
+
     # ---- report --------------------------------------------------------------------------------
 
     def failures(self) -> List[Result]:
@@ -1453,7 +1896,13 @@ class Recorder(Checker):
           weight of a fusion 1x1 conv: one wgrad per source);
         * (b) it is the bias gradient of a head whose dgrad call read a rescaled dlogits buffer: then it must pass
           head_bias_grad against the final contents of THAT buffer, whatever else it may equal;
-        * it is a bias gradient cut from the front of a checked channel_sums output, bit for bit."""
+        * it is a bias gradient cut from the front of a checked channel_sums / column_sums output, bit for bit; column
+          sums count only if the tensor they summed was also an operand of a checked conv_wgrad call of the same
+          backward node (WGRAD_WINDOW calls around it, while the tensor is alive and its address its own) -- the gradient
+          of the layer's output, which its weight gradient is taken from --, not just any tensor of the right width;
+        * it is the front of a checked dgamma / dbeta vector (a class-score layer stored at the logits pitch);
+        * it is a Conv1d [O, I, 1] or Linear [O, I] weight's view of a checked 1x1 conv_wgrad output [O, I, 1, 1];
+        * it is dQ [n_head, d_k] as ltae_attention_bwd returned it (a view of its column sums, checked there)."""
         by_shape = defaultdict(list)
         for _, t in self.grad_sources:
             by_shape[tuple(t.shape)].append(t)
@@ -1475,10 +1924,27 @@ class Recorder(Checker):
                 continue
             if g.dim() == 4 and self._is_concat_of_wgrads(g, dws):
                 continue
-            if g.dim() == 1 and any(t.numel() >= g.numel() and torch.equal(g, t[:g.numel()]) for t in self.sum_sources):
+            if g.dim() == 1 and any(t.numel() >= g.numel() and torch.equal(g, t[:g.numel()]) and self._summed_a_wgrad_operand(t)
+                                    for t in self.sum_sources):
+                continue
+            if g.dim() == 1 and any(t.dim() == 1 and t.numel() > g.numel() and torch.equal(g, t[:g.numel()])
+                                    for tag, t in self.grad_sources if tag in ("dgamma", "dbeta")):
+                continue
+            if g.dim() in (2, 3) and g.numel() == g.shape[0] * g.shape[1] and any(
+                    tuple(t.shape) == (g.shape[0], g.shape[1], 1, 1) and torch.equal(g.reshape(t.shape), t) for t in dws):
                 continue
             orphans.append(name)
         return orphans
+
+    WGRAD_WINDOW = (-4, 8)  # a node's wgrad calls come at most 4 calls before and 8 after the column sums of its bias
+
+    def _summed_a_wgrad_operand(self, t) -> bool:
+        src = self.sum_inputs.get(id(t))
+        if src is None:  # channel_sums: the statistics pass of the layer's own output
+            return True
+        c, key = src
+        lo, hi = self.WGRAD_WINDOW
+        return any(k == key and lo <= w - c <= hi for w, k in self.wgrad_operands)
 
     @staticmethod
     def _is_concat_of_wgrads(g, dws) -> bool:

@@ -1409,3 +1409,480 @@ def test_onehot_to_index_is_held_to_the_first_maximum():
         ck = Checker("full", chunk=1)
         ck.onehot_to_index({"op": "onehot_to_index"}, oh, out)
         assert [r.ok for r in ck.results] == [ok]
+
+
+# --------------------------------------------------------------------------------------------------
+# the references of the U-TAE time-series branch (csrc/temporal.hip through flairhip/utae.py).  Per op: a float32 torch
+# emulation with its output rounded once to the storage type must pass for bf16 and f32 storage (the worst error / bound
+# ratio is printed), and each mutant -- the ways these ops go subtly wrong -- must fail.  Shapes are small on purpose:
+# a variance taken with n - 1 moves a bf16 output by more than its rounding only while a group holds few values.
+
+UDT = pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+UB, UT, UH, UW, UNH, UDK, UDV = 2, 4, 5, 7, 16, 4, 16   # sample 0 has its last two dates padded
+UEPS = 1e-5
+
+
+def _verdict(ck, honest, what):
+    worst = max(r["worst"] for r in ck.results)
+    bad = [r.line() for r in ck.results if not r.ok]
+    print(f"\n{what}: worst error / bound {worst:.3g}" + (f"; flagged: {bad[:3]}" if bad else ""))
+    assert (not bad) if honest else bad, (what, bad[:5])
+    return worst
+
+
+def _upad():
+    pad = torch.zeros(UB, UT, dtype=torch.uint8)
+    pad[0, UT - 2:] = 1
+    return pad.reshape(-1)
+
+
+def _gn_unrows(r, shape, seq):
+    """inverse of Checker._gn_rows"""
+    if seq is None:
+        return r.reshape(shape)
+    Bq, Tq = seq
+    return r.reshape(Bq, -1, Tq, r.shape[2], r.shape[3]).permute(0, 2, 1, 3, 4).reshape(shape)
+
+
+def _gn_inputs(seq, dt, seed=71):
+    g = torch.Generator().manual_seed(seed)
+    if seq is None:
+        N, Hh, Ww, C, G = 2, 3, 3, 32, 4           # 72 values per group
+    else:
+        N, Hh, Ww, C, G = seq[0] * seq[1], 2, 3, 128, 16   # T * 8 values per group
+    x = torch.randn(N, Hh, Ww, C, generator=g) * 2 + 0.5
+    x[-1] = torch.randn(Hh, Ww, C, generator=g) * 1e-3          # variance 1e-6: eps = 1e-5 decides the result
+    if seq is not None:
+        x = x.reshape(seq[0], seq[1], Hh, Ww, C)
+        x[-1] = torch.randn(seq[1], Hh, Ww, C, generator=g) * 1e-3   # every date of the last series
+        x[0, -1] = 0.0                                          # a padded date as mask_images_ leaves it
+        x = x.reshape(N, Hh, Ww, C)
+    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g)
+    res = torch.randn(N, Hh, Ww, C, generator=g)
+    dy = torch.randn(N, Hh, Ww, C, generator=g)
+    return x.to(dt), gamma, beta, res.to(dt), dy.to(dt), G
+
+
+def _gn_emulate(x, gamma, beta, G, relu, res, seq, dy=None, mutant=None):
+    """float32 GroupNorm forward (dy None) or backward on storage-typed tensors -> f32 results"""
+    rows = lambda t: Checker._gn_rows(t.float(), G, seq)
+    xg = rows(x)
+    src = rows(torch.roll(x.float(), -1, dims=-1)) if mutant == "group_shift" else xg
+    n = xg.shape[1] * xg.shape[3]
+    if mutant == "skip_padded":  # statistics over the real dates only: sample 0's last date is padded
+        keep = torch.ones(xg.shape[0], xg.shape[1], 1, 1)
+        keep[: xg.shape[0] // seq[0], -1] = 0
+        cnt = keep.sum((1, 3), keepdim=True) * xg.shape[3]
+        m = (src * keep).sum((1, 3), keepdim=True) / cnt
+        var = (((src - m) ** 2) * keep).sum((1, 3), keepdim=True) / cnt
+    else:
+        m = src.mean((1, 3), keepdim=True)
+        var = ((src - m) ** 2).mean((1, 3), keepdim=True)
+    if mutant == "n_minus_1":
+        var = var * n / (n - 1)
+    rs = 1.0 / torch.sqrt(var + (0.0 if mutant == "no_eps" else UEPS))
+    g, b = gamma.reshape(G, -1), beta.reshape(G, -1)
+    xh = (xg - m) * rs
+    pre = xh * g + b
+    if dy is None:
+        if mutant == "relu_after_residual":
+            y = torch.relu(pre + rows(res))
+        else:
+            y = torch.relu(pre) if relu else pre
+            if res is not None:
+                y = y + rows(res)
+        return _gn_unrows(y, x.shape, seq)
+    gm = rows(dy)
+    if relu:
+        gm = torch.where(pre > 0, gm, torch.zeros(()))
+    prod = gm * xh
+    if mutant == "dgamma_bf16":
+        prod = _bf(prod)
+    dgamma, dbeta = prod.sum((0, 1)).reshape(-1), gm.sum((0, 1)).reshape(-1)
+    gg = gm * g
+    if mutant == "const_stats":
+        dx = rs * gg
+    else:
+        dx = rs * (gg - gg.mean((1, 3), keepdim=True) - xh * (gg * xh).mean((1, 3), keepdim=True))
+    return _gn_unrows(dx, x.shape, seq), dgamma, dbeta
+
+
+def _run_gn(dt, seq, relu, with_res, mutant=None):
+    x, gamma, beta, res, _, G = _gn_inputs(seq, dt)
+    res = res if with_res else None
+    y = _gn_emulate(x, gamma, beta, G, relu, res, seq, mutant=mutant).to(dt)
+    ck = Checker("full")
+    ck.group_norm({"op": "group_norm"}, x, gamma, beta, G, UEPS, relu, res, y, seq=seq)
+    return ck
+
+
+def _run_gn_bwd(dt, seq, relu, mutant=None):
+    x, gamma, beta, _, dy, G = _gn_inputs(seq, dt)
+    dx, dgamma, dbeta = _gn_emulate(x, gamma, beta, G, relu, None, seq, dy=dy, mutant=mutant)
+    ck = Checker("full")
+    ck.group_norm_bwd({"op": "group_norm_bwd"}, x, dy, gamma, beta, G, UEPS, relu, dx.to(dt), dgamma, dbeta, seq=seq)
+    return ck
+
+
+@UDT
+@pytest.mark.parametrize("seq,relu,with_res", [(None, False, False), (None, True, True), ((2, 3), False, False),
+                                               ((6, 1), False, False)], ids=["2d", "2d-relu-res", "seq", "seq-T1"])
+def test_group_norm_emulation_passes(dt, seq, relu, with_res):
+    _verdict(_run_gn(dt, seq, relu, with_res), True, f"group_norm {seq} {dt}")
+    _verdict(_run_gn_bwd(dt, seq, relu), True, f"group_norm_bwd {seq} {dt}")
+
+
+@UDT
+@pytest.mark.parametrize("mutant,seq", [("n_minus_1", None), ("n_minus_1", (2, 3)), ("no_eps", None), ("no_eps", (2, 3)),
+                                        ("group_shift", None), ("group_shift", (2, 3)), ("skip_padded", (2, 3)),
+                                        ("relu_after_residual", None)], ids=str)
+def test_group_norm_mutant_is_flagged(dt, mutant, seq):
+    relu = mutant == "relu_after_residual"
+    _verdict(_run_gn(dt, seq, relu, relu, mutant), False, f"group_norm {mutant} {seq} {dt}")
+
+
+@UDT
+@pytest.mark.parametrize("seq", [None, (2, 3)], ids=["2d", "seq"])
+@pytest.mark.parametrize("mutant", ["const_stats", "dgamma_bf16"])
+def test_group_norm_bwd_mutant_is_flagged(dt, mutant, seq):
+    ck = _run_gn_bwd(dt, seq, seq is None, mutant)
+    _verdict(ck, False, f"group_norm_bwd {mutant} {seq} {dt}")
+    flagged = {r["what"] for r in ck.results if not r.ok}
+    assert flagged == ({"dx"} if mutant == "const_stats" else {"dgamma"}), flagged
+
+
+def test_group_norm_bwd_counts_too_many_ambiguous_relu_masks_on_the_reference_alone():
+    """gamma = beta = 0 puts every pre-activation at zero: the mask is open wherever dy is not 0, which is too often"""
+    x, gamma, beta, _, dy, G = _gn_inputs(None, torch.float32)
+    ck = Checker("full")
+    zero = torch.zeros_like(gamma)
+    dx, dgamma, dbeta = _gn_emulate(x, zero, zero, G, True, None, None, dy=dy)
+    ck.group_norm_bwd({"op": "group_norm_bwd"}, x, dy, zero, zero, G, UEPS, True, dx, dgamma, dbeta)
+    assert [r["what"] for r in ck.results if not r.ok] == ["ambiguous ReLU masks"]
+
+
+# ---- L-TAE attention
+
+def _ltae_inputs(dt, seed=73):
+    g = torch.Generator().manual_seed(seed)
+    N = UB * UT
+    k = torch.randn(N, UH, UW, UNH * UDK, generator=g).to(dt)
+    v = torch.randn(N, UH, UW, UNH * UDV, generator=g).to(dt)
+    Q = torch.randn(UNH, UDK, generator=g) * (2.0 / UDK) ** 0.5
+    drop = torch.empty(UNH, UB, UT, UH * UW).bernoulli_(0.9, generator=g) / 0.9
+    dout = torch.randn(UB, UH, UW, UNH * UDV, generator=g).to(dt)
+    ext = torch.randn(UNH, UB, UT, UH * UW, generator=g)
+    return k, v, Q, _upad(), drop, dout, ext
+
+
+def _ltae_emulate(k, v, Q, pad, drop, mutant=None):
+    P = UH * UW
+    k5, v5 = k.float().reshape(UB, UT, P, UNH, UDK), v.float().reshape(UB, UT, P, UNH, UDV)
+    padm = pad.reshape(UB, UT).bool()[:, :, None, None]
+    temp = float(UDK) if mutant == "temperature" else float(UDK) ** 0.5
+    s = (k5 * Q).sum(-1) / temp
+    if mutant != "pad_keeps_weight":
+        s = s.masked_fill(padm, -1e3)
+    dr = torch.ones_like(s) if drop is None else drop.permute(1, 2, 3, 0)
+    p = torch.softmax(s, dim=1)
+    if mutant == "drop_before_norm":
+        e = torch.exp(s - s.max(1, keepdim=True).values) * dr
+        at = e / e.sum(1, keepdim=True).clamp_min(1e-30)
+    else:
+        at = p * dr
+    used = _bf(at) if mutant == "prob_bf16" else at
+    out = (used[..., None] * v5).sum(1)
+    return out.reshape(UB, UH, UW, -1), at.permute(3, 0, 1, 2).contiguous(), p.permute(3, 0, 1, 2).contiguous()
+
+
+def _run_ltae(dt, train, mutant=None):
+    k, v, Q, pad, drop, _, _ = _ltae_inputs(dt)
+    drop = drop if train else None
+    out, attn, prob = _ltae_emulate(k, v, Q, pad, drop, mutant)
+    ck = Checker("full")
+    ck.ltae_attention({"op": "ltae_attention"}, k, v, Q, pad, drop, UB, UT, out.to(dt), attn, prob if train else None)
+    return ck
+
+
+def _ltae_bwd_emulate(k, v, Q, pad, drop, prob, dout, ext, mutant=None):
+    P = UH * UW
+    k5, v5 = k.float().reshape(UB, UT, P, UNH, UDK), v.float().reshape(UB, UT, P, UNH, UDV)
+    padm = pad.reshape(UB, UT).bool()[:, :, None, None]
+    p, dr = prob.permute(1, 2, 3, 0), drop.permute(1, 2, 3, 0)
+    go = dout.float().reshape(UB, 1, P, UNH, UDV)
+    da = (go * v5).sum(-1)
+    if mutant != "no_dattn_ext":
+        da = da + ext.permute(1, 2, 3, 0)
+    if mutant == "through_dropped_attn":
+        at = p * dr
+        ds = at * (da - (at * da).sum(1, keepdim=True))
+    else:
+        dp = da * dr
+        ds = p * (dp - (p * dp).sum(1, keepdim=True))
+    ds = ds.masked_fill(padm, 0.0) / float(UDK) ** 0.5
+    dk = (ds[..., None] * Q).reshape(k.shape)
+    dv = ((p * dr)[..., None] * go).reshape(v.shape)
+    prod = ds[..., None] * k5
+    dq = prod[:1].sum((0, 1, 2)) if mutant == "dq_one_sample" else prod.sum((0, 1, 2))
+    return dk, dv, dq
+
+
+def _run_ltae_bwd(dt, mutant=None):
+    k, v, Q, pad, drop, dout, ext = _ltae_inputs(dt)
+    _, _, prob = _ltae_emulate(k, v, Q, pad, drop)
+    dk, dv, dq = _ltae_bwd_emulate(k, v, Q, pad, drop, prob, dout, ext, mutant)
+    ck = Checker("full")
+    ck.ltae_attention_bwd({"op": "ltae_attention_bwd"}, k, v, Q, pad, drop, prob, dout, ext, UB, UT, dk.to(dt), dv.to(dt), dq)
+    return ck
+
+
+@UDT
+def test_ltae_attention_emulation_passes(dt):
+    _verdict(_run_ltae(dt, False), True, f"ltae_attention {dt}")
+    _verdict(_run_ltae(dt, True), True, f"ltae_attention_train {dt}")
+    ck = _run_ltae_bwd(dt)
+    _verdict(ck, True, f"ltae_attention_bwd {dt}")
+    assert [t for t, _ in ck.grad_sources] == ["dQ"]
+
+
+@UDT
+@pytest.mark.parametrize("mutant", ["temperature", "pad_keeps_weight", "drop_before_norm", "prob_bf16"])
+def test_ltae_attention_mutant_is_flagged(dt, mutant):
+    _verdict(_run_ltae(dt, True, mutant), False, f"ltae_attention_train {mutant} {dt}")
+
+
+@UDT
+@pytest.mark.parametrize("mutant", ["no_dattn_ext", "dq_one_sample", "through_dropped_attn"])
+def test_ltae_attention_bwd_mutant_is_flagged(dt, mutant):
+    ck = _run_ltae_bwd(dt, mutant)
+    _verdict(ck, False, f"ltae_attention_bwd {mutant} {dt}")
+    if mutant == "dq_one_sample":
+        assert {r["what"] for r in ck.results if not r.ok} == {"dQ"}
+
+
+# ---- temporal_aggregate
+
+def _agg_inputs(dt, seed=79, C=64):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(UB * UT, UH, UW, C, generator=g).to(dt)
+    attn = torch.rand(UNH, UB, UT, UH * UW, generator=g) + 0.05  # non-zero at the padded dates: the mask matters
+    dout = torch.randn(UB, UH, UW, C, generator=g).to(dt)
+    return x, attn, _upad(), dout
+
+
+def _run_aggregate(dt, mutant=None):
+    x, attn, pad, dout = _agg_inputs(dt)
+    C, P = x.shape[-1], UH * UW
+    x5 = x.float().reshape(UB, UT, P, UNH, C // UNH)
+    a4 = attn.permute(1, 2, 3, 0)
+    if mutant == "heads_rotated":
+        a4 = torch.roll(a4, 1, dims=-1)
+    dead = pad.reshape(UB, UT).bool()[:, :, None, None]
+    am = a4 if mutant == "no_pad_mask" else a4.masked_fill(dead, 0.0)
+    out = (am[..., None] * x5).sum(1).reshape(UB, UH, UW, C)
+    go = dout.float().reshape(UB, 1, P, UNH, C // UNH)
+    dx = (am[..., None] * go).reshape(x.shape)
+    dattn = (x5 * go).sum(-1)
+    if mutant != "no_pad_mask":
+        dattn = dattn.masked_fill(dead, 0.0)
+    if mutant == "dattn_group_missing":
+        dattn[..., 5] = 0.0
+    ck = Checker("full")
+    ck.temporal_aggregate({"op": "temporal_aggregate"}, x, attn, pad, UB, UT, True, out.to(dt))
+    ck.temporal_aggregate_bwd({"op": "temporal_aggregate_bwd"}, x, attn, pad, dout, UB, UT, True, dx.to(dt),
+                              dattn.permute(3, 0, 1, 2).contiguous())
+    return ck
+
+
+@UDT
+def test_temporal_aggregate_emulation_passes(dt):
+    _verdict(_run_aggregate(dt), True, f"temporal_aggregate and its backward {dt}")
+
+
+@UDT
+@pytest.mark.parametrize("mutant", ["heads_rotated", "no_pad_mask", "dattn_group_missing"])
+def test_temporal_aggregate_mutant_is_flagged(dt, mutant):
+    ck = _run_aggregate(dt, mutant)
+    _verdict(ck, False, f"temporal_aggregate {mutant} {dt}")
+    flagged = {r["what"] for r in ck.results if not r.ok}
+    assert flagged == ({"dattn"} if mutant == "dattn_group_missing" else {"out", "dx", "dattn"} - (
+        {"dattn"} if mutant == "heads_rotated" else set())), flagged
+
+
+# ---- reflect padding, column sums, the encoding, the elementwise kernels
+
+def _run_reflect(dt, hw, mutant=None):
+    g = torch.Generator().manual_seed(83)
+    x = torch.randn(2, 16, *hw, generator=g).to(dt)
+    dpad = torch.randn(2, 16, hw[0] + 2, hw[1] + 2, generator=g).to(dt)
+    xx = x.float().requires_grad_()
+    y = F.pad(xx, (1, 1, 1, 1), mode="reflect")
+    d = dpad.float().clone()
+    if mutant == "corners_dropped":
+        for cy in (0, -1):
+            for cx in (0, -1):
+                d[:, :, cy, cx] = 0.0
+    (y * d).sum().backward()
+    ck = Checker("full")
+    ck.reflect_pad1({"op": "reflect_pad1"}, _nhwc(x), _nhwc(y.detach()).to(dt))
+    ck.reflect_pad1_bwd({"op": "reflect_pad1_bwd"}, _nhwc(dpad), _nhwc(xx.grad).to(dt))
+    return ck
+
+
+@UDT
+@pytest.mark.parametrize("hw", [(2, 2), (3, 3), (5, 7), (10, 10)], ids=str)
+def test_reflect_pad_emulation_passes_and_dropped_corners_are_flagged(dt, hw):
+    _verdict(_run_reflect(dt, hw), True, f"reflect_pad1 and its backward {hw} {dt}")
+    ck = _run_reflect(dt, hw, "corners_dropped")
+    _verdict(ck, False, f"reflect_pad1_bwd corners_dropped {hw} {dt}")
+    bad = [r for r in ck.results if not r.ok]
+    # the four pixels next to the corners (they receive up to four contributions), and nothing else
+    assert [r["what"] for r in bad] == ["dx"] and bad[0]["fail"] <= 4 * 2 * 16
+
+
+@UDT
+def test_column_sums_emulation_passes_and_a_dropped_partial_block_is_flagged(dt):
+    g = torch.Generator().manual_seed(89)
+    x = torch.randn(70, 24, generator=g).to(dt)          # 70 rows: two blocks of 32 and a partial one of 6
+    blocks = [x.float()[i:i + 32].sum(0) for i in range(0, 70, 32)]
+    for parts, honest in ((blocks, True), (blocks[:-1], False)):
+        ck = Checker("full")
+        ck.column_sums({"op": "column_sums"}, x, sum(parts))
+        _verdict(ck, honest, f"column_sums {'all blocks' if honest else 'last partial block dropped'} {dt}")
+
+
+def _encoding_emulate(pos, d, repeat, mutant=None, period=1000.0):
+    j = torch.arange(d * repeat)
+    jj, head = j % d, j // d
+    pair = head if mutant == "exponent_per_head" else torch.div(jj, 2, rounding_mode="floor")
+    arg = pos.float()[:, None] / torch.pow(torch.tensor(period), 2.0 * pair.float() / d)
+    odd = (jj % 2 == 1)[None, :]
+    if mutant == "sin_cos_swapped":
+        odd = ~odd
+    return torch.where(odd, torch.cos(arg), torch.sin(arg))
+
+
+@pytest.mark.parametrize("mutant", [None, "sin_cos_swapped", "exponent_per_head"])
+def test_positional_encoding_emulation_and_mutants(mutant):
+    pos = torch.tensor([0.0, 1.0, 17.0, 203.0, 364.0])
+    ck = Checker("full")
+    ck.positional_encoding({"op": "positional_encoding"}, pos, 16, 16, 1000.0, _encoding_emulate(pos, 16, 16, mutant))
+    _verdict(ck, mutant is None, f"positional_encoding {mutant}")
+
+
+@UDT
+def test_elementwise_utae_kernels(dt):
+    g = torch.Generator().manual_seed(97)
+    N, C = UB * UT, 32
+    x = torch.randn(N, UH, UW, C, generator=g).to(dt)
+    pad = _upad()
+    vec = torch.randn(N, C, generator=g)
+    m = (torch.empty(N, UH, UW, C).bernoulli_(0.8, generator=g) / 0.8).to(dt)
+    flags = torch.tensor([0, 0, 1, 1, 0, 0, 0, 0], dtype=torch.uint8)
+    raw = torch.randn(N, 3, UH, UW, generator=g)
+    raw[2:4] = 0.0
+    padm = pad.bool()[:, None, None, None]
+    for mutant in (None, "leak", "double_rounding", "flags"):
+        ck = Checker("full")
+        ck.add_rowvec({"op": "add_rowvec_"}, x, vec, (x.float() + vec[:, None, None, :]).to(dt))
+        masked = torch.where(padm & (mutant != "leak" or torch.arange(C) > 0), torch.tensor(1.5, dtype=dt), x)
+        ck.mask_images({"op": "mask_images_"}, x, pad, 1.5, masked)
+        ck.mul({"op": "mul"}, x, m, ((_bf(x.float() * 1.0078125) if mutant == "double_rounding" else x.float()) * m.float()
+                                     ).to(dt))
+        ck.detect_pad_images({"op": "detect_pad_images"}, raw, 0.0, flags if mutant != "flags" else 1 - flags)
+        _verdict(ck, mutant is None, f"add_rowvec / mask_images / mul / detect_pad_images {mutant} {dt}")
+        want = {None: [], "leak": ["mask_images_"], "double_rounding": ["mul"], "flags": ["detect_pad_images"]}[mutant]
+        assert [r["op"] for r in ck.results if not r.ok] == want
+
+
+# ---- the transposed-operand paths of flairhip/utae.py
+
+@UDT
+def test_transposed_operand_references_disagree_with_the_untransposed_weight(dt):
+    """ConvTranspose2d(3, 1, 1) as a pad-1 conv with a transposed operand, and the input gradient of a reflect-padded
+    (pad-0) 3x3 conv as a pad-2 conv with out_hw: correct emulations pass conv_transposed, and a reference built from
+    the same weight taken as it stands (no exchange of the channel axes, no flipped taps) rejects them"""
+    g = torch.Generator().manual_seed(101)
+    q = _bf if dt == torch.bfloat16 else (lambda t: t)
+    C, Hh, Ww = 16, 5, 7
+    w = q(torch.randn(C, C, 3, 3, generator=g) / 8)          # in == out, so that the untransposed weight has a valid shape
+    x = q(torch.randn(2, C, Hh, Ww, generator=g))
+    bias = torch.randn(C, generator=g)
+    up = torch.relu(F.conv_transpose2d(x, w, padding=1) + bias[None, :, None, None])
+    dxp = F.conv_transpose2d(x, w, padding=0)                # [2, C, H + 2, W + 2]
+    for what, out, pad_t, pad_call, b, relu in (("ConvTranspose2d forward", up, 1, 1, bias, True),
+                                                ("reflect conv input gradient", dxp, 0, 2, None, False)):
+        ck = Checker("full")
+        ck.conv_transposed({"op": "conv2d"}, _nhwc(x).to(dt), w.double(), pad_t, _nhwc(out).to(dt), bias=b, relu=relu)
+        _verdict(ck, True, f"{what} {dt}")
+        ck = Checker("full")
+        ck.conv_forward({"op": "conv2d"}, _nhwc(x).to(dt), w.double(), 1, pad_call, _nhwc(out).to(dt), bias=b, relu=relu)
+        _verdict(ck, False, f"{what} against the untransposed weight {dt}")
+    # and the adjoint really is the adjoint: <conv(x', w), d> == <x', conv_transposed(d, w)> in float64
+    xp, d = torch.randn(2, C, Hh + 2, Ww + 2, generator=g).double(), x.double()
+    lhs = (F.conv2d(xp, w.double()) * d).sum()
+    rhs = (xp * F.conv_transpose2d(d, w.double())).sum()
+    assert abs(lhs - rhs) <= 1e-9 * abs(lhs)
+
+
+def test_conv_transpose_weight_gradient_must_take_the_output_gradient_as_its_input():
+    """the backward of ConvTranspose2d as the product evaluates it: right after the forward conv of the output gradient d0
+    (the ':D' operand), conv_wgrad(d0, x) -- with the operands the other way round the values are those of another layer"""
+    g = torch.Generator().manual_seed(109)
+    C, Hh, Ww = 16, 5, 7
+    d0, xa = torch.randn(2, Hh, Ww, C, generator=g), torch.randn(2, Hh, Ww, C, generator=g)
+    for x, dy, ok in ((d0, xa, True), (xa, d0, False)):
+        rec = insitu.Recorder(torch.nn.Module(), "full")
+        rec._convT_grad = (6, (d0.data_ptr(), tuple(d0.shape)))
+        dw = conv2d_weight(_nchw(x), (C, C, 3, 3), _nchw(dy), padding=1)
+        args = {"x": x, "dy": dy, "kh": 3, "kw": 3, "stride": 1, "pad": 1, "accumulate": False, "out": None}
+        rec._op_conv_wgrad({"op": "conv_wgrad", "call": 7}, args, args, dw)
+        assert [r["what"] for r in rec.results if not r.ok] == ([] if ok else
+                                                               ["ConvTranspose2d weight gradient: x is the output gradient"])
+        assert rec._convT_grad is None
+
+
+def test_packed_bias_vector_of_the_utae_operands():
+    g = torch.Generator().manual_seed(103)
+    n, pitch = 19, 24
+    b, scale, shift = torch.randn(n, generator=g), torch.rand(pitch, generator=g) + 0.5, torch.randn(pitch, generator=g)
+    train, folded = torch.zeros(pitch), torch.zeros(pitch)
+    train[:n] = b
+    folded[:n] = shift[:n] + scale[:n] * b
+    for vec, sc, sh, hb, ok in ((train, None, None, b, True), (folded, scale, shift, b, True), (train, scale, shift, b, False),
+                                (folded, None, None, b, False), (torch.zeros(pitch), None, None, None, True),
+                                (train, None, None, None, False), (shift.clone(), scale, shift, b, False)):
+        ck = Checker("full")
+        ck.packed_bias({"op": "utae_packed"}, vec, hb, n, sc, sh)
+        assert [r.ok for r in ck.results] == [ok]
+
+
+def test_grad_source_rules_of_the_utae_step():
+    """dW as the dim=1 concatenation of two consecutive wgrads, [:n].clone() slices of checked sums and of checked
+    dgamma / dbeta vectors, Conv1d / Linear views of a 1x1 dW and dQ as returned -- and nothing looser"""
+    g = torch.Generator().manual_seed(107)
+    rec = insitu.Recorder(torch.nn.Module(), "full")
+    dwa, dwb, lin = torch.randn(8, 6, 3, 3, generator=g), torch.randn(8, 10, 3, 3, generator=g), torch.randn(12, 20, 1, 1, generator=g)
+    dgam, sums, dq = torch.randn(24, generator=g), torch.randn(32, generator=g), torch.randn(16, 4, generator=g)
+    rec.grad_sources += [("dW", dwa), ("dW", dwb), ("dW", lin), ("dgamma", dgam), ("dQ", dq)]
+    rec.sum_sources.append(sums)
+
+    def orphan(t, name="m.weight"):
+        p = torch.nn.Parameter(torch.zeros_like(t))
+        p.grad = t.clone()
+        return rec.grad_orphans([(name, p)]) != []
+
+    assert not orphan(torch.cat([dwa, dwb], 1)) and orphan(torch.cat([dwb, dwa], 1))
+    assert not orphan(lin.view(12, 20, 1)) and not orphan(lin.view(12, 20)) and orphan(lin.view(12, 20).t().contiguous())
+    assert orphan(lin.view(12, 20)[:, :10].contiguous()) and orphan(lin.view(20, 12))
+    assert not orphan(dgam[:19].clone(), "m.weight") and orphan(dgam[1:20].clone()) and orphan(dgam[:19] * 1.0000001)
+    assert not orphan(sums[:19].clone(), "m.bias") and orphan(sums[2:21].clone(), "m.bias")
+    # column sums of a tensor that no checked conv_wgrad call read are not a bias gradient (dy in place of d0)
+    rec.sum_inputs[id(sums)] = (40, (4096, (2, 5, 7, 32)))
+    assert orphan(sums[:19].clone(), "m.bias")
+    rec.wgrad_operands += [(20, (4096, (2, 5, 7, 32))), (41, (8192, (2, 5, 7, 32))), (49, (4096, (2, 5, 7, 32)))]
+    assert orphan(sums[:19].clone(), "m.bias")      # the same address in another node, another tensor in this one
+    rec.wgrad_operands.append((45, (4096, (2, 5, 7, 32))))
+    assert not orphan(sums[:19].clone(), "m.bias")
+    assert not orphan(dq, "Q") and orphan(dq.t().contiguous().t(), "Q") is False  # the same values in another layout
+    assert orphan(dq[:8].clone(), "Q") and orphan(dq + 1e-6, "Q")
