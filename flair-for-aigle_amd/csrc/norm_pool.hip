@@ -249,13 +249,14 @@ extern "C" int ffa_nhwc_to_nchw(int dtype, const void* src, float* dst, int B, i
 // pass used -- saves reading y (one third of the reduce pass, one quarter of the apply pass)
 struct StatOp {  // sum(x), sum(x^2)
   static constexpr bool kChunk = false;
+  static constexpr bool kStoreG = false;
   __device__ __forceinline__ void init(int, const float*, const float*, const float*, const float*) {}
   template <typename R, typename T>
   __device__ __forceinline__ void load(long long off, R& xr, R&, R&, const T* x, const T*, const T*, int) const {
     xr.load(x + off);
   }
-  template <typename R>
-  __device__ __forceinline__ void acc(float (&a)[8], float (&b)[8], const R& xr, const R&, const R&, int) const {
+  template <typename R, typename T>
+  __device__ __forceinline__ void acc(float (&a)[8], float (&b)[8], const R& xr, const R&, const R&, int, T*) const {
     float v[8];
     xr.get(v);
 #pragma unroll
@@ -268,6 +269,7 @@ struct StatOp {  // sum(x), sum(x^2)
 
 struct BnBwdOp {  // sum(g), sum(g * xhat) with g = dy masked by the ReLU
   static constexpr bool kChunk = true;
+  static constexpr bool kStoreG = false;
   float mean[8], rstd[8], sc[8], sh[8];
   __device__ __forceinline__ void init(int c0, const float* m, const float* r, const float* gamma, const float* beta) {
 #pragma unroll
@@ -285,9 +287,10 @@ struct BnBwdOp {  // sum(g), sum(g * xhat) with g = dy masked by the ReLU
     gr.load(dy + off);
     if (relu == 1) yr.load(y + off);
   }
-  template <typename R>
+  // gout (BnBwdStoreOp): where the masked gradient of these 8 channels goes
+  template <typename R, typename T>
   __device__ __forceinline__ void acc(float (&a)[8], float (&b)[8], const R& xr, const R& gr, const R& yr,
-                                      int relu) const {
+                                      int relu, T* gout) const {
     float xv[8], gv[8];
     xr.get(xv);
     gr.get(gv);
@@ -296,6 +299,7 @@ struct BnBwdOp {  // sum(g), sum(g * xhat) with g = dy masked by the ReLU
       yr.get(yv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) gv[e] = yv[e] > 0.f ? gv[e] : 0.f;
+      if (gout) gr.store_where_positive(gout, yv);  // never taken in BnBwdOp's kernel, which passes a literal null
     } else if (relu == 2) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) gv[e] = (xv[e] * sc[e] + sh[e]) > 0.f ? gv[e] : 0.f;
@@ -306,6 +310,13 @@ struct BnBwdOp {  // sum(g), sum(g * xhat) with g = dy masked by the ReLU
       b[e] += gv[e] * (xv[e] - mean[e]) * rstd[e];
     }
   }
+};
+
+// BnBwdOp that also leaves the masked gradient g in memory (relu mode 1 with a residual branch: g IS the residual
+// gradient).  g is dy or 0, so the stored value is exact in bf16 as in f32, and the apply pass reads it back instead of
+// dy and y.  A kernel of its own: the store costs registers that the other modes' reduction does not pay.
+struct BnBwdStoreOp : BnBwdOp {
+  static constexpr bool kStoreG = true;
 };
 
 // Streaming loops below keep FFA_EW_UNROLL independent 16-byte loads per operand in flight per thread (issued before
@@ -330,6 +341,15 @@ template <>
 struct Raw8<ffa_bf16> {
   uint4 u;
   __device__ __forceinline__ void load(const ffa_bf16* p) { u = *reinterpret_cast<const uint4*>(p); }
+  // p[e] = (m[e] > 0 ? this : 0)[e], on the stored bits: nothing is converted, so nothing is rounded
+  __device__ __forceinline__ void store_where_positive(ffa_bf16* p, const float (&m)[8]) const {
+    uint4 o;
+    o.x = u.x & ((m[0] > 0.f ? 0x0000ffffu : 0u) | (m[1] > 0.f ? 0xffff0000u : 0u));
+    o.y = u.y & ((m[2] > 0.f ? 0x0000ffffu : 0u) | (m[3] > 0.f ? 0xffff0000u : 0u));
+    o.z = u.z & ((m[4] > 0.f ? 0x0000ffffu : 0u) | (m[5] > 0.f ? 0xffff0000u : 0u));
+    o.w = u.w & ((m[6] > 0.f ? 0x0000ffffu : 0u) | (m[7] > 0.f ? 0xffff0000u : 0u));
+    *reinterpret_cast<uint4*>(p) = o;
+  }
   __device__ __forceinline__ void get(float (&v)[8]) const {
     v[0] = __uint_as_float(u.x << 16);
     v[1] = __uint_as_float(u.x & 0xffff0000u);
@@ -348,6 +368,12 @@ struct Raw8<float> {
     a = reinterpret_cast<const float4*>(p)[0];
     b = reinterpret_cast<const float4*>(p)[1];
   }
+  __device__ __forceinline__ void store_where_positive(float* p, const float (&m)[8]) const {
+    reinterpret_cast<float4*>(p)[0] = make_float4(m[0] > 0.f ? a.x : 0.f, m[1] > 0.f ? a.y : 0.f,
+                                                  m[2] > 0.f ? a.z : 0.f, m[3] > 0.f ? a.w : 0.f);
+    reinterpret_cast<float4*>(p)[1] = make_float4(m[4] > 0.f ? b.x : 0.f, m[5] > 0.f ? b.y : 0.f,
+                                                  m[6] > 0.f ? b.z : 0.f, m[7] > 0.f ? b.w : 0.f);
+  }
   __device__ __forceinline__ void get(float (&v)[8]) const {
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
     v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
@@ -356,10 +382,12 @@ struct Raw8<float> {
 
 template <typename T, typename Op>
 __global__ void __launch_bounds__(FFA_EW_THREADS)
-channel_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, const T* __restrict__ y,
+channel_reduce_kernel(const T* __restrict__ x, const T* dy, const T* __restrict__ y,
                       const float* __restrict__ mean, const float* __restrict__ rstd,
                       const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ ws,
-                      long long npix, int C, int relu) {
+                      long long npix, int C, int relu, T* gout) {
+  // gout (BnBwdStoreOp only, relu mode 1): receives the masked gradient; may be dy itself (a thread reads its elements of an
+  // iteration before it writes them, and no other thread touches them), hence no __restrict__ on the two
   __shared__ float red[FFA_EW_THREADS][17];
   const int CG = C / 8;
   const int PL = FFA_EW_THREADS / CG;
@@ -372,6 +400,7 @@ channel_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, const T
     Op op;
     op.init(cg * 8, mean, rstd, gamma, beta);
     constexpr int U = EwUnroll<T>::U;
+    const int mode = Op::kStoreG ? 1 : relu;  // the storing form exists in mode 1 only: the other modes' state is dead there
     const long long S = (long long)gridDim.x * PL;
     // Forward statistics (StatOp) keep the grid-stride pixel order: with the in-order accumulation below every thread's
     // sum is then the same chain of additions as a plain one-pixel-per-iteration loop, bit for bit.  (E[x^2] - mean^2 in
@@ -389,11 +418,14 @@ channel_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, const T
       for (int u = 0; u < U; ++u) {
         const long long q = p + us * u;
         ok[u] = q < npix;
-        op.load((ok[u] ? q : p) * C + cg * 8, xv[u], gv[u], yv[u], x, dy, y, relu);
+        op.load((ok[u] ? q : p) * C + cg * 8, xv[u], gv[u], yv[u], x, dy, y, mode);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        if (ok[u]) op.acc(a, b, xv[u], gv[u], yv[u], relu);
+        if (ok[u]) {
+          if constexpr (Op::kStoreG) op.acc(a, b, xv[u], gv[u], yv[u], mode, gout + (p + us * u) * C + cg * 8);
+          else op.acc(a, b, xv[u], gv[u], yv[u], mode, (T*)nullptr);
+        }
     }
   }
 #pragma unroll
@@ -512,11 +544,11 @@ extern "C" int ffa_bn_stats(int dtype, const void* x, long long npix, int C, con
   if (dtype == FFA_BF16)
     hipLaunchKernelGGL((channel_reduce_kernel<ffa_bf16, StatOp>), dim3(nb), dim3(FFA_EW_THREADS), 0, stream,
                        (const ffa_bf16*)x, (const ffa_bf16*)nullptr, (const ffa_bf16*)nullptr, nullptr, nullptr, nullptr, nullptr, ws,
-                       npix, C, 0);
+                       npix, C, 0, (ffa_bf16*)nullptr);
   else
     hipLaunchKernelGGL((channel_reduce_kernel<float, StatOp>), dim3(nb), dim3(FFA_EW_THREADS), 0, stream,
                        (const float*)x, (const float*)nullptr, (const float*)nullptr, nullptr, nullptr, nullptr, nullptr, ws, npix,
-                       C, 0);
+                       C, 0, (float*)nullptr);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(ffa_cdiv(C, 8)), dim3(FFA_FIN_THREADS), 0, stream, ws, nb, (double)npix,
                      C, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, mean_out, rstd_out);
   return ffa_check_launch("bn_stats");
@@ -769,7 +801,8 @@ bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy, const T* 
 // stages: bit 0 = reduction + finalize (dgamma, dbeta, apply coefficients into the workspace), bit 1 = apply (dx,
 // dres from the coefficients a stage-1 call left in the SAME workspace), bit 2 = the reduction alone, bit 3 = the
 // finalize alone (1 == 4 | 8).  ffa_bn_bwd = all; the split exists so that a profiler-free harness can bracket each
-// kernel with its own events (bench.py's HBM roofline entry).
+// kernel with its own events (bench.py's HBM roofline entry).  In relu mode 1 with dres the reduction (bit 0 or 2)
+// writes dres and the apply (bit 1) reads it: an apply-only call needs the dres its reduction call left.
 extern "C" int ffa_bn_bwd(int dtype, const void* x, const void* dy, const void* y, const float* gamma,
                           const float* beta, const float* mean, const float* rstd, void* dx, void* dres,
                           float* dgamma, float* dbeta,
@@ -797,29 +830,56 @@ extern "C" int ffa_bn_bwd_stages(int dtype, const void* x, const void* dy, const
   const long long nvec = npix * (C / 8);
   const float inv_count = (float)(1.0 / (double)npix);
   float* coef = ws + (long long)FFA_MAX_PARTIALS * 2 * C;
+  // Mode 1 with a residual branch: the reduction leaves the masked gradient g in dres and the apply pass reads x and
+  // dres alone, as a mode-0 call on g (dx = kg*g + kx*x + k0, the same operands in the same expression) -- seven
+  // passes over the tensor instead of eight.  dres may be dy itself; it must not overlap x, y or dx.
+  const bool g_in_dres = relu == 1 && dres != nullptr;
+  if (g_in_dres) {
+    const size_t bytes = (size_t)npix * C * (dtype == FFA_BF16 ? 2 : 4);
+    const char* r = static_cast<const char*>(dres);
+    auto overlaps = [&](const void* o) {
+      const char* c = static_cast<const char*>(o);
+      return c < r + bytes && r < c + bytes;
+    };
+    FFA_REQUIRE(!overlaps(x) && !overlaps(y) && !overlaps(dx), "bn_bwd: dres overlaps x, y or dx");
+    FFA_REQUIRE(dres == dy || !overlaps(dy), "bn_bwd: dres may be dy itself, not a shifted view of it");
+  }
+  const void* ag = g_in_dres ? dres : dy;       // what the apply pass reads as the gradient ...
+  const void* ay = g_in_dres ? nullptr : y;     // ... masks with ...
+  void* ares = g_in_dres ? nullptr : dres;      // ... and writes beside dx
+  const int arelu = g_in_dres ? 0 : relu;
   if (dtype == FFA_BF16) {
-    if (stages & 5)
+    if ((stages & 5) && g_in_dres)
+      hipLaunchKernelGGL((channel_reduce_kernel<ffa_bf16, BnBwdStoreOp>), dim3(nb), dim3(FFA_EW_THREADS), 0, stream,
+                         (const ffa_bf16*)x, (const ffa_bf16*)dy, (const ffa_bf16*)y, mean, rstd, gamma, beta, ws, npix,
+                         C, relu, (ffa_bf16*)dres);
+    else if (stages & 5)
       hipLaunchKernelGGL((channel_reduce_kernel<ffa_bf16, BnBwdOp>), dim3(nb), dim3(FFA_EW_THREADS), 0, stream,
                          (const ffa_bf16*)x, (const ffa_bf16*)dy, (const ffa_bf16*)y, mean, rstd, gamma, beta, ws, npix,
-                         C, relu);
+                         C, relu, (ffa_bf16*)nullptr);
     if (stages & 9)
       hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ffa_cdiv(C, 8)), dim3(FFA_FIN_THREADS), 0, stream, ws, nb, C,
                          gamma, beta, mean, rstd, inv_count, dgamma, dbeta, coef);
     if (stages & 2)
       hipLaunchKernelGGL(bn_bwd_apply_kernel<ffa_bf16>, dim3(ew_grid_c(nvec, C)), dim3(FFA_EW_THREADS), 0, stream,
-                         (const ffa_bf16*)x, (const ffa_bf16*)dy, (const ffa_bf16*)y, coef, (ffa_bf16*)dx,
-                         (ffa_bf16*)dres, nvec, C, relu);
+                         (const ffa_bf16*)x, (const ffa_bf16*)ag, (const ffa_bf16*)ay, coef, (ffa_bf16*)dx,
+                         (ffa_bf16*)ares, nvec, C, arelu);
   } else {
-    if (stages & 5)
+    if ((stages & 5) && g_in_dres)
+      hipLaunchKernelGGL((channel_reduce_kernel<float, BnBwdStoreOp>), dim3(nb), dim3(FFA_EW_THREADS), 0, stream,
+                         (const float*)x, (const float*)dy, (const float*)y, mean, rstd, gamma, beta, ws, npix, C, relu,
+                         (float*)dres);
+    else if (stages & 5)
       hipLaunchKernelGGL((channel_reduce_kernel<float, BnBwdOp>), dim3(nb), dim3(FFA_EW_THREADS), 0, stream,
-                         (const float*)x, (const float*)dy, (const float*)y, mean, rstd, gamma, beta, ws, npix, C, relu);
+                         (const float*)x, (const float*)dy, (const float*)y, mean, rstd, gamma, beta, ws, npix, C, relu,
+                         (float*)nullptr);
     if (stages & 9)
       hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ffa_cdiv(C, 8)), dim3(FFA_FIN_THREADS), 0, stream, ws, nb, C,
                          gamma, beta, mean, rstd, inv_count, dgamma, dbeta, coef);
     if (stages & 2)
       hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(ew_grid_c(nvec, C)), dim3(FFA_EW_THREADS), 0, stream,
-                         (const float*)x, (const float*)dy, (const float*)y, coef, (float*)dx, (float*)dres, nvec, C,
-                         relu);
+                         (const float*)x, (const float*)ag, (const float*)ay, coef, (float*)dx, (float*)ares, nvec, C,
+                         arelu);
   }
   return ffa_check_launch("bn_bwd");
 }
@@ -1241,11 +1301,11 @@ extern "C" int ffa_channel_sums(int dtype, const void* x, long long npix, int C,
   if (dtype == FFA_BF16)
     hipLaunchKernelGGL((channel_reduce_kernel<ffa_bf16, StatOp>), dim3(nb), dim3(FFA_EW_THREADS), 0, stream,
                        (const ffa_bf16*)x, (const ffa_bf16*)nullptr, (const ffa_bf16*)nullptr, nullptr, nullptr, nullptr, nullptr, ws,
-                       npix, C, 0);
+                       npix, C, 0, (ffa_bf16*)nullptr);
   else
     hipLaunchKernelGGL((channel_reduce_kernel<float, StatOp>), dim3(nb), dim3(FFA_EW_THREADS), 0, stream,
                        (const float*)x, (const float*)nullptr, (const float*)nullptr, nullptr, nullptr, nullptr, nullptr, ws, npix,
-                       C, 0);
+                       C, 0, (float*)nullptr);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ffa_cdiv(C, 8)), dim3(FFA_FIN_THREADS), 0, stream, ws, nb, C,
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f,
                      sumsq_out, sum_out, (float*)nullptr);

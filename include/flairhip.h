@@ -380,6 +380,9 @@ int ffa_bn_bwd(int dtype, const void* x, const void* dy, const void* y, const fl
 /* ffa_bn_bwd in separate calls: stages bit 0 = reduction + finalize (dgamma, dbeta and the apply coefficients, left in
  * the workspace), bit 1 = apply (dx, dres) from the coefficients of an earlier call on the SAME workspace, bit 2 = the
  * reduction kernel alone, bit 3 = the finalize kernel alone (1 == 4 | 8); 3 = everything.
+ * relu 1 with dres: the reduction (bit 0 or 2) writes dres = dy masked by y > 0 and the apply (bit 1) reads x and
+ * dres only, so an apply-only call needs the dres that the reduction call of the same arguments left.  dres may be
+ * dy itself (in place); it must not overlap x, y or dx (FFA_ERR_ARG).
  * Lets a harness bracket each kernel with its own events (bench.py's HBM roofline entry). */
 int ffa_bn_bwd_stages(int dtype, const void* x, const void* dy, const void* y, const float* gamma, const float* beta,
                       const float* mean, const float* rstd, void* dx, void* dres, float* dgamma, float* dbeta,
