@@ -16,6 +16,7 @@
 //               pointer; with accumulate the bytes are ORed into the mask.
 // The plane is cleared at the head of every call (hipMemsetAsync), so the workspace may hold anything.
 #include "ffa_common.h"
+#include "ffa_zone.h"  // the crossing predicate and column, shared with zone_stats.hip
 
 // xc = x0 + ((yc - y0) * (x1 - x0)) / (y1 - y0) must round every operation separately: no a * b + c -> fma
 #pragma clang fp contract(off)
@@ -133,12 +134,8 @@ __global__ __launch_bounds__(kT) void zone_toggle_kernel(const double* __restric
     const int r = rfirst[e] + (int)(i - offs[e]);
     if (r < 0 || r >= H) continue;
     const double x0 = xy[2ll * e], y0 = xy[2ll * e + 1], x1 = xy[2ll * nx], y1 = xy[2ll * nx + 1];
-    const double yc = (double)r + 0.5;
-    if ((y0 <= yc) == (y1 <= yc)) continue;
-    const double xc = x0 + ((yc - y0) * (x1 - x0)) / (y1 - y0);
-    double t = floor(xc - 0.5) + 1.0;
-    t = fmin(fmax(t, 0.0), (double)W);  // a NaN (overflow in the product) lands on column 0, like any far-left crossing
-    const int c = (int)t;
+    int c;
+    if (!ffa_zone_crossing(x0, y0, x1, y1, r, W, &c)) continue;
     if (c < W) atomicXor(&tog[(long long)r * WW + (c >> 5)], 1u << (c & 31));
   }
 }
@@ -154,11 +151,7 @@ __global__ __launch_bounds__(kT) void zone_row_scan_kernel(int H, int WW, unsign
   for (int w0 = 0; w0 < WW; w0 += 64) {
     const int w = w0 + lane;
     unsigned int p = w < WW ? bits[w] : 0u;
-    p ^= p << 1;
-    p ^= p << 2;
-    p ^= p << 4;
-    p ^= p << 8;
-    p ^= p << 16;  // bit k = XOR of the word's toggles at bits <= k; bit 31 = parity of the word
+    p = ffa_zone_prefix_xor(p);  // bit k = XOR of the word's toggles at bits <= k; bit 31 = parity of the word
     const unsigned long long odd = __ballot((p >> 31) != 0);
     const unsigned int in = (unsigned int)(__popcll(odd & ((1ull << lane) - 1ull)) & 1) ^ carry;
     if (in) p = ~p;

@@ -105,6 +105,27 @@ def validate_compare(config: dict):
     return (None if path is None else os.fspath(path)), float(iou), mode
 
 
+def validate_zone_stats(config: dict):
+    """The optional keys of zonal statistics, all off by default: zone_stats (a path to a GeoJSON layer of zones; after
+    the tile loop every written class raster ``<name>.tif`` gets ``<name>_zone_stats.csv``, the table of
+    zonal_stats.zonal_class_stats), zone_stats_id (the Feature property that names a zone; default: its index) and
+    zone_stats_crs (the CRS the layer is given in, or 'auto'; default: the raster's).  Returns the three; a bad value
+    raises ValueError."""
+    path = config.get("zone_stats")
+    if path is not None and not isinstance(path, (str, os.PathLike)):
+        raise ValueError(f"zone_stats must be a path to a GeoJSON file, got {path!r}")
+    field = config.get("zone_stats_id")
+    if field is not None and not isinstance(field, str):
+        raise ValueError(f"zone_stats_id must be a property name, got {field!r}")
+    crs_name = config.get("zone_stats_crs")
+    if crs_name is not None and not (isinstance(crs_name, str) and crs_name.strip().lower() == "auto"):
+        from flair_zonal_detection import crs
+        if isinstance(crs_name, bool) or not isinstance(crs_name, (str, int)):
+            raise ValueError(f"zone_stats_crs must be 'auto', 'EPSG:NNNN' or an EPSG code, got {crs_name!r}")
+        crs.parse(crs_name)
+    return (None if path is None else os.fspath(path)), field, crs_name
+
+
 COG_OVERVIEW_RESAMPLING = ("nearest", "mode", "average")
 
 
@@ -171,6 +192,7 @@ def validate_config(config: dict) -> None:
     validate_geozone_crs(config)
     validate_sieve_area(config)
     validate_compare(config)
+    validate_zone_stats(config)
     validate_cog_conversion(config)
     validate_cog_overview_resampling(config)
     if not os.path.isfile(config["model_weights"]):

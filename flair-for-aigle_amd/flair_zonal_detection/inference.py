@@ -51,7 +51,7 @@ from flairhip.augment import tta_views
 from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_cog_conversion,
                                           validate_cog_overview_resampling, validate_config, validate_geozone_crs,
                                           threshold_file, validate_skip_tiles_outside_zone, validate_threshold_fallback,
-                                          validate_tta, validate_write_confidence)
+                                          validate_tta, validate_write_confidence, validate_zone_stats)
 from flair_zonal_detection.dataset import MultiModalSlicedDataset, TileBatcher, pad_series_collate
 from flair_zonal_detection.model_utils import build_inference_model, compute_patch_sizes
 from flair_zonal_detection.postprocess import convert, convert_to_cog  # noqa: F401  (re-exported like the reference)
@@ -472,6 +472,37 @@ def postpro_outputs(temp_paths: Dict[str, str], config: Dict) -> Dict[str, str]:
     return paths
 
 
+ZONE_STATS_SUFFIX = "_zone_stats.csv"  # <name>.tif -> <name>_zone_stats.csv
+
+
+def write_zone_stats(outputs: Dict[str, object], config: Dict, zones, id_field=None, zone_crs=None) -> Dict[str, str]:
+    """The config key ``zone_stats``: for every class raster the run wrote to a file ``<name>.tif``, the table of
+    zonal_stats.zonal_class_stats over the zone layer ``zones`` as ``<name>_zone_stats.csv``; with write_confidence
+    the table has the confidence columns.  Class-probability and in-memory outputs are left alone.  Returns
+    {output key: path of the table}."""
+    from flair_zonal_detection.geotiff import GeoTiffWriter
+    from flair_zonal_detection.zonal_stats import write_zone_stats_csv, zonal_class_stats
+    if config.get("output_type", "argmax") != "argmax":
+        logger.info("zone_stats: needs class rasters (output_type: argmax), not %s", config.get("output_type"))
+        return {}
+    names = {t["name"]: t.get("class_names") for t in config.get("tasks", [])}
+    written = {}
+    for key, out in outputs.items():
+        if str(key).endswith(CONFIDENCE_SUFFIX):
+            continue
+        out_path = getattr(out, "path", None) or getattr(out, "name", None)
+        if (isinstance(out, ArrayRaster) and not isinstance(out, GeoTiffWriter)) or not out_path:
+            logger.info("zone_stats: the in-memory output %s is not tabulated (zonal_class_stats takes it directly)", key)
+            continue
+        t0 = time.time()
+        table = zonal_class_stats(out, zones, id_field=id_field, confidence=outputs.get(str(key) + CONFIDENCE_SUFFIX),
+                                  zone_crs=zone_crs, class_names=names.get(key) or None)
+        path = os.path.splitext(str(out_path))[0] + ZONE_STATS_SUFFIX
+        written[key] = write_zone_stats_csv(table, path)
+        logger.info("zone statistics of %d zones in %.1f s: %s", table.n_zones, time.time() - t0, path)
+    return written
+
+
 def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tuple[int, int]] = None,
                   before_loop=None, geozone_crs=None) -> Dict[str, object]:
     """End-to-end zonal run with upstream FLAIR-HUB's one-argument semantics (the fork's own run_inference is
@@ -519,6 +550,12 @@ def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tu
                 o.track_writes()
     inference_and_write(model, loader, tiles, config, outputs, ref_img)
     logger.info("zonal inference of %d tiles took %.1f s", len(tiles), time.time() - t0)
+    zone_layer, zone_id, zone_layer_crs = validate_zone_stats(config)
+    if zone_layer is not None:  # before the COG conversion removes the plain rasters
+        if shard is not None:
+            logger.info("zone_stats: the part files of a sharded run are not tabulated")
+        else:
+            write_zone_stats(outputs, config, zone_layer, zone_id, zone_layer_crs)
     if validate_cog_conversion(config):
         from flair_zonal_detection.geotiff import GeoTiffWriter
         files = {k: o.path for k, o in outputs.items() if isinstance(o, GeoTiffWriter)}

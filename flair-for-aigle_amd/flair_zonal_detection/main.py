@@ -141,6 +141,17 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--compare-classes", type=str, default=None, choices=("same", "any"),
                         help="whether only objects of the same class may match.  Default: the config key "
                              "compare_classes, else same")
+    parser.add_argument("--zone-stats", type=str, default=None, metavar="PATH.geojson",
+                        help="a layer of zones (GeoJSON Features: parcels, communes, a grid): after the tile loop each "
+                             "written class raster <name>.tif gets <name>_zone_stats.csv, the pixels and area of every "
+                             "class in every zone, with the mean confidence when the config sets write_confidence.  "
+                             "Default: the config key zone_stats, else none")
+    parser.add_argument("--zone-stats-id", type=str, default=None, metavar="FIELD",
+                        help="the Feature property that names a zone in the table.  Default: the config key "
+                             "zone_stats_id, else the zone's index")
+    parser.add_argument("--zone-stats-crs", type=str, default=None, metavar="EPSG:NNNN|auto",
+                        help="CRS the --zone-stats layer is given in.  Default: the config key zone_stats_crs, else the "
+                             "raster's CRS")
     return parser
 
 
@@ -173,8 +184,9 @@ def main(argv=None) -> None:
         parser.error(f"--compare-iou expects a number in (0, 1], got {args.compare_iou}")
     if args.sieve_area is not None and not 0.0 <= args.sieve_area < float("inf"):
         parser.error(f"--sieve-area expects a number >= 0, got {args.sieve_area}")
-    for opt, value in (("--zone-crs", args.zone_crs), ("--target-crs", args.target_crs)):
-        if value is not None and not (opt == "--zone-crs" and value.strip().lower() == "auto"):
+    for opt, value in (("--zone-crs", args.zone_crs), ("--target-crs", args.target_crs),
+                       ("--zone-stats-crs", args.zone_stats_crs)):
+        if value is not None and not (opt != "--target-crs" and value.strip().lower() == "auto"):
             from flair_zonal_detection import crs
             try:
                 crs.parse(value)
@@ -189,9 +201,15 @@ def main(argv=None) -> None:
     config = args.config
     if args.threshold_fallback is not None and not 0 <= args.threshold_fallback <= 255:
         parser.error(f"--threshold-fallback expects an integer in 0..255, got {args.threshold_fallback}")
-    if args.cog or args.tta is not None or args.thresholds is not None or args.threshold_fallback is not None:
+    zone_stats_args = (("zone_stats", args.zone_stats), ("zone_stats_id", args.zone_stats_id),
+                       ("zone_stats_crs", args.zone_stats_crs))
+    if (args.cog or args.tta is not None or args.thresholds is not None or args.threshold_fallback is not None
+            or any(v is not None for _, v in zone_stats_args)):
         from flair_zonal_detection.config import load_config  # the keys, for this run only
         config = load_config(args.config)
+        for key, value in zone_stats_args:
+            if value is not None:
+                config[key] = value
         if args.thresholds is not None:
             config["model_threshold_filepath"] = args.thresholds
         if args.threshold_fallback is not None:

@@ -98,6 +98,56 @@ def zone_rings(geozone) -> List[Rings]:
     return out
 
 
+def _one_zone(obj) -> Rings:
+    """every ring of a geometry (or bounds, or anything zone_rings reads), as one zone"""
+    return [r for poly in zone_rings(obj) for r in poly]
+
+
+def _collect_features(geozone, out: List[Tuple[dict, Rings]]) -> None:
+    if hasattr(geozone, "__geo_interface__"):
+        geozone = dict(geozone.__geo_interface__)
+    if isinstance(geozone, (str, os.PathLike)):
+        path = os.fspath(geozone)
+        if not str(path).lower().endswith((".geojson", ".json")):
+            raise ValueError(f"zone: {path!r} is not a .geojson / .json file")
+        with open(path, "r", encoding="utf-8") as f:
+            geozone = json.load(f)
+    if isinstance(geozone, dict):
+        kind = geozone.get("type")
+        if kind == "FeatureCollection":
+            for f in geozone.get("features", []):
+                _collect_features(f, out)
+        elif kind == "Feature":
+            geom = geozone.get("geometry")
+            if geom is None:
+                raise ValueError("zone: GeoJSON Feature without a geometry")
+            if geom.get("type") not in ("Polygon", "MultiPolygon"):
+                raise ValueError(f"zone: a zone Feature needs a Polygon or MultiPolygon, got {geom.get('type')!r}")
+            out.append((dict(geozone.get("properties") or {}), _one_zone(geom)))
+        else:  # a bare geometry; a type that is not polygonal raises in zone_rings
+            out.append(({}, _one_zone(geozone)))
+    elif _is_bounds(geozone):
+        out.append(({}, _one_zone(geozone)))
+    elif isinstance(geozone, Sequence) and not isinstance(geozone, bytes):
+        for g in geozone:
+            _collect_features(g, out)
+    else:
+        raise ValueError(f"zone: cannot read zones from {type(geozone).__name__}")
+
+
+def zone_features(geozone) -> List[Tuple[dict, Rings]]:
+    """The zones of a zone layer as (properties, rings) pairs, the rings float64 [n, 2] in map coordinates as given.
+    A GeoJSON Feature with a Polygon or MultiPolygon is one zone with its properties: the rings of all parts of a
+    MultiPolygon together (parts of a valid MultiPolygon do not overlap, so even-odd over all of them is their union).
+    A FeatureCollection is its Features in order.  A bare geometry or a (left, bottom, right, top) tuple is one zone
+    with empty properties; paths to .geojson / .json files and objects with ``__geo_interface__`` are read first;
+    sequences concatenate.  Anything that is not polygonal raises ValueError.  ``zone_rings`` reads the same inputs as
+    one contour and stays as it is."""
+    out: List[Tuple[dict, Rings]] = []
+    _collect_features(geozone, out)
+    return out
+
+
 def zone_bounds(geozone) -> Tuple[float, float, float, float]:
     """(minx, miny, maxx, maxy) over every ring of the zone -- what ``.bounds`` of the geometry would give."""
     polys = zone_rings(geozone)

@@ -230,6 +230,14 @@ OBJECT_SIGNATURES = {
     "ffa_region_overlap_pairs": (_i, [_p, _ll, _i, _i, _ll, _ll, _ll, _p, _ll] + [_p] * 11),
 }
 
+# the prototypes of include/flairhip_zonestats.h (per-zone class counts and confidence sums), which include/flairhip.h
+# brings along
+ZONESTATS_SIGNATURES = {
+    "ffa_zone_stats_workspace_bytes": (_ll, [_ll, _ll, _ll]),
+    "ffa_zone_stats_u8": (_i, [_p, _p, _i, _i, _i, _p, _ll, _p, _i, _p, _i, _p, _p, _ll, _p, _ll, _p, _ll, _p, _p, _p,
+                               _ll, _p]),
+}
+
 _lib = None
 
 
@@ -248,7 +256,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES, **GATHER_SIGNATURES, **SERIES_SIGNATURES,
-                              **CALIB_SIGNATURES, **OBJECT_SIGNATURES}.items():
+                              **CALIB_SIGNATURES, **OBJECT_SIGNATURES, **ZONESTATS_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args

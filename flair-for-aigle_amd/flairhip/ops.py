@@ -1751,6 +1751,177 @@ def zone_window_counts(mask: torch.Tensor, windows) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------------------
+# zonal statistics: class counts and confidence sums per zone (csrc/zone_stats.hip)
+
+ZONE_STATS_CHUNK_WORDS = 2048   # FFA_ZONE_STATS_CHUNK_WORDS: plane words per tabulation chunk (a wave each)
+ZONE_STATS_NARROW_WORDS = 8     # FFA_ZONE_STATS_NARROW_WORDS: up to this many words per row the scan takes a lane per row
+ZONE_STATS_WORKSPACE_SLOT = "zone_stats"
+# the default plane budget of zone_class_stats: this share of the device memory that is free at the call.  A quarter
+# leaves room for the rasters of the caller's next step and for the allocator's fragmentation; the planes of 10^5
+# parcels on a 25 Mpx raster take 14 MB, so the budget only binds for many large overlapping zones
+ZONE_STATS_MEMORY_FRACTION = 0.25
+
+
+def zone_stats_flatten(zones_pix):
+    """(float64 [V, 2] vertices, int32 [R + 1] ring offsets, int32 [Z + 1] ring offsets of the zones) of a list of
+    zones, each a list of [n, 2] rings in pixel coordinates."""
+    import numpy as np
+    rings, zro = [], [0]
+    for z, zone in enumerate(zones_pix):
+        for ring in zone:
+            r = np.asarray(ring, dtype=np.float64)
+            if r.ndim != 2 or r.shape[1] != 2:
+                raise ValueError(f"zone_class_stats: zone {z}: a ring must be an [n, 2] array, got shape {r.shape}")
+            rings.append(r)
+        zro.append(len(rings))
+    xy = np.ascontiguousarray(np.concatenate(rings)) if rings else np.zeros((0, 2), dtype=np.float64)
+    ro = np.concatenate([[0], np.cumsum([len(r) for r in rings], dtype=np.int64)])
+    if len(xy) >= (1 << 31) - 1:
+        raise ValueError(f"zone_class_stats: {len(xy)} vertices, fewer than 2^31 - 1 expected")
+    return xy, ro.astype(np.int32), np.asarray(zro, dtype=np.int32)
+
+
+def zone_stats_windows(xy, ring_offsets, zone_ring_offsets, H: int, W: int):
+    """int32 [Z, 4] windows (r0, c0, r1, c1) by the conservative rule of include/flairhip_zonestats.h, clamped to the
+    raster, c0 rounded down to a multiple of 32.  A zone without a vertex, or whose bounds miss the raster, gets an
+    empty window (r1 <= r0 or c1 <= c0)."""
+    import numpy as np
+    ro = np.asarray(ring_offsets, dtype=np.int64)
+    zv = ro[np.asarray(zone_ring_offsets, dtype=np.int64)]  # the first vertex of each zone, and V
+    Z = len(zv) - 1
+    win = np.zeros((Z, 4), dtype=np.int32)
+    some = np.flatnonzero(np.diff(zv) > 0)
+    if len(some) == 0:
+        return win
+    starts = zv[some]
+    xmin, xmax = np.minimum.reduceat(xy[:, 0], starts), np.maximum.reduceat(xy[:, 0], starts)
+    ymin, ymax = np.minimum.reduceat(xy[:, 1], starts), np.maximum.reduceat(xy[:, 1], starts)
+
+    def clamp(v, hi):
+        return np.clip(v, 0, hi).astype(np.int32)  # clipped as float64 first: far-off coordinates must not wrap
+
+    win[some, 0] = clamp(np.floor(ymin - 0.5), H)
+    win[some, 1] = clamp(np.floor(xmin - 0.5), W) & ~31
+    win[some, 2] = clamp(np.ceil(ymax - 0.5) + 1, H)
+    win[some, 3] = clamp(np.floor(xmax - 0.5) + 2, W)
+    return win
+
+
+def zone_stats_plane_words(windows):
+    """(rows, words per row, plane words) of each window, int64 [Z] each; all 0 for an empty window"""
+    import numpy as np
+    w = np.asarray(windows, dtype=np.int64).reshape(-1, 4)
+    rows = np.maximum(w[:, 2] - w[:, 0], 0)
+    ww = np.where(w[:, 3] > w[:, 1], (w[:, 3] - w[:, 1] + 31) // 32, 0)
+    ww = np.where(rows > 0, ww, 0)
+    rows = np.where(ww > 0, rows, 0)
+    return rows, ww, rows * ww
+
+
+def zone_stats_plan(windows, chunk_words: int = ZONE_STATS_CHUNK_WORDS):
+    """The tables ffa_zone_stats_u8 takes beside the windows: (plane_offsets int64 [Z], plane_words, scan_starts int64
+    [Z + 1], chunks int32 [n, 3] = (zone, first word, words)).  The chunks cover every plane word once, none crosses
+    a zone and none holds more than ``chunk_words`` words."""
+    import numpy as np
+    rows, ww, words = zone_stats_plane_words(windows)
+    Z = len(words)
+    if Z and int(words.max()) >= 1 << 31:
+        raise ValueError(f"zone_class_stats: zone {int(words.argmax())} needs a plane of {int(words.max())} words, "
+                         "fewer than 2^31 expected")
+    ends = np.cumsum(words)
+    plane_offsets = (ends - words).astype(np.int64)
+    items = np.where(ww == 0, 0, np.where(ww <= ZONE_STATS_NARROW_WORDS, (rows + 63) // 64, rows))
+    scan_starts = np.concatenate([[0], np.cumsum(items)]).astype(np.int64)
+    per_zone = (words + chunk_words - 1) // chunk_words
+    zone = np.repeat(np.arange(Z, dtype=np.int64), per_zone)
+    first = (np.arange(len(zone), dtype=np.int64) - np.repeat(np.cumsum(per_zone) - per_zone, per_zone)) * chunk_words
+    chunks = np.stack([zone, first, np.minimum(chunk_words, words[zone] - first)], axis=1).astype(np.int32)
+    return plane_offsets, int(ends[-1]) if Z else 0, scan_starts, np.ascontiguousarray(chunks.reshape(-1, 3))
+
+
+def zone_stats_batches(plane_words, max_workspace_bytes: int):
+    """Consecutive zone ranges [(a, b), ...] whose planes (4 bytes a word) fit ``max_workspace_bytes`` each, as few as
+    a greedy walk gives.  A zone whose own plane exceeds the budget raises ValueError naming it."""
+    import numpy as np
+    words = np.asarray(plane_words, dtype=np.int64)
+    budget = int(max_workspace_bytes) // 4
+    if len(words) and int(words.max()) > budget:
+        z = int(np.flatnonzero(words > budget)[0])
+        raise ValueError(f"zone_class_stats: zone {z} alone needs a plane of {4 * int(words[z])} bytes, more than "
+                         f"max_workspace_bytes = {int(max_workspace_bytes)}")
+    ends = np.cumsum(words)
+    out, a = [], 0
+    while a < len(words):
+        before = int(ends[a] - words[a])
+        b = max(int(np.searchsorted(ends, before + budget, side="right")), a + 1)
+        out.append((a, b))
+        a = b
+    return out
+
+
+def zone_class_stats(cls: torch.Tensor, zones_pix, n_classes: int, conf: Optional[torch.Tensor] = None,
+                     max_workspace_bytes: Optional[int] = None):
+    """Per-zone class counts of a device uint8 class raster [H, W]: (counts, conf_sums), device int64 [Z, K + 1] each,
+    K = ``n_classes`` in 1..256.  ``zones_pix`` is a list of zones, each a list of float64 [n, 2] rings in pixel
+    coordinates (a MultiPolygon is one zone holding the rings of all its parts).  A pixel belongs to a zone when its
+    centre is inside, even-odd over the zone's rings, by the rule of ``rasterize_zone``; zones may overlap.
+    counts[z, k] is the number of pixels of zone z with class k, column K collects the classes >= K.  With ``conf``
+    (device uint8 [H, W]) conf_sums holds the sums of its bytes over the same pixels, else it is None.
+
+    Each zone gets a bit plane over its own window; when all planes together exceed ``max_workspace_bytes`` the zones
+    are split into consecutive batches (the results are the same bytes: zones are independent).  The default budget is
+    ZONE_STATS_MEMORY_FRACTION of the free device memory.  A single zone beyond the budget raises ValueError."""
+    import numpy as np
+    K = int(n_classes)
+    if not 1 <= K <= 256:
+        raise ValueError(f"zone_class_stats: n_classes {n_classes} outside 1..256")
+    if not (torch.is_tensor(cls) and cls.is_cuda and cls.dtype == torch.uint8 and cls.dim() == 2 and cls.numel() > 0):
+        raise ValueError("zone_class_stats: a CUDA uint8 [H, W] class raster expected")
+    if conf is not None and not (torch.is_tensor(conf) and conf.is_cuda and conf.dtype == torch.uint8
+                                 and conf.shape == cls.shape and conf.device == cls.device):
+        raise ValueError(f"zone_class_stats: conf must be a CUDA uint8 {tuple(cls.shape)} tensor on the device of cls")
+    H, W = (int(v) for v in cls.shape)
+    dev = cls.device
+    xy, ro, zro = zone_stats_flatten(zones_pix)
+    if not np.all(np.isfinite(xy)):
+        raise ValueError("zone_class_stats: non-finite ring coordinate")
+    Z = len(zro) - 1
+    counts = torch.empty((Z, K + 1), dtype=torch.int64, device=dev)
+    sums = torch.empty((Z, K + 1), dtype=torch.int64, device=dev) if conf is not None else None
+    if Z == 0:
+        return counts, sums
+    windows = zone_stats_windows(xy, ro, zro, H, W)
+    words = zone_stats_plane_words(windows)[2]
+    if max_workspace_bytes is None:
+        max_workspace_bytes = int(torch.cuda.mem_get_info(dev)[0] * ZONE_STATS_MEMORY_FRACTION)
+    batches = zone_stats_batches(words, max_workspace_bytes)
+    lib = _l.load()
+    cls = cls.contiguous()
+    conf = conf.contiguous() if conf is not None else None
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    for a, b in batches:
+        r0, r1 = int(zro[a]), int(zro[b])
+        v0, v1 = int(ro[r0]), int(ro[r1])
+        plane_offsets, plane_words, scan_starts, chunks = zone_stats_plan(windows[a:b])
+        nbytes = lib.ffa_zone_stats_workspace_bytes(v1 - v0, plane_words, len(chunks))
+        if nbytes < 0:
+            _l.check(int(nbytes), "zone_class_stats")
+        ws = workspace(int(nbytes), dev, ZONE_STATS_WORKSPACE_SLOT)
+        tables = [up(xy[v0:v1]) if v1 > v0 else None, up(ro[r0:r1 + 1] - ro[r0]), up(zro[a:b + 1] - zro[a]),
+                  up(windows[a:b]), up(plane_offsets), up(scan_starts), up(chunks) if len(chunks) else None]
+        _l.check(lib.ffa_zone_stats_u8(cls.data_ptr(), _ptr(conf), H, W, K, _ptr(tables[0]), v1 - v0,
+                                       tables[1].data_ptr(), r1 - r0, tables[2].data_ptr(), b - a,
+                                       tables[3].data_ptr(), tables[4].data_ptr(), plane_words, tables[5].data_ptr(),
+                                       int(scan_starts[-1]), _ptr(tables[6]), len(chunks), counts[a:b].data_ptr(),
+                                       _ptr(sums[a:b]) if sums is not None else None, ws.data_ptr(), int(ws.numel()),
+                                       _stream()), "zone_stats_u8")
+    return counts, sums
+
+
+# --------------------------------------------------------------------------------------------------
 # overview pyramid of a uint8 raster (csrc/overview.hip)
 
 OVERVIEW_METHODS = {"nearest": 0, "mode": 1, "average": 2}

@@ -524,6 +524,9 @@ int ffa_confusion_matrix(const uint8_t* pred, const uint8_t* target, long long n
 /* Object matching (the overlaps between the regions of two class rasters: region tables and the list of region pairs
  * that share pixels, with the size of each intersection) is declared in flairhip_objects.h, likewise. */
 #include "flairhip_objects.h"
+/* Zonal statistics (for a layer of zones over a class raster: the pixel count per zone and class, and the sum of a
+ * confidence raster over the same pixels) are declared in flairhip_zonestats.h, likewise. */
+#include "flairhip_zonestats.h"
 
 /* ---- host-side tile bookkeeping, bit-exact with the reference's float64 arithmetic
  *      (flair_zonal_detection/slicing.py:51-112, flair_zonal_detection/inference.py:318-335) -------- */
