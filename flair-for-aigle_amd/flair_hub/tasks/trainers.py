@@ -111,8 +111,28 @@ class AugmentedLoader:
             yield batch
 
 
+def _capturable(optimizer) -> bool:
+    """the optimizers whose step GraphedTrainStep can capture: torch's Adam / AdamW and flairhip.optim.HipAdamW / HipAdam
+    (what SegmentationTask._init_optimizer builds on the GPU by default; they derive from torch.optim.Optimizer alone).
+    All of them keep step counters and, after make_capturable, the learning rate on the device.  SGD stays eager."""
+    from flairhip.optim import HipAdamW
+    return isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW, HipAdamW))
+
+
 class HipTrainer:
-    """The subset of pytorch_lightning.Trainer the reference relies on."""
+    """The subset of pytorch_lightning.Trainer the reference relies on.
+
+    ``hip_graph=True``: fit() runs two ordinary steps (they size every workspace, fill the weight-pack plan and create the
+    optimizer state), captures forward + loss + backward + optimizer step into a hipGraph at the third
+    (flairhip.graph.GraphedTrainStep; several ranks: graph(forward + backward) -> GradSync.reduce_grads -> graph(optimizer))
+    and replays it for every later batch of the captured shapes and dtypes.  Captured: Adam / AdamW, torch's or
+    flairhip.optim's.  Eager, by design: SGD; modality dropout (the model draws on the host per step); a batch whose
+    tensors differ in key, shape or dtype from the captured one (that step alone: the batches after it replay again).
+    What a fit did is left on the trainer, and train() returns that trainer:
+      ``graph_built``   a GraphedTrainStep was constructed
+      ``graph_replays`` optimizer steps that were replays of it
+      ``eager_steps``   optimizer steps that ran eagerly (the two before the capture and every fallback)
+    graph_replays + eager_steps is the number of optimizer steps of the last fit()."""
 
     def __init__(self, accelerator: str = "gpu", devices: int = 1, strategy: str = "auto", num_nodes: int = 1,
                  max_epochs: int = 1, default_root_dir: Optional[str] = None, monitor: str = "val_miou",
@@ -149,6 +169,7 @@ class HipTrainer:
         self.callback_metrics: Dict[str, Any] = {}
         self.best_model_path = None
         self.optimizers = []
+        self.graph_built, self.graph_replays, self.eager_steps = False, 0, 0  # of the last fit(): see the class docstring
 
     # ---- fit -------------------------------------------------------------------------------------
 
@@ -192,13 +213,15 @@ class HipTrainer:
         interval = sched_cfg.get("interval", "epoch") if sched_cfg else None
         model._lr_scheduler = scheduler
         self.optimizers = [optimizer]
-        use_graph = (self.hip_graph and not getattr(model, "mod_dropout", False) and
-                     isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW)))
+        use_graph = self.hip_graph and not getattr(model, "mod_dropout", False) and _capturable(optimizer)
+        self.graph_built, self.graph_replays, self.eager_steps = False, 0, 0
         graph_ddp = use_graph and self.world_size > 1
         # exact_unused: a parameter no rank produced a gradient for keeps grad = None, as under the reference's
         # ddp_find_unused_parameters_true and as in the single-GPU path (AdamW then skips it instead of decaying it);
         # graph mode runs without autograd hooks: the finished gradients are handed to reduce_grads()
-        # graph mode reduces after backward (nothing to overlap with): one collective over all gradients
+        # graph mode reduces after backward (nothing to overlap with): one collective over all gradients; reduce_grads takes
+        # every decision about a collective from values that are equal on all ranks (its docstring), so the two eager steps
+        # before the capture and an eager fallback on one rank's odd batch keep the ranks' sequences of collectives equal
         sync = GradSync(model, hooks=not graph_ddp, exact_unused=True, **({"bucket_bytes": 1 << 30} if graph_ddp else {}))
 
         def reduce_now():
@@ -224,10 +247,13 @@ class HipTrainer:
                     graphed = GraphedTrainStep(model, optimizer, {k: v for k, v in batch.items() if torch.is_tensor(v)},
                                                warmup_steps=0, grad_reduce=sync.reduce_grads if graph_ddp else None)
                     graph_sig = {k: (tuple(v.shape), v.dtype) for k, v in batch.items() if torch.is_tensor(v)}
+                    self.graph_built = True
                 if graphed is not None and graph_sig == {k: (tuple(v.shape), v.dtype) for k, v in batch.items()
                                                          if torch.is_tensor(v)}:
                     loss = graphed({k: v for k, v in batch.items() if torch.is_tensor(v)})
+                    self.graph_replays += 1
                 else:
+                    self.eager_steps += 1
                     loss = model.training_step(batch, i)
                     optimizer.zero_grad(set_to_none=True)
                     loss.backward()

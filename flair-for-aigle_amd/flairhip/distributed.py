@@ -26,7 +26,9 @@ its own backward did -- the property ``find_unused_parameters`` gives the refere
     gradients in ``p.grad`` -- zeros when no rank had one.  ``exact_unused=True`` adds one small all-reduce of
     "had a gradient" flags per step and leaves ``p.grad`` untouched (None) for parameters no rank produced a gradient
     for, exactly what DDP's find_unused_parameters does (AdamW then skips them instead of applying weight decay
-    alone); it costs a host read per step whenever some parameter had no local gradient;
+    alone); it costs a host read per step whenever some parameter had no local gradient.  The hook-less form
+    (``reduce_grads``) exchanges the flags only in a call where SOME rank's set of gradients changed: every rank always
+    reduces one spare "my set changed" f32 with the last bucket and reads it, so all ranks take that decision alike;
   * ``p.grad`` is a view into the bucket.  Producers that know about the bucket (the weight-gradient
     kernels: ``grad_buffer(p)``) write there directly and autograd adopts the tensor they return, so a
     step moves no gradient bytes besides the collective itself; any other gradient is copied into its
@@ -66,7 +68,12 @@ class GradSync:
         self.always_sync = always_sync
         self.exact_unused = exact_unused
         self._flags: Optional[torch.Tensor] = None
-        self._given_key, self._given_any = None, None  # reduce_grads: cached 'some rank has a gradient' mask
+        # reduce_grads: this rank's set of givers at the last flags exchange and the 'some rank has a gradient' mask that
+        # exchange gave; whether the spare slot of the last bucket still holds the zero of the last reduction; the
+        # zero-fill runs of this rank's current set
+        self._given_key, self._given_any = None, None
+        self._slot_is_zero = False
+        self._zero_runs = (None, [])
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.params: List[torch.nn.Parameter] = [p for p in module.parameters() if p.requires_grad]
         self._index = {p: i for i, p in enumerate(self.params)}
@@ -111,9 +118,12 @@ class GradSync:
         if cur:
             groups.append(cur)
         self._buckets = []
-        for plist in groups:
+        for gi, plist in enumerate(groups):
             total = sum(p.numel() for p in plist)
-            flat = torch.zeros(total, dtype=torch.float32, device=plist[0].device)
+            # exact_unused: one more f32 behind the last bucket's gradients, the "some rank's set of givers changed" slot
+            # of reduce_grads -- it travels inside a collective that is issued anyway
+            extra = 1 if (self.exact_unused and gi == len(groups) - 1) else 0
+            flat = torch.zeros(total + extra, dtype=torch.float32, device=plist[0].device)
             slots, off = [], 0
             for p in plist:
                 slots.append((p, off))
@@ -219,8 +229,22 @@ class GradSync:
         30 ms when the stream is idle at the call, 4.7 s when it is not, one bucket at a time or three), so for gloo on
         device tensors the stream is drained first and the buckets go one by one.
 
-        ``exact_unused``: parameters outside ``params`` keep ``grad = None`` unless another rank handed one in (the set
-        is exchanged once per distinct ``params`` set, not per step: under a replayed graph it never changes)."""
+        Collectives of one call, in this order, on every rank:
+          1. (first call only) the broadcast of rank 0's bucket order -- ``_buckets`` is None on every rank exactly then;
+          2. one all-reduce per bucket, in index order, each over the whole flat buffer of its bucket: the number and the
+             sizes were fixed by the broadcast layout;
+          3. (``exact_unused`` only) one all-reduce of len(params) "handed in" flags, if and only if the changed-slot that
+             step 2 reduced is positive.
+        Parameters outside ``params`` take part with zeros.  ``exact_unused``: they keep ``grad = None`` unless some rank
+        handed one in.  Which parameters some rank handed in is exchanged in step 3 and cached; the cache is dropped when
+        ANY rank's set differs from the set that rank had at the last exchange.  Every rank writes "my set changed" (1 or
+        0) into the one spare f32 behind the last bucket's gradients before step 2, reads the reduced value afterwards (one
+        host read per call, the price of a decision that every rank takes alike) and enters step 3 when it is positive.
+        The value is the same on every rank after the all-reduce, so either every rank issues step 3 or none does, whatever
+        each rank handed in: nothing a rank knows only about itself (the size of its own set, its own cache) decides about
+        a collective.  Under a replayed graph no set ever changes: the slot stays zero and step 3 is never entered.
+        Without ``exact_unused`` there is no slot, no host read and no step 3.  (``_zero_runs`` is a memo of a function of
+        this rank's own set alone -- which of its slots to fill with zeros -- and influences no collective.)"""
         if self._buckets is None:
             self._build_buckets([self._index[p] for p in params])
         given = set()
@@ -229,12 +253,12 @@ class GradSync:
             if g.data_ptr() != view.data_ptr():
                 view.copy_(g)
             given.add(p)
+        key = frozenset(self._index[p] for p in given)
         # slots of parameters without a gradient take part with zeros: merged into contiguous runs (they sit together at
         # the end of the arrival order: one fill instead of one per parameter), the run list cached per set of givers
-        zkey = (len(given), frozenset(self._index[p] for p in given)) if len(given) < len(self.params) else None
-        if zkey is None:
-            self._zero_runs = (None, [])
-        elif getattr(self, "_zero_runs", (None, None))[0] != zkey:
+        if len(given) == len(self.params):
+            self._zero_runs = (key, [])
+        elif self._zero_runs[0] != key:
             runs = []
             for bi, b in enumerate(self._buckets):
                 cur = None
@@ -247,10 +271,16 @@ class GradSync:
                             runs.append((bi, cur))
                     else:
                         cur = None
-            self._zero_runs = (zkey, runs)
+            self._zero_runs = (key, runs)
         for bi, (lo, hi) in self._zero_runs[1]:
             self._buckets[bi].flat[lo:hi].zero_()
-        if self.world > 1 or self.always_sync:
+        collective = self.world > 1 or self.always_sync
+        slot = self._buckets[-1].flat[-1:] if (self.exact_unused and collective) else None
+        if slot is not None:
+            changed = key != self._given_key  # against this rank's set at the last exchange (None before the first)
+            if changed or not self._slot_is_zero:  # (a reduced zero is still there: the steady state writes nothing)
+                slot.fill_(1.0 if changed else 0.0)
+        if collective:
             backend = dist.get_backend(self.group)
             serial = backend == "gloo"
             # RCCL averages inside the collective (ncclAvg: sum, then one division in f32 -- the same value as the
@@ -271,15 +301,20 @@ class GradSync:
                 if not avg:
                     b.flat.mul_(1.0 / self.world)
         somewhere = None
-        if self.exact_unused and len(given) < len(self.params):
-            key = frozenset(self._index[p] for p in given)
-            if self._given_key != key:
-                flags = torch.zeros(len(self.params), dtype=torch.float32, device=self.params[0].device)
-                if given:
-                    flags[torch.tensor(sorted(key), device=flags.device)] = 1.0
-                if self.world > 1 or self.always_sync:
+        if self.exact_unused:
+            if not collective:  # a lone rank: its own set is all there is
+                if key != self._given_key:
+                    self._given_key, self._given_any = key, [i in key for i in range(len(self.params))]
+            else:
+                # a sum or mean of 0s and 1s: positive on every rank alike iff some rank's set changed
+                any_changed = float(slot.item()) > 0.0
+                self._slot_is_zero = not any_changed
+                if any_changed:
+                    flags = torch.zeros(len(self.params), dtype=torch.float32, device=self.params[0].device)
+                    if key:
+                        flags[torch.tensor(sorted(key), device=flags.device)] = 1.0
                     dist.all_reduce(flags, op=dist.ReduceOp.SUM, group=self.group)
-                self._given_key, self._given_any = key, [v > 0 for v in flags.tolist()]
+                    self._given_key, self._given_any = key, [v > 0 for v in flags.tolist()]
             somewhere = self._given_any
         for p in self.params:
             if somewhere is None or somewhere[self._index[p]]:

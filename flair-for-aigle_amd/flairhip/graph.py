@@ -78,6 +78,15 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
         pending = [bn._pending_batches for bn in self._bns]
+        # nn.PackPlan uploads its descriptor tables whenever the set of operand buffers differs from the last training
+        # step's -- an evaluation pass in between (HipTrainer validates after every epoch) rebuilds the operands it used
+        # in new buffers -- and a host-to-device copy cannot be captured ("operation not permitted when stream is
+        # capturing"): bring the plans up to date here, so that the captured step finds its tables and records the
+        # pack kernels alone
+        for m in task.modules():
+            plan = getattr(m, "_pack_plan", None)
+            if isinstance(plan, hnn.PackPlan) and m.training:
+                plan.refresh(m.compute_dtype)
         # every packed operand counts as stale from here: the pack kernels MUST be part of the captured step (a plan
         # that happens to be fresh at capture time would otherwise leave the replays training on frozen operands)
         hnn.bump_state_epoch()

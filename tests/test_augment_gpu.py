@@ -391,16 +391,16 @@ def _host_batches(n, B=2, with_aug=None):
     return out
 
 
+@pytest.mark.parametrize("optimizer", ["default", "torch"])
 @pytest.mark.parametrize("hip_graph", [False, True])
-def test_trainer_adds_the_codes_to_training_batches_only(cuda, hip_graph):
+def test_trainer_adds_the_codes_to_training_batches_only(cuda, hip_graph, optimizer):
     from flairhip.augment import draw_codes, rank_epoch_rng
     from flair_hub.tasks.trainers import HipTrainer
     task, _, cfg = make_pair(precision="bf16", seed=3)
     cfg["hyperparams"].update({"learning_rate": 1e-3, "total_steps": 12})
     cfg["modalities"]["pre_processings"]["use_augmentation"] = True
     assert task.config["modalities"]["pre_processings"]["use_augmentation"] is True
-    if hip_graph:
-        cfg["hyperparams"]["torch_optimizer"] = True  # the trainer captures the step for torch's Adam / AdamW
+    cfg["hyperparams"]["torch_optimizer"] = optimizer == "torch"  # the trainer captures the step for either
     seen = _record(task)
     losses = []
     orig = task.on_train_batch_end
@@ -411,6 +411,7 @@ def test_trainer_adds_the_codes_to_training_batches_only(cuda, hip_graph):
     assert len(losses) == 6 and all(np.isfinite(losses))
     # eager: every training batch passes training_step; graph mode: the two eager steps and the capture
     assert len(seen["train"]) == (6 if not hip_graph else 3)
+    assert (tr.graph_built, tr.graph_replays, tr.eager_steps) == ((True, 4, 2) if hip_graph else (False, 0, 6))
     assert all("AUG" in b for b in seen["train"])
     assert seen["val"] and not any("AUG" in b for b in seen["val"])
     assert seen["predict"] and not any("AUG" in b for b in seen["predict"])

@@ -297,3 +297,116 @@ def test_reduce_grads_hookless_protocol_leaves_unused_parameters_alone(tmp_path)
     # mean of the per-rank gradients at the common weights of step 3 is what both ranks hold
     for k in g0:
         assert torch.equal(g0[k], g1[k]), k
+
+
+# --------------------------------------------------------------------------------------------------
+# reduce_grads when the ranks hand in DIFFERENT sets of parameters, and sets that change on one rank only: the sequence
+# of collectives must be the same on every rank whatever each rank handed in (a rank that decides on its own whether
+# to exchange the "handed in" flags pairs that all-reduce with another rank's next bucket), and every rank must learn
+# that another rank's set changed (or it leaves grad = None for a parameter the other rank steps).
+
+
+class ThreeNet(torch.nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.a = torch.nn.Linear(8, 16)
+        self.b = torch.nn.Linear(16, 16)
+        self.c = torch.nn.Linear(16, 4)
+
+
+ABC, AC = ("a", "b", "c"), ("a", "c")
+# name -> per step, per rank: the layers whose gradients the rank hands in
+SCHEDULES = {
+    "rank1-leaves-b-out-from-the-start": [[ABC, AC]] * 4,
+    "only-rank1-starts-handing-b-in": [[AC, AC]] + [[AC, ABC]] * 3,
+    "grows-then-shrinks-on-rank1": [[AC, AC], [AC, ABC], [AC, ABC], [AC, AC], [AC, AC]],
+    "nobody-ever-hands-b-in": [[AC, AC]] * 4,
+    "symmetric": [[ABC, ABC]] * 4,
+}
+
+
+def _handed_grad(step, rank, name, shape):
+    g = torch.Generator().manual_seed(1000 * step + 100 * rank + sum(map(ord, name)))
+    return torch.randn(shape, generator=g)
+
+
+def _schedule_worker(rank, world, port, out_dir, exact):
+    from datetime import timedelta
+    sys.path.insert(0, os.path.join(ROOT, "flair-for-aigle_amd"))
+    from flairhip.distributed import GradSync
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    # a mismatch between the ranks' collectives raises after 30 s where gloo does not notice it at once: never a hang
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=30))
+    calls, real = [], dist.all_reduce
+
+    def recorded(tensor, op=dist.ReduceOp.SUM, group=None, async_op=False):
+        calls.append((tensor.numel(), str(op)))
+        return real(tensor, op=op, group=group, async_op=async_op)
+
+    dist.all_reduce = recorded
+    out = {}
+    for name, schedule in SCHEDULES.items():
+        torch.manual_seed(5)
+        net = ThreeNet()
+        sync = GradSync(net, bucket_bytes=1024, hooks=False, exact_unused=exact)
+        del calls[:]
+        steps = []
+        for step, per_rank in enumerate(schedule):
+            for p in net.parameters():
+                p.grad = None  # optimizer.zero_grad(set_to_none=True)
+            ps, gs, mark = [], [], len(calls)
+            for k, p in net.named_parameters():
+                if k.split(".")[0] in per_rank[rank]:
+                    ps.append(p)
+                    gs.append(_handed_grad(step, rank, k, p.shape))
+            sync.reduce_grads(ps, gs)
+            steps.append({"grads": {k: (None if p.grad is None else p.grad.clone()) for k, p in net.named_parameters()},
+                          "calls": list(calls[mark:])})
+        assert len(sync._buckets) >= 2
+        steps[0]["buckets"] = len(sync._buckets)
+        out[name] = steps
+    torch.save(out, os.path.join(out_dir, f"sched_{int(exact)}_{rank}.pt"))
+    dist.all_reduce = real
+    dist.destroy_process_group()
+
+
+@pytest.fixture(scope="module", params=[True, False], ids=["exact-unused", "zero-fill"])
+def schedule_runs(request, tmp_path_factory):
+    """all schedules in one pair of processes per mode (a fresh net and GradSync per schedule)"""
+    out = tmp_path_factory.mktemp("sched")
+    mp.spawn(_schedule_worker, args=(2, _free_port(), str(out), request.param), nprocs=2, join=True)
+    return request.param, [torch.load(out / f"sched_{int(request.param)}_{r}.pt") for r in range(2)]
+
+
+@pytest.mark.parametrize("name", list(SCHEDULES))
+def test_reduce_grads_when_ranks_hand_in_different_and_changing_sets(schedule_runs, name):
+    exact, per_rank_out = schedule_runs
+    shapes = {k: p.shape for k, p in ThreeNet().named_parameters()}
+    got0, got1 = per_rank_out[0][name], per_rank_out[1][name]
+    assert len(got0) == len(got1) == len(SCHEDULES[name])
+    for step, handed in enumerate(SCHEDULES[name]):
+        # the invariant: the same collectives, of the same sizes, in the same order on both ranks (the values alone would
+        # not show a mismatch that happens to pair tensors of equal size)
+        assert got0[step]["calls"] == got1[step]["calls"], (name, step, got0[step]["calls"], got1[step]["calls"])
+        assert len(got0[step]["calls"]) >= 2, "at least two buckets"
+        for k, shape in shapes.items():
+            givers = [r for r in range(2) if k.split(".")[0] in handed[r]]
+            a, b = got0[step]["grads"][k], got1[step]["grads"][k]
+            if not givers and exact:
+                assert a is None and b is None, (name, step, k)
+                continue
+            assert a is not None and b is not None, (name, step, k, "a rank kept grad = None for a gradient some rank handed in")
+            # the sum over the ranks in rank order, a missing gradient counting as zero, times 1 / world: one f32 addition,
+            # rounded here as in the collective (and exact when one addend is zero), and an exact multiplication by 0.5
+            want = torch.zeros(shape)
+            for r in range(2):
+                want = want + (_handed_grad(step, r, k, shape) if r in givers else torch.zeros(shape))
+            want = want * 0.5
+            assert torch.equal(a, want), (name, step, k, "rank 0")
+            assert torch.equal(b, want), (name, step, k, "rank 1")
+            assert torch.equal(a, b)
+    if name in ("nobody-ever-hands-b-in", "symmetric") or not exact:
+        # sets that never change (and the zero-fill mode always): after the first call the buckets alone, no further
+        # collective -- what a replayed graph step pays
+        assert all(len(s["calls"]) == got0[0]["buckets"] for s in got0[1:]), [len(s["calls"]) for s in got0]
+        assert len(got0[0]["calls"]) <= got0[0]["buckets"] + 1

@@ -62,26 +62,198 @@ def test_graph_replay_matches_eager(cuda):
     assert ng == ne
 
 
-def test_trainer_graph_mode_follows_the_eager_trainer(cuda):
-    """HipTrainer(hip_graph=True): two eager steps, then the captured step; same loss trajectory as the eager trainer"""
+# ---- HipTrainer(hip_graph=True) ----------------------------------------------------------------------------------------
+# The trainer says what it did (graph_built, graph_replays, eager_steps): without the counts a "graph" run that silently
+# stayed eager -- the gate once named torch's Adam / AdamW only, and the default optimizer is flairhip.optim.HipAdamW --
+# compares two eager runs and passes.
+
+LAYER = f"encoders.{MOD}.seg_model.layer2.0.conv1.weight"
+
+
+def _host_batches(n, seed=2, sizes=None):
+    g = torch.Generator().manual_seed(seed)
+    return [{MOD: torch.randn(B, 5, 64, 64, generator=g), TASK: torch.randint(0, 19, (B, 64, 64), generator=g)}
+            for B in (sizes or [2] * n)]
+
+
+def _trainer_fit(hip_graph, hyper=None, batches=None, val=None, epochs=1, val_losses=None, prepare=None):
+    """one HipTrainer.fit of the seeded bf16 U-Net -> dict(losses, lrs [(value, data_ptr or None) after every step and
+    after the fit], w (one named layer), trainer, task).  ``val_losses``: the values logged as val_loss, in order, in
+    place of the measured ones (what the plateau schedulers see)."""
     from flair_hub.tasks.trainers import HipTrainer
+    task, _, cfg = make_pair(precision="bf16", seed=3)
+    cfg["hyperparams"].update({"learning_rate": 1e-3, "total_steps": 6})
+    cfg["hyperparams"].update(hyper or {})
+    if prepare is not None:
+        prepare(task)
+    trainer = HipTrainer(max_epochs=epochs, hip_graph=hip_graph)
+    losses, lrs = [], []
 
-    def fit(hip_graph):
-        task, _, cfg = make_pair(precision="bf16", seed=3)
-        cfg["hyperparams"].update({"learning_rate": 1e-3, "total_steps": 6})
-        g = torch.Generator().manual_seed(2)
-        batches = [{MOD: torch.randn(2, 5, 64, 64, generator=g), TASK: torch.randint(0, 19, (2, 64, 64), generator=g)}
-                   for _ in range(6)]
-        losses = []
-        orig = task.on_train_batch_end
-        task.on_train_batch_end = lambda loss, batch, i: (losses.append(float(loss)), orig(loss, batch, i))[1]
-        HipTrainer(max_epochs=1, hip_graph=hip_graph).fit(task, train_dataloaders=batches)
-        return losses
+    def lr_now():
+        lr = trainer.optimizers[0].param_groups[0]["lr"]
+        return (float(lr), lr.data_ptr()) if torch.is_tensor(lr) else (lr, None)
 
-    eager, graph = fit(False), fit(True)
-    assert len(eager) == len(graph) == 6 and all(l == l for l in graph)
-    assert eager[:3] == graph[:3]  # the first two steps are the same code; the third loss depends only on them
-    assert all(abs(a - b) <= 5e-3 * abs(a) for a, b in zip(eager, graph))
+    orig = task.on_train_batch_end
+
+    def on_train_batch_end(loss, batch, i):
+        losses.append(float(loss))
+        orig(loss, batch, i)  # (cycle_then_plateau steps its warm-up schedule in here)
+        lrs.append(lr_now())
+
+    task.on_train_batch_end = on_train_batch_end
+    if val_losses is not None:
+        forced, log = iter(val_losses), task.log
+        task.log = lambda name, value, **kw: log(name, next(forced) if name == "val_loss" else value, **kw)
+    trainer.fit(task, train_dataloaders=batches if batches is not None else _host_batches(6), val_dataloaders=val)
+    torch.cuda.synchronize()
+    lrs.append(lr_now())
+    return {"losses": losses, "lrs": lrs, "w": task.model.state_dict()[LAYER].float().cpu(), "trainer": trainer, "task": task}
+
+
+def _counts(run):
+    t = run["trainer"]
+    return t.graph_built, t.graph_replays, t.eager_steps
+
+
+@pytest.fixture(scope="module")
+def eager_default(cuda):
+    """the eager trainer under the default optimizer on the six standard batches: the reference of several tests"""
+    return _trainer_fit(False)
+
+
+@pytest.mark.parametrize("optimizer", ["default", "torch"])
+def test_trainer_graph_mode_follows_the_eager_trainer(cuda, optimizer, eager_default):
+    """HipTrainer(hip_graph=True): two eager steps, then the captured step; same loss trajectory as the eager trainer.
+    Under the default optimizer (flairhip.optim.HipAdamW) the replayed trajectory is the eager one bit for bit: every kernel
+    is deterministic, and the learning rate reaches the kernel as the same f32 from a host number (eager: a fill) and from
+    the device tensor the schedule writes (graph).  Under ``torch_optimizer: true`` it is not, and is held to 5e-3: see
+    below."""
+    hyper = {"torch_optimizer": True} if optimizer == "torch" else None
+    eager = eager_default if optimizer == "default" else _trainer_fit(False, hyper)
+    graph = _trainer_fit(True, hyper)
+    assert _counts(graph) == (True, 4, 2), _counts(graph)
+    assert _counts(eager) == (False, 0, 6), _counts(eager)
+    kind = type(graph["trainer"].optimizers[0])
+    assert (kind.__module__ == "flairhip.optim") == (optimizer == "default"), kind
+    le, lg = eager["losses"], graph["losses"]
+    rel = ((graph["w"] - eager["w"]).norm() / eager["w"].norm()).item()
+    print(f"\n{optimizer}: eager {le}\n{'':9s}graph {lg}\n{'':9s}|dw|/|w| of {LAYER}: {rel:.3e}")
+    assert len(le) == len(lg) == 6 and all(l == l for l in lg)
+    assert le[:3] == lg[:3]  # the first two steps are the same code; the third loss depends only on them
+    assert all(abs(a - b) <= 5e-3 * abs(a) for a, b in zip(le, lg))
+    # torch's fused AdamW takes a host learning rate as a double and a device one as the f32 it is stored in
+    # (make_capturable): steps 2 .. 5 of its graph run see another lr than the eager trainer's by up to 2^-24 relative,
+    # which Adam's normalised update carries into the weights (measured: DESIGN.md 6) -- equality for the default only
+    if optimizer == "default":
+        assert le == lg, (le, lg)
+        assert torch.equal(eager["w"], graph["w"]), rel
+
+
+def test_a_batch_of_another_shape_runs_eagerly_between_replays(cuda):
+    """batch 3 at step 4: that step runs eagerly and is counted so, step 5 replays again, and the trajectory is the
+    eager trainer's on the same batches"""
+    sizes = [2, 2, 2, 2, 3, 2]
+    eager = _trainer_fit(False, batches=_host_batches(6, sizes=sizes))
+    graph = _trainer_fit(True, batches=_host_batches(6, sizes=sizes))
+    assert _counts(graph) == (True, 3, 3), _counts(graph)
+    assert _counts(eager) == (False, 0, 6)
+    print(f"\neager {eager['losses']}\ngraph {graph['losses']}")
+    assert eager["losses"] == graph["losses"]
+    assert torch.equal(eager["w"], graph["w"]), ((graph["w"] - eager["w"]).norm() / eager["w"].norm()).item()
+
+
+@pytest.mark.parametrize("why", ["mod_dropout", "sgd"])
+def test_what_the_trainer_does_not_capture_stays_eager(cuda, why, eager_default):
+    if why == "mod_dropout":
+        # what a config with a modality_dropout > 0 sets (SegmentationTask.__init__); with one modality the model draws
+        # nothing, so the run is the plain eager one
+        run = _trainer_fit(True, prepare=lambda task: setattr(task, "mod_dropout", True))
+        assert run["losses"] == eager_default["losses"] and torch.equal(run["w"], eager_default["w"])
+    else:
+        run = _trainer_fit(True, {"optimizer": "sgd"})
+        assert isinstance(run["trainer"].optimizers[0], torch.optim.SGD)
+        assert len(run["losses"]) == 6 and all(l == l for l in run["losses"])
+    assert _counts(run) == (False, 0, 6), _counts(run)
+
+
+def test_validation_inside_fit_after_replays_equals_the_eager_trainers(cuda):
+    """two epochs of three batches with a validation pass after each: the first validation follows one replay, the second
+    four, and training replays again after the first.  A stale packed operand or eval-mode BatchNorm fold after a replay
+    would move val_loss / val_miou off the eager trainer's"""
+    runs = {}
+    for hip_graph in (False, True):
+        runs[hip_graph] = _trainer_fit(hip_graph, batches=_host_batches(3), val=_host_batches(2, seed=9), epochs=2)
+    eager, graph = runs[False], runs[True]
+    assert _counts(graph) == (True, 4, 2) and _counts(eager) == (False, 0, 6)
+    me, mg = eager["trainer"].callback_metrics, graph["trainer"].callback_metrics
+    print(f"\neager val_loss {me['val_loss']!r} val_miou {me['val_miou']!r}\ngraph val_loss {mg['val_loss']!r} "
+          f"val_miou {mg['val_miou']!r}")
+    assert eager["losses"] == graph["losses"]
+    assert mg["val_loss"] == me["val_loss"] and mg["val_miou"] == me["val_miou"]
+    assert 0.0 < me["val_miou"] <= 1.0 and me["val_loss"] == me["val_loss"]
+    assert sorted(me) == sorted(mg)
+    for k in me:
+        if k.startswith("val_"):
+            assert mg[k] == me[k] or (mg[k] != mg[k] and me[k] != me[k]), k
+
+
+def _zero_patience(task):
+    """cycle_then_plateau builds its ReduceLROnPlateau with patience 10, whatever ``plateau_patience`` says (as the
+    reference does): the test sets 0 on the scheduler itself, on both twins alike"""
+    make = task.configure_optimizers
+
+    def configure():
+        out = make()
+        if task._plateau_scheduler is not None:
+            task._plateau_scheduler.patience = 0
+        return out
+
+    task.configure_optimizers = configure
+
+
+# scheduler, epochs x batches per epoch, warmup_fraction, forced val_loss per epoch (None: no validation)
+SCHEDULES = {
+    "one_cycle_lr": ("one_cycle_lr", 1, 6, 0.2, None),
+    # the validation loss rises from the first epoch on: patience 0 reduces after the second epoch
+    "reduce_on_plateau-rising": ("reduce_on_plateau", 3, 1, 0.2, [1.0, 2.0, 3.0]),
+    "cycle_then_plateau-rising": ("cycle_then_plateau", 3, 1, 0.7, [1.0, 2.0, 3.0]),
+    # ... and rises only after the capture: the reduction is written into the device lr and a replay reads it
+    "reduce_on_plateau-late": ("reduce_on_plateau", 5, 1, 0.2, [5.0, 4.0, 3.0, 6.0, 7.0]),
+    "cycle_then_plateau-late": ("cycle_then_plateau", 5, 1, 0.4, [5.0, 4.0, 3.0, 6.0, 7.0]),
+}
+
+
+@pytest.mark.parametrize("case", list(SCHEDULES))
+def test_schedulers_write_the_captured_lr_in_place(cuda, case):
+    """the lr tensor make_capturable put on the device is the one address the captured optimizer kernel reads: it must
+    stay where it is for the rest of the fit, and after every step hold float32 of what the same scheduler gives an eager
+    twin (a scheduler that assigned a new object, or a number, would leave the replays on the old value)"""
+    name, epochs, per_epoch, warmup, val_losses = SCHEDULES[case]
+    hyper = {"scheduler": name, "warmup_fraction": warmup, "plateau_patience": 0}
+    kw = dict(hyper=hyper, epochs=epochs, val_losses=val_losses, prepare=_zero_patience)
+    runs = {}
+    for hip_graph in (False, True):
+        runs[hip_graph] = _trainer_fit(hip_graph, batches=_host_batches(per_epoch),
+                                       val=_host_batches(1, seed=9) if val_losses else None, **kw)
+    eager, graph = runs[False], runs[True]
+    steps = epochs * per_epoch
+    assert _counts(graph) == (True, steps - 2, 2) and _counts(eager) == (False, 0, steps)
+    le, lg = [v for v, _ in eager["lrs"]], graph["lrs"]
+    print(f"\n{case}: eager {le}\n{'':{len(case)}s}  graph {lg}")
+    assert len(le) == len(lg) == steps + 1 and all(ptr is None for _, ptr in eager["lrs"])
+    assert len(set(le)) > 1, "the schedule never moved the lr"
+    if val_losses:
+        reductions = sum(1 for a, b in zip(le, le[1:]) if b == 0.5 * a)
+        assert reductions >= 1, le  # the test must not pass because nothing was reduced
+    ptrs = [ptr for _, ptr in lg]
+    assert ptrs[:2] == [None, None] and None not in ptrs[2:], ptrs  # a number until the capture, a device tensor after
+    assert len(set(ptrs[2:])) == 1, ptrs
+    for i, (want, (got, ptr)) in enumerate(zip(le, lg)):
+        if ptr is not None:
+            want = float(torch.tensor(want, dtype=torch.float32))
+        assert got == want, (i, got, want)
+    if case.endswith("-late"):  # a replayed step ran under the reduced lr
+        assert le[steps - 1] == 0.5 * le[steps - 2] and lg[steps - 1][1] is not None
 
 
 def test_graph_plus_bucket_reduce_equals_the_eager_step(cuda):

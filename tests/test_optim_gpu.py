@@ -8,7 +8,9 @@ Checker.adamw's docstring, emulated and attacked with mutants on the CPU in test
 maximize x weight decay {0, 0.02} x eps {1e-8, 1e-3}; tensors of 1, 4095, 4096, 4097, 8192 and 12289 elements; descriptor
 tables of 72, 73, 144 and 145 tensors with multi-block tensors at their ends, in the middle and in every launch; p, g or the
 moments alone at element offsets 1, 2, 3; two param_groups; skipped steps and a state loaded at step 1000; lr on the device;
-a captured step replayed with lr rewritten in between; vector and scalar path bit for bit.  Gradients span 1e-9 .. 10 per
+a captured step replayed with lr rewritten in between; vector and scalar path bit for bit; a state that a default
+torch.optim.AdamW / Adam saved (step counters on the host, capturable: False), loaded from disk and continued for two steps; a
+hand-assigned host state refused before any launch.  Gradients span 1e-9 .. 10 per
 element with exact zeros, so eps decides some quotients and not others.
 One MI355X run (37 tests, 6.6 s): largest error as a fraction of the bound over all cases (f32 only):
   adamw_multi_kernel   p 0.199   exp_avg 0.288   exp_avg_sq 0.341
@@ -319,3 +321,81 @@ def test_captured_step_replays_with_the_lr_on_the_device(cuda):
         _checked_step(opt, ck, f"replay {k + 1}", run=graph.replay)
         assert float(opt.state[ps[-1]]["step"]) == 2.0 + k
     _assert_ok(ck, 4 * 3 * len(ps))
+
+
+# ---- a state that torch's optimizer saved ------------------------------------------------------------------------------------
+# torch's default Adam / AdamW (not fused, not capturable: what the reference constructs) keeps ``step`` in a CPU tensor and
+# saves ``capturable: False``; torch.optim.Optimizer.load_state_dict hands both through as they are.  The kernel reads the
+# counter through a device pointer, so HipAdamW.load_state_dict has to move it (tests/test_optim_state_cpu.py holds the layout
+# to that without a GPU); here the loaded state is continued on the kernel and held to float64 and to torch's own next steps.
+
+
+@pytest.mark.parametrize("kind", ["adamw", "adam"])
+def test_a_default_torch_state_from_disk_continues_on_the_kernel(cuda, kind, tmp_path):
+    from flairhip.optim import HipAdam, HipAdamW
+    from insitu import Checker
+    g = torch.Generator().manual_seed(41)
+    ref_p = _params(cuda, 7)[:6] + [torch.randn(12289, generator=g).to(cuda).requires_grad_()]
+    kw = dict(lr=3e-3, betas=(0.9, 0.95), weight_decay=0.02 if kind == "adamw" else 0.01)
+    ref = (torch.optim.AdamW if kind == "adamw" else torch.optim.Adam)(ref_p, **kw)
+    assert not ref.param_groups[0]["capturable"] and not ref.param_groups[0]["fused"]
+    for _ in range(3):
+        for q in ref_p:
+            q.grad = _grad_like(q.shape, g, cuda)
+        ref.step()
+    assert ref.state[ref_p[0]]["step"].device.type == "cpu"  # the case: a counter on the host
+    torch.save(ref.state_dict(), tmp_path / "optimizer.pt")
+    sd = torch.load(tmp_path / "optimizer.pt", map_location="cpu")
+    ours_p = [q.detach().clone().requires_grad_() for q in ref_p]
+    ours = (HipAdamW if kind == "adamw" else HipAdam)(ours_p, lr=1.0)
+    ours.load_state_dict(sd)
+    assert all(grp["capturable"] is True for grp in ours.param_groups) and ours.param_groups[0]["lr"] == 3e-3
+    for p in ours_p:
+        st = ours.state[p]
+        assert st["step"].is_cuda and st["step"].dtype == torch.float32 and st["step"].dim() == 0
+        assert st["exp_avg"].is_cuda and st["exp_avg_sq"].is_cuda and st["exp_avg"].dtype == torch.float32
+    ck = Checker("full")
+    for step in range(2):
+        for p, q in zip(ours_p, ref_p):
+            gr = _grad_like(p.shape, g, cuda)
+            p.grad, q.grad = gr.clone(), gr.clone()
+        _checked_step(ours, ck, f"{kind} continued from torch's state, step {4 + step}")
+        ref.step()
+    torch.cuda.synchronize()
+    _assert_ok(ck, 2 * 3 * len(ours_p))
+    for p, q in zip(ours_p, ref_p):
+        d, bound = (p - q).detach().abs().max().item(), 2e-6 * float(q.detach().abs().max())
+        print(f"n={p.numel():6d} max|p - q| {d:.3e}  bound {bound:.3e}")
+        assert d <= bound, (p.numel(), d, bound)
+        assert float(ours.state[p]["step"]) == 5.0
+
+
+def test_step_refuses_a_hand_assigned_host_state_before_any_launch(cuda):
+    """a ``step`` counter on the host, assigned by hand: the kernel would dereference a host address.  step() raises before
+    it launches anything: the parameter, the moments and the other group's tensors are untouched"""
+    from flairhip.optim import HipAdamW
+    g = torch.Generator().manual_seed(43)
+    a = torch.randn(300, generator=g).to(cuda).requires_grad_()
+    b = torch.randn(50, generator=g).to(cuda).requires_grad_()
+    opt = HipAdamW([{"params": [a]}, {"params": [b]}], lr=1e-2)
+    for p in (a, b):
+        p.grad = torch.ones_like(p)
+    opt.step()  # a valid state and pointer tables first: the refusal must not depend on a first step
+    torch.cuda.synchronize()
+    a0, b0 = a.detach().clone(), b.detach().clone()
+    m0 = opt.state[a]["exp_avg"].clone()
+    for bad in (torch.ones(()), 1.0, torch.ones((), dtype=torch.float64, device=cuda)):
+        opt.state[b]["step"] = bad  # the SECOND group: the first one's launch must not have happened either
+        with pytest.raises(TypeError, match="step"):
+            opt.step()
+        torch.cuda.synchronize()
+        assert torch.equal(a, a0) and torch.equal(b, b0) and torch.equal(opt.state[a]["exp_avg"], m0)
+        assert float(opt.state[a]["step"]) == 1.0
+    opt.state[b]["step"] = torch.ones((), dtype=torch.float32, device=cuda)
+    opt.state[b]["exp_avg"] = torch.zeros(50)  # a moment on the host
+    with pytest.raises(TypeError, match="exp_avg"):
+        opt.step()
+    opt.state[b]["exp_avg"] = torch.zeros(50, device=cuda)
+    opt.step()
+    torch.cuda.synchronize()
+    assert float(opt.state[a]["step"]) == 2.0 and float(opt.state[b]["step"]) == 2.0 and not torch.equal(a, a0)

@@ -115,7 +115,13 @@ def run(root, out, cache, hip_graph, seed=None, reverse_epoch=None):
 @pytest.fixture(scope="module")
 def runs(cuda, dataset, tmp_path_factory):
     out = tmp_path_factory.mktemp("out")
-    return {(cache, graph): run(dataset, out, cache, graph) for cache in ("device", "none") for graph in (False, True)}, out
+    got = {(cache, graph): run(dataset, out, cache, graph) for cache in ("device", "none") for graph in (False, True)}
+    for (cache, graph), r in got.items():
+        # a hip_graph run really replays: two ordinary steps, the capture, four replays (the tests below that speak of
+        # a replayed step would otherwise compare eager runs)
+        did = (r[2].graph_built, r[2].graph_replays, r[2].eager_steps)
+        assert did == ((True, 4, 2) if graph else (False, 0, 6)), (cache, graph, did)
+    return got, out
 
 
 def test_resident_and_streamed_training_are_bit_identical(runs):

@@ -15,7 +15,9 @@ A dataset written with --sentinel2 adds the U-TAE branch; DIR/config says whethe
 --augment: the same run with modalities.pre_processings.use_augmentation on (per-sample flips / rotations drawn by the
 trainer, applied inside the layout and label kernels).  --schemas picks the schemas to run and --repeat N runs each N
 times in this process (a fresh model per run): the spread of the number, which a comparison against another commit or
-against --augment has to be read next to.  One JSON line per run, then the box's pinned H2D rate.
+against --augment has to be read next to.  One JSON line per run, then the box's pinned H2D rate.  Every line says how many
+of the run's steps were graph replays and how many ran eagerly (HipTrainer.graph_replays / eager_steps); --no-graph runs
+the eager trainer for comparison.
 """
 from __future__ import annotations
 
@@ -47,7 +49,7 @@ class Cycle:
             yield self.batches[i % len(self.batches)]
 
 
-def run(schema: str, B: int, steps: int, warm: int = 10, augment: bool = False):
+def run(schema: str, B: int, steps: int, warm: int = 10, augment: bool = False, hip_graph: bool = True):
     from flairhip.configs import unet_resnet34_config
     from flair_hub.tasks.module_setup import build_segmentation_module
     from flair_hub.tasks.trainers import HipTrainer
@@ -77,14 +79,15 @@ def run(schema: str, B: int, steps: int, warm: int = 10, augment: bool = False):
         return orig(loss, batch, i)
 
     task.on_train_batch_end = hook
-    tr = HipTrainer(max_epochs=1, max_steps=warm + steps, hip_graph=True)
+    tr = HipTrainer(max_epochs=1, max_steps=warm + steps, hip_graph=hip_graph)
     tr.fit(task, train_dataloaders=Cycle(batches, warm + steps + 1))
     dt = marks[warm + steps] - marks[warm]
-    return {"schema": schema, "augment": bool(augment), "host_MB_per_batch": round(mb, 1), "ms_per_step": round(dt / steps * 1e3, 3),
+    return {"schema": schema, "augment": bool(augment), "graph_replays": tr.graph_replays, "eager_steps": tr.eager_steps,
+            "host_MB_per_batch": round(mb, 1), "ms_per_step": round(dt / steps * 1e3, 3),
             "tiles_per_s": round(B * steps / dt, 1), "h2d_GBps_needed": round(mb / 1024 / (dt / steps), 1)}
 
 
-def run_dataset(root: str, cache: str, B: int, steps: int, warm: int = 10):
+def run_dataset(root: str, cache: str, B: int, steps: int, warm: int = 10, hip_graph: bool = True):
     """the training step fed by FlairDataModule from the on-disk dataset tools/make_patch_dataset.py wrote under
     ``root``: cache='device' gathers every batch from the device-resident sample store, cache='none' decodes the
     GeoTIFF patches per batch and streams the raw samples.  Aerial, plus the Sentinel-2 branch when the dataset was
@@ -129,12 +132,13 @@ def run_dataset(root: str, cache: str, B: int, steps: int, warm: int = 10):
     if dm.store is not None:
         task.attach_store(dm.store)  # fit() is handed the loader, not the data module
     per_epoch = max(len(dm.train_dataloader()), 1)
-    tr = HipTrainer(max_epochs=-(-(warm + steps) // per_epoch), max_steps=warm + steps, hip_graph=True)
+    tr = HipTrainer(max_epochs=-(-(warm + steps) // per_epoch), max_steps=warm + steps, hip_graph=hip_graph)
     tr.fit(task, train_dataloaders=dm.train_dataloader())
     dt = marks[warm + steps] - marks[warm]
     return {"dataset": root, "cache": cache, "resident": dm.store is not None, "sentinel2": s2,
             "s2_average": average, "series_resident": dm.store is not None and bool(dm.store.series),
             "store_MB": round(dm.store.bytes / 2 ** 20, 1) if dm.store is not None else 0, "setup_s": round(fill_s, 2),
+            "graph_replays": tr.graph_replays, "eager_steps": tr.eager_steps,
             "ms_per_step": round(dt / steps * 1e3, 3), "tiles_per_s": round(B * steps / dt, 1)}
 
 
@@ -147,14 +151,16 @@ def main():
     ap.add_argument("--schemas", default="compact,reference")
     ap.add_argument("--augment", action="store_true", help="use_augmentation on")
     ap.add_argument("--repeat", type=int, default=1, help="runs per schema (the spread of the number)")
+    ap.add_argument("--no-graph", action="store_true", help="HipTrainer(hip_graph=False): every step eager")
     args = ap.parse_args()
     if args.dataset:
         for _ in range(args.repeat):
-            print(json.dumps(run_dataset(os.path.abspath(args.dataset), args.cache, args.batch, args.steps)), flush=True)
+            print(json.dumps(run_dataset(os.path.abspath(args.dataset), args.cache, args.batch, args.steps,
+                                         hip_graph=not args.no_graph)), flush=True)
         return
     for schema in args.schemas.split(","):
         for _ in range(args.repeat):
-            print(json.dumps(run(schema, args.batch, args.steps, augment=args.augment)), flush=True)
+            print(json.dumps(run(schema, args.batch, args.steps, augment=args.augment, hip_graph=not args.no_graph)), flush=True)
     # raw H2D rate of this box for scale
     x = torch.empty(1 << 30, dtype=torch.uint8).pin_memory()
     d = torch.empty_like(x, device="cuda")
