@@ -22,6 +22,10 @@
 //               registers, then added to a per-wave LDS table uint32 [K + 1] (a second one for the confidence sums);
 //               non-zero entries are flushed with 64-bit integer atomicAdd.  No floating point in this pass.
 // The planes are cleared at the head of every call and the outputs too, so the workspace may hold anything.
+//
+// ffa_zone_change_u8 (include/flairhip_change.h) tabulates two rasters over the same zones: stages 1 - 3 are the one
+// host function zstat_build_planes for both entry points, stage 4 is zchange_tabulate_kernel, a transition matrix
+// uint32 [K + 1][K + 1] per wave in place of the class table.
 #include "ffa_common.h"
 #include "ffa_zone.h"  // the crossing predicate and column, shared with zone_mask.hip
 
@@ -38,6 +42,10 @@ constexpr int kMaxK = 256;
 constexpr int kNarrow = FFA_ZONE_STATS_NARROW_WORDS;
 constexpr int kChunkWords = FFA_ZONE_STATS_CHUNK_WORDS;
 static_assert(255ll * 32 * kChunkWords < (1ll << 32), "a per-wave 32-bit confidence sum must not overflow");
+constexpr int kChangeMaxK = FFA_CHANGE_MAX_CLASSES;
+constexpr int kChangeTab = (kChangeMaxK + 1) * (kChangeMaxK + 1);  // entries of one per-wave transition table
+static_assert(2 * kWaves * kChangeTab * 4 <= 48 * 1024, "the transition tables of a block must fit static LDS");
+static_assert(kChangeMaxK < 64, "a lane per column and a 64-bit row mask in the flush");
 
 inline long long align_up(long long v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
@@ -346,6 +354,124 @@ __global__ __launch_bounds__(kT) void zstat_tabulate_kernel(const uint8_t* __res
   }
 }
 
+// ---- 4b. tabulate two rasters: transition matrices --------------------------------------------------------------------
+
+// The sibling of zstat_tabulate_kernel for ffa_zone_change_u8: the key of a member pixel is a * (K + 1) + b with
+// a = min(before, K), b = min(after, K), the per-wave tables hold (K + 1)^2 entries.  Clearing and flushing 1089 entries
+// per chunk would cost a parcel of a few words more than its pixels do, so the tables are cleared once per block, the
+// blocks walk the chunk list with a stride, and a wave flushes and re-clears only the rows a its chunk touched (a
+// 64-bit mask per lane, OR-ed over the wave): 2 LDS reads per touched row, lane b taking column b.  Every wave of a block
+// makes the same number of trips (the bound depends on blockIdx alone), so the barriers are reached by all of them.
+template <bool kConf>
+__global__ __launch_bounds__(kT) void zchange_tabulate_kernel(const uint8_t* __restrict__ before,
+                                                              const uint8_t* __restrict__ after,
+                                                              const uint8_t* __restrict__ conf, int H, int W, int K,
+                                                              const int* __restrict__ win,
+                                                              const long long* __restrict__ plane_off,
+                                                              long long plane_words, int Z,
+                                                              const int* __restrict__ chunks, long long n_chunks,
+                                                              const unsigned int* __restrict__ planes,
+                                                              unsigned long long* __restrict__ counts,
+                                                              unsigned long long* __restrict__ sums) {
+  __shared__ unsigned int s_cnt[kWaves * kChangeTab];
+  __shared__ unsigned int s_sum[kConf ? kWaves * kChangeTab : 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int k = threadIdx.x; k < kWaves * kChangeTab; k += kT) {
+    s_cnt[k] = 0;
+    if (kConf) s_sum[k] = 0;
+  }
+  __syncthreads();
+  unsigned int* cnt = s_cnt + wave * kChangeTab;
+  unsigned int* sum = s_sum + (kConf ? wave * kChangeTab : 0);
+  const int K1 = K + 1;
+  const long long N = (long long)H * W;
+
+  for (long long first_chunk = (long long)blockIdx.x * kWaves; first_chunk < n_chunks;
+       first_chunk += (long long)gridDim.x * kWaves) {
+    const long long chunk = first_chunk + wave;
+    int z = -1;
+    unsigned long long rows = 0;  // bit a: this lane added to row a of the wave's tables
+    if (chunk < n_chunks) {
+      const int* q = chunks + 3 * chunk;
+      z = q[0];
+      const int first = q[1];
+      const int nw = min(q[2], kChunkWords);  // more would overflow the 32-bit partial sums
+      if (z >= 0 && z < Z && first >= 0) {
+        const Win w = load_window(win, z, H, W);
+        const long long base = plane_off[z];
+        const long long zone_words = (long long)(w.r1 - w.r0) * w.ww;
+        for (int j = lane; j < nw; j += 64) {
+          const long long wi = (long long)first + j;
+          if (w.ww == 0 || wi >= zone_words || base + wi < 0 || base + wi >= plane_words) break;  // j only rises
+          unsigned int bits = planes[base + wi];
+          const int r = w.r0 + (int)(wi / w.ww);
+          const int col = w.c0 + 32 * (int)(wi % w.ww);
+          const int valid = w.c1 - col;  // >= 1, as in zstat_tabulate_kernel
+          if (valid < 32) bits &= (1u << valid) - 1u;
+          if (bits == 0) continue;
+          const long long off = (long long)r * W + col;
+          unsigned int av[8], bv[8], fv[8];
+          load32(before, off, N, av);
+          load32(after, off, N, bv);
+          if (kConf) load32(conf, off, N, fv);
+          // runs of one key are summed in registers: an unchanged uniform field costs one LDS atomic per word
+          int cur = 0;
+          unsigned int run = 0, rsum = 0;
+#pragma unroll
+          for (int k = 0; k < 32; ++k) {
+            if ((bits >> k) & 1u) {
+              const int sh = 8 * (k & 3);
+              const int a = min((int)((av[k >> 2] >> sh) & 255u), K);
+              const int b = min((int)((bv[k >> 2] >> sh) & 255u), K);
+              const int key = a * K1 + b;  // < (K + 1)^2 <= kChangeTab
+              if (key != cur && run) {
+                atomicAdd(&cnt[cur], run);
+                if (kConf) atomicAdd(&sum[cur], rsum);
+                run = 0;
+                rsum = 0;
+              }
+              if (run == 0) rows |= 1ull << a;
+              cur = key;
+              run += 1;
+              if (kConf) rsum += (fv[k >> 2] >> sh) & 255u;
+            }
+          }
+          atomicAdd(&cnt[cur], run);  // bits != 0: the last run is never empty
+          if (kConf) atomicAdd(&sum[cur], rsum);
+        }
+      } else {
+        z = -1;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rows |= __shfl_xor(rows, o, 64);  // wave-uniform from here
+    if (z >= 0) {
+      const long long out0 = (long long)z * K1 * K1;
+      while (rows) {
+        const int a = __builtin_ctzll(rows);  // <= K: only clamped classes set a bit
+        rows &= rows - 1;
+        if (lane <= K) {
+          const int key = a * K1 + lane;
+          const unsigned int c = cnt[key];
+          if (c) {
+            atomicAdd(&counts[out0 + key], (unsigned long long)c);
+            cnt[key] = 0;
+          }
+          if (kConf) {
+            const unsigned int s = sum[key];
+            if (s) {
+              atomicAdd(&sums[out0 + key], (unsigned long long)s);
+              sum[key] = 0;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();  // the tables are clear again before the next chunk's adds
+  }
+}
+
 }  // namespace
 
 extern "C" long long ffa_zone_stats_workspace_bytes(long long n_vertices, long long plane_words, long long n_chunks) {
@@ -358,34 +484,38 @@ extern "C" long long ffa_zone_stats_workspace_bytes(long long n_vertices, long l
   return make_layout(plane_words, n_vertices < 1 ? 1 : n_vertices).total;
 }
 
-extern "C" int ffa_zone_stats_u8(const uint8_t* cls, const uint8_t* conf, int H, int W, int K, const double* xy_pix,
-                                 long long n_vertices, const int32_t* ring_offsets, int n_rings,
-                                 const int32_t* zone_ring_offsets, int n_zones, const int32_t* windows,
-                                 const int64_t* plane_offsets, long long plane_words, const int64_t* scan_starts,
-                                 long long n_scan_items, const int32_t* chunks, long long n_chunks, int64_t* counts,
-                                 int64_t* conf_sums, void* ws, long long ws_bytes, hipStream_t st) {
-  FFA_REQUIRE(H >= 1 && W >= 1, "zone_stats: raster %d x %d outside 1 <= H, W", H, W);
-  FFA_REQUIRE(K >= 1 && K <= kMaxK, "zone_stats: %d classes outside 1..256", K);
+namespace {
+
+// The argument ranges both entry points accept (their K ranges differ: max_k).
+int zstat_check_args(const char* what, int H, int W, int K, int max_k, int n_zones, int n_rings, long long n_vertices,
+                     long long plane_words, long long n_scan_items, long long n_chunks) {
+  FFA_REQUIRE(H >= 1 && W >= 1, "%s: raster %d x %d outside 1 <= H, W", what, H, W);
+  FFA_REQUIRE(K >= 1 && K <= max_k, "%s: %d classes outside 1..%d", what, K, max_k);
   FFA_REQUIRE(n_zones >= 0 && n_rings >= 0 && n_vertices >= 0 && n_vertices < (1ll << 31) - 1,
-              "zone_stats: %d zones, %d rings, %lld vertices outside 0 <= zones, rings and 0 <= vertices < 2^31 - 1",
+              "%s: %d zones, %d rings, %lld vertices outside 0 <= zones, rings and 0 <= vertices < 2^31 - 1", what,
               n_zones, n_rings, n_vertices);
   FFA_REQUIRE(plane_words >= 0 && plane_words <= (1ll << 40) && n_scan_items >= 0 && n_chunks >= 0 &&
                   n_scan_items <= kWaves * ((1ll << 31) - 1) && n_chunks <= (1ll << 31) - 1,
-              "zone_stats: %lld plane words, %lld scan items, %lld chunks out of range", plane_words, n_scan_items,
+              "%s: %lld plane words, %lld scan items, %lld chunks out of range", what, plane_words, n_scan_items,
               n_chunks);
-  if (n_zones == 0) return FFA_OK;
-  FFA_REQUIRE(cls && counts && (!conf || conf_sums), "zone_stats: null raster or output");
-  const long long out_bytes = 8ll * n_zones * (K + 1);
-  (void)hipMemsetAsync(counts, 0, out_bytes, st);
-  if (conf) (void)hipMemsetAsync(conf_sums, 0, out_bytes, st);
-  if (plane_words == 0 || n_chunks == 0) return ffa_check_launch("zone_stats");  // no zone reaches the raster
-  FFA_REQUIRE(windows && plane_offsets && scan_starts && chunks && ws, "zone_stats: null table or workspace");
+  return FFA_OK;
+}
+
+// Stages 1 - 3 for both entry points: the planes of all zones in the workspace, cleared, toggled and scanned, so that
+// bit b of word w of a row of zone z's plane says whether column c0 + 32 w + b of that row is inside.  One function:
+// the member pixels of ffa_zone_change_u8 are those of ffa_zone_stats_u8 because the same launches made them.
+int zstat_build_planes(const char* what, int H, int W, const double* xy_pix, long long n_vertices,
+                       const int32_t* ring_offsets, int n_rings, const int32_t* zone_ring_offsets, int n_zones,
+                       const int32_t* windows, const int64_t* plane_offsets, long long plane_words,
+                       const int64_t* scan_starts, long long n_scan_items, const int32_t* chunks, void* ws,
+                       long long ws_bytes, hipStream_t st, unsigned int** planes_out) {
+  FFA_REQUIRE(windows && plane_offsets && scan_starts && chunks && ws, "%s: null table or workspace", what);
   FFA_REQUIRE(n_vertices == 0 || (xy_pix && ring_offsets && zone_ring_offsets && n_rings >= 1),
-              "zone_stats: vertices without rings");
+              "%s: vertices without rings", what);
   const long long n = n_vertices;
   const Layout lo = make_layout(plane_words, n < 1 ? 1 : n);
   if (ws_bytes < lo.total) {
-    ffa_set_error("zone_stats: workspace %lld bytes < %lld", ws_bytes, lo.total);
+    ffa_set_error("%s: workspace %lld bytes < %lld", what, ws_bytes, lo.total);
     return FFA_ERR_WORKSPACE;
   }
   unsigned int* planes = at<unsigned int>(ws, lo.planes);
@@ -409,6 +539,32 @@ extern "C" int ffa_zone_stats_u8(const uint8_t* cls, const uint8_t* conf, int H,
                          0, st, windows, reinterpret_cast<const long long*>(plane_offsets), plane_words,
                          reinterpret_cast<const long long*>(scan_starts), n_zones, n_scan_items, H, W, planes);
   }
+  *planes_out = planes;
+  return FFA_OK;
+}
+
+}  // namespace
+
+extern "C" int ffa_zone_stats_u8(const uint8_t* cls, const uint8_t* conf, int H, int W, int K, const double* xy_pix,
+                                 long long n_vertices, const int32_t* ring_offsets, int n_rings,
+                                 const int32_t* zone_ring_offsets, int n_zones, const int32_t* windows,
+                                 const int64_t* plane_offsets, long long plane_words, const int64_t* scan_starts,
+                                 long long n_scan_items, const int32_t* chunks, long long n_chunks, int64_t* counts,
+                                 int64_t* conf_sums, void* ws, long long ws_bytes, hipStream_t st) {
+  int rc = zstat_check_args("zone_stats", H, W, K, kMaxK, n_zones, n_rings, n_vertices, plane_words, n_scan_items,
+                            n_chunks);
+  if (rc != FFA_OK) return rc;
+  if (n_zones == 0) return FFA_OK;
+  FFA_REQUIRE(cls && counts && (!conf || conf_sums), "zone_stats: null raster or output");
+  const long long out_bytes = 8ll * n_zones * (K + 1);
+  (void)hipMemsetAsync(counts, 0, out_bytes, st);
+  if (conf) (void)hipMemsetAsync(conf_sums, 0, out_bytes, st);
+  if (plane_words == 0 || n_chunks == 0) return ffa_check_launch("zone_stats");  // no zone reaches the raster
+  unsigned int* planes = nullptr;
+  rc = zstat_build_planes("zone_stats", H, W, xy_pix, n_vertices, ring_offsets, n_rings, zone_ring_offsets, n_zones,
+                          windows, plane_offsets, plane_words, scan_starts, n_scan_items, chunks, ws, ws_bytes, st,
+                          &planes);
+  if (rc != FFA_OK) return rc;
   const dim3 grid((unsigned int)((n_chunks + kWaves - 1) / kWaves));
   auto* c64 = reinterpret_cast<unsigned long long*>(counts);
   auto* s64 = reinterpret_cast<unsigned long long*>(conf_sums);
@@ -420,4 +576,39 @@ extern "C" int ffa_zone_stats_u8(const uint8_t* cls, const uint8_t* conf, int H,
     hipLaunchKernelGGL(zstat_tabulate_kernel<false>, grid, dim3(kT), 0, st, cls, conf, H, W, K, windows, po,
                        plane_words, n_zones, chunks, n_chunks, planes, c64, s64);
   return ffa_check_launch("zone_stats");
+}
+
+extern "C" int ffa_zone_change_u8(const uint8_t* before, const uint8_t* after, const uint8_t* conf, int H, int W, int K,
+                                  const double* xy_pix, long long n_vertices, const int32_t* ring_offsets, int n_rings,
+                                  const int32_t* zone_ring_offsets, int n_zones, const int32_t* windows,
+                                  const int64_t* plane_offsets, long long plane_words, const int64_t* scan_starts,
+                                  long long n_scan_items, const int32_t* chunks, long long n_chunks, int64_t* counts,
+                                  int64_t* conf_sums, void* ws, long long ws_bytes, hipStream_t st) {
+  int rc = zstat_check_args("zone_change", H, W, K, kChangeMaxK, n_zones, n_rings, n_vertices, plane_words,
+                            n_scan_items, n_chunks);
+  if (rc != FFA_OK) return rc;
+  if (n_zones == 0) return FFA_OK;
+  FFA_REQUIRE(before && after && counts && (!conf || conf_sums), "zone_change: null raster or output");
+  const long long out_bytes = 8ll * n_zones * (K + 1) * (K + 1);
+  (void)hipMemsetAsync(counts, 0, out_bytes, st);
+  if (conf) (void)hipMemsetAsync(conf_sums, 0, out_bytes, st);
+  if (plane_words == 0 || n_chunks == 0) return ffa_check_launch("zone_change");  // no zone reaches the raster
+  unsigned int* planes = nullptr;
+  rc = zstat_build_planes("zone_change", H, W, xy_pix, n_vertices, ring_offsets, n_rings, zone_ring_offsets, n_zones,
+                          windows, plane_offsets, plane_words, scan_starts, n_scan_items, chunks, ws, ws_bytes, st,
+                          &planes);
+  if (rc != FFA_OK) return rc;
+  // the tables take 34848 bytes of LDS: 4 blocks fit a CU (160 KB), and the blocks stride over the chunk list
+  const long long blocks = (n_chunks + kWaves - 1) / kWaves;
+  const dim3 grid((unsigned int)(blocks < 1024 ? blocks : 1024));
+  auto* c64 = reinterpret_cast<unsigned long long*>(counts);
+  auto* s64 = reinterpret_cast<unsigned long long*>(conf_sums);
+  const auto* po = reinterpret_cast<const long long*>(plane_offsets);
+  if (conf)
+    hipLaunchKernelGGL(zchange_tabulate_kernel<true>, grid, dim3(kT), 0, st, before, after, conf, H, W, K, windows, po,
+                       plane_words, n_zones, chunks, n_chunks, planes, c64, s64);
+  else
+    hipLaunchKernelGGL(zchange_tabulate_kernel<false>, grid, dim3(kT), 0, st, before, after, conf, H, W, K, windows,
+                       po, plane_words, n_zones, chunks, n_chunks, planes, c64, s64);
+  return ffa_check_launch("zone_change");
 }

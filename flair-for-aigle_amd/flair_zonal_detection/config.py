@@ -126,6 +126,38 @@ def validate_zone_stats(config: dict):
     return (None if path is None else os.fspath(path)), field, crs_name
 
 
+def validate_change(config: dict):
+    """The optional keys of land-cover change, all off by default: change_from (the class raster of an earlier run on
+    the same grid: a path, or {task name: path}; after the tile loop every written class raster ``<name>.tif`` gets
+    ``<name>_zone_change.csv`` and ``<name>_zone_transitions.csv``, the tables of change.zonal_change_stats over the
+    zones of the zone_stats layer, or over the whole raster as one zone) and change_transitions (a list of transition
+    specs such as '*:6' or '4:0' for change.change_polygons; default: 'became k' for every class).  Returns the two;
+    a bad value raises ValueError."""
+    source = config.get("change_from")
+    if isinstance(source, dict):
+        for task, path in source.items():
+            if not isinstance(task, str) or not isinstance(path, (str, os.PathLike)):
+                raise ValueError(f"change_from must map task names to paths, got {task!r}: {path!r}")
+        source = {task: os.fspath(path) for task, path in source.items()}
+    elif source is not None:
+        if not isinstance(source, (str, os.PathLike)):
+            raise ValueError(f"change_from must be a path to a class raster or {{task: path}}, got {source!r}")
+        source = os.fspath(source)
+    specs = config.get("change_transitions")
+    if specs is not None:
+        from flair_zonal_detection.change import parse_transition
+        if isinstance(specs, str) or not isinstance(specs, (list, tuple)):
+            raise ValueError(f"change_transitions must be a list of specs such as '*:6', got {specs!r}")
+        for spec in specs:
+            if not isinstance(spec, str):
+                raise ValueError(f"change_transitions must be a list of spec strings, got {spec!r}")
+            parse_transition(spec)
+        specs = list(specs)
+        if source is None:
+            raise ValueError("change_transitions needs change_from")
+    return source, specs
+
+
 COG_OVERVIEW_RESAMPLING = ("nearest", "mode", "average")
 
 
@@ -193,6 +225,7 @@ def validate_config(config: dict) -> None:
     validate_sieve_area(config)
     validate_compare(config)
     validate_zone_stats(config)
+    validate_change(config)
     validate_cog_conversion(config)
     validate_cog_overview_resampling(config)
     if not os.path.isfile(config["model_weights"]):

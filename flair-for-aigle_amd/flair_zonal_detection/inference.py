@@ -51,7 +51,8 @@ from flairhip.augment import tta_views
 from flair_zonal_detection.config import (config_recap_1, config_recap_2, load_config, validate_cog_conversion,
                                           validate_cog_overview_resampling, validate_config, validate_geozone_crs,
                                           threshold_file, validate_skip_tiles_outside_zone, validate_threshold_fallback,
-                                          validate_tta, validate_write_confidence, validate_zone_stats)
+                                          validate_change, validate_tta, validate_write_confidence,
+                                          validate_zone_stats)
 from flair_zonal_detection.dataset import MultiModalSlicedDataset, TileBatcher, pad_series_collate
 from flair_zonal_detection.model_utils import build_inference_model, compute_patch_sizes
 from flair_zonal_detection.postprocess import convert, convert_to_cog  # noqa: F401  (re-exported like the reference)
@@ -503,6 +504,60 @@ def write_zone_stats(outputs: Dict[str, object], config: Dict, zones, id_field=N
     return written
 
 
+ZONE_CHANGE_SUFFIX = "_zone_change.csv"            # <name>.tif -> <name>_zone_change.csv (one line per zone)
+ZONE_TRANSITIONS_SUFFIX = "_zone_transitions.csv"  # ... and <name>_zone_transitions.csv (one per zone, from, to)
+
+
+def change_source(change_from, key, class_keys):
+    """the ``before`` raster of the output ``key``: the {task: path} entry, or the bare path when the run has one class
+    raster (ValueError with more: a bare path cannot say which); None when the dict does not list the task"""
+    if isinstance(change_from, dict):
+        return change_from.get(key)
+    if len(class_keys) > 1:
+        raise ValueError(f"change_from is one path but the run wrote {len(class_keys)} class rasters "
+                         f"({', '.join(map(str, class_keys))}): give {{task: path}}")
+    return change_from
+
+
+def write_change_stats(outputs: Dict[str, object], config: Dict, change_from, zones=None, id_field=None,
+                       zone_crs=None) -> Dict[str, Tuple[str, str]]:
+    """The config key ``change_from``: for every class raster the run wrote to a file ``<name>.tif`` (``outputs``
+    values: closed writers or paths), the tables of change.zonal_change_stats against the earlier run's raster as
+    ``<name>_zone_change.csv`` and ``<name>_zone_transitions.csv`` -- over the zone layer ``zones``, or with None over
+    the whole raster as one zone; with write_confidence the tables have the confidence columns.  Class-probability and
+    in-memory outputs are left alone.  Returns {output key: (wide path, long path)}."""
+    from flair_zonal_detection.change import write_change_csv, write_transitions_csv, zonal_change_stats
+    from flair_zonal_detection.geotiff import GeoTiffWriter
+    if config.get("output_type", "argmax") != "argmax":
+        logger.info("change_from: needs class rasters (output_type: argmax), not %s", config.get("output_type"))
+        return {}
+    names = {t["name"]: t.get("class_names") for t in config.get("tasks", [])}
+    files = {}
+    for key, out in outputs.items():
+        if str(key).endswith(CONFIDENCE_SUFFIX):
+            continue
+        out_path = out if isinstance(out, (str, os.PathLike)) else getattr(out, "path", None) or getattr(out, "name", None)
+        if (isinstance(out, ArrayRaster) and not isinstance(out, GeoTiffWriter)) or not out_path:
+            logger.info("change_from: the in-memory output %s is not tabulated (zonal_change_stats takes it directly)", key)
+            continue
+        files[key] = (out, str(out_path))
+    written = {}
+    for key, (out, out_path) in files.items():
+        before = change_source(change_from, key, list(files))
+        if before is None:
+            logger.info("change_from: no earlier raster listed for %s", key)
+            continue
+        t0 = time.time()
+        table = zonal_change_stats(before, out, zones, id_field=id_field,
+                                   confidence=outputs.get(str(key) + CONFIDENCE_SUFFIX), zone_crs=zone_crs,
+                                   class_names=names.get(key) or None)
+        stem = os.path.splitext(out_path)[0]
+        written[key] = (write_change_csv(table, stem + ZONE_CHANGE_SUFFIX),
+                        write_transitions_csv(table, stem + ZONE_TRANSITIONS_SUFFIX))
+        logger.info("class transitions of %d zones in %.1f s: %s, %s", table.n_zones, time.time() - t0, *written[key])
+    return written
+
+
 def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tuple[int, int]] = None,
                   before_loop=None, geozone_crs=None) -> Dict[str, object]:
     """End-to-end zonal run with upstream FLAIR-HUB's one-argument semantics (the fork's own run_inference is
@@ -556,6 +611,12 @@ def run_inference(config_path, ref_raster=None, geozone=None, shard: Optional[Tu
             logger.info("zone_stats: the part files of a sharded run are not tabulated")
         else:
             write_zone_stats(outputs, config, zone_layer, zone_id, zone_layer_crs)
+    change_from, _ = validate_change(config)
+    if change_from is not None:  # likewise before the COG conversion
+        if shard is not None:
+            logger.info("change_from: the part files of a sharded run are not tabulated (rank 0 does it after the merge)")
+        else:
+            write_change_stats(outputs, config, change_from, zone_layer, zone_id, zone_layer_crs)
     if validate_cog_conversion(config):
         from flair_zonal_detection.geotiff import GeoTiffWriter
         files = {k: o.path for k, o in outputs.items() if isinstance(o, GeoTiffWriter)}

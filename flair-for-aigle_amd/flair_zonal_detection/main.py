@@ -152,6 +152,20 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--zone-stats-crs", type=str, default=None, metavar="EPSG:NNNN|auto",
                         help="CRS the --zone-stats layer is given in.  Default: the config key zone_stats_crs, else the "
                              "raster's CRS")
+    parser.add_argument("--change-from", type=str, default=None, metavar="PATH",
+                        help="the class raster of an earlier run on the same grid: after the tile loop each written "
+                             "class raster <name>.tif gets <name>_zone_change.csv (per zone: changed pixels and area, "
+                             "gain, loss and net per class) and <name>_zone_transitions.csv (per zone, from-class and "
+                             "to-class), over the --zone-stats zones or the whole raster as one zone.  Default: the "
+                             "config key change_from, else none")
+    parser.add_argument("--change-polygons", type=str, default=None, metavar="OUT.gpkg",
+                        help="with a change_from: write the regions that changed class as a GeoPackage (class_id = the "
+                             "index of the transition, with from_class and to_class; -1 = any), honouring --zone, "
+                             "--zone-crs, --target-crs and --sieve-area")
+    parser.add_argument("--change-transitions", type=str, default=None, metavar="SPEC[,SPEC...]",
+                        help="with a change_from: the transitions --change-polygons draws, FROM:TO with * for any "
+                             "class, e.g. *:6,4:0; the earlier spec wins where two overlap.  Default: the config key "
+                             "change_transitions, else *:k for every class k")
     return parser
 
 
@@ -167,6 +181,46 @@ def _write_object_summary(path: str, gdf, compare, compare_iou: float, sink: dic
     return out
 
 
+def _change_products(args, config, outputs, tables: bool) -> None:
+    """what a run with a change_from writes outside run_inference: the change tables of a sharded run (``tables``;
+    rank 0, over the merged rasters) and the --change-polygons GeoPackage"""
+    from flair_zonal_detection.config import load_config, validate_change, validate_geozone_crs, validate_sieve_area
+    from flair_zonal_detection.config import validate_zone_stats
+    cfg = config if isinstance(config, dict) else load_config(config)
+    change_from, transitions = validate_change(cfg)
+    if change_from is None:
+        return
+    from flair_zonal_detection.inference import CONFIDENCE_SUFFIX, change_source, write_change_stats
+    if tables:
+        write_change_stats(outputs, cfg, change_from, *validate_zone_stats(cfg))
+    if not args.change_polygons:
+        return
+    from flair_zonal_detection.change import change_polygons, transition_specs, write_change_polygons
+    class_keys = [k for k in outputs if not str(k).endswith(CONFIDENCE_SUFFIX)]
+    if len(class_keys) != 1:
+        raise ValueError(f"--change-polygons draws one class raster, the run wrote {len(class_keys)}")
+    key = class_keys[0]
+    before = change_source(change_from, key, class_keys)
+    if before is None:
+        raise ValueError(f"--change-polygons: change_from lists no earlier raster for {key}")
+    names = {t["name"]: t.get("class_names") for t in cfg.get("tasks", [])}.get(key) or None
+    zone_crs = args.zone_crs
+    if zone_crs is None and args.zone is not None:
+        zone_crs = validate_geozone_crs(cfg)
+    sieve_area = args.sieve_area if args.sieve_area is not None else validate_sieve_area(cfg)
+    pair = {key: outputs[key]}
+    with_conf = key + CONFIDENCE_SUFFIX in outputs
+    if with_conf:
+        pair[key + CONFIDENCE_SUFFIX] = outputs[key + CONFIDENCE_SUFFIX]
+    extra = {k: v for k, v in (("zone", args.zone), ("zone_crs", zone_crs), ("target_crs", args.target_crs),
+                               ("sieve_area", sieve_area or None)) if v is not None}
+    specs = transition_specs(transitions, class_names=names)
+    frame = change_polygons(before, pair, transitions=specs, class_names=names,
+                            **({"confidence": True} if with_conf else {}), **extra)
+    write_change_polygons(frame, args.change_polygons, specs)
+    logger.info("wrote %d change polygons against %s to %s", len(frame), before, args.change_polygons)
+
+
 def main(argv=None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -180,6 +234,20 @@ def main(argv=None) -> None:
                        ("--compare-classes", args.compare_classes)):
         if value is not None and args.polygons is None:
             parser.error(f"{opt} needs --polygons")
+    transitions = None
+    if args.change_transitions is not None:
+        from flair_zonal_detection.change import parse_transition
+        transitions = [t.strip() for t in args.change_transitions.split(",") if t.strip()]
+        try:
+            for spec in transitions:
+                parse_transition(spec)
+        except ValueError as exc:
+            parser.error(f"--change-transitions: {exc}")
+    if (args.change_polygons is not None or transitions is not None) and args.change_from is None:
+        from flair_zonal_detection.config import load_config
+        if (load_config(args.config) or {}).get("change_from") is None:
+            opt = "--change-polygons" if args.change_polygons is not None else "--change-transitions"
+            parser.error(f"{opt} needs --change-from (or the config key change_from)")
     if args.compare_iou is not None and not 0.0 < args.compare_iou <= 1.0:
         parser.error(f"--compare-iou expects a number in (0, 1], got {args.compare_iou}")
     if args.sieve_area is not None and not 0.0 <= args.sieve_area < float("inf"):
@@ -203,11 +271,12 @@ def main(argv=None) -> None:
         parser.error(f"--threshold-fallback expects an integer in 0..255, got {args.threshold_fallback}")
     zone_stats_args = (("zone_stats", args.zone_stats), ("zone_stats_id", args.zone_stats_id),
                        ("zone_stats_crs", args.zone_stats_crs))
+    change_args = (("change_from", args.change_from), ("change_transitions", transitions))
     if (args.cog or args.tta is not None or args.thresholds is not None or args.threshold_fallback is not None
-            or any(v is not None for _, v in zone_stats_args)):
+            or any(v is not None for _, v in zone_stats_args + change_args)):
         from flair_zonal_detection.config import load_config  # the keys, for this run only
         config = load_config(args.config)
-        for key, value in zone_stats_args:
+        for key, value in zone_stats_args + change_args:
             if value is not None:
                 config[key] = value
         if args.thresholds is not None:
@@ -224,6 +293,8 @@ def main(argv=None) -> None:
     else:
         from flair_zonal_detection.inference import run_inference
         outputs = run_inference(config, geozone=args.zone, geozone_crs=args.zone_crs)
+    if outputs is not None and (world > 1 or args.change_polygons):
+        _change_products(args, config, outputs, tables=world > 1)
     if args.polygons and outputs is not None:
         from flair_zonal_detection.inference import raster_to_polygons
         # a write_confidence run also returns f"{task}_confidence" rasters: the polygons then carry their mean

@@ -113,6 +113,24 @@ def _features_in_raster_crs(zones, features, zone_crs, raster_crs):
     return out
 
 
+def _zones_in_pixels(zones, id_field, zone_crs, raster_crs, left, top, xres, yres, name: str):
+    """(identifiers [Z], zones in pixel coordinates: a list of ring lists) of a zone layer as zone.zone_features reads
+    it, reprojected to the raster's CRS first when ``zone_crs`` says so; ValueError messages start with ``name``"""
+    from flair_zonal_detection.zone import zone_features
+    features = _features_in_raster_crs(zones, zone_features(zones), zone_crs, raster_crs)
+    if id_field is None:
+        ids = np.arange(len(features), dtype=np.int64)
+    else:
+        missing = [i for i, (props, _) in enumerate(features) if id_field not in props]
+        if missing:
+            raise ValueError(f"{name}: zone {missing[0]} has no property {id_field!r}")
+        ids = np.asarray([props[id_field] for props, _ in features])
+    zones_pix = []
+    for _, rings in features:  # rings_to_pixels' two lines, ring by ring
+        zones_pix.append([np.stack([(r[:, 0] - left) / xres, (top - r[:, 1]) / yres], axis=1) for r in rings])
+    return ids, zones_pix
+
+
 def zonal_class_stats(raster, zones, id_field: Optional[str] = None, confidence=None, zone_crs=None, class_names=None,
                       n_classes: Optional[int] = None) -> ZoneStatsTable:
     """Per-zone class areas of a class raster, and their confidence.
@@ -133,7 +151,6 @@ def zonal_class_stats(raster, zones, id_field: Optional[str] = None, confidence=
     from flairhip import ops
     from flair_zonal_detection.inference import (_bounds4, _class_band, _confidence_band, _confidence_source,
                                                  _polygon_source)
-    from flair_zonal_detection.zone import zone_features
     name = "zonal_class_stats"
     src = _polygon_source(raster)
     data = _class_band(src, name)
@@ -150,17 +167,7 @@ def zonal_class_stats(raster, zones, id_field: Optional[str] = None, confidence=
     if not 1 <= int(n_classes) <= 256:
         raise ValueError(f"{name}: n_classes {n_classes} outside 1..256")
     crs = getattr(src, "crs", None)
-    features = _features_in_raster_crs(zones, zone_features(zones), zone_crs, crs)
-    if id_field is None:
-        ids = np.arange(len(features), dtype=np.int64)
-    else:
-        missing = [i for i, (props, _) in enumerate(features) if id_field not in props]
-        if missing:
-            raise ValueError(f"{name}: zone {missing[0]} has no property {id_field!r}")
-        ids = np.asarray([props[id_field] for props, _ in features])
-    zones_pix = []
-    for _, rings in features:  # rings_to_pixels' two lines, ring by ring
-        zones_pix.append([np.stack([(r[:, 0] - left) / xres, (top - r[:, 1]) / yres], axis=1) for r in rings])
+    ids, zones_pix = _zones_in_pixels(zones, id_field, zone_crs, crs, left, top, xres, yres, name)
     dev = torch.device("cuda", torch.cuda.current_device())
     counts, sums = ops.zone_class_stats(torch.from_numpy(np.ascontiguousarray(data)).to(dev), zones_pix, int(n_classes),
                                         conf=None if conf is None else torch.from_numpy(np.ascontiguousarray(conf)).to(dev))

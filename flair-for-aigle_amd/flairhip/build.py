@@ -16,13 +16,14 @@ CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 OUT = os.path.join(HERE, "libflairhip.so")
 OBJ = os.path.join(CSRC, "build")
 
-HIP_SOURCES = ["ffa_runtime.hip", "conv_igemm.hip", "conv3x3_ring.hip", "conv3x3_thin.hip", "conv7x7_stem.hip", "conv_pack.hip", "conv_wgrad.hip", "norm_pool.hip", "augment.hip", "sample_gather.hip", "series_gather.hip", "tta.hip", "resample_loss.hip", "eval_stats.hip", "calibration.hip", "temporal.hip", "transformer.hip", "gemm.hip", "optim.hip", "polygonize.hip", "sieve.hip", "region_overlap.hip", "zone_mask.hip", "zone_stats.hip", "crs_transform.hip", "overview.hip"]
+HIP_SOURCES = ["ffa_runtime.hip", "conv_igemm.hip", "conv3x3_ring.hip", "conv3x3_thin.hip", "conv7x7_stem.hip", "conv_pack.hip", "conv_wgrad.hip", "norm_pool.hip", "augment.hip", "sample_gather.hip", "series_gather.hip", "tta.hip", "resample_loss.hip", "eval_stats.hip", "calibration.hip", "temporal.hip", "transformer.hip", "gemm.hip", "optim.hip", "polygonize.hip", "sieve.hip", "region_overlap.hip", "zone_mask.hip", "zone_stats.hip", "change.hip", "crs_transform.hip", "overview.hip"]
 CXX_SOURCES = ["conv_call.cpp", "tile_grid.cpp", "tiff_codec.cpp", "polygon_simplify.cpp"]
 HEADERS = ["ffa_common.h", "ffa_gfx950.h", "ffa_common_host.h", "ffa_ccl.h", "ffa_workspace.h", "ffa_d4.h", "ffa_zone.h", "conv7x7_stem.h", "conv_call.h", os.path.join("..", "..", "include", "flairhip.h"),
            os.path.join("..", "..", "include", "flairhip_eval.h"), os.path.join("..", "..", "include", "flairhip_gather.h"),
            os.path.join("..", "..", "include", "flairhip_series.h"), os.path.join("..", "..", "include", "flairhip_calib.h"),
            os.path.join("..", "..", "include", "flairhip_objects.h"),
-           os.path.join("..", "..", "include", "flairhip_zonestats.h")]
+           os.path.join("..", "..", "include", "flairhip_zonestats.h"),
+           os.path.join("..", "..", "include", "flairhip_change.h")]
 ARCH = "gfx950"
 
 

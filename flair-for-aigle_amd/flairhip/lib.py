@@ -238,6 +238,14 @@ ZONESTATS_SIGNATURES = {
                                _ll, _p]),
 }
 
+# the prototypes of include/flairhip_change.h (per-zone class transitions between two rasters, change codes), which
+# include/flairhip.h brings along
+CHANGE_SIGNATURES = {
+    "ffa_zone_change_u8": (_i, [_p, _p, _p, _i, _i, _i, _p, _ll, _p, _i, _p, _i, _p, _p, _ll, _p, _ll, _p, _ll, _p, _p,
+                                _p, _ll, _p]),
+    "ffa_change_code_u8": (_i, [_p, _p, _ll, _i, _p, _p, _p]),
+}
+
 _lib = None
 
 
@@ -256,7 +264,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **EVAL_SIGNATURES, **GATHER_SIGNATURES, **SERIES_SIGNATURES,
-                              **CALIB_SIGNATURES, **OBJECT_SIGNATURES, **ZONESTATS_SIGNATURES}.items():
+                              **CALIB_SIGNATURES, **OBJECT_SIGNATURES, **ZONESTATS_SIGNATURES, **CHANGE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args

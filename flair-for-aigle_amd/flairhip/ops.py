@@ -1859,6 +1859,37 @@ def zone_stats_batches(plane_words, max_workspace_bytes: int):
     return out
 
 
+def _zone_stats_calls(xy, ro, zro, H: int, W: int, dev, max_workspace_bytes, name: str):
+    """The per-batch part shared by zone_class_stats and zone_transition_stats: windows and batches of the flattened
+    zones, then per batch of zones [a, b) the planning in numpy, the workspace and the uploads.  Yields (a, b, the
+    thirteen table arguments of ffa_zone_stats_u8 from xy_pix to n_chunks, the workspace tensor); the uploaded tables
+    stay alive until the next batch is asked for."""
+    import numpy as np
+    windows = zone_stats_windows(xy, ro, zro, H, W)
+    words = zone_stats_plane_words(windows)[2]
+    if max_workspace_bytes is None:
+        max_workspace_bytes = int(torch.cuda.mem_get_info(dev)[0] * ZONE_STATS_MEMORY_FRACTION)
+    batches = zone_stats_batches(words, max_workspace_bytes)
+    lib = _l.load()
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    for a, b in batches:
+        r0, r1 = int(zro[a]), int(zro[b])
+        v0, v1 = int(ro[r0]), int(ro[r1])
+        plane_offsets, plane_words, scan_starts, chunks = zone_stats_plan(windows[a:b])
+        nbytes = lib.ffa_zone_stats_workspace_bytes(v1 - v0, plane_words, len(chunks))
+        if nbytes < 0:
+            _l.check(int(nbytes), name)
+        ws = workspace(int(nbytes), dev, ZONE_STATS_WORKSPACE_SLOT)
+        tables = [up(xy[v0:v1]) if v1 > v0 else None, up(ro[r0:r1 + 1] - ro[r0]), up(zro[a:b + 1] - zro[a]),
+                  up(windows[a:b]), up(plane_offsets), up(scan_starts), up(chunks) if len(chunks) else None]
+        yield a, b, (_ptr(tables[0]), v1 - v0, tables[1].data_ptr(), r1 - r0, tables[2].data_ptr(), b - a,
+                     tables[3].data_ptr(), tables[4].data_ptr(), plane_words, tables[5].data_ptr(),
+                     int(scan_starts[-1]), _ptr(tables[6]), len(chunks)), ws
+
+
 def zone_class_stats(cls: torch.Tensor, zones_pix, n_classes: int, conf: Optional[torch.Tensor] = None,
                      max_workspace_bytes: Optional[int] = None):
     """Per-zone class counts of a device uint8 class raster [H, W]: (counts, conf_sums), device int64 [Z, K + 1] each,
@@ -1890,35 +1921,114 @@ def zone_class_stats(cls: torch.Tensor, zones_pix, n_classes: int, conf: Optiona
     sums = torch.empty((Z, K + 1), dtype=torch.int64, device=dev) if conf is not None else None
     if Z == 0:
         return counts, sums
-    windows = zone_stats_windows(xy, ro, zro, H, W)
-    words = zone_stats_plane_words(windows)[2]
-    if max_workspace_bytes is None:
-        max_workspace_bytes = int(torch.cuda.mem_get_info(dev)[0] * ZONE_STATS_MEMORY_FRACTION)
-    batches = zone_stats_batches(words, max_workspace_bytes)
     lib = _l.load()
     cls = cls.contiguous()
     conf = conf.contiguous() if conf is not None else None
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-    for a, b in batches:
-        r0, r1 = int(zro[a]), int(zro[b])
-        v0, v1 = int(ro[r0]), int(ro[r1])
-        plane_offsets, plane_words, scan_starts, chunks = zone_stats_plan(windows[a:b])
-        nbytes = lib.ffa_zone_stats_workspace_bytes(v1 - v0, plane_words, len(chunks))
-        if nbytes < 0:
-            _l.check(int(nbytes), "zone_class_stats")
-        ws = workspace(int(nbytes), dev, ZONE_STATS_WORKSPACE_SLOT)
-        tables = [up(xy[v0:v1]) if v1 > v0 else None, up(ro[r0:r1 + 1] - ro[r0]), up(zro[a:b + 1] - zro[a]),
-                  up(windows[a:b]), up(plane_offsets), up(scan_starts), up(chunks) if len(chunks) else None]
-        _l.check(lib.ffa_zone_stats_u8(cls.data_ptr(), _ptr(conf), H, W, K, _ptr(tables[0]), v1 - v0,
-                                       tables[1].data_ptr(), r1 - r0, tables[2].data_ptr(), b - a,
-                                       tables[3].data_ptr(), tables[4].data_ptr(), plane_words, tables[5].data_ptr(),
-                                       int(scan_starts[-1]), _ptr(tables[6]), len(chunks), counts[a:b].data_ptr(),
+    for a, b, tables, ws in _zone_stats_calls(xy, ro, zro, H, W, dev, max_workspace_bytes, "zone_class_stats"):
+        _l.check(lib.ffa_zone_stats_u8(cls.data_ptr(), _ptr(conf), H, W, K, *tables, counts[a:b].data_ptr(),
                                        _ptr(sums[a:b]) if sums is not None else None, ws.data_ptr(), int(ws.numel()),
                                        _stream()), "zone_stats_u8")
     return counts, sums
+
+
+# --------------------------------------------------------------------------------------------------
+# land-cover change between two class rasters on one grid: per-zone transition matrices (csrc/zone_stats.hip) and
+# change codes (csrc/change.hip)
+
+CHANGE_MAX_CLASSES = 32  # FFA_CHANGE_MAX_CLASSES: the per-wave transition tables of (K + 1)^2 entries must fit LDS
+
+
+def zone_transition_stats(before: torch.Tensor, after: torch.Tensor, zones_pix, n_classes: int,
+                          conf: Optional[torch.Tensor] = None, max_workspace_bytes: Optional[int] = None):
+    """Per-zone class transitions between two device uint8 class rasters [H, W] on one grid: (counts, conf_sums),
+    device int64 [Z, K + 1, K + 1] each, K = ``n_classes`` in 1..32.  counts[z, a, b] is the number of pixels of zone z
+    with min(before, K) == a and min(after, K) == b: row and column K collect the values >= K.  With ``conf`` (device
+    uint8 [H, W], the confidence of the *after* run) conf_sums holds the sums of its bytes over the same pixels, else it
+    is None.  Zones, membership, batching beyond ``max_workspace_bytes`` and the workspace slot are those of
+    ``zone_class_stats``; the marginals of counts are its counts for ``before`` (sum over b) and ``after`` (over a)."""
+    import numpy as np
+    name = "zone_transition_stats"
+    K = int(n_classes)
+    if not 1 <= K <= CHANGE_MAX_CLASSES:
+        raise ValueError(f"{name}: n_classes {n_classes} outside 1..{CHANGE_MAX_CLASSES}")
+    for what, t in (("before", before), ("after", after)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.numel() > 0):
+            raise ValueError(f"{name}: {what} must be a CUDA uint8 [H, W] class raster")
+    if before.shape != after.shape or before.device != after.device:
+        raise ValueError(f"{name}: before is {tuple(before.shape)} on {before.device}, after {tuple(after.shape)} on "
+                         f"{after.device}: one grid on one device expected")
+    if conf is not None and not (torch.is_tensor(conf) and conf.is_cuda and conf.dtype == torch.uint8
+                                 and conf.shape == after.shape and conf.device == after.device):
+        raise ValueError(f"{name}: conf must be a CUDA uint8 {tuple(after.shape)} tensor on the device of the rasters")
+    H, W = (int(v) for v in after.shape)
+    dev = after.device
+    xy, ro, zro = zone_stats_flatten(zones_pix)
+    if not np.all(np.isfinite(xy)):
+        raise ValueError(f"{name}: non-finite ring coordinate")
+    Z = len(zro) - 1
+    counts = torch.empty((Z, K + 1, K + 1), dtype=torch.int64, device=dev)
+    sums = torch.empty((Z, K + 1, K + 1), dtype=torch.int64, device=dev) if conf is not None else None
+    if Z == 0:
+        return counts, sums
+    lib = _l.load()
+    before, after = before.contiguous(), after.contiguous()
+    conf = conf.contiguous() if conf is not None else None
+    for a, b, tables, ws in _zone_stats_calls(xy, ro, zro, H, W, dev, max_workspace_bytes, name):
+        _l.check(lib.ffa_zone_change_u8(before.data_ptr(), after.data_ptr(), _ptr(conf), H, W, K, *tables,
+                                        counts[a:b].data_ptr(), _ptr(sums[a:b]) if sums is not None else None,
+                                        ws.data_ptr(), int(ws.numel()), _stream()), "zone_change_u8")
+    return counts, sums
+
+
+def _byte_range(t: torch.Tensor):
+    return t.data_ptr(), t.data_ptr() + t.numel()
+
+
+def change_codes(before: torch.Tensor, after: torch.Tensor, lut, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = lut[min(before, K), min(after, K)] element by element: ``before`` and ``after`` are device uint8 tensors of
+    one shape (contiguous; views at any byte offset are fine), ``lut`` a host or device uint8 array [K + 1, K + 1] with
+    K in 1..32 (change.transition_lut makes one).  ``out``: None for a new tensor, or a contiguous device uint8 tensor of
+    the same shape -- ``before`` or ``after`` itself for an in-place recode; any other overlap with an input raises
+    ValueError."""
+    import numpy as np
+    name = "change_codes"
+    for what, t in (("before", before), ("after", after)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must be a contiguous CUDA uint8 tensor")
+    if before.shape != after.shape or before.device != after.device:
+        raise ValueError(f"{name}: before is {tuple(before.shape)} on {before.device}, after {tuple(after.shape)} on "
+                         f"{after.device}: one shape on one device expected")
+    dev = after.device
+    if torch.is_tensor(lut):
+        if lut.dtype != torch.uint8:
+            raise ValueError(f"{name}: lut must be uint8, got {lut.dtype}")
+        d_lut = lut.to(dev).contiguous()
+    else:
+        h = np.asarray(lut)
+        if h.dtype != np.uint8:
+            raise ValueError(f"{name}: lut must be uint8, got {h.dtype}")
+        d_lut = torch.from_numpy(np.ascontiguousarray(h)).to(dev)
+    if d_lut.dim() != 2 or d_lut.shape[0] != d_lut.shape[1]:
+        raise ValueError(f"{name}: lut must be [K + 1, K + 1], got {tuple(d_lut.shape)}")
+    K = int(d_lut.shape[0]) - 1
+    if not 1 <= K <= CHANGE_MAX_CLASSES:
+        raise ValueError(f"{name}: a lut of {K + 1} x {K + 1} means n_classes {K}, outside 1..{CHANGE_MAX_CLASSES}")
+    if out is None:
+        out = torch.empty_like(after)
+    else:
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+                and out.shape == after.shape and out.device == dev):
+            raise ValueError(f"{name}: out must be a contiguous CUDA uint8 {tuple(after.shape)} tensor on {dev}")
+        o0, o1 = _byte_range(out)
+        for what, t in (("before", before), ("after", after)):
+            t0, t1 = _byte_range(t)
+            if o0 < t1 and t0 < o1 and o0 != t0:  # the same bytes are fine: a lane reads its bytes before it writes them
+                raise ValueError(f"{name}: out overlaps {what} without being it")
+    n = int(after.numel())
+    if n:
+        _l.check(_l.load().ffa_change_code_u8(before.data_ptr(), after.data_ptr(), n, K, d_lut.data_ptr(),
+                                              out.data_ptr(), _stream()), "change_code_u8")
+    return out
 
 
 # --------------------------------------------------------------------------------------------------

@@ -527,6 +527,10 @@ int ffa_confusion_matrix(const uint8_t* pred, const uint8_t* target, long long n
 /* Zonal statistics (for a layer of zones over a class raster: the pixel count per zone and class, and the sum of a
  * confidence raster over the same pixels) are declared in flairhip_zonestats.h, likewise. */
 #include "flairhip_zonestats.h"
+/* Land-cover change (for two class rasters on one grid: the class transition matrix per zone over the same zone
+ * tables, and a recode of the two rasters into one raster of change codes) is declared in flairhip_change.h,
+ * likewise. */
+#include "flairhip_change.h"
 
 /* ---- host-side tile bookkeeping, bit-exact with the reference's float64 arithmetic
  *      (flair_zonal_detection/slicing.py:51-112, flair_zonal_detection/inference.py:318-335) -------- */
