@@ -64,6 +64,7 @@ struct Ring3Args {
   int nchunks;          // Ci * sizeof(T) / 64
   int tiles_x, tiles_y, npt, ncb;
   long long cb64_stride;  // bytes between the operands of consecutive 64-row groups
+  unsigned m_ncb, m_tx, m_ty;  // ffa_udiv_magic multipliers of ncb, tiles_x, tiles_y (ring16: tile walk on the scalar unit)
 };
 
 template <int WCO, int WPX, int NT, int TH, int TW>
@@ -570,7 +571,16 @@ struct Ring16Geom {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
-template <int WCO, int WPX, int NT, int TH, int TW, int OCC, bool PRO>
+// Epilogue forms, chosen once per launch from the block-uniform flags (ring16_epilogue_form): inside a form the
+// per-pixel loops test nothing but the lane's own bounds.
+enum : int {
+  RING16_EPI_GENERAL = 0,  // bias and / or ReLU, with or without residual and statistics (flags read once per tile)
+  RING16_EPI_STATS = 1,    // statistics only: the forward convolution in front of a training-mode BatchNorm
+  RING16_EPI_PLAIN = 2,    // nothing: dgrad
+  RING16_EPI_RES = 3,      // residual only: dgrad joining a skip gradient
+};
+
+template <int WCO, int WPX, int NT, int TH, int TW, int OCC, bool PRO, int EPI>
 __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Ring3Args a) {
   using G = Ring16Geom<WCO, WPX, NT, TH, TW>;
   using T = ffa_bf16;
@@ -585,7 +595,6 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
   const int col = lane & 15;  // operand row (weights) / column (pixels) of a fragment; accumulator column
   const int kg = lane >> 4;   // channels 8*kg .. 8*kg+7 of a chunk; accumulator rows 4*kg .. 4*kg+3
   const int NC = a.nchunks;
-  const int PT = NC * 3;  // phases per tile
   const int total_vb = ((a.npt + 7) / 8) * 8 * a.ncb;
 
   // ---- per-lane LDS read addresses (ring slot, tap, tile and kernel row are immediates) ----
@@ -611,48 +620,79 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
   struct TileId {
     int pt, cb, b, oy0, ox0;
   };
+  // tile walk on the scalar unit: vb is block uniform, the divisions by ncb / tiles_x / tiles_y are multiplications by
+  // the host's multipliers (a run-time division expands into a reciprocal sequence on the vector unit, per tile)
+  auto tile_of = [&](int vb, int& cb) {
+    unsigned r;
+    const unsigned q = ffa_udiv_magic((unsigned)vb >> 3, (unsigned)a.ncb, a.m_ncb, r);
+    cb = (int)r;
+    return (int)(q * 8 + (vb & 7));  // the co blocks of a pixel tile share an XCD's L2 (speed only)
+  };
   auto decode = [&](int vb) {
     TileId t;
-    const int j = vb >> 3;
-    t.pt = (j / a.ncb) * 8 + (vb & 7);  // the co blocks of a pixel tile share an XCD's L2 (speed only)
-    t.cb = j % a.ncb;
-    const int tx = t.pt % a.tiles_x;
-    const int t2 = t.pt / a.tiles_x;
-    t.b = t2 / a.tiles_y;
-    t.oy0 = (t2 % a.tiles_y) * TH;
-    t.ox0 = tx * TW;
+    t.pt = __builtin_amdgcn_readfirstlane(tile_of(vb, t.cb));
+    t.cb = __builtin_amdgcn_readfirstlane(t.cb);
+    unsigned tx, ty;
+    const unsigned t2 = ffa_udiv_magic((unsigned)t.pt, (unsigned)a.tiles_x, a.m_tx, tx);
+    t.b = __builtin_amdgcn_readfirstlane((int)ffa_udiv_magic(t2, (unsigned)a.tiles_y, a.m_ty, ty));
+    t.oy0 = __builtin_amdgcn_readfirstlane((int)ty * TH);
+    t.ox0 = __builtin_amdgcn_readfirstlane((int)tx * TW);
     return t;
   };
   auto next_valid = [&](int vb) {
-    while (vb < total_vb && decode(vb).pt >= a.npt) vb += gridDim.x;
-    return vb;
+    int cb;
+    while (vb < total_vb && tile_of(vb, cb) >= a.npt) vb += gridDim.x;
+    return __builtin_amdgcn_readfirstlane(vb);
   };
   const int pix_bytes = a.Ci * 2;
+  // the lane's halo pieces are launch constants: position in the halo tile and byte offset from the tile's halo origin
+  // (input pixel (oy0 - 1, ox0 - 1), chunk 0) with the slot XOR applied -- a tile adds a scalar base and tests bounds
+  int hyx[G::NHP];   // (hy << 16) | hx, negative past the last piece
+  int hrel[G::NHP];
+#pragma unroll
+  for (int k = 0; k < G::NHP; ++k) {
+    const int q = (tid >> 2) + k * (G::NTHR / 4);
+    const int hy = q / G::IW, hx = q % G::IW;
+    const int slot = jj ^ (((hx >> 2) & 1) << 1);
+    hyx[k] = q < G::IH * G::IW ? ((hy << 16) | hx) : -1;
+    hrel[k] = (hy * a.W + hx) * pix_bytes + slot * 16;
+  }
   int hoff[G::NHP];  // byte offset of the piece from the input base (chunk 0), -1 = zero fill
   auto halo_offsets = [&](const TileId& t) {
+    const int base = ((t.b * a.H + t.oy0 - 1) * a.W + t.ox0 - 1) * pix_bytes;
+    const int ylo = 1 - t.oy0, yhi = a.H + 1 - t.oy0, xlo = 1 - t.ox0, xhi = a.W + 1 - t.ox0;
 #pragma unroll
     for (int k = 0; k < G::NHP; ++k) {
-      const int q = (tid >> 2) + k * (G::NTHR / 4);
-      const int hy = q / G::IW, hx = q % G::IW;
-      const int vy = t.oy0 - 1 + hy, vx = t.ox0 - 1 + hx;
-      const bool ok = q < G::IH * G::IW && vy >= 0 && vx >= 0 && vy < a.H && vx < a.W;
-      const int slot = jj ^ (((hx >> 2) & 1) << 1);
-      hoff[k] = ok ? (((t.b * a.H + vy) * a.W + vx) * pix_bytes + slot * 16) : -1;
+      const int hy = hyx[k] >> 16, hx = hyx[k] & 0xffff;
+      const bool ok = hyx[k] >= 0 && hy >= ylo && hy < yhi && hx >= xlo && hx < xhi;
+      hoff[k] = ok ? base + hrel[k] : -1;
     }
   };
 
   const unsigned char* in_b = static_cast<const unsigned char*>(a.in);
   const unsigned char* w_all = static_cast<const unsigned char*>(a.w);
 
-  auto issue_w = [&](int cb, int ph, int slot) {
+  // Weight DMA of one phase: the slab at `slab` (w_slab: kernel row `ph` of chunk ph / 3 of co block cb) -> ring slot
+  // `slot`.  The source is a wave-uniform 64-bit base in scalar registers plus the lane's 16-byte offset: the main loop
+  // advances the base by SLAB64 per phase and re-seats it where the tile or the co block changes, so no address is
+  // rebuilt from (cb, ph) per instruction.
+  const unsigned lane16 = lane * 16;
+  auto w_slab = [&](int cb, int ph) {
+    return w_all + (long long)(cb * WCO) * a.cb64_stride + (long long)ph * G::SLAB64;
+  };
+  auto issue_w = [&](const unsigned char* slab, int slot) {
 #pragma unroll
     for (int i = 0; i < G::NWI; ++i) {
       const int ii = wave + i * G::NW;  // 1-KB piece of the slot (wave uniform)
-      const int g64 = ii / (G::SLAB64 / 1024), pi = ii % (G::SLAB64 / 1024);
-      const unsigned char* src = w_all + (long long)(cb * WCO + g64) * a.cb64_stride + (long long)ph * G::SLAB64 +
-                                 pi * 1024 + lane * 16;
-      ffa_lds_dma16(src, (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + G::RING_OFF + slot * G::SLOT +
-                                                                                  ii * 1024));
+      const unsigned char* src;
+      if constexpr (WCO == 1) {
+        src = slab + ii * 1024;
+      } else {
+        const int g64 = ii / (G::SLAB64 / 1024), pi = ii % (G::SLAB64 / 1024);
+        src = slab + (long long)g64 * a.cb64_stride + pi * 1024;
+      }
+      ffa_lds_dma16_uniform(src, lane16, (unsigned)(size_t)(__attribute__((address_space(3))) void*)(
+                                             smem + G::RING_OFF + slot * G::SLOT + ii * 1024));
     }
   };
   // LDS-DMA halo fill (no prologue): chunk `chunk` of the tile hoff[] describes -> halo buffer `buf`.  The tail
@@ -715,8 +755,9 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
   // ---- prologue of the block's first tile (the only exposed one) ----
   halo_offsets(cur);
   dma_h(0, 0);
-  issue_w(cur.cb, 0, 0);
-  issue_w(cur.cb, 1, 1);
+  issue_w(w_slab(cur.cb, 0), 0);
+  issue_w(w_slab(cur.cb, 1), 1);
+  const unsigned char* wp = w_slab(cur.cb, 2);  // the slab the next phase synchronisation issues
   if constexpr (PRO) {
     ffa_wait_vm<0>();
     fix_h(0, 0);
@@ -740,11 +781,15 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
     const int nvb = next_valid(vb + gridDim.x);
     const bool has_next = nvb < total_vb;
     const TileId nxt = decode(has_next ? nvb : vb);
+    const unsigned char* wnext = w_slab(nxt.cb, 0);
 
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = ffa_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int nt = 0; nt < NT; ++nt) {
+        acc[mt][nt] = ffa_f32x4{0.f, 0.f, 0.f, 0.f};
+        asm volatile("" : "+v"(acc[mt][nt]));  // zeroed here, once: not again on every path into the chunk loop
+      }
 
     for (int c = 0; c < NC; ++c) {
       const bool last_c = (c + 1 == NC);
@@ -753,15 +798,6 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
       const int hchunk = last_c ? 0 : c + 1;
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        int wcb_ = cur.cb, wph_ = c * 3 + r + 2;
-        if (wph_ >= PT) {
-          if (has_next) {
-            wcb_ = nxt.cb;
-            wph_ -= PT;
-          } else {
-            wph_ = PT - 1;
-          }
-        }
         const unsigned char* sA = smem + a0 + r * G::SLOT;
         const unsigned char* sAn = smem + a0 + ((r + 1) % 3) * G::SLOT;
 #pragma unroll
@@ -819,7 +855,14 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
             } else {
               ffa_wait_vm_barrier<0>();
             }
-            issue_w(wcb_, wph_, (r + 2) % 3);
+            // weight slab two phases ahead: this tile's, the next tile's first ones, or (no next tile) a re-read of
+            // this tile's last slab, which lands in a slot nobody reads again (keeps every wave's DMA count uniform)
+            issue_w(wp, (r + 2) % 3);
+            if (last_c && r == 0) {
+              if (has_next) wp = wnext;
+            } else if (hvalid) {
+              wp += G::SLAB64;
+            }
             if (r == 0 && hvalid) dma_h(hchunk, hb ^ 1);
           }
         }
@@ -838,65 +881,130 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
     }
 
     // ---- epilogue of `cur`: lane (col, kg) owns pixel n = wave px base + nt*16 + col and 16 consecutive channels ----
+    // Straight line per form: every load of the tile (residual vectors, bias) is requested first and waited for
+    // once, the eight output vectors are finished in registers, then stored back to back -- no wait between two
+    // stores -- and the statistics are taken from the stored words afterwards.  A lane reads its own residual
+    // elements before it writes them, so res == out stays legal.
     {
       T* out = static_cast<T*>(a.out);
       const T* res = static_cast<const T*>(a.res);
+      constexpr bool GEN = EPI == RING16_EPI_GENERAL;
+      const bool has_bias = GEN && a.bias != nullptr;
+      const bool has_res = EPI == RING16_EPI_RES || (GEN && res != nullptr);
+      const bool do_relu = GEN && a.relu != 0;
+      const bool want_stats = EPI == RING16_EPI_STATS || (GEN && a.stats != nullptr);
       const int co_lane = cur.cb * G::BCO + wco * 64 + 16 * kg;
-      float st[32];  // [16 sums | 16 sums of squares] of this lane's channels
-      const bool want_stats = a.stats != nullptr;
-#pragma unroll
-      for (int i = 0; i < 32; ++i) st[i] = 0.f;
+      const bool cok[2] = {co_lane < a.Co, co_lane + 8 < a.Co};
+      long long pix[NT];  // element offset of the lane's pixel
+      bool ok[NT];        // ... which lies inside the image
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int n = wpx * (NT * 16) + nt * 16 + col;
         const int oy = cur.oy0 + n / TW, ox = cur.ox0 + n % TW;
-        if (oy >= a.H || ox >= a.W) continue;
-        const long long pix = ((long long)(cur.b * a.H + oy) * a.W + ox) * (long long)a.Co;
+        ok[nt] = oy < a.H && ox < a.W;
+        pix[nt] = ((long long)(cur.b * a.H + oy) * a.W + ox) * (long long)a.Co;
+      }
+      // -0.0 is the neutral element of the f32 addition for EVERY value (x + -0.0 == x bit for bit, +0.0 included):
+      // the general form adds it where a launch has no bias / no residual instead of branching per vector
+      constexpr unsigned NEG0X2 = 0x80008000u;
+      ffa_u32x4 rw[NT][2];
+      float bv[GEN ? 16 : 1];
+      if constexpr (GEN || EPI == RING16_EPI_RES) {
+        if (has_res) {
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)  // a lane outside the image / past Co reads the tensor's first vector and drops it
+              rw[nt][h] = *reinterpret_cast<const ffa_u32x4*>((ok[nt] && cok[h]) ? res + pix[nt] + co_lane + 8 * h : res);
+        } else {
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) rw[nt][h] = ffa_u32x4{NEG0X2, NEG0X2, NEG0X2, NEG0X2};
+        }
+      }
+      if constexpr (GEN) {
+        if (has_bias) {  // the lane's 16 bias values: once per tile, in flight together with the residual
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            float b8[8];
+            ffa_load8<float>(cok[h] ? a.bias + co_lane + 8 * h : a.bias, b8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) bv[8 * h + i] = b8[i];
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) bv[i] = -0.f;
+        }
+      }
+      if constexpr (GEN || EPI == RING16_EPI_RES) ffa_wait_vm<0>();  // the one wait of the tile's loads
+      ffa_u32x4 u[NT][2];  // the stored words: rounded once, also what the statistics are taken from
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          const int c0 = co_lane + 8 * h;
-          if (c0 >= a.Co) continue;
           float v[8];
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             v[i] = acc[2 * h][nt][i];
             v[4 + i] = acc[2 * h + 1][nt][i];
           }
-          if (a.bias) {
+          if constexpr (GEN) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] += a.bias[c0 + i];
+            for (int i = 0; i < 8; ++i) v[i] += bv[8 * h + i];
           }
-          if (res) {
-            float rv[8];
-            ffa_load8<T>(res + pix + c0, rv);
+          if constexpr (GEN || EPI == RING16_EPI_RES) {
+            const ffa_u32x4 r4 = rw[nt][h];
+            const float rv[8] = {__uint_as_float(r4.x << 16), __uint_as_float(r4.x & 0xffff0000u),
+                                 __uint_as_float(r4.y << 16), __uint_as_float(r4.y & 0xffff0000u),
+                                 __uint_as_float(r4.z << 16), __uint_as_float(r4.z & 0xffff0000u),
+                                 __uint_as_float(r4.w << 16), __uint_as_float(r4.w & 0xffff0000u)};
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] += rv[i];
           }
-          if (a.relu) {
+          if constexpr (GEN) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
+            for (int i = 0; i < 8; ++i) v[i] = do_relu ? fmaxf(v[i], 0.f) : v[i];
           }
-          // rounded once: the stored words are also what the statistics are taken from (the values BatchNorm will read)
-          ffa_u32x4 u;
-          u.x = ffa_pack_bf16x2(v[0], v[1]);
-          u.y = ffa_pack_bf16x2(v[2], v[3]);
-          u.z = ffa_pack_bf16x2(v[4], v[5]);
-          u.w = ffa_pack_bf16x2(v[6], v[7]);
-          *reinterpret_cast<ffa_u32x4*>(out + pix + c0) = u;
-          if (want_stats) {
-            const float rr[8] = {__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u),
-                                 __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u),
-                                 __uint_as_float(u.z << 16), __uint_as_float(u.z & 0xffff0000u),
-                                 __uint_as_float(u.w << 16), __uint_as_float(u.w & 0xffff0000u)};
+          u[nt][h].x = ffa_pack_bf16x2(v[0], v[1]);
+          u[nt][h].y = ffa_pack_bf16x2(v[2], v[3]);
+          u[nt][h].z = ffa_pack_bf16x2(v[4], v[5]);
+          u[nt][h].w = ffa_pack_bf16x2(v[6], v[7]);
+          // pinned here: left alone the compiler sinks this arithmetic into the (per-lane conditional) store blocks
+          // below, and its own wait for the residual load in front of it then also waits for the stores before it
+          asm volatile("" : "+v"(u[nt][h]));
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);  // every vector is finished before the first store
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-              st[h * 8 + i] += rr[i];
-              st[16 + h * 8 + i] = __builtin_fmaf(rr[i], rr[i], st[16 + h * 8 + i]);  // explicit: all conv kernels round alike
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          if (ok[nt] && cok[h]) *reinterpret_cast<ffa_u32x4*>(out + pix[nt] + co_lane + 8 * h) = u[nt][h];
+      if (want_stats) {
+        float st[32];  // [16 sums | 16 sums of squares] of this lane's channels, taken from the stored words
+#pragma unroll
+        for (int i = 0; i < 32; ++i) st[i] = 0.f;
+        // a vector the lane did not store counts as zeros: st starts at +0.0 and a sum that started there is never
+        // -0.0, so adding +0.0 (and 0 * 0) leaves every bit of it -- no per-lane branch around the chains
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const bool stored = ok[nt] && cok[h];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+              const unsigned word = stored ? u[nt][h][w] : 0u;
+              const float rr[2] = {__uint_as_float(word << 16), __uint_as_float(word & 0xffff0000u)};
+#pragma unroll
+              for (int e = 0; e < 2; ++e) {
+                const int ch = 8 * h + 2 * w + e;
+                st[ch] += rr[e];
+                st[16 + ch] = __builtin_fmaf(rr[e], rr[e], st[16 + ch]);  // explicit: all conv kernels round alike
+              }
             }
           }
         }
-      }
-      if (want_stats) {
         // transposing reduction over the 16 lanes that share kg: afterwards lane col holds entries 2*col and 2*col + 1
         // of [sums | sums of squares]
 #pragma unroll
@@ -944,14 +1052,32 @@ __global__ void __launch_bounds__(64 * WCO * WPX, OCC) conv3x3_ring16_kernel(Rin
 // ------------------------------------------------------------------------------------------------
 // host side
 
-template <int WCO, int WPX, int NT, int TH, int TW, int OCC>
-static int ring16_launch(const Ring3Args& a, int grid, hipStream_t stream) {
+// The epilogue form of a launch: the three forms of the training step, anything with a bias or a ReLU is general.
+static int ring16_epilogue_form(const Ring3Args& a) {
+  if (a.bias || a.relu) return RING16_EPI_GENERAL;
+  if (a.stats) return a.res ? RING16_EPI_GENERAL : RING16_EPI_STATS;
+  return a.res ? RING16_EPI_RES : RING16_EPI_PLAIN;
+}
+
+template <int WCO, int WPX, int NT, int TH, int TW, int OCC, int EPI>
+static void ring16_launch_form(const Ring3Args& a, int grid, hipStream_t stream) {
   if (!a.pro_sc)  // measurement session open (bench.py): the kernel's own duration from launch-attached events
     ffa_launch_timed(WCO == 2 ? FFA_KT_RING16_128CO : (TW == 32 ? FFA_KT_RING16_8x32 : FFA_KT_RING16_16x16),
-                     conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, false>, dim3(grid), dim3(64 * WCO * WPX), stream, a);
+                     conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, false, EPI>, dim3(grid), dim3(64 * WCO * WPX),
+                     stream, a);
   else
-    hipLaunchKernelGGL((conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, true>), dim3(grid), dim3(64 * WCO * WPX), 0,
-                       stream, a);
+    hipLaunchKernelGGL((conv3x3_ring16_kernel<WCO, WPX, NT, TH, TW, OCC, true, EPI>), dim3(grid),
+                       dim3(64 * WCO * WPX), 0, stream, a);
+}
+
+template <int WCO, int WPX, int NT, int TH, int TW, int OCC>
+static int ring16_launch(const Ring3Args& a, int grid, hipStream_t stream) {
+  switch (ring16_epilogue_form(a)) {
+    case RING16_EPI_STATS: ring16_launch_form<WCO, WPX, NT, TH, TW, OCC, RING16_EPI_STATS>(a, grid, stream); break;
+    case RING16_EPI_PLAIN: ring16_launch_form<WCO, WPX, NT, TH, TW, OCC, RING16_EPI_PLAIN>(a, grid, stream); break;
+    case RING16_EPI_RES: ring16_launch_form<WCO, WPX, NT, TH, TW, OCC, RING16_EPI_RES>(a, grid, stream); break;
+    default: ring16_launch_form<WCO, WPX, NT, TH, TW, OCC, RING16_EPI_GENERAL>(a, grid, stream); break;
+  }
   return ffa_check_launch("conv3x3_ring16");
 }
 
@@ -1026,6 +1152,9 @@ int ffa_ring_launch(const ffa_conv_call_t& c, const ffa_conv_route_t& r, hipStre
   a.npt = r.ntiles;
   a.ncb = r.ncb;
   a.cb64_stride = (long long)a.nchunks * 3 * (3 * 2 * 64 * 32);
+  a.m_ncb = ffa_udiv_magic_of(a.ncb);
+  a.m_tx = ffa_udiv_magic_of(a.tiles_x);
+  a.m_ty = ffa_udiv_magic_of(a.tiles_y);
   if (c.dtype == FFA_BF16) {  // v_mfma_f32_16x16x32_bf16 kernel (NT counts 16-pixel fragments there)
     switch (r.variant) {
       case 1: return ring16_launch<1, 4, 4, 8, 32, 2>(a, r.grid, stream);

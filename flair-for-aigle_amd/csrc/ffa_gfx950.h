@@ -1,5 +1,6 @@
 // The gfx950 device primitives every MFMA kernel family of libflairhip shares: the LDS-DMA statement and its zero
-// source, the hand-written wait / barrier forms that go with it, the transposing LDS read and the 32x32 MFMA step.
+// source, the hand-written wait / barrier forms that go with it, the division of block-uniform indices by host-made
+// multipliers, the transposing LDS read and the 32x32 MFMA step.
 // One copy: a change to one of these idioms (a hazard nop, the M0 rule) is made here and nowhere else.
 #pragma once
 #include "ffa_common.h"
@@ -23,6 +24,32 @@ __device__ __forceinline__ void ffa_lds_dma16(const unsigned char* src, unsigned
       : "v"(src), "s"(lds_base)
       : "memory");
 }
+
+// The same with a wave-uniform source: `base` stays in a scalar register pair, the lane contributes the 32-bit byte
+// offset `voff` -- no 64-bit vector address is built per instruction.
+__device__ __forceinline__ void ffa_lds_dma16_uniform(const unsigned char* base, unsigned voff, unsigned lds_base) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(base), "s"(lds_base)
+      : "memory");
+}
+
+// n / d and the remainder for a block-uniform n < 2^31 on the scalar unit.  m = 0xffffffff / d comes from the host
+// (ffa_udiv_magic_of); mulhi(n, m) is the quotient or one short of it (n / d - n * m / 2^32 < 2 n / 2^32 < 1), so one
+// correction step makes it exact for every d >= 1.
+__device__ __forceinline__ unsigned ffa_udiv_magic(unsigned n, unsigned d, unsigned m, unsigned& rem) {
+  unsigned q = __umulhi(n, m);
+  unsigned r = n - q * d;
+  if (r >= d) {
+    ++q;
+    r -= d;
+  }
+  rem = r;
+  return q;
+}
+static inline unsigned ffa_udiv_magic_of(int d) { return 0xffffffffu / (unsigned)d; }
 
 // 16 zero bytes in global memory: the source of LDS-DMA pieces that lie outside the image (padding, ragged edges).
 // Internal linkage: every translation unit that uses it has a copy of its own (-fno-gpu-rdc).
